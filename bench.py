@@ -7,11 +7,18 @@ the "128k-pt frame" of BASELINE.json) on every registration context kept in flig
 outer iterations, continuous-time translation LM stage — all enqueued on the context's HIP stream with the two clouds
 already resident in HBM when the timed region starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode replicas|shard] [--no-cpu] [--sensor os1-128]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode replicas|shard] [--sensor os1-128] [--dump-outputs DIR] [--full [--no-cpu]]
 
-Timing: W untimed warm-up steps, then rounds of EXACTLY K steps each, every round bracketed by barrier +
-torch.cuda.synchronize() on both sides and reduced with MAX over the ranks; at least 5 rounds and at least 0.5 s of
-timed work; `value` / `ms_per_step` are the MEDIAN round (all rounds are listed under "rounds_ms_per_step").
+Timing: W untimed warm-up steps, then EXACTLY K timed steps, bracketed by barrier + torch.cuda.synchronize() on both
+sides and reduced with MAX over the ranks; `ms_per_step` = that time / K, `value` = the frames of the K steps / that time.
+
+A plain run measures the headline alone and prints its line. --full adds every other leg after it (layout check, frame
+HBM figures, HBM copy rate, single-frame latency, roofline, VALU issue, the sharded leg at N > 1, convergence-driven /
+iteration sweep / host clouds, config5, pipeline, back end, C++ operator, CPU baselines).
+
+--dump-outputs DIR: the poses the last timed step handed back (rolo_register_wait: the 4x4 transformation in float32 and float64,
+translation), one row per frame in context order (rank 0's contexts at N > 1), as DIR/<name>.npy. The inputs are seeded:
+the same arguments give the same frames to the same contexts in every run.
 
 N > 1: `python bench.py --gpus N` re-executes itself under torch.distributed.run (one rank per GPU, RCCL); launched by
 torch.distributed.run directly it reads RANK / LOCAL_RANK / WORLD_SIZE. Rank 0 prints the single JSON line.
@@ -19,9 +26,9 @@ torch.distributed.run directly it reads RANK / LOCAL_RANK / WORLD_SIZE. Rank 0 p
                        "scaling": "weak"; value = total frames / max-over-ranks time.
   sharded (extra)    — BASELINE configs[3]: ONE OS1-128 2048-column frame (262 144 points), K5 sharded by query point
                        with an all-gather of the covariances, source points of the LM passes sharded with one RCCL
-                       all-reduce of 32 fp64 per pass; reported under "sharded" at N > 1.
+                       all-reduce of 32 fp64 per pass; reported under "sharded" at N > 1 with --full.
   config5 (extra)    — BASELINE configs[4]: 512 distinct OS1-64 pairs resident in HBM streamed through the contexts
-                       (pairs dealt round-robin to the ranks), hipGraph replay; "config5" in the JSON line.
+                       (pairs dealt round-robin to the ranks), hipGraph replay; "config5" in the JSON line with --full.
 """
 from __future__ import annotations
 
@@ -39,7 +46,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
-MIN_TIMED_S = 3.0       # the headline's timed rounds add up to at least this (they run first, before any CPU leg)
+MIN_TIMED_S = 3.0       # timed(): the rounds of a --full leg add up to at least this unless the leg asks for less
 
 
 def parse():
@@ -50,6 +57,8 @@ def parse():
     ap.add_argument("--sensor", default="os1-128")
     ap.add_argument("--leaf", type=float, default=0.5)
     ap.add_argument("--mode", default="replicas", choices=["replicas", "shard"])
+    ap.add_argument("--full", action="store_true", help="after the headline, every other leg of this script (off: the headline alone; the --no-* switches below pick among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the poses of the last timed step as DIR/<name>.npy")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay (profiling runs)")
     ap.add_argument("--no-shard-leg", action="store_true", help="N>1: skip the point-sharded 262k-point leg")
@@ -380,6 +389,13 @@ def config5_leg(args, torch, dist, rank, world, local_rank, new_ctx, barrier):
     return out
 
 
+def dump_outputs(d, results):
+    """results: what register_wait returned to each context in the last timed step, (Tf, Td, t) per context (a batch: B rows each)"""
+    os.makedirs(d, exist_ok=True)
+    for j, (name, shape) in enumerate((("final_transformation", (4, 4)), ("final_transformation_d", (4, 4)), ("translation", (3,)))):
+        np.save(os.path.join(d, name + ".npy"), np.concatenate([np.reshape(r[j], (-1,) + shape) for r in results]))
+
+
 def cpu_baseline_legs(args, src, tgt, guess, last):
     """The oracle (CPU restatement of the reference, same OpenMP structure) on this box's host cores: the headline workload with all
     usable cores (`cpu_baseline`), BASELINE configs[0] (VLP-16 pair, POLAR voxels, convergence-driven, ONE thread), per-stage ms."""
@@ -497,8 +513,9 @@ def main():
             self.b.register_async(None, self.zero, self.guess, self.last, 0.1, 0.1, 0.3)
 
         def register_wait(self):
-            self.b.register_wait()
+            r = self.b.register_wait()
             self.last_stats = self.b.members[0].last_stats; self.last_translation_stats = self.b.members[0].last_translation_stats
+            return r
 
     def enqueue(g, data):
         ds, dt_, npts = data
@@ -512,11 +529,12 @@ def main():
     pass_log_on = [False]
     cursor = [0]    # next pair of the pool
 
-    def run_steps(gs, k, data):
+    def run_steps(gs, k, data, keep=None):
         """k steps; one step = one frame pair on every context of `gs`. Contexts are serviced round-robin
         (wait for a context's frame, immediately enqueue its next one) so the GPU always has work queued.
         data = a list of resident pairs: every enqueue takes the NEXT pair of the pool, so the contexts in flight hold different
-        pairs at any time and a context sees a different pair every frame."""
+        pairs at any time and a context sees a different pair every frame. keep: a list that receives what register_wait returned
+        to each context in the last step."""
         if not isinstance(gs, (list, tuple)):
             gs = [gs]
         if k <= 0:
@@ -531,14 +549,16 @@ def main():
             enqueue(g, nxt())
         for it in range(k):
             for g in gs:
-                g.register_wait()
+                r = g.register_wait()
+                if keep is not None and it + 1 == k:
+                    keep.append(r)
                 if pass_log_on[0] and not isinstance(g, Batch):
                     pass_log.append((g.last_stats.n_passes, g.last_translation_stats.n_passes, g.last_stats.n_cost_only + g.last_translation_stats.n_cost_only,
                                      g.last_stats.n_outer, g.last_translation_stats.n_outer))
                 if it + 1 < k:
                     enqueue(g, nxt())
 
-    def timed_round(g, steps, data):
+    def timed_round(g, steps, data, keep=None):
         import gc
         # CPython's cyclic GC walks every tracked object (torch is imported: ~40 ms per full collection) and fired once
         # per ~140 frames in the middle of the timed loop; collect now, keep it off while timing
@@ -546,7 +566,7 @@ def main():
         gc.disable()
         barrier()
         t0 = time.perf_counter()
-        run_steps(g, steps, data)
+        run_steps(g, steps, data, keep)
         barrier()
         dt = time.perf_counter() - t0
         gc.enable()
@@ -600,8 +620,13 @@ def main():
         shard_info = connect(g, "rccl" if args.shard_exchange in ("rccl", "rccl-inproc", "both") else "peer", 2 * n)
         rccl_ranks = shard_info["ranks"]
     pass_log_on[0] = True
-    dt, rounds = timed(ctxs, args.steps, args.warmup, data)
+    run_steps(ctxs, args.warmup, data)
+    last_out = []
+    dt = timed_round(ctxs, args.steps, data, last_out)
+    rounds = [dt]
     pass_log_on[0] = False
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_out)
     # how many of a frame's passes were cost-only (a pass right after a rejected trial stops after the trial's cost: LmState::lin_skip): counted ON THE
     # DEVICE by the controller that consumes such a pass (rolo_stats::n_cost_only), over every frame of the timed rounds — round 5 inferred it from the LM trace of one
     # untimed frame per pool pair
@@ -664,6 +689,15 @@ def main():
         if cost_only:
             out["config"]["cost_only_passes"] = cost_only
 
+    if not args.full:   # a plain run: the headline alone
+        for c_ in ctxs:
+            (c_.b if isinstance(c_, Batch) else c_).close()
+        if rank == 0:
+            print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     # ---- layout check: throughput must not depend on WHEN the contexts are created relative to other streams of the process ----------------
     # (HIP deals streams to its four hardware queues in creation order; rounds 1-3 depended on it: 2140 vs 2940 scans/s for the same four contexts.
     # The library now takes its streams from a per-device bank created in bursts — rolo_ctx_create / api.hip — so contexts closed and re-created
@@ -678,7 +712,7 @@ def main():
             dt2, rounds2 = timed(ctxs, args.steps, args.warmup, data)
             v2 = args.steps * len(ctxs) / dt2
             out["layout_check"] = {"scans_per_s_contexts_recreated_after_foreign_streams": v2, "ratio": v2 / value, "foreign_streams": len(foreign),
-                                   "what": "the headline's contexts closed, three foreign HIP streams created, the same number of contexts created again, the same timed rounds"}
+                                   "what": "the headline's contexts closed, three foreign HIP streams created, the same number of contexts created again, timed rounds of the same steps"}
         except Exception as e:  # pragma: no cover
             out["layout_check"] = {"error": repr(e)}
 

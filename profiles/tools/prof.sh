@@ -7,12 +7,12 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${TAG}prof; mkdir -p $O
 # one context, eager launches (every kernel a separate dispatch), the bench's own input pool: the 8 distinct pairs in rotation
 # (round 5: --load-hint busy — the profiled context runs alone, the headline runs four: pin the kernels the busy device picks, i.e. the 64-query packet walk)
-B="python $R/bench.py --steps 24 --warmup 8 --no-cpu --no-config5 --no-pipeline --streams 1 --no-graph --single-round --load-hint busy"
+B="python $R/bench.py --full --steps 24 --warmup 8 --no-cpu --no-config5 --no-pipeline --streams 1 --no-graph --single-round --load-hint busy"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s1 -- $B > $O/stats.log 2>&1
 # the same on the nominal pair alone (--pool 1: what rounds 1 and 2 profiled)
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats0 -o s0 -- $B --pool 1 > $O/stats0.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/pipe -o pipe -- python $R/bench.py --pipeline-only > $O/pipe.log 2>&1
-B2="python $R/bench.py --steps 8 --warmup 1 --no-cpu --no-config5 --no-pipeline --streams 1 --no-graph --single-round --load-hint busy"   # PMC passes: the bench's own pool, every pair once in the timed steps (round 5: was --pool 1)
+B2="python $R/bench.py --full --steps 8 --warmup 1 --no-cpu --no-config5 --no-pipeline --streams 1 --no-graph --single-round --load-hint busy"   # PMC passes: the bench's own pool, every pair once in the timed steps (round 5: was --pool 1)
 export ROLO_PROF_COMMAND="$B2"   # (ROLO_PROF_COMMIT: the box has no .git — export it from the authoring side: gpurun -- 'ROLO_PROF_COMMIT=<hash> bash profiles/tools/prof.sh r05')
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -o f -- $B2 > $O/pmc_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -o w -- $B2 > $O/pmc_write.log 2>&1

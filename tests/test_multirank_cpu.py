@@ -128,7 +128,7 @@ def test_bench_control_flow_world8_gloo_dry_run():
     world = 8
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "tests", "dryrun_bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--sensor", "vlp16", "--pool", "2", "--streams", "2",
-           "--config5-pairs", "8", "--single-round", "--no-cpu"]
+           "--config5-pairs", "8", "--single-round", "--no-cpu", "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
@@ -153,3 +153,41 @@ def test_bench_control_flow_world8_gloo_dry_run():
     assert set(d["iteration_sweep"]) >= {"20", "10", "2", "per_trial_us_under_load"}, d["iteration_sweep"]
     assert all(d["host_clouds"][k]["scans_per_s"] > 0 for k in ("pinned_1ctx", "pinned_2ctx", "pageable_1ctx", "pageable_2ctx")), d["host_clouds"]
     assert "cost_only_passes" in d["config"] and d["config"]["cost_only_passes"]["frames"] > 0
+
+
+def _plain_dry_run(out_dir):
+    """bench.py --gpus 1 without --full on the stand-in device of tests/dryrun_bench.py (one process, no launcher): returns the JSON line"""
+    import json
+    import subprocess
+    cmd = [sys.executable, os.path.join(ROOT, "tests", "dryrun_bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--sensor", "vlp16", "--pool", "2",
+           "--streams", "2", "--dump-outputs", str(out_dir)]
+    env = dict(os.environ, OMP_NUM_THREADS="1")
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{") and '"metric"' in l]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_poses(tmp_path):
+    """A plain run times exactly --steps steps after --warmup, prints the headline's keys and none of the --full legs, and --dump-outputs writes the
+    poses of the last timed step (one row per context), the same in two runs with the same arguments."""
+    d = _plain_dry_run(tmp_path / "a")
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["timed_rounds"] == 1 and d["frames_per_step"] == 2
+    assert d["metric"] == "scans/sec (128k-pt frame, 20 GN iters)" and d["unit"] == "scans/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 1e3 * d["frames_per_step"] / d["ms_per_step"]) <= 1e-6 * d["value"]
+    for k in ("layout_check", "frame_hbm", "hbm_measured_copy_GBps", "roofline", "valu_issue", "convergence_driven", "iteration_sweep", "host_clouds", "config5",
+              "pipeline", "backend", "cpp_operator_per_frame", "cpu_baseline", "cpu_baseline_1thread"):
+        assert k not in d, k
+    assert "single_frame_latency_ms" not in d["config"]
+    shapes = {"final_transformation": ((2, 4, 4), np.float32), "final_transformation_d": ((2, 4, 4), np.float64), "translation": ((2, 3), np.float64)}
+    a = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in shapes}
+    for k, (shape, dt) in shapes.items():
+        assert a[k].shape == shape and a[k].dtype == dt and np.isfinite(a[k]).all(), (k, a[k].shape, a[k].dtype)
+    assert not np.array_equal(a["final_transformation_d"][0], a["final_transformation_d"][1])   # the two contexts registered different pairs of the pool
+    _plain_dry_run(tmp_path / "b")
+    for k in shapes:
+        assert np.array_equal(a[k], np.load(tmp_path / "b" / (k + ".npy"))), k
