@@ -282,6 +282,10 @@ int rolo_peer_info(rolo_ctx* ctx, int* rank, int* world, char* mem_kind16);
  * admission time and gave the stage back to the host, which finished it with pass + controller launches, [13] what the context has LEARNED about load it cannot count (another
  * process on the GPU): 0 = its frames last what they last alone (idle-device kernels), 1 = trying the busy-device kernels, 2 = keeping them (rolo_set_load_hint -1 only). */
 int rolo_ctx_counters(rolo_ctx* ctx, long long* out, int n);
+/* the form of the context's last resident LM launch (fused_lm = 2, one launch per frame): out[0] workgroups, [1] threads per workgroup, [2] points per thread,
+ * [3] points per thread of the interleaved body (1, 2, 4; 0: the generic body, one point after the other), [4] points of a thread that go through a body together,
+ * [5] 1 if the Mahalanobis cache sits in LDS, [6] dynamic LDS in bytes. All zero if the last LM chain of the context did not use the resident kernel. */
+int rolo_ctx_lm_form(rolo_ctx* ctx, int* out, int n);
 /* device buffer (re)allocations made so far by the registration contexts of this process (every hipMalloc behind a rolo_ctx's buffers; a captured hipGraph is keyed on it):
  * a steady-state frame loop must stop moving it */
 long long rolo_alloc_count(void);

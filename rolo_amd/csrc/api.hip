@@ -157,6 +157,7 @@ struct rolo_ctx {
   int lm_rows = 1;   // workgroups (= partial rows) of one fused LM launch
   unsigned long long* xbuf = nullptr; size_t xbuf_cap = 0;   // row exchange of the resident LM kernel (fused_lm = 2): header + 2 parities x workgroups x 64 words, zeroed when (re)allocated
   int lmp_rows = 1, lmp_ppt = 1, lmp_threads = 512;   // its grid, the points per thread and the workgroup size
+  LmpForm lmp_form{};   // the form of its last launch (rolo_ctx_lm_form); all zero after a chain of the other launch forms
   double* sums = nullptr; size_t sums_cap = 0;
   LmState* state = nullptr; size_t state_cap = 0;
   rolo_trace_rec* trace = nullptr; size_t trace_cap = 0;
@@ -533,6 +534,8 @@ int prepare_pass(rolo_ctx* c, PassArgs& a, int& grid) {
       if ((rc = ensure(c->xbuf, c->xbuf_cap, need))) return rc;
       HIPCHK(hipMemsetAsync(c->xbuf, 0, c->xbuf_cap * sizeof(unsigned long long), c->stream));
     }
+  } else {
+    c->lmp_form = LmpForm{};
   }
   a.src = c->src.xyz; a.cov = c->src.cov; a.n_total = c->src.n; a.begin = begin; a.end = end; a.n_off = noff;
   // the source covariances as I - m m^T: only what the library computed itself for THIS cloud under PLANE (ROLO_PASS_NRM=0: the six-entry form always — the A/B)
@@ -583,7 +586,9 @@ int enqueue_lm_chunk(rolo_ctx* c, const PassArgs& a, int k, bool publish = false
 int enqueue_lm_persist(rolo_ctx* c, const PassArgs& a, bool publish = false) {
   ProfScope ps(c, ROLO_PROF_LM_PASS);
   const int cap = (std::max(c->P.max_iterations, c->P.fixed_iterations) + 2) * (std::max(c->P.lm_max_iterations, 0) + 2) * 2 + 16;
-  HIPCHK(launch_lm_persist(c->P.optimizer == ROLO_OPT_SO3_LM ? 3 : 6, c->lmp_threads, c->lmp_ppt, a, c->state, c->xbuf, c->lmp_rows, c->trace, publish ? c->h_state : nullptr,
+  const int dof = c->P.optimizer == ROLO_OPT_SO3_LM ? 3 : 6;
+  c->lmp_form = lm_persist_form(dof, c->lmp_threads, c->lmp_ppt, a.n_off, c->lmp_rows);
+  HIPCHK(launch_lm_persist(dof, c->lmp_threads, c->lmp_ppt, a, c->state, c->xbuf, c->lmp_rows, c->trace, publish ? c->h_state : nullptr,
                            lm_persist_timeout_ticks(), lm_persist_admit_ticks(), cap, c->stream));
   return ROLO_OK;
 }
@@ -1628,6 +1633,14 @@ int rolo_ctx_counters(rolo_ctx* c, long long* out, int n) {
   const long long v[14] = {c->n_frames, c->n_replays, c->n_captures, c->n_eager, c->n_topup_frames, c->n_topup_chunks, c->hint_rot, c->hint_trans, c->walk_lanes,
                            c->ns_enqueue, c->ns_wait_blocked, c->ns_wait_other, c->n_persist_bails, c->learn.mode};
   for (int i = 0; i < n && i < 14; i++) out[i] = v[i];
+  return ROLO_OK;
+}
+
+int rolo_ctx_lm_form(rolo_ctx* c, int* out, int n) {
+  if (!c || !out || n < 0) return ROLO_EINVAL;
+  const LmpForm& f = c->lmp_form;
+  const int v[7] = {f.rows, f.threads, f.ppt, f.sp, f.batch, f.mcache, (int)f.lds};
+  for (int i = 0; i < n && i < 7; i++) out[i] = v[i];
   return ROLO_OK;
 }
 

@@ -1728,17 +1728,26 @@ hipError_t launch_lm(int dof, int threads, int ppt, const PassArgs& a, const LmS
   }
   return hipGetLastError();
 }
+// the largest dynamic LDS a resident launch may take: the `fits` bound of lm_persist_form AND the limit lmp_launch raises the function attribute to. It must stay below a CU's
+// 160 KiB minus the kernels' static LDS (the state, the summation rows: 10 328 B at 512 threads, 8 280 B at 256 — lmp_launch checks it before it raises the attribute)
+constexpr size_t LMP_DYN_LDS_MAX = 148 * 1024;
+constexpr size_t LMP_CU_LDS = 160 * 1024;
 // one launch of an instantiation: dynamic LDS = the G rows of the exchange (+ the Mahalanobis cache); above 64 KB the function's limit is raised first — once per
 // instantiation (KERN is a template argument: a static per kernel, not per signature) and per device of the process
 template <auto KERN, typename... Args>
 hipError_t lmp_launch(int nrows, int threads, size_t lds, hipStream_t s, Args... args) {
+  if (lds > LMP_DYN_LDS_MAX) return hipErrorInvalidValue;
   if (lds > 64 * 1024) {
     static std::atomic<unsigned long long> raised{0};   // bit d: done on device d
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return hipGetLastError();
     const unsigned long long bit = 1ull << (dev & 63);
     if (!(raised.load(std::memory_order_relaxed) & bit)) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
+      hipFuncAttributes fa{};
+      hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(KERN));
+      if (e != hipSuccess) return e;
+      if (fa.sharedSizeBytes + LMP_DYN_LDS_MAX > LMP_CU_LDS) return hipErrorInvalidConfiguration;   // the static LDS grew: LMP_DYN_LDS_MAX must shrink with it
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LMP_DYN_LDS_MAX);
       if (e != hipSuccess) return e;
       raised.fetch_or(bit, std::memory_order_relaxed);
     }
@@ -1746,32 +1755,43 @@ hipError_t lmp_launch(int nrows, int threads, size_t lds, hipStream_t s, Args...
   KERN<<<nrows, threads, lds, s>>>(args...);
   return hipGetLastError();
 }
-hipError_t launch_lm_persist(int dof, int threads, int ppt, const PassArgs& a, LmState* st, unsigned long long* xbuf, int nrows, rolo_trace_rec* trace, LmState* pub, unsigned long long timeout_ticks,
-                             unsigned long long admit_ticks, int max_trials, hipStream_t s) {
+LmpForm lm_persist_form(int dof, int threads, int ppt, int n_off, int nrows) {
   // the interleaved bodies (1, 2 or 4 points per thread in registers) for the reference's own configuration — SO(3) optimiser, DIRECT1; everything else one point after the other
   static const bool interleave = [] { const char* e = getenv("ROLO_LM_PERSIST_INTERLEAVE"); return !(e && atoi(e) == 0); }();
-  const int sp = (interleave && dof == 3 && a.n_off == 1 && (ppt == 1 || ppt == 2 || ppt == 4)) ? ppt : 0;
   // ROLO_LM_PERSIST_MCACHE=0 (A/B): no Mahalanobis cache in LDS — every trial inverts again, as the pass kernels do
   static const int mcache_on = [] { const char* e = getenv("ROLO_LM_PERSIST_MCACHE"); return (e && atoi(e) == 0) ? 0 : 1; }();
-  // (the A/B form exists for the headline's case; it is also the form of a launch whose rows + cache would not fit a CU's LDS: four points per thread AND more than ~220
-  // workgroups — a cloud of more than 450 000 points on an idle device — is 60 KB of rows + 96 KB of cache + 10 KB of state)
-  const bool fits = sizeof(unsigned) * (size_t)nrows * 60 + sizeof(double) * 6 * (size_t)threads * sp <= (size_t)(160 - 12) * 1024;
-  const bool mcache = sp > 0 && !(sp == 4 && threads == 512 && (!mcache_on || !fits));
-  const size_t lds = sizeof(unsigned) * (size_t)nrows * 60 + (mcache ? sizeof(double) * 6 * (size_t)threads * sp : 0);
   // (builds for four wavefronts per SIMD — 128 registers, so that a walk's wavefronts could share the SIMDs — spill 85 / 159 / 270 registers at 1 / 2 / 4 points per thread and are
   // not instantiated: lm_persist_kernel<3, 512, PPT, 1, 4>, profiles/DEAD_ENDS.md round 6)
   static const int batch4 = [] { const char* e = getenv("ROLO_LM_PERSIST_BATCH"); const int v = e ? atoi(e) : 2; return (v == 1 || v == 4) ? v : 2; }();   // four points per thread go through the bodies in batches of 2 (default: 4 087 scans/s with four contexts, final kernels) / 1 (4 046: twice the dependent round trips and the same 6.6 us per linearising body — the bodies are bound by their fp64 issue at two wavefronts per SIMD, not by their fetches) / 4 (3 761: 144 spilled registers)
+  LmpForm f;
+  f.rows = nrows; f.threads = threads; f.ppt = ppt;
+  f.sp = (interleave && dof == 3 && n_off == 1 && (ppt == 1 || ppt == 2 || ppt == 4)) ? ppt : 0;
+  const size_t rows_lds = sizeof(unsigned) * (size_t)nrows * 60, cache_lds = sizeof(double) * 6 * (size_t)threads * f.sp;
+  // (the A/B form exists for the headline's case; it is also the form of a launch whose rows + cache would not fit a CU's LDS: four points per thread AND more than 221
+  // workgroups — a cloud of more than 452 608 points on an idle device — is 52 KB of rows + 96 KB of cache + 10 KB of state)
+  const bool fits = rows_lds + cache_lds <= LMP_DYN_LDS_MAX;
+  f.mcache = f.sp > 0 && !(f.sp == 4 && threads == 512 && (!mcache_on || !fits));
+  f.lds = rows_lds + (f.mcache ? cache_lds : 0);
+  // the form without the cache has batches of 2 whatever ROLO_LM_PERSIST_BATCH says (lm_persist_kernel<3, 512, 4, 2, 2, false>: the only one without it)
+  f.batch = f.sp == 0 ? 1 : (f.sp != 4 ? f.sp : (threads == 256 || !f.mcache ? 2 : batch4));
+  return f;
+}
+hipError_t launch_lm_persist(int dof, int threads, int ppt, const PassArgs& a, LmState* st, unsigned long long* xbuf, int nrows, rolo_trace_rec* trace, LmState* pub, unsigned long long timeout_ticks,
+                             unsigned long long admit_ticks, int max_trials, hipStream_t s) {
+  const LmpForm f = lm_persist_form(dof, threads, ppt, a.n_off, nrows);
+  const size_t lds = f.lds;
 #define LMP_GO(...) lmp_launch<&lm_persist_kernel<__VA_ARGS__>>(nrows, threads, lds, s, a, st, xbuf, trace, ppt, pub, timeout_ticks, admit_ticks, max_trials)
   // (A/B, ROLO_LM_PERSIST_BUSY_THREADS=256: 128 workgroups of 256 threads — one wavefront per SIMD at 256 registers, so that other kernels' wavefronts share the SIMDs
   // instead of finding 64 CUs closed: 3 353 / 3 339 against 3 639 / 3 635 scans/s, profiles/DEAD_ENDS.md round 6)
-  if (threads == 256) return (dof == 3 && sp == 4) ? LMP_GO(3, 256, 4, 2) : hipErrorInvalidValue;
+  if (threads == 256) return (dof == 3 && f.sp == 4 && f.mcache) ? LMP_GO(3, 256, 4, 2) : hipErrorInvalidValue;
   if (dof != 3) return LMP_GO(6, 512, 0);
-  if (sp == 1) return LMP_GO(3, 512, 1);
-  if (sp == 2) return LMP_GO(3, 512, 2);
-  if (sp == 4 && batch4 == 1) return LMP_GO(3, 512, 4, 1);
-  if (sp == 4 && !mcache) return LMP_GO(3, 512, 4, 2, 2, false);
-  if (sp == 4 && batch4 == 2) return LMP_GO(3, 512, 4, 2);
-  if (sp == 4) return LMP_GO(3, 512, 4);
+  if (f.sp == 1) return LMP_GO(3, 512, 1);
+  if (f.sp == 2) return LMP_GO(3, 512, 2);
+  // (the cache-less form is picked before the batch: every other four-point form reads and writes the cache, which a launch without it has no LDS for)
+  if (f.sp == 4 && !f.mcache) return LMP_GO(3, 512, 4, 2, 2, false);
+  if (f.sp == 4 && f.batch == 1) return LMP_GO(3, 512, 4, 1);
+  if (f.sp == 4 && f.batch == 2) return LMP_GO(3, 512, 4, 2);
+  if (f.sp == 4) return LMP_GO(3, 512, 4);
   return LMP_GO(3, 512, 0);
 #undef LMP_GO
 }

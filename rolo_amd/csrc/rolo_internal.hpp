@@ -234,6 +234,15 @@ hipError_t launch_lm(int dof, int threads, int ppt /* slabs of `threads` points 
 // host (LmState::lmp_bailed); timeout_ticks: what a poll may last after that (a bug guard: ROLO_ECOMM); max_trials: hard cap on the trials of one launch
 hipError_t launch_lm_persist(int dof, int threads, int ppt, const PassArgs& a, LmState* st, unsigned long long* xbuf, int nrows, rolo_trace_rec* trace, LmState* pub, unsigned long long timeout_ticks,
                              unsigned long long admit_ticks, int max_trials, hipStream_t s);
+// the instantiation one resident launch takes (passes.hip lm_persist_form): launch_lm_persist launches exactly this and rolo_ctx_lm_form reports it
+struct LmpForm {
+  int rows = 0, threads = 0, ppt = 0;
+  int sp = 0;       // points per thread of the interleaved body (1, 2, 4); 0: the generic body, one point after the other
+  int batch = 0;    // points of a thread that go through a body together
+  int mcache = 0;   // the Mahalanobis cache sits in LDS behind the exchange rows
+  size_t lds = 0;   // dynamic LDS of the launch, bytes
+};
+LmpForm lm_persist_form(int dof, int threads, int ppt, int n_off, int nrows);
 size_t lm_persist_words(int nrows);
 hipError_t launch_reduce(const double* partials, int nblocks, double* sums, const LmState* st, int stage, hipStream_t s);
 // controller: sums the rows of `partials` itself (single GPU) or takes all-reduced `sums` (partials == nullptr)

@@ -373,6 +373,12 @@ class RotVGICP:
         return dict(zip(("frames", "graph_replays", "graph_captures", "eager_frames", "topup_frames", "sync_chunks", "hint_rot", "hint_trans", "walk_lanes",
                          "host_enqueue_ns", "host_wait_blocked_ns", "host_wait_other_ns", "persist_bails", "load_mode"), [int(x) for x in v]))
 
+    def lm_form(self) -> dict:
+        """rolo_ctx_lm_form as a dict: the form of the last resident LM launch (all zero if the last LM chain did not use the resident kernel)"""
+        v = (C.c_int * 7)()
+        check(lib().rolo_ctx_lm_form(self._h, v, 7), "rolo_ctx_lm_form")
+        return dict(zip(("rows", "threads", "ppt", "sp", "batch", "mcache", "lds"), [int(x) for x in v]))
+
     def debug_chain(self, kind: int, n_pairs: int, grid: int, reps: int):
         """experiment hook (rolo_debug_chain): `reps` replays of a captured chain of launch pairs on this context's stream; asynchronous"""
         check(lib().rolo_debug_chain(self._h, kind, n_pairs, grid, reps), "rolo_debug_chain")
