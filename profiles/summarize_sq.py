@@ -18,7 +18,7 @@ def short(n):
 
 
 def full(n):
-    """name with its template arguments: `knn_walk_kernel<20, false, false, true>` (the key of profiles/tools/codeobj_notes.py's table)"""
+    """name with its template arguments: `knn_walk_kernel<20, false, true>` (the key of profiles/tools/codeobj_notes.py's table)"""
     m = re.search(r"rolo::\(anonymous namespace\)::([A-Za-z_0-9]+)(<[^()]*>)?\(", n)
     return (m.group(1) + (m.group(2) or "")) if m else None
 

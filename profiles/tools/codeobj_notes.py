@@ -48,7 +48,7 @@ def demangle(names):
 
 
 def short(dem):
-    """`knn_walk_kernel<20, false, false, true>` from `void rolo::(anonymous namespace)::knn_walk_kernel<20, false, false, true>(rolo::KnnPair, int, int, int)` — the same
+    """`knn_walk_kernel<20, false, true>` from `void rolo::(anonymous namespace)::knn_walk_kernel<20, false, true>(rolo::KnnPair, int, int)` — the same
     form summarize_sq.py makes of rocprofv3's Kernel_Name"""
     m = re.search(r"([A-Za-z_0-9]+)(<[^()]*>)?\(", dem)
     return (m.group(1) + (m.group(2) or "")) if m else dem

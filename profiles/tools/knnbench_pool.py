@@ -1,7 +1,7 @@
 """Search build / walk / tail per launch (HIP events) over the bench's POOL of distinct frame pairs and at the pipeline's cloud size — the figure VERDICT r03 item 2
-is measured on. ROLO_KNN_BUDGET=<leaves> (0: the plain walk) selects the walk; one process per setting:
+is measured on:
 
-    for b in 0 20 28 36; do ROLO_KNN_BUDGET=$b python profiles/tools/knnbench_pool.py; done
+    python profiles/tools/knnbench_pool.py
 """
 import os, sys, json; sys.path.insert(0, '.')   # run from the repository root
 import numpy as np
@@ -22,7 +22,7 @@ if __name__ == "__main__":
     cases = [("os1-128", i, 1) for i in range(npool)] + [("os1-128", i, 3) for i in range(min(npool, 4))] + [("os1-64", 0, 1)]
     with ProcessPoolExecutor(max_workers=min(len(cases), os.cpu_count() or 4)) as ex:
         pairs = list(ex.map(pair, cases))
-    out = {"budget": os.environ.get("ROLO_KNN_BUDGET", "default"), "rows": []}
+    out = {"rows": []}
     for (sensor, i, stride), (src, tgt) in zip(cases, pairs):
         g = RotVGICP(); g.setResolution(0.5)
         ds = torch.from_numpy(src).cuda(); dt = torch.from_numpy(tgt).cuda()

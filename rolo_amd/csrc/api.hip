@@ -292,19 +292,6 @@ int prepare_cloud(rolo_ctx* c, CloudDev& cl, size_t& cov_cap, size_t& sorted_cap
 
 // Morton sort, BVH, neighbour search and covariances of the source and / or the target in ONE chain of launches.
 // A pair shares the scratch set 0; a lone target uses set 1 so that it can run next to a lone source on another stream.
-// ROLO_KNN_FUSE_TAIL=1: the covariance tail inside the walk kernel instead of its own launch (an A/B: slower, see knn_walk.hpp)
-static bool fused_tail_env() {
-  static const bool v = [] { const char* e = getenv("ROLO_KNN_FUSE_TAIL"); return e && atoi(e) != 0; }();
-  return v;
-}
-// ROLO_KNN_BUDGET=<leaves>: the cooperative walk (knn_walk.hpp) — after that many leaves a packet starts handing sub-trees to the idle wavefronts of its workgroup.
-// Default 0 = the plain walk: measured in round 4, the cooperative form is exact (all list tests pass with it) but no faster (0.224 against 0.223 ms over the
-// pool at 24 leaves): what thieves can take are the far sub-trees at the bottom of a stack, which prune to nothing, and the kernel is bound by the spread of the
-// work over the CUs (x 1.21 - 1.34 between the busiest CU and the mean), which nothing inside a workgroup can move.
-static int knn_budget_env() {
-  static const int v = [] { const char* e = getenv("ROLO_KNN_BUDGET"); const int b = e ? atoi(e) : 0; return b < 0 ? 0 : b; }();
-  return v;
-}
 // ROLO_VOXEL_FUSE=0: the voxel map as its own launches after the search (the A/B of VoxelFuse)
 static bool voxel_fuse_env() {
   static const bool v = [] { const char* e = getenv("ROLO_VOXEL_FUSE"); return !(e && atoi(e) == 0); }();
@@ -372,7 +359,7 @@ int build_clouds(rolo_ctx* c, bool do_src, bool do_tgt, hipStream_t stream, bool
   // sharded with every rank's covariances exchanged (peers / RCCL): the map is still built inside the search's launches — clear and insert ride
   // on the key / sort launches each rank runs on the whole cloud anyway, the accumulation moves from the tail to the scatter after the exchange
   const bool all_ranks = c->comm != nullptr || peers(c);
-  vf.enabled = vf.enabled && do_tgt && (!sharded || all_ranks) && !tree_only && !fused_tail_env();
+  vf.enabled = vf.enabled && do_tgt && (!sharded || all_ranks) && !tree_only;
   if (vf.enabled) { vf.which = do_src ? 1 : 0; vf.bbox6 = S.bbox + 6 * vf.which; vf.tgt_xyz = c->tgt.xyz; vf.n_tgt = c->tgt.n; }
   c->vf_done = vf.enabled != 0;
   { ProfScope ps(c, ROLO_PROF_KNN_BUILD, stream); HIPCHK(launch_knn_build(A, S.sort_tmp, tmp, S.keys0, S.keys1, S.vals0, S.vals1, S.bbox, vf, stream)); }
@@ -382,13 +369,12 @@ int build_clouds(rolo_ctx* c, bool do_src, bool do_tgt, hipStream_t stream, bool
     if (do_tgt) { c->tgt.have_sorted = true; c->tgt.have_cov = false; c->tgt.bbox6 = S.bbox + (do_src ? 6 : 0); }
     return ROLO_OK;
   }
-  const bool split_tail = !fused_tail_env() || kc > 64;
   // default (round 6, k = 20): the walk's epilogue leaves the six centred moments of every neighbourhood, by sorted position, where the index lists used to go, and the tail
   // finishes them (knn_walk.hpp walk_write_moments); ROLO_KNN_MOMENTS=0: the neighbour indices through A.c[].nbr and the tail's own gather (rounds 1-5, the A/B)
   static const bool moments_on = [] { const char* e = getenv("ROLO_KNN_MOMENTS"); return !(e && atoi(e) == 0); }();
-  const bool moments = moments_on && kc == 20 && split_tail && knn_budget_env() == 0;
-  { ProfScope ps(c, ROLO_PROF_KNN_WALK, stream); HIPCHK(launch_knn_walk(A, c->P.k_correspondences, split_tail ? -1 : c->P.regularization, vf, stream, (kc == 20 && split_tail) ? knn_budget_env() : 0, &c->walk_lanes, c->device_busy, moments)); }
-  if (split_tail) { ProfScope ps(c, ROLO_PROF_KNN_TAIL, stream); HIPCHK(launch_knn_tail(A, c->P.k_correspondences, c->P.regularization, vf, stream, moments)); }
+  const bool moments = moments_on && kc == 20;
+  { ProfScope ps(c, ROLO_PROF_KNN_WALK, stream); HIPCHK(launch_knn_walk(A, c->P.k_correspondences, stream, &c->walk_lanes, c->device_busy, moments)); }
+  { ProfScope ps(c, ROLO_PROF_KNN_TAIL, stream); HIPCHK(launch_knn_tail(A, c->P.k_correspondences, c->P.regularization, vf, stream, moments)); }
   if (sharded) {
     const size_t seg = A.c[0].seg;
     if (peers(c)) {   // every rank pushes its segment into every peer's area, flags, and waits for the others' flags (peer.hip)

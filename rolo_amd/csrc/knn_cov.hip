@@ -317,51 +317,6 @@ __global__ __launch_bounds__(SORT_T) void sort_hist_kernel(const uint32_t* __res
   if (tid < SORT_D) cnt[(size_t)pass * SORT_NB * SORT_D + blk * SORT_D + tid] = hist[tid];
 }
 
-#ifdef ROLO_KNN_KD_REFINE
-// 256 threads, one point each (padding: +inf coordinates, sorts last on every axis): returns the point of this thread's slot after the splits
-ROLO_DEV float4 kd_refine_block(float4 cur) {
-  __shared__ float4 pts[256];
-  __shared__ unsigned long long key[256];
-  __shared__ float w_lo[4][3], w_hi[4][3];
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  for (int seg = 256; seg >= 2 * KNN_LEAF; seg >>= 1) {
-    const bool pad = __float_as_int(cur.w) == INT_MAX;
-    float lo[3] = {pad ? INFINITY : cur.x, pad ? INFINITY : cur.y, pad ? INFINITY : cur.z};
-    float hi[3] = {pad ? -INFINITY : cur.x, pad ? -INFINITY : cur.y, pad ? -INFINITY : cur.z};
-    const int in_wave = seg < 64 ? seg : 64;
-#pragma unroll
-    for (int d = 0; d < 3; d++)
-      for (int m = 1; m < in_wave; m <<= 1) { lo[d] = fminf(lo[d], __shfl_xor(lo[d], m)); hi[d] = fmaxf(hi[d], __shfl_xor(hi[d], m)); }
-    if (seg > 64) {
-      if (lane == 0) for (int d = 0; d < 3; d++) { w_lo[wv][d] = lo[d]; w_hi[wv][d] = hi[d]; }
-      __syncthreads();
-      const int w0 = (t / seg) * (seg / 64);
-      for (int d = 0; d < 3; d++) { lo[d] = w_lo[w0][d]; hi[d] = w_hi[w0][d]; for (int w = 1; w < seg / 64; w++) { lo[d] = fminf(lo[d], w_lo[w0 + w][d]); hi[d] = fmaxf(hi[d], w_hi[w0 + w][d]); } }
-    }
-    const float ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
-    const int axis = (ey > ex && ey >= ez) ? 1 : ((ez > ex && ez > ey) ? 2 : 0);
-    const float c = axis == 0 ? cur.x : (axis == 1 ? cur.y : cur.z);
-    unsigned u = __float_as_uint(c); u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;
-    pts[t] = cur;
-    key[t] = ((unsigned long long)u << 32) | (unsigned)t;
-    __syncthreads();
-    for (int k = 2; k <= seg; k <<= 1)
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        const int ixj = t ^ j;
-        if (ixj > t) {
-          const unsigned long long a = key[t], b = key[ixj];
-          const bool up = ((t & (seg - 1)) & k) == 0;
-          if ((a > b) == up) { key[t] = b; key[ixj] = a; }
-        }
-        __syncthreads();
-      }
-    cur = pts[(int)(unsigned)(key[t] & 0xffffffffull)];
-    __syncthreads();
-  }
-  return cur;
-}
-#endif
-
 // one thread per slot of the sorted copy: gather the point in curve order, write it + (first lane of a leaf) the leaf box
 __global__ __launch_bounds__(256) void leaf_kernel(KnnPair A, int split, const uint32_t* __restrict__ order) {
   ROLO_ALL_KERNEL_PRIO();
@@ -380,12 +335,6 @@ __global__ __launch_bounds__(256) void leaf_kernel(KnnPair A, int split, const u
     const float4 q = p[idx];
     o = make_float4(q.x, q.y, q.z, __int_as_float((int)idx));
   }
-#ifdef ROLO_KNN_KD_REFINE
-  // (experiment) the 256 curve-consecutive points of this workgroup re-ordered by four median splits on the widest axis (256 -> 16 x 16): the curve
-  // keeps the block together in space, the splits make its packets (64) and leaves (16) compact boxes instead of stretches of a curve that
-  // enters and leaves a surface. Padding sorts last at every level, so the real points stay a prefix of the block. (P >= 16: whole blocks.)
-  if (P >= 16) o = kd_refine_block(o);
-#endif
   if (g >= P) return;   // whole leaves only: KNN_LEAF divides the block size
   const bool real = __float_as_int(o.w) != INT_MAX;
   float lox = real ? o.x : INFINITY, loy = real ? o.y : INFINITY, loz = real ? o.z : INFINITY;
@@ -742,89 +691,47 @@ constexpr int KNN_SUB_MAX_PACKETS = 1792;   // (the pipeline's pair launch is 14
 // against 0.76 ms); with other contexts' frames in flight the packets — half the wavefronts, the same instructions — leave the other frames' short LM kernels more of
 // every SIMD's issue slots: 3.04 against 2.98 k scans/s, and 3.17 against 3.01 k once those kernels run at raised priority (ROLO_SHORT_PRIO). The caller says which
 // case it is (frames in flight on the device when this one is enqueued, api.hip); a captured hipGraph is keyed on it.
-hipError_t launch_knn_walk(const KnnPair& A, int k, int regularization_or_minus1, const VoxelFuse& vf, hipStream_t s, int coop_budget, int* lanes_out, bool device_busy, bool moments) {
+hipError_t launch_knn_walk(const KnnPair& A, int k, hipStream_t s, int* lanes_out, bool device_busy, bool moments) {
   if (lanes_out) *lanes_out = 1;
   constexpr int QPB = 256;   // queries per workgroup of the plain walk: four wavefronts of 64
   const int n0 = A.c[0].q_end - A.c[0].q_begin, n1 = A.n_clouds > 1 ? A.c[1].q_end - A.c[1].q_begin : 0;
   const int g0 = (n0 + QPB - 1) / QPB, g1 = (n1 + QPB - 1) / QPB;
   if (g0 + g1 == 0) return hipSuccess;
-  (void)vf;   // (insert workgroups appended to THIS launch made its wave-uniform leaf loads vector loads: a store anywhere in the kernel is a potential clobber)
-  constexpr int pad = 0;   // (an LDS pad here limited the walk to 3 / 2 workgroups per CU: 0.216 / 0.259 ms against 0.196)
   if (k > 64) {   // any k: rounds of 64 — round r searches the 64 (the last: k - 64 r) nearest ABOVE the previous round's last key (KnnCloud::lower).
                   // ceil(k / 64) full walks: correct, as slow as it sounds; the reference accepts any k, its default is 20 and ROLO never changes it
-    if (regularization_or_minus1 >= 0) return hipErrorInvalidValue;   // the covariance tail is its own launch here
     KnnPair R = A;
     for (int r = 0; 64 * r < k; r++) {
       const int kr = k - 64 * r < 64 ? k - 64 * r : 64;
       for (int i = 0; i < R.n_clouds; i++) { R.c[i].slot0 = 64 * r; R.c[i].k_total = k; }
-      if (r == 0) knn_walk_kernel<64, false><<<g0 + g1, 256, pad, s>>>(R, g0, kr, -1);
-      else knn_walk_kernel<64, false, true><<<g0 + g1, 256, pad, s>>>(R, g0, kr, -1);
+      if (r == 0) knn_walk_kernel<64><<<g0 + g1, 256, 0, s>>>(R, g0, kr);
+      else knn_walk_kernel<64, true><<<g0 + g1, 256, 0, s>>>(R, g0, kr);
     }
     return hipGetLastError();
   }
   if (k == 20) {
-    if (regularization_or_minus1 >= 0) knn_walk_kernel<20, true><<<g0 + g1, 256, pad, s>>>(A, g0, k, regularization_or_minus1);
-    else if (coop_budget > 0) {
-      // the cooperative walk (knn_walk.hpp): NW packets per workgroup, a heavy packet's remaining sub-trees go to the workgroup's idle wavefronts.
-      // NW follows the launch size — a workgroup per CU at least: 4 for the pipeline's ~48 k-point feature clouds, 16 for the 2 x 131 072-point frame
-      const int packets = (n0 + 63) / 64 + (n1 + 63) / 64;
-      static const int force_nw = [] {   // 4 / 8 / 16 wavefronts per workgroup; anything else would run the NW = 4 kernel with a grid sized for another: ignored
-        const char* e = getenv("ROLO_KNN_COOP_NW");
-        if (!e) return 0;
-        const int v = atoi(e);
-        if (v == 4 || v == 8 || v == 16) return v;
-        fprintf(stderr, "librolo_hip: ROLO_KNN_COOP_NW=%s is not one of 4 / 8 / 16: ignored\n", e);
-        return 0;
-      }();
-      const int nw = force_nw ? force_nw : (packets >= 16 * 256 ? 16 : (packets >= 8 * 256 ? 8 : 4));
-      const int G4 = g0 + g1, G = (G4 + nw / 4 - 1) / (nw / 4);   // a workgroup = nw / 4 runs of four consecutive packets (the plain walk's blocks), strided by G
-      if (nw == 16) knn_walk_coop_kernel<16><<<G, 1024, 0, s>>>(A, g0, G4, coop_budget);
-      else if (nw == 8) knn_walk_coop_kernel<8><<<G, 512, 0, s>>>(A, g0, G4, coop_budget);
-      else knn_walk_coop_kernel<4><<<G, 256, 0, s>>>(A, g0, G4, coop_budget);
-    }
-    else {
-      // small clouds: 16 queries x 4 lanes per wavefront (knn_walk_sub_kernel) — below ~2 packets of 64 per SIMD the walk is a chain of fetches, not
-      // inserts. ROLO_KNN_SUB (an A/B switch): 0 = the 64-query packets at every size, 2 = two lanes per query always, 4 (or 1) = four lanes always; unset = by size.
-      // Any other value is ignored with a warning instead of silently picking a kernel (advisor, round 4).
-      static const int sub_env = [] {
-        const char* e = getenv("ROLO_KNN_SUB");
-        if (!e) return -1;
-        const int v = atoi(e);
-        if (v == 0 || v == 1 || v == 2 || v == 4) return v;
-        fprintf(stderr, "librolo_hip: ROLO_KNN_SUB=%s is not one of 0 / 1 / 2 / 4: ignored (the walk is picked by size)\n", e);
-        return -1;
-      }();
-      const int packets = (n0 + 63) / 64 + (n1 + 63) / 64;
-      const int lanes = sub_env < 0 ? (packets <= KNN_SUB_MAX_PACKETS ? 4 : (device_busy ? 0 : 2)) : (sub_env == 2 ? 2 : (sub_env ? 4 : 0));
-      if (lanes_out) *lanes_out = lanes ? lanes : 1;
-      // ROLO_KNN_WALK_WGS = workgroups of the walk a CU may hold at a time (through a dynamic-LDS pad; unset / 0: as many as fit): with two lanes per query the
-      // dense frame's 8192 wavefronts fill all 8 wave slots of every SIMD, and whatever another context has queued waits for slots until the walk thins out
-      static const int walk_pad = [] {
-        const char* e = getenv("ROLO_KNN_WALK_WGS"); const int v = e ? atoi(e) : 0;
-        const int pad_bytes = (v >= 1 && v <= 8) ? (160 * 1024 / v - 1024 - 512) & ~255 : 0;
-        if (pad_bytes > 48 * 1024) {   // above the default limit of dynamic LDS a launch needs the attribute raised (1 or 2 workgroups per CU); if the runtime refuses, the pad is dropped
-          bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&knn_walk_kernel<20, false>), hipFuncAttributeMaxDynamicSharedMemorySize, pad_bytes) == hipSuccess;
-          ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(&knn_walk_sub_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, pad_bytes) == hipSuccess;
-          ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(&knn_walk_sub_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, pad_bytes) == hipSuccess;
-          if (!ok) { (void)hipGetLastError(); fprintf(stderr, "librolo_hip: ROLO_KNN_WALK_WGS=%d needs %d bytes of dynamic LDS, which this runtime refuses: ignored\n", v, pad_bytes); return 0; }
-        }
-        return pad_bytes;
-      }();
-      // moments: the walk's epilogue gathers each query's twenty winners once and leaves the six centred second moments of the neighbourhood where its covariance
-      // will go — no 80 B/pt index array to write, read back and gather through again in the tail (round 6)
-      if (lanes == 4) { const int s0 = (n0 + 63) / 64, s1 = (n1 + 63) / 64; if (moments) knn_walk_sub_kernel<4, true><<<s0 + s1, 256, walk_pad, s>>>(A, s0); else knn_walk_sub_kernel<4><<<s0 + s1, 256, walk_pad, s>>>(A, s0); }
-      else if (lanes == 2) { const int s0 = (n0 + 127) / 128, s1 = (n1 + 127) / 128; if (moments) knn_walk_sub_kernel<2, true><<<s0 + s1, 256, walk_pad, s>>>(A, s0); else knn_walk_sub_kernel<2><<<s0 + s1, 256, walk_pad, s>>>(A, s0); }
-      else if (moments) knn_walk_kernel<20, false, false, true><<<g0 + g1, 256, walk_pad, s>>>(A, g0, k, -1);
-      else knn_walk_kernel<20, false><<<g0 + g1, 256, walk_pad, s>>>(A, g0, k, -1);
-    }
+    // small clouds: 16 queries x 4 lanes per wavefront (knn_walk_sub_kernel) — below ~2 packets of 64 per SIMD the walk is a chain of fetches, not
+    // inserts. ROLO_KNN_SUB (an A/B switch): 0 = the 64-query packets at every size, 2 = two lanes per query always, 4 (or 1) = four lanes always; unset = by size.
+    // Any other value is ignored with a warning instead of silently picking a kernel (advisor, round 4).
+    static const int sub_env = [] {
+      const char* e = getenv("ROLO_KNN_SUB");
+      if (!e) return -1;
+      const int v = atoi(e);
+      if (v == 0 || v == 1 || v == 2 || v == 4) return v;
+      fprintf(stderr, "librolo_hip: ROLO_KNN_SUB=%s is not one of 0 / 1 / 2 / 4: ignored (the walk is picked by size)\n", e);
+      return -1;
+    }();
+    const int packets = (n0 + 63) / 64 + (n1 + 63) / 64;
+    const int lanes = sub_env < 0 ? (packets <= KNN_SUB_MAX_PACKETS ? 4 : (device_busy ? 0 : 2)) : (sub_env == 2 ? 2 : (sub_env ? 4 : 0));
+    if (lanes_out) *lanes_out = lanes ? lanes : 1;
+    // moments: the walk's epilogue gathers each query's twenty winners once and leaves the six centred second moments of the neighbourhood where its covariance
+    // will go — no 80 B/pt index array to write, read back and gather through again in the tail (round 6)
+    if (lanes == 4) { const int s0 = (n0 + 63) / 64, s1 = (n1 + 63) / 64; if (moments) knn_walk_sub_kernel<4, true><<<s0 + s1, 256, 0, s>>>(A, s0); else knn_walk_sub_kernel<4><<<s0 + s1, 256, 0, s>>>(A, s0); }
+    else if (lanes == 2) { const int s0 = (n0 + 127) / 128, s1 = (n1 + 127) / 128; if (moments) knn_walk_sub_kernel<2, true><<<s0 + s1, 256, 0, s>>>(A, s0); else knn_walk_sub_kernel<2><<<s0 + s1, 256, 0, s>>>(A, s0); }
+    else if (moments) knn_walk_kernel<20, false, true><<<g0 + g1, 256, 0, s>>>(A, g0, k);
+    else knn_walk_kernel<20><<<g0 + g1, 256, 0, s>>>(A, g0, k);
   }
-  else {
-    if (k > 32) {   // up to 64 neighbours: 128 key registers per lane — correct, not tuned (the reference accepts any k; its default is 20)
-      if (regularization_or_minus1 >= 0) knn_walk_kernel<64, true><<<g0 + g1, 256, pad, s>>>(A, g0, k, regularization_or_minus1);
-      else knn_walk_kernel<64, false><<<g0 + g1, 256, pad, s>>>(A, g0, k, -1);
-    } else if (regularization_or_minus1 >= 0) knn_walk_kernel<32, true><<<g0 + g1, 256, pad, s>>>(A, g0, k, regularization_or_minus1);
-    else knn_walk_kernel<32, false><<<g0 + g1, 256, pad, s>>>(A, g0, k, -1);
-  }
+  else if (k > 32) knn_walk_kernel<64><<<g0 + g1, 256, 0, s>>>(A, g0, k);   // up to 64 neighbours: 128 key registers per lane — correct, not tuned (the reference accepts any k; its default is 20)
+  else knn_walk_kernel<32><<<g0 + g1, 256, 0, s>>>(A, g0, k);
   return hipGetLastError();
 }
 

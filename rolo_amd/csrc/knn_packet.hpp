@@ -1,6 +1,6 @@
 // The packet walk of the exact k-nearest-neighbour search, as device functions: packed (d2, index) keys and their min / max sorted insert, wave-uniform
-// fetches as explicit scalar loads, leaf scoring, the walk itself and the hooks of the cooperative kernel. Included by knn_walk.hpp (K5: the queries are the
-// cloud's own points) and by scan2map.hip (8f.4: foreign queries — the scan's features against the sub-map's tree). Design notes: knn_walk.hpp.
+// fetches, leaf scoring and the walk itself. Included by knn_walk.hpp (K5: the queries are the cloud's own points) and by scan2map.hip (8f.4: foreign
+// queries — the scan's features against the sub-map's tree). Design notes: knn_walk.hpp.
 #pragma once
 #include "rolo_internal.hpp"
 #include "dev_math.hpp"
@@ -73,76 +73,27 @@ ROLO_DEV void insert_tiered(double (&K)[KMAX], double ck) {
   }
 }
 
-// ---- wave-uniform fetches as EXPLICIT scalar loads ----------------------------------------------------------------------------------------
-// Node boxes and leaf points are fetched through wave-uniform addresses: one s_load per 64 bytes per WAVE instead of a vector load per lane. Rounds
-// 1-3 left that to the compiler, which emits scalar loads only while it can prove that nothing in the kernel may have written memory before them
-// — a store, an atomic, a fence, a clock builtin or a volatile asm ahead of the loop (or on any path that reaches it again) turned the leaf's 64
-// floats into vector loads: 64 more VGPRs, spills, a 5-10 x slower walk ("the clobber rule"). That rule forbade every form of
-// work sharing between wavefronts. The loads are inline asm now (s_load_dwordx16 + the wait, outputs in SGPR tuples): scalar by construction,
-// whatever else the kernel does. The data they read (sorted points, boxes) is written by EARLIER launches only, so a non-volatile asm is exact.
-typedef float sgpr16 __attribute__((ext_vector_type(16)));
-#ifndef ROLO_KNN_ASM_LOADS
-#define ROLO_KNN_ASM_LOADS 0   // the PLAIN walk kernels (no store, atomic or fence ahead of their loops: the compiler's own scalar loads, as measured in rounds 1-3; 1 = the asm loads there too, an A/B: +2-3 %);
-#endif                         // the cooperative kernel, which fences and stores between walks, always takes the asm loads
-constexpr bool KNN_PLAIN_ASM = ROLO_KNN_ASM_LOADS != 0;
-// (the "s" constraint does not make a pointer uniform by itself: one the compiler believes divergent — e.g. picked through a value read from LDS — would be
-// substituted as a VGPR pair, which the instruction does not take)
-ROLO_DEV const float4* uniform_ptr(const float4* p) {
-  const unsigned long long v = (unsigned long long)p;
-  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
-  return (const float4*)(((unsigned long long)hi << 32) | lo);
-}
-template <bool ASM>
-ROLO_DEV void sload_leaf(const float4* __restrict__ p_, float4 (&pts)[KNN_LEAF]) {
-  if (!ASM) {
-#pragma unroll
-    for (int u = 0; u < KNN_LEAF; u++) pts[u] = p_[u];
-    return;
-  }
-  const float4* p = uniform_ptr(p_);
-#if 1
-  static_assert(KNN_LEAF == 16 || KNN_LEAF == 8, "leaf size");
-  sgpr16 a, b;
-  if (KNN_LEAF == 16) {
-    sgpr16 c, d;
-    asm("s_load_dwordx16 %0, %4, 0x0\n\ts_load_dwordx16 %1, %4, 0x40\n\ts_load_dwordx16 %2, %4, 0x80\n\ts_load_dwordx16 %3, %4, 0xc0\n\ts_waitcnt lgkmcnt(0)"
-        : "=&s"(a), "=&s"(b), "=&s"(c), "=&s"(d) : "s"(p));
-#pragma unroll
-    for (int u = 0; u < 4; u++) { pts[8 + u] = make_float4(c[4 * u], c[4 * u + 1], c[4 * u + 2], c[4 * u + 3]); pts[12 + u] = make_float4(d[4 * u], d[4 * u + 1], d[4 * u + 2], d[4 * u + 3]); }
-  } else {
-    asm("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx16 %1, %2, 0x40\n\ts_waitcnt lgkmcnt(0)" : "=&s"(a), "=&s"(b) : "s"(p));
-  }
-#pragma unroll
-  for (int u = 0; u < 4; u++) { pts[u] = make_float4(a[4 * u], a[4 * u + 1], a[4 * u + 2], a[4 * u + 3]); pts[4 + u] = make_float4(b[4 * u], b[4 * u + 1], b[4 * u + 2], b[4 * u + 3]); }
-#else
+// ---- wave-uniform fetches ----------------------------------------------------------------------------------------------------------------
+// Node boxes and leaf points are fetched through wave-uniform addresses: one scalar load per 64 bytes per WAVE instead of a vector load per lane. The
+// compiler emits scalar loads only while it can prove that nothing in the kernel may have written memory before them. Hence THE CLOBBER RULE
+// (profiles/ANALYSIS.md, kernel notes): no store, atomic, fence, clock builtin or volatile asm may come ahead of the walk loop, nor on any path that
+// reaches it again. After one of them the leaf's 64 floats become vector loads: 64 more VGPRs, spills, a 5-10 x slower walk. Every kernel that walks
+// writes its results after the loop. (Loads written as inline asm are scalar whatever the kernel does, but cost the walk 2-3 %: DEAD_ENDS, round 4.)
+ROLO_DEV void sload_leaf(const float4* __restrict__ p, float4 (&pts)[KNN_LEAF]) {
 #pragma unroll
   for (int u = 0; u < KNN_LEAF; u++) pts[u] = p[u];
-#endif
 }
 // the two child boxes of node h: boxes[4h .. 4h + 3] = left lo, left hi, right lo, right hi (64 bytes)
-template <bool ASM>
-ROLO_DEV void sload_node(const float4* __restrict__ p_, float4& llo, float4& lhi, float4& rlo, float4& rhi) {
-  if (!ASM) { llo = p_[0]; lhi = p_[1]; rlo = p_[2]; rhi = p_[3]; return; }
-  const float4* p = uniform_ptr(p_);
-#if 1
-  sgpr16 a;
-  asm("s_load_dwordx16 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(a) : "s"(p));
-  llo = make_float4(a[0], a[1], a[2], a[3]); lhi = make_float4(a[4], a[5], a[6], a[7]); rlo = make_float4(a[8], a[9], a[10], a[11]); rhi = make_float4(a[12], a[13], a[14], a[15]);
-#else
-  llo = p[0]; lhi = p[1]; rlo = p[2]; rhi = p[3];
-#endif
-}
+ROLO_DEV void sload_node(const float4* __restrict__ p, float4& llo, float4& lhi, float4& rlo, float4& rhi) { llo = p[0]; lhi = p[1]; rlo = p[2]; rhi = p[3]; }
 
 // score the KNN_LEAF (16) points of leaf g against this lane's query and insert the ones that beat its current k-th best
-// CAP (continuation of a budgeted walk, below): the lane's list starts EMPTY but its bound does not — bkey never rises above bcap, the k-th best
-// of the list the first part of the walk left behind
-template <int KMAX, bool LOWER = false, bool CAP = false, bool ASM = false>
+template <int KMAX, bool LOWER = false>
 ROLO_DEV void knn_score_leaf(const float4* __restrict__ sorted, int g, const float4& q, double (&K)[KMAX], int kk, double& bkey, float& bd,
-                             unsigned& n_ins, unsigned& lane_acc, unsigned& rounds, double lo = 0.0, double bcap = 0.0) {
+                             unsigned& n_ins, unsigned& lane_acc, unsigned& rounds, double lo = 0.0) {
   // fetch the whole leaf first: the address is wave-uniform, so these are KNN_LEAF scalar loads in flight behind ONE wait
   // (loading inside the loop serialised the scalar-cache round trips of a leaf behind the insert branch)
   float4 pts[KNN_LEAF];
-  sload_leaf<ASM>(sorted + KNN_LEAF * (size_t)g, pts);
+  sload_leaf(sorted + KNN_LEAF * (size_t)g, pts);
   KNN_STAT(const double bkey0 = bkey; unsigned my_acc = 0;)   // accepted against the bound at leaf entry: what a per-lane queue would hold
 #ifdef ROLO_KNN_STATS2
   unsigned my_cur = 0;
@@ -167,7 +118,6 @@ ROLO_DEV void knn_score_leaf(const float4* __restrict__ sorted, int g, const flo
       insert_tiered<KMAX>(K, ck);
 #pragma unroll
       for (int s = 0; s < KMAX; s++) if (s == kk - 1) bkey = K[s];
-      if (CAP) bkey = vmin_f64(bkey, bcap);
       bd = key_d2(bkey);
     }
   }
@@ -232,25 +182,19 @@ ROLO_DEV int xcd_contiguous_block(int b, int G, int wpb = 4) {
 
 // ---- the packet walk proper --------------------------------------------------------------------------------------------------------------
 // One wavefront, 64 queries, from node h down; the far children wait on a small per-wave stack in LDS. Every control decision is wave-uniform.
-// PUBLISH (knn_walk_coop_kernel): once the walk has scored `budget` leaves, whenever everything it published before has been taken it moves the
-// BOTTOM entries of its stack — the oldest, i.e. the largest sub-trees — into a small ring in LDS where the idle wavefronts of its workgroup
-// steal them (work stealing: the owner works at the top of its stack, thieves take from the bottom).
 typedef __attribute__((address_space(3))) int lds_int;
-typedef __attribute__((address_space(3))) double lds_double;
-constexpr int COOP_RING = 16;
-struct CoopPub { lds_int* ring; lds_int* head; lds_int* tail; lds_double* cap; int budget; };   // head: entries published so far, tail: entries taken so far
 
-template <int KMAX, bool LOWER, bool CAP, bool PUBLISH, bool ASM>
+template <int KMAX, bool LOWER>
 ROLO_DEV void packet_walk(const float4* __restrict__ sorted, const float4* __restrict__ boxes, int P, int g_own0, int g_own1, const float4& q, double (&K)[KMAX], int kk,
-                          double& bkey, float& bd, double lo, double bcap, lds_int* stk, int& sp, int h, const CoopPub& pub, int& n_scored, int& n_published,
+                          double& bkey, float& bd, double lo, lds_int* stk, int& sp, int h,
                           unsigned& st_nodes, unsigned& st_leaves, unsigned& st_ins, unsigned& st_lane, unsigned& st_rounds, unsigned& st_push) {
-  (void)st_push; (void)pub; (void)n_scored; (void)n_published;
+  (void)st_push;
   while (true) {
     h = __builtin_amdgcn_readfirstlane(h);
     if (h < P) {
       st_nodes++;
       float4 llo, lhi, rlo, rhi;
-      sload_node<ASM>(boxes + 4 * (size_t)h, llo, lhi, rlo, rhi);
+      sload_node(boxes + 4 * (size_t)h, llo, lhi, rlo, rhi);
       const float bl = box_d2(llo, lhi, q), br = box_d2(rlo, rhi, q);
       const bool okl = (bl <= bd) && (bl < INFINITY), okr = (br <= bd) && (br < INFINITY);
       const unsigned long long ml = __ballot(okl), mr = __ballot(okr);
@@ -268,50 +212,14 @@ ROLO_DEV void packet_walk(const float4* __restrict__ sorted, const float4* __res
     } else {
       const int g = h - P;
       if (g < g_own0 || g >= g_own1) {   // (the wavefront's own leaves and their neighbours along the curve were scored as seeds)
-        knn_score_leaf<KMAX, LOWER, CAP, ASM>(sorted, g, q, K, kk, bkey, bd, st_ins, st_lane, st_rounds, lo, bcap);
+        knn_score_leaf<KMAX, LOWER>(sorted, g, q, K, kk, bkey, bd, st_ins, st_lane, st_rounds, lo);
         st_leaves++;
-        if (PUBLISH) n_scored++;
       }
     }
     if (sp == 0) return;
-    if (PUBLISH && n_scored >= pub.budget && sp >= 2) {
-      const int lane = threadIdx.x & 63;
-      const int hd = __builtin_amdgcn_readfirstlane(*pub.head);
-      const int tl = __builtin_amdgcn_readfirstlane(__hip_atomic_load((int*)pub.tail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-      if (hd == tl) {   // the ring is empty: hand out the bottom half of the stack (at most 4 entries), and the bound the thieves may prune with
-        const int m = min(sp >> 1, 4);
-        if (lane < m) pub.ring[(hd + lane) % COOP_RING] = stk[lane];
-        pub.cap[lane] = bkey;
-        const int keep = sp - m;
-        const int e = lane < keep ? stk[m + lane] : 0;
-        if (lane < keep) stk[lane] = e;
-        sp = keep;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        if (lane == 0) __hip_atomic_store((int*)pub.head, hd + m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        n_published += m;
-      }
-    }
     sp--;
     h = stk[sp];
   }
-}
-
-// a thief's (or the owner's own) take from the bottom ring of wavefront d: the oldest published sub-tree, or -1. Lane 0 acts for the wavefront.
-// The entry is read BEFORE the compare-and-swap on `tail`: slot t is only rewritten by its owner once tail has moved past t, so a successful swap proves the read was of entry t.
-ROLO_DEV int coop_steal(lds_int* ring, lds_int* head, lds_int* tail) {
-  int e = -1;
-  if ((threadIdx.x & 63) == 0) {
-    while (true) {
-      const int t = __hip_atomic_load((int*)tail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      const int hd = __hip_atomic_load((int*)head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      if (t >= hd) break;
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-      const int v = ring[t % COOP_RING];
-      int expect = t;
-      if (__hip_atomic_compare_exchange_strong((int*)tail, &expect, t + 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) { e = v; break; }
-    }
-  }
-  return __builtin_amdgcn_readfirstlane(e);
 }
 
 }  // namespace

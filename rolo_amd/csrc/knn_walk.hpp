@@ -20,7 +20,7 @@
 #else
 #define KNN_STAT(x)
 #endif
-#include "knn_packet.hpp"   // keys, sorted insert, explicit scalar loads, leaf scoring, the packet walk and its work-stealing hooks
+#include "knn_packet.hpp"   // keys, sorted insert, wave-uniform fetches, leaf scoring, the packet walk
 
 namespace rolo {
 namespace {
@@ -67,7 +67,7 @@ ROLO_DEV void walk_write_lists(const KnnCloud& cl, const double (&K)[KMAX], int 
 // Round 6: a finished query gathers its kk winners ONCE, right here, and leaves the six centred second moments of its neighbourhood (the oracle's order: mean first,
 // then the products summed over the list, rot_vgicp_impl.hpp:438-455) in cov[] — 48 B/pt that the tail finishes in place — instead of 80 B/pt of indices that the tail
 // read back and gathered through again (70 MB of fabric traffic for 6 MB of algorithmic bytes, 202 VGPRs: round 5's verdict, item 4). The light wavefronts do this while
-// the heavy ones still walk; it is the gather and ~250 fp64 instructions, not the SVD (the whole tail inside the walk lost: ROLO_KNN_FUSE_TAIL).
+// the heavy ones still walk; it is the gather and ~250 fp64 instructions, not the SVD (the whole tail inside the walk lost: DEAD_ENDS, round 6).
 template <int KMAX>
 ROLO_DEV void walk_write_moments(const KnnCloud& cl, const double (&K)[KMAX], int kk, int qi, int j, int (*s_ki)[256]) {
   if (cl.knn_idx) {   // the debug lists (rolo_get_knn)
@@ -115,19 +115,19 @@ static_assert(ROLO_KNN_PACKET == 64, "one query per lane");
 
 // the seeds of a packet: its own 64 / KNN_LEAF leaves first, then ROLO_KNN_SEED_EXTRA leaves on either side (the own points are the nearer ones, so
 // fewer keys are inserted only to be pushed out again: walk 0.1763 -> 0.1725 ms at 2 x 131 072 points, 0.1486 -> 0.1470 at 2 x 43 776)
-template <int KMAX, bool LOWER, bool ASM>
+template <int KMAX, bool LOWER>
 ROLO_DEV void walk_seeds(const float4* __restrict__ sorted, int g_mine0, int g_own0, int g_own1, int n_leaves, const float4& q, double (&K)[KMAX], int kk, double& bkey, float& bd, double lo,
                          unsigned& st_leaves, unsigned& st_ins, unsigned& st_lane, unsigned& st_rounds) {
   const int n_own = min(g_mine0 + 64 / KNN_LEAF, n_leaves) - g_mine0, n_before = g_mine0 - g_own0;
   for (int i = 0; i < g_own1 - g_own0; i++) {
     const int g = i < n_own ? g_mine0 + i : (i - n_own < n_before ? g_own0 + (i - n_own) : g_mine0 + (i - n_before));
-    knn_score_leaf<KMAX, LOWER, false, ASM>(sorted, g, q, K, kk, bkey, bd, st_ins, st_lane, st_rounds, lo);
+    knn_score_leaf<KMAX, LOWER>(sorted, g, q, K, kk, bkey, bd, st_ins, st_lane, st_rounds, lo);
     st_leaves++;
   }
 }
 
-template <int KMAX, bool FUSE_TAIL, bool LOWER = false, bool MOMENTS = false>
-__global__ __launch_bounds__(256, KMAX > 32 ? 2 : (MOMENTS ? 6 : ROLO_KNN_WALK_OCC)) void knn_walk_kernel(KnnPair A, int split, int k, int reg) {   // 64 slots = 128 key registers: 256 VGPRs, 2 waves per SIMD
+template <int KMAX, bool LOWER = false, bool MOMENTS = false>
+__global__ __launch_bounds__(256, KMAX > 32 ? 2 : (MOMENTS ? 6 : ROLO_KNN_WALK_OCC)) void knn_walk_kernel(KnnPair A, int split, int k) {   // 64 slots = 128 key registers: 256 VGPRs, 2 waves per SIMD
   __shared__ int stk[4][WALK_STACK];
   __shared__ int s_ki[MOMENTS ? KMAX : 1][256];   // MOMENTS: every lane's neighbour indices for the epilogue's loops (walk_write_moments)
   const int tid = threadIdx.x;
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256, KMAX > 32 ? 2 : (MOMENTS ? 6 : ROLO_KNN_WALK_O
   double lo = 0.0;
   if (LOWER && active) lo = A.c[which].lower[j];
   (void)lo;
-  walk_seeds<KMAX, LOWER, KNN_PLAIN_ASM>(sorted, g_mine0, g_own0, g_own1, n_leaves, q, K, kk, bkey, bd, lo, st_leaves, st_ins, st_lane, st_rounds);
+  walk_seeds<KMAX, LOWER>(sorted, g_mine0, g_own0, g_own1, n_leaves, q, K, kk, bkey, bd, lo, st_leaves, st_ins, st_lane, st_rounds);
 
   // ---- packet walk ----
   // (a stack in one vector register — slot i in lane i, v_writelane / v_readlane — measured the same as this LDS stack: 0.202 vs 0.200 ms;
@@ -176,8 +176,7 @@ __global__ __launch_bounds__(256, KMAX > 32 ? 2 : (MOMENTS ? 6 : ROLO_KNN_WALK_O
   unsigned long long wt0;
   asm("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)\n\ts_mov_b32 %1, 1" : "=s"(wt0), "=s"(h));
 #endif
-  { const CoopPub none{}; int n_scored = 0, n_pub = 0;
-    packet_walk<KMAX, LOWER, false, false, KNN_PLAIN_ASM>(sorted, boxes, P, g_own0, g_own1, q, K, kk, bkey, bd, lo, 0.0, (lds_int*)&stk[wv][0], sp, h, none, n_scored, n_pub, st_nodes, st_leaves, st_ins, st_lane, st_rounds, st_push); }
+  packet_walk<KMAX, LOWER>(sorted, boxes, P, g_own0, g_own1, q, K, kk, bkey, bd, lo, (lds_int*)&stk[wv][0], sp, h, st_nodes, st_leaves, st_ins, st_lane, st_rounds, st_push);
 #ifdef ROLO_KNN_STATS
   { unsigned long long wt1; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(wt1));
     unsigned st_rounds_rec = st_rounds;
@@ -198,27 +197,8 @@ __global__ __launch_bounds__(256, KMAX > 32 ? 2 : (MOMENTS ? 6 : ROLO_KNN_WALK_O
     walk_write_moments<KMAX>(A.c[which], K, kk, qi, j, s_ki);
     return;
   }
-  if (!FUSE_TAIL) {   // neighbour indices only (slot-major, coalesced): knn_tail_kernel turns them into covariances
-    walk_write_lists<KMAX>(A.c[which], K, kk, bkey, qi, j);
-    return;
-  }
-  // FUSE_TAIL (ROLO_KNN_FUSE_TAIL=1, an A/B): covariance + regularisation right here, so that the light wavefronts do theirs while the heavy
-  // ones are still walking and the 42 MB of index traffic disappear. Measured: 0.2335 ms against 0.1884 + 0.0394 ms for walk + tail launch,
-  // and the 4-context throughput falls from 2750 to 2490 scans/s — the tails' fp64 work competes with the walking wavefronts for issue slots.
-  const KnnCloud& cl = A.c[which];
-  int ki[KMAX];
-#pragma unroll
-  for (int u = 0; u < KMAX; u++) ki[u] = key_idx(K[u]);
-  if (cl.knn_idx) {
-#pragma unroll
-    for (int u = 0; u < KMAX; u++) if (u < kk) { cl.knn_idx[(size_t)qi * kk + u] = ki[u]; cl.knn_d2[(size_t)qi * kk + u] = key_d2(K[u]); }
-  }
-  if (cl.stage) {   // multi-GPU: into the exchange buffer, sorted order
-    double* o = stage_area(cl, 1) + (size_t)(j / cl.chunk) * cl.seg + cl.stage_off + (size_t)(j % cl.chunk) * 6;
-    double c6[6]; knn_covariance_tail<KMAX>(ki, kk, cl.xyz, 1, 0, reg, o, c6);
-  } else {
-    double c6[6]; knn_covariance_tail<KMAX>(ki, kk, cl.xyz, cl.n, qi, reg, cl.cov, c6, cl.nrm);
-  }
+  // neighbour indices only (slot-major, coalesced): knn_tail_kernel turns them into covariances
+  walk_write_lists<KMAX>(A.c[which], K, kk, bkey, qi, j);
 }
 
 // ---- four lanes per query (round 4): the walk of the SMALL clouds ------------------------------------------------------------------------------------
@@ -257,15 +237,8 @@ template <int ST> ROLO_DEV void merge20(double (&K)[20]) {
   }
 }
 
-// ROLO_KNN_WALK_MAXOCC (A/B builds): an upper bound on the wavefronts per SIMD the compiler allocates registers for — the way to keep wave slots free for
-// other contexts' kernels WITHOUT an LDS pad (which takes the CU's LDS away from them as well)
-#ifdef ROLO_KNN_WALK_MAXOCC
-#define ROLO_KNN_WALK_OCC_ATTR __attribute__((amdgpu_waves_per_eu(ROLO_KNN_WALK_MAXOCC, ROLO_KNN_WALK_MAXOCC)))
-#else
-#define ROLO_KNN_WALK_OCC_ATTR
-#endif
 template <int SUB, bool MOMENTS = false>
-__global__ __launch_bounds__(256, MOMENTS ? 6 : ROLO_KNN_WALK_OCC) ROLO_KNN_WALK_OCC_ATTR void knn_walk_sub_kernel(KnnPair A, int split /* first block of cloud 1 */) {
+__global__ __launch_bounds__(256, MOMENTS ? 6 : ROLO_KNN_WALK_OCC) void knn_walk_sub_kernel(KnnPair A, int split /* first block of cloud 1 */) {
   constexpr int SH = SUB == 2 ? 1 : 2, QPW = 64 / SUB, PPL = KNN_LEAF / SUB, KMAX = 20, E = 4 / SUB /* grandchild boxes per lane */, OWN = QPW / KNN_LEAF;
   static_assert(SUB == 2 || SUB == 4, "lanes per query");
   static_assert(KNN_LEAF == 16, "a wavefront's queries are whole leaves");
@@ -408,179 +381,6 @@ __global__ __launch_bounds__(256, MOMENTS ? 6 : ROLO_KNN_WALK_OCC) ROLO_KNN_WALK
 #pragma unroll
     for (int u = 0; u < KMAX; u++) { cl.knn_idx[(size_t)qi * KMAX + u] = key_idx(K[u]); cl.knn_d2[(size_t)qi * KMAX + u] = key_d2(K[u]); }
   }
-}
-
-// ---- the cooperative walk: a heavy packet's sub-trees are stolen by the idle wavefronts of its workgroup ------------------------------------------
-// The plain walk lasts as long as its heaviest packets: mean wavefront 78 us, p99 134 us, max 214 us of a 168 us kernel — packets whose 64
-// curve-adjacent queries lie on scattered fragments pay the SUM of what every lane needs, and no static quantity predicts them (DESIGN.md
-// sections 4, 9). Here a workgroup is NW wavefronts = NW packets (NW / 4 runs of four consecutive packets from distant stretches of the curve, the
-// mix a CU gets from the dispatcher under the plain kernel), and work moves between them through LDS:
-//   * every wavefront walks its own packet. Once it has scored `budget` leaves it is a donor: whenever the small ring it publishes to is empty it
-//     moves the bottom entries of its stack (the largest sub-trees) and its lanes' current bounds there, and goes on at the top of its stack;
-//   * a wavefront whose packet is done writes its lists and turns thief: it picks a donor of its workgroup, steals entries from that ring and walks
-//     them WITH THE DONOR'S 64 queries into a fresh, empty list whose bound is capped by the donor's published bound (CAP) — so it collects exactly
-//     the points of those sub-trees that beat that bound — until the donor is done, and leaves the list in an LDS result slot;
-//   * after a workgroup barrier every donor merges the result lists addressed to it into its own with the same min / max network and writes.
-// Exactness: stolen sub-trees are disjoint from each other and from everything the donor scores itself, every point of the final k beats every
-// bound ever published (bounds only tighten), so the k smallest of (donor's list + result lists) are the k smallest of the whole cloud: lists and
-// float distances stay bit-identical to the oracle's. LDS traffic is a few words per hand-over; nothing crosses workgroups (device-scope
-// atomics would: the XCDs' L2s are not coherent with each other without write-back / invalidate).
-// Measured and not kept: (1) TWO launches — budgeted walk + a continuation launch with eight wavefronts per unfinished packet: slower than the
-// plain walk at every budget (0.266 against 0.220 ms at 28 leaves; the second launch starts with cold L2s and thousands of empty workgroups);
-// (2) publishing the stack ONCE at the budget and popping from it: the donor itself walks the big entries it pops, the ring is empty by the
-// time anybody is free to help (0.217 against 0.223 ms).
-template <int NW> struct CoopCfg { static constexpr int NSLOT = NW == 16 ? 14 : (NW == 8 ? 7 : 3); };   // result slots of 10 KB: the workgroup's LDS share (160 KB per CU at 4 waves per SIMD)
-
-template <int NW>
-__global__ __launch_bounds__(64 * NW, ROLO_KNN_WALK_OCC) void knn_walk_coop_kernel(KnnPair A, int split4 /* first 4-packet block of cloud 1 */, int G4 /* 4-packet blocks */, int budget) {
-  constexpr int KMAX = 20, kk = 20, NSLOT = CoopCfg<NW>::NSLOT;
-  __shared__ int pstk[NW][WALK_STACK];     // private stacks
-  __shared__ int ring[NW][COOP_RING];      // published sub-trees
-  __shared__ double d_cap[NW][64];         // published bounds (the donor's k-th key per lane)
-  __shared__ double res[NSLOT][KMAX][64];  // result lists of thieves
-  __shared__ int r_head[NW], r_tail[NW], r_done[NW], d_j0[NW], d_which[NW];
-  __shared__ int res_owner[NSLOT];         // the donor a result list belongs to (-1: none)
-  __shared__ int n_res, n_p1;              // result slots handed out; wavefronts done with their own packet
-  const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), lane_ = tid & 63;   // (w in a scalar register: everything derived from it — cloud, tree, first query — stays wave-uniform for the compiler)
-  // this wavefront's packet: run k = w / 4 of the workgroup is 4-packet block (blockIdx.x + gridDim.x * k) of the plain walk's launch geometry
-  const int vb = (int)blockIdx.x + (int)gridDim.x * (w >> 2);
-  const int blk4 = vb < G4 ? xcd_contiguous_block(vb, G4, 4) : G4;
-  const int which = (blk4 >= split4 && A.n_clouds > 1) ? 1 : 0;
-  const KnnCloud& cl = A.c[which];
-  const int j0 = blk4 < G4 ? cl.q_begin + (blk4 - (which ? split4 : 0)) * 256 + (w & 3) * 64 : cl.q_end;
-  if (lane_ == 0) { r_head[w] = 0; r_tail[w] = 0; r_done[w] = 0; d_j0[w] = j0; d_which[w] = which; }
-  if (tid < NSLOT) res_owner[tid] = -1;
-  if (tid == 0) { n_res = 0; n_p1 = 0; }
-  __syncthreads();
-  const int j = j0 + lane_;
-  float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-  int qi = INT_MAX;
-  if (j < cl.q_end) { q = cl.sorted[j]; qi = __float_as_int(q.w); }
-  const bool active = qi != INT_MAX;
-  unsigned st_nodes = 0, st_leaves = 0, st_ins = 0, st_lane = 0, st_rounds = 0, st_push = 0;
-  const double sentinel = key_pack(INFINITY, INT_MAX);
-  double K[KMAX];
-#pragma unroll
-  for (int u = 0; u < KMAX; u++) K[u] = sentinel;
-  float bd = active ? INFINITY : -1.0f;
-  double bkey = active ? sentinel : key_pack(0.f, 0);
-#ifdef ROLO_KNN_STATS
-  unsigned long long ct0, ct1 = 0, ct2 = 0; unsigned c_sessions = 0, c_p1_leaves = 0, c_full = 0;
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ct0));
-#endif
-
-  // ---- the own packet ----
-  int n_published = 0;
-  {
-    const float4* __restrict__ sorted = cl.sorted;
-    const float4* __restrict__ boxes = cl.boxes;
-    const int P = cl.P, n_leaves = cl.n_sorted / KNN_LEAF;
-    const int g_mine0 = __builtin_amdgcn_readfirstlane(j0 / KNN_LEAF);
-    const int g_own0 = max(g_mine0 - ROLO_KNN_SEED_EXTRA, 0);
-    const int g_own1 = min(g_mine0 + 64 / KNN_LEAF + ROLO_KNN_SEED_EXTRA, n_leaves);
-    walk_seeds<KMAX, false, true>(sorted, g_mine0, g_own0, g_own1, n_leaves, q, K, kk, bkey, bd, 0.0, st_leaves, st_ins, st_lane, st_rounds);
-    const CoopPub pub{(lds_int*)&ring[w][0], (lds_int*)&r_head[w], (lds_int*)&r_tail[w], (lds_double*)&d_cap[w][0], budget};
-    int sp = 0, n_scored = 0, h = 1;
-    while (h >= 0) {   // the tree from the root, then whatever of the own published sub-trees nobody took
-      packet_walk<KMAX, false, false, true, true>(sorted, boxes, P, g_own0, g_own1, q, K, kk, bkey, bd, 0.0, 0.0, (lds_int*)&pstk[w][0], sp, h, pub, n_scored, n_published,
-                                            st_nodes, st_leaves, st_ins, st_lane, st_rounds, st_push);
-      h = n_published ? coop_steal(pub.ring, pub.head, pub.tail) : -1;
-    }
-    if (lane_ == 0) {
-      __hip_atomic_store(&r_done[w], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      __hip_atomic_fetch_add(&n_p1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    KNN_STAT(c_p1_leaves = st_leaves; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ct1));)
-  }
-  const bool donor = n_published > 0;
-  // a packet nobody helped with is final: its lists go out now, so that no list is live in registers while the wavefront helps
-  // (global stores before further walks are harmless: the tree fetches are explicit scalar loads)
-  if (!donor && active) walk_write_lists<KMAX>(cl, K, kk, bkey, qi, j);
-
-  // ---- thief: ONE donor per wavefront (its result list needs an LDS slot until the barrier); donors wait at the barrier, their lists stay in registers ----
-  while (!donor) {
-    int d = -1;
-    for (int o = 1; o < NW; o++) {
-      const int c = (w + o) % NW;
-      if (__hip_atomic_load(&r_head[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) > __hip_atomic_load(&r_tail[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) { d = c; break; }
-    }
-    d = __builtin_amdgcn_readfirstlane(d);
-    if (d < 0) {
-      if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&n_p1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) >= NW) break;   // nobody is left who could publish
-      __builtin_amdgcn_s_sleep(8);
-      continue;
-    }
-    int slot = 0;
-    if (lane_ == 0) slot = __hip_atomic_fetch_add(&n_res, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    slot = __builtin_amdgcn_readfirstlane(slot);
-    if (slot >= NSLOT) { KNN_STAT(c_full = 1;) break; }   // no room for another result list: the donors finish on their own
-    KNN_STAT(c_sessions++;)
-    // the donor's packet
-    const KnnCloud& dc = A.c[__builtin_amdgcn_readfirstlane(d_which[d])];
-    const float4* __restrict__ sorted = dc.sorted;
-    const float4* __restrict__ boxes = dc.boxes;
-    const int P = dc.P, n_leaves = dc.n_sorted / KNN_LEAF;
-    const int jd0 = __builtin_amdgcn_readfirstlane(d_j0[d]), jd = jd0 + lane_;
-    float4 qd = make_float4(0.f, 0.f, 0.f, 0.f);
-    bool act_d = false;
-    if (jd < dc.q_end) { qd = sorted[jd]; act_d = __float_as_int(qd.w) != INT_MAX; }
-    const int gd0 = __builtin_amdgcn_readfirstlane(jd0 / KNN_LEAF);
-    const int gd_own0 = max(gd0 - ROLO_KNN_SEED_EXTRA, 0), gd_own1 = min(gd0 + 64 / KNN_LEAF + ROLO_KNN_SEED_EXTRA, n_leaves);
-    double L[KMAX];
-#pragma unroll
-    for (int u = 0; u < KMAX; u++) L[u] = sentinel;
-    double bk = act_d ? sentinel : key_pack(0.f, 0);
-    float bdd = -1.0f;
-    const CoopPub none{};
-    while (true) {
-      const int e = coop_steal((lds_int*)&ring[d][0], (lds_int*)&r_head[d], (lds_int*)&r_tail[d]);
-      if (e < 0) {
-        if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&r_done[d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))) break;
-        __builtin_amdgcn_s_sleep(4);
-        continue;
-      }
-      const double cap = act_d ? d_cap[d][lane_] : key_pack(0.f, 0);   // the donor's bound as of its last hand-over: it only tightens
-      bk = vmin_f64(bk, cap);
-      bdd = act_d ? key_d2(bk) : -1.0f;
-      int sp = 0, ns = 0, np = 0;
-      packet_walk<KMAX, false, true, false, true>(sorted, boxes, P, gd_own0, gd_own1, qd, L, kk, bk, bdd, 0.0, cap, (lds_int*)&pstk[w][0], sp, e, none, ns, np,
-                                            st_nodes, st_leaves, st_ins, st_lane, st_rounds, st_push);
-    }
-#pragma unroll
-    for (int u = 0; u < KMAX; u++) res[slot][u][lane_] = L[u];
-    if (lane_ == 0) res_owner[slot] = d;
-    break;
-  }
-#ifdef ROLO_KNN_STATS
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ct2));
-  { const unsigned wid = blockIdx.x * NW + w;   // [0] nodes [1] leaves of the own packet [2] leaves scored as a thief [3] donor | entries published << 8 | sessions << 16 | slots full << 31
-    if (lane_ == 0 && wid < 16384) {            // [4] start [5] own packet done [6] stealing done (100 MHz) [7] -
-      g_knn_wave_rec[wid][0] = st_nodes; g_knn_wave_rec[wid][1] = c_p1_leaves; g_knn_wave_rec[wid][2] = st_leaves - c_p1_leaves;
-      g_knn_wave_rec[wid][3] = (donor ? 1u : 0u) | ((unsigned)min(n_published, 255) << 8) | (c_sessions << 16) | (c_full << 31);
-      g_knn_wave_rec[wid][4] = (unsigned)ct0; g_knn_wave_rec[wid][5] = (unsigned)ct1; g_knn_wave_rec[wid][6] = (unsigned)ct2; g_knn_wave_rec[wid][7] = 0;
-    } }
-#endif
-  (void)st_nodes; (void)st_leaves; (void)st_ins; (void)st_lane; (void)st_rounds; (void)st_push;
-  __syncthreads();
-
-  // ---- donors merge what the thieves found and write ----
-  if (!donor) return;
-  const int nr = min(n_res, NSLOT);
-  for (int s = 0; s < nr; s++) {
-    if (res_owner[s] != w) continue;
-    for (int u = 0; u < KMAX; u++) {   // ascending: once no lane's key beats its bound, none of the list's later keys will
-      const double ck = res[s][u][lane_];
-      if (!__any(ck < bkey)) break;
-      if (ck < bkey) {
-#pragma unroll
-        for (int t = KMAX - 1; t >= 1; t--) insert_slot(K[t], K[t - 1], ck);
-        K[0] = vmin_f64(ck, K[0]);
-        bkey = K[kk - 1];
-      }
-    }
-  }
-  if (!active) return;
-  walk_write_lists<KMAX>(cl, K, kk, bkey, qi, j);
 }
 
 #ifndef ROLO_KNN_TAIL_OCC

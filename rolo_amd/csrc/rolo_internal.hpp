@@ -201,15 +201,13 @@ size_t knn_sort_temp_bytes(int n_total);
 bool knn_voxel_fuse_supported();
 size_t knn_bbox_ints();   // ints of the bounding-box buffer: 12 for the final boxes of a pair + the partial boxes behind them
 constexpr int KNN_WALK_STACK = 48;
-// regularization >= 0: the walk ends in the covariance tail (A.c[].cov / the exchange buffer); -1: neighbour indices -> A.c[].nbr only
-// coop_budget > 0 (k = 20, own covariance launch): the cooperative walk — a packet that has scored that many leaves with sub-trees left publishes them to the
-// idle wavefronts of its workgroup (knn_walk.hpp); 0: the plain walk, every wavefront for itself
+// the exact k-nearest-neighbour walk: neighbour indices -> A.c[].nbr (slot-major), which launch_knn_tail turns into covariances
+// lanes_out: lanes per query of the walk the launch took (1: the 64-query packets)
 // device_busy: other contexts have frames in flight on this device — large launches then take the 64-query packets (half the wavefronts: shares the chip better) instead of two lanes per query (finishes sooner alone)
-// moments (k = 20, plain and sub-lane walks, regularization -1): the walk's epilogue leaves the six centred second moments of every query's neighbourhood in A.c[].cov
-// (SoA, by original index) instead of the neighbour indices in A.c[].nbr; launch_knn_tail(..., moments = true) finishes them in place
-hipError_t launch_knn_walk(const KnnPair& A, int k, int regularization_or_minus1, const VoxelFuse& vf, hipStream_t s, int coop_budget = 0, int* lanes_out = nullptr, bool device_busy = false,
-                           bool moments = false);
-hipError_t launch_knn_tail(const KnnPair& A, int k, int regularization, const VoxelFuse& vf, hipStream_t s, bool moments = false);   // covariances from A.c[].nbr (or from the moments in A.c[].cov)
+// moments (k = 20): the walk's epilogue leaves the six centred second moments of every query's neighbourhood in A.c[].nbr's scratch (by sorted position)
+// instead of the neighbour indices; launch_knn_tail(..., moments = true) finishes them
+hipError_t launch_knn_walk(const KnnPair& A, int k, hipStream_t s, int* lanes_out = nullptr, bool device_busy = false, bool moments = false);
+hipError_t launch_knn_tail(const KnnPair& A, int k, int regularization, const VoxelFuse& vf, hipStream_t s, bool moments = false);   // covariances from the neighbour indices (or the moments) in A.c[].nbr
 // multi-GPU: exchange buffer (sorted order, all ranks' slices after the all-gather, or [q_begin, q_end) only) -> cov[] by original index
 // vf.enabled: the target's points are accumulated into the voxel map by this scatter (sharded VoxelFuse)
 hipError_t launch_knn_unstage(const KnnPair& A, bool own_slice_only, const VoxelFuse& vf, hipStream_t s);

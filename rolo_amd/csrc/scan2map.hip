@@ -411,9 +411,8 @@ __global__ __launch_bounds__(256) void s2m_packet_kernel(S2mArgs A, int split /*
   double bkey = active ? sentinel : key_pack(0.f, 0);
   {
     unsigned s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0;
-    int sp = 0, ns = 0, np = 0;
-    const CoopPub none{};
-    packet_walk<5, false, false, false, false>(M.sorted, M.boxes, M.P, 0, 0, q, K, 5, bkey, bd, 0.0, 0.0, (lds_int*)&stk[wv][0], sp, 1, none, ns, np, s0, s1, s2, s3, s4, s5);
+    int sp = 0;
+    packet_walk<5, false>(M.sorted, M.boxes, M.P, 0, 0, q, K, 5, bkey, bd, 0.0, (lds_int*)&stk[wv][0], sp, 1, s0, s1, s2, s3, s4, s5);
   }
   bool sel = false;
   float4 coeff = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -572,7 +571,7 @@ __global__ __launch_bounds__(256) void s2m_sub_kernel(S2mArgs A, int split /* fi
       } else if (h < P) {
         n_nodes++;
         float4 llo, lhi, rlo, rhi;
-        sload_node<false>(boxes + 4 * (size_t)h, llo, lhi, rlo, rhi);
+        sload_node(boxes + 4 * (size_t)h, llo, lhi, rlo, rhi);
         const float bl = box_d2(llo, lhi, q), br = box_d2(rlo, rhi, q);
         const bool okl = (bl <= bd) && (bl < INFINITY), okr = (br <= bd) && (br < INFINITY);
         const unsigned long long ml = __ballot(okl), mr = __ballot(okr);

@@ -1106,11 +1106,11 @@ def test_ill_conditioned_normal_equations_match_the_pivoted_solve(optimizer):
     assert len(tg) == len(to) and [r["accepted"] for r in tg] == [r["accepted"] for r in to]
 
 
-def _coop_walk_main():
-    """body of test_cooperative_walk_lists_bit_exact (own process: ROLO_KNN_BUDGET is read once per process)"""
+def _walk_lists_main():
+    """body of test_both_walk_kernels_lists_bit_exact (own process: ROLO_KNN_SUB is read once per process)"""
     out = []
     cases = [("os1-128", 1, None), ("os1-128", 1, synth.pool_origin(4)), ("os1-64", 1, None), ("os1-128", 3, None), ("vlp16", 1, None)]
-    for sensor, stride, origin in cases:   # 16, 16, 8 and 4 wavefronts per workgroup; pool pair 4 holds the heaviest packets of the bench's pool
+    for sensor, stride, origin in cases:   # pool pair 4 holds the heaviest packets of the bench's pool
         src, tgt, _ = synth.dense_pair(sensor, col_stride=stride, origin=origin)
         g = RotVGICP(); g.setResolution(0.5)
         g.setInputTarget(tgt); g.setInputSource(src)
@@ -1121,36 +1121,22 @@ def _coop_walk_main():
         o = pyorc.Reg(pyorc.default_params(voxel_type=1, voxel_resolution=0.5)); o.set_target(tgt); o.set_source(src); o.compute_covariances()
         out.append((sensor, stride, "covs", bool(np.abs(g.getSourceCovariances() - o.source_covs()).max() < 1e-9), bool(np.abs(g.getTargetCovariances() - o.target_covs()).max() < 1e-9)))
         g.close()
-    print("COOP", out)
+    print("LISTS", out)
     assert all(a and b for *_, a, b in out), out
-
-
-@pytest.mark.parametrize("budget", [6, 24])
-def test_cooperative_walk_lists_bit_exact(budget):
-    """knn_walk_coop_kernel (ROLO_KNN_BUDGET > 0, an opt-in: measured no faster than the plain walk) — a heavy packet's sub-trees stolen by the idle
-    wavefronts of its workgroup, walked into fresh lists under the donor's published bound and merged after a barrier: neighbour lists and float
-    distances bit-identical to the oracle's at every workgroup shape (4 / 8 / 16 packets), with an early budget (most packets donate) and a late one."""
-    import subprocess, sys, os
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, ROLO_KNN_BUDGET=str(budget))
-    r = subprocess.run([sys.executable, "-c", "import sys; sys.path.insert(0, %r); from tests.test_gpu_registration import _coop_walk_main; _coop_walk_main()" % root],
-                       env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "COOP" in r.stdout
 
 
 @pytest.mark.parametrize("sub", [0, 1, 2])
 def test_both_walk_kernels_lists_bit_exact(sub):
     """launch_knn_walk picks the k = 20 walk by size: 16 queries x 4 lanes per wavefront for small clouds (knn_walk_sub_kernel: per-sub-lane lists under a shared
     bound, two tree levels per step, merged at the end), 64-query packets for large ones. ROLO_KNN_SUB forces one or the other: both must give the oracle's
-    neighbour lists and float distances bit for bit at every size (the cases of the cooperative walk's test: 131 072, a heavy pool pair, 65 536, 43 776, 28 800)."""
+    neighbour lists and float distances bit for bit at every size (131 072, a heavy pool pair, 65 536, 43 776, 28 800 points per cloud)."""
     import subprocess, sys, os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, ROLO_KNN_SUB=str(sub)); env.pop("ROLO_KNN_BUDGET", None)
-    r = subprocess.run([sys.executable, "-c", "import sys; sys.path.insert(0, %r); from tests.test_gpu_registration import _coop_walk_main; _coop_walk_main()" % root],
+    env = dict(os.environ, ROLO_KNN_SUB=str(sub))
+    r = subprocess.run([sys.executable, "-c", "import sys; sys.path.insert(0, %r); from tests.test_gpu_registration import _walk_lists_main; _walk_lists_main()" % root],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "COOP" in r.stdout
+    assert "LISTS" in r.stdout
 
 
 @pytest.mark.parametrize("sub", [0, 2])
