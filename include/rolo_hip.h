@@ -426,6 +426,45 @@ int rolo_scan2map_optimize(rolo_ctx* ctx, const float* corner, int n_corner, con
                            const float* map_surf, int m_surf, float* transformTobeMapped6, int edge_min, int surf_min, rolo_scan2map_stats* stats,
                            unsigned char* selected_out, float* coeff_out);
 
+/* ---- back end: device-resident key frames and sub-map assembly ---------------------------------------------------------------------
+ * What the back end does before scan2MapOptimization, on the device: the key frames' corner / surface clouds (n x 4 floats: x, y, z, intensity) and their
+ * poses (transformTobeMapped order: roll, pitch, yaw, x, y, z) stay in a rolo_keymap; rolo_keymap_extract fuses the listed ones into the two sub-maps
+ * (transformPointCloud + pcl::VoxelGrid) and rolo_scan2map_set_submap_keymap hands them to the registration without a host round trip.
+ * The voxel filter is bit-identical to pcl::VoxelGrid<PointXYZI> as the oracle states it (cells in ascending index order, each centroid's float sums
+ * taken serially in point order); a cloud of up to ROLO_KEYMAP_MAX_POINTS points per call; "leaf size too small" (more than INT32_MAX cells) copies the
+ * input through as PCL does; a non-finite coordinate is ROLO_ENONFINITE. transformPointCloud evaluates each row as T0 x + (T1 y + (T2 z + T3)) in float
+ * without contraction — the order of the oracle's orc_transform_cloud_f (PCL's own transformPointCloud), which the tests hold it to; src/backMapping.cpp:314-316
+ * writes the same sum left to right, which can differ in the last bit of a coordinate.
+ * A key map is single-threaded like a context and works on a stream of its own; its store and scratch only grow until rolo_keymap_destroy. */
+#define ROLO_KEYMAP_MAX_POINTS (1 << 26)   /* largest cloud one filter call / one fused sub-map cloud may hold (67 108 864 points) */
+typedef struct rolo_keymap rolo_keymap;
+int rolo_keymap_create(int device, rolo_keymap** out);
+void rolo_keymap_destroy(rolo_keymap* km);
+/* saveKeyFramesAndFactor (src/backMapping.cpp:1140-1181): cornerCloudKeyFrames / surfCloudKeyFrames .push_back and cloudKeyPoses6D.push_back; returns the key frame's index (>= 0) */
+int rolo_keymap_add_keyframe(rolo_keymap* km, const float* corner, int n_corner, const float* surf, int n_surf, const float* pose6, double time);
+/* correctPoses (:1301-1314): a key frame's pose after a graph update; the next extraction uses it (nothing transformed is cached) */
+int rolo_keymap_set_pose(rolo_keymap* km, int index, const float* pose6);
+int rolo_keymap_size(rolo_keymap* km);
+/* extractNearby (:575-614) with extractCloud's range filter (:626), host only (no device needed): the key frames extractCloud would fuse, in its order.
+ * xyz: n x 3 key-pose positions, times: their stamps. Radius search around the LAST pose (squared float distance below search_radius^2, ordered by
+ * (distance, index)), VoxelGrid at `density` on those poses, each down-sampled pose re-indexed to its nearest key pose (lowest index on ties), then from the
+ * newest backwards every pose with time_cur - time < recent_seconds (10.0 in the reference); entries whose listed position (the centroid, for down-sampled
+ * ones) is farther than search_radius from the last pose are dropped. Returns the number of entries (duplicates are possible and meant) and writes the
+ * first min(count, cap) of them. Parity unpinned: the strict "<" and the (distance, index) tie order restate FLANN's radius result set from its source as
+ * remembered, not from a recorded vector. */
+int rolo_keyposes_select_nearby(const float* xyz, const double* times, int n, float search_radius, float density, double time_cur, double recent_seconds,
+                                int32_t* out_indices, int cap);
+/* extractCloud (:617-658): for the listed key frames in list order (a duplicate's clouds go in twice), *transformPointCloud (:301-320) of the corner and
+ * the surface cloud, concatenated, downSizeFilterCorner / downSizeFilterSurf (mappingCornerLeafSize 0.2 / mappingSurfLeafSize 0.4). The two sub-maps stay
+ * on the device; m_corner / m_surf receive their sizes. */
+int rolo_keymap_extract(rolo_keymap* km, const int32_t* indices, int n, float corner_leaf, float surf_leaf, int* m_corner, int* m_surf);
+/* download of the last extraction's sub-maps (laserCloudCornerFromMapDS / laserCloudSurfFromMapDS); caps in points */
+int rolo_keymap_get_submap(rolo_keymap* km, float* corner_out, int cap_corner, float* surf_out, int cap_surf);
+/* downsampleCurrentScan (:666-678) for one cloud, also usable alone: out holds up to n points, *m receives the count */
+int rolo_keymap_downsample(rolo_keymap* km, const float* pts, int n, float leaf, float* out, int* m);
+/* kdtree*FromMap->setInputCloud (:690-691) without the host round trip: rolo_scan2map_set_submap on the key map's last extraction (same device) */
+int rolo_scan2map_set_submap_keymap(rolo_ctx* ctx, rolo_keymap* km);
+
 #ifdef __cplusplus
 }
 #endif

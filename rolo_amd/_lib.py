@@ -128,6 +128,16 @@ SYMBOLS = {
     "rolo_scan2map_optimize": (C.c_int, [vp, fp, C.c_int, fp, C.c_int, fp, C.c_int, fp, C.c_int, fp, C.c_int, C.c_int, C.POINTER(Scan2MapStats),
                                           C.POINTER(C.c_ubyte), fp]),
     "rolo_scan2map_set_submap": (C.c_int, [vp, fp, C.c_int, fp, C.c_int]),
+    "rolo_scan2map_set_submap_keymap": (C.c_int, [vp, vp]),
+    "rolo_keymap_create": (C.c_int, [C.c_int, C.POINTER(vp)]),
+    "rolo_keymap_destroy": (None, [vp]),
+    "rolo_keymap_add_keyframe": (C.c_int, [vp, fp, C.c_int, fp, C.c_int, fp, C.c_double]),
+    "rolo_keymap_set_pose": (C.c_int, [vp, C.c_int, fp]),
+    "rolo_keymap_size": (C.c_int, [vp]),
+    "rolo_keyposes_select_nearby": (C.c_int, [fp, dp, C.c_int, C.c_float, C.c_float, C.c_double, C.c_double, ip, C.c_int]),
+    "rolo_keymap_extract": (C.c_int, [vp, ip, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rolo_keymap_get_submap": (C.c_int, [vp, fp, C.c_int, fp, C.c_int]),
+    "rolo_keymap_downsample": (C.c_int, [vp, fp, C.c_int, C.c_float, fp, C.POINTER(C.c_int)]),
     "rolo_num_voxels": (C.c_int, [vp]),
     "rolo_num_edge_points": (C.c_int, [vp]),
     "rolo_get_voxels": (C.c_int, [vp, ip, ip, dp, dp]),

@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librolo_hip.so")
-SOURCES = ["api.hip", "knn_cov.hip", "voxelmap.hip", "passes.hip", "misc.hip", "front.hip", "odometry.hip", "fusion.hip", "scan2map.hip", "peer.hip"]
+SOURCES = ["api.hip", "knn_cov.hip", "voxelmap.hip", "passes.hip", "misc.hip", "front.hip", "odometry.hip", "fusion.hip", "scan2map.hip", "submap.hip", "peer.hip"]
 HEADERS = ["rolo_internal.hpp", "dev_math.hpp", "voxel_dev.hpp", "knn_walk.hpp", "knn_packet.hpp", "polar_exact.hpp", "polar_exact_consts.hpp", "peer_dev.hpp", "polar_f32.hpp", "lm_begin.hpp", "load_learner.hpp", os.path.join("..", "..", "include", "rolo_hip.h"),
            os.path.join("..", "..", "include", "rolo_fusion.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -23,7 +23,8 @@ FLAGS = os.environ.get("ROLO_EXTRA_FLAGS", "").split() + ["--offload-arch=gfx950
 # float32 paths whose results must be bit-identical to the CPU statement (kNN distances and their pruning bounds,
 # pcl::transformPointCloud, range-image projection, curvature): no FMA contraction (HIP's __fmul_rn/__fadd_rn are
 # plain operators that the compiler is otherwise free to fuse)
-EXTRA = {"knn_cov.hip": ["-ffp-contract=off"], "scan2map.hip": ["-ffp-contract=off"], "misc.hip": ["-ffp-contract=off"], "front.hip": ["-ffp-contract=off"]}
+EXTRA = {"knn_cov.hip": ["-ffp-contract=off"], "scan2map.hip": ["-ffp-contract=off"], "misc.hip": ["-ffp-contract=off"], "front.hip": ["-ffp-contract=off"],
+         "submap.hip": ["-ffp-contract=off"]}
 # (front.hip was built at -O2 through round 3: hipcc 7.2 -O3 died in the backend — "Illegal instruction detected: Operand has incorrect register class" — on the
 # round-1 form of extract_kernel's serial greedy walk; that function was rewritten in rounds 2-3 and the file has compiled at -O3 since: profiles/tools/README.md)
 

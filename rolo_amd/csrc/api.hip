@@ -714,11 +714,12 @@ int ctx_set_pair_device(rolo_ctx* c, const float* d_src, int n_src, int stride_s
   c->cloud_epoch++;
   return ROLO_OK;
 }
-// scan2map.hip: the two sub-map clouds (corner, surface) as the context's source / target with their search trees built
-int ctx_build_map_trees(rolo_ctx* c, const float* corner, int nc, const float* surf, int ns, int stride, KnnPair* out) {
+// scan2map.hip: the two sub-map clouds (corner, surface) as the context's source / target with their search trees built.
+// on_device: the clouds are device memory already (the key map's sub-maps: rolo_scan2map_set_submap_keymap); the caller has ordered c->stream behind their producer
+int ctx_build_map_trees(rolo_ctx* c, const float* corner, int nc, const float* surf, int ns, int stride, KnnPair* out, bool on_device) {
   int rc = set_device(c); if (rc) return rc;
-  if ((rc = upload_cloud(c, c->src, c->src_xyz_cap, corner, nc, stride, false))) return rc;
-  if ((rc = upload_cloud(c, c->tgt, c->tgt_xyz_cap, surf, ns, stride, false))) return rc;
+  if ((rc = upload_cloud(c, c->src, c->src_xyz_cap, corner, nc, stride, on_device))) return rc;
+  if ((rc = upload_cloud(c, c->tgt, c->tgt_xyz_cap, surf, ns, stride, on_device))) return rc;
   c->have_map = false; c->have_corr = false;
   return build_clouds(c, true, true, c->stream, true, out);
 }

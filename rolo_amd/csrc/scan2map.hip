@@ -25,7 +25,9 @@
 #include <vector>
 
 namespace rolo {
-int ctx_build_map_trees(rolo_ctx* c, const float* corner, int nc, const float* surf, int ns, int stride, KnnPair* out);
+int ctx_build_map_trees(rolo_ctx* c, const float* corner, int nc, const float* surf, int ns, int stride, KnnPair* out, bool on_device = false);
+int keymap_device_submap(rolo_keymap* km, const float** d_corner, int* m_corner, const float** d_surf, int* m_surf, hipEvent_t* ready, hipEvent_t* consumed, int* device);   // submap.hip
+void keymap_mark_consumed(rolo_keymap* km);
 extern "C" int rolo_ctx_acquire(int device, rolo_ctx** out);
 extern "C" void rolo_ctx_release(rolo_ctx* c);
 hipStream_t ctx_stream(rolo_ctx* c);
@@ -763,6 +765,32 @@ extern "C" int rolo_scan2map_set_submap(rolo_ctx* c, const float* map_corner, in
   if (m_corner < 5 || m_surf < 5) { W->map_set = true; W->m_corner = m_corner; W->m_surf = m_surf; return ROLO_OK; }   // nothing a 5-NN query could be answered from: rolo_scan2map_optimize reports skipped = 2
   KnnPair built{};
   const int rc = ctx_build_map_trees(c, map_corner, m_corner, map_surf, m_surf, 4, &built);
+  if (rc) return rc;
+  W->maps = built; W->m_corner = m_corner; W->m_surf = m_surf; W->maps_epoch = ctx_cloud_epoch(c);
+  W->have_maps = true; W->map_set = true;
+  return ROLO_OK;
+}
+
+// the same from a key map's last extraction (rolo_keymap_extract): the context's stream waits for the key map's, packs the two device clouds into its source /
+// target and builds the trees — the state rolo_scan2map_set_submap leaves, without the download and upload in between
+extern "C" int rolo_scan2map_set_submap_keymap(rolo_ctx* c, rolo_keymap* km) {
+  if (!c || !km) return ROLO_EINVAL;
+  const float *d_corner = nullptr, *d_surf = nullptr;
+  int m_corner = 0, m_surf = 0, device = -1;
+  hipEvent_t ready = nullptr, consumed = nullptr;
+  int rc = keymap_device_submap(km, &d_corner, &m_corner, &d_surf, &m_surf, &ready, &consumed, &device);
+  if (rc) return rc;
+  if (device != ctx_device(c)) { ctx_set_error("rolo_scan2map_set_submap_keymap: the key map lives on another device"); return ROLO_EINVAL; }
+  S2mScratch* W = static_cast<S2mScratch*>(*ctx_s2m_slot(c));
+  if (!W) { W = new S2mScratch(); *ctx_s2m_slot(c) = W; }
+  W->have_maps = false; W->map_set = false; W->m_corner = 0; W->m_surf = 0;
+  if (m_corner < 5 || m_surf < 5) { W->map_set = true; W->m_corner = m_corner; W->m_surf = m_surf; return ROLO_OK; }
+  SCHK(hipStreamWaitEvent(ctx_stream(c), ready, 0));
+  KnnPair built{};
+  rc = ctx_build_map_trees(c, d_corner, m_corner, d_surf, m_surf, 4, &built, true);
+  // the key map may overwrite its sub-map only after this context has read it (also after a failed build: the pack may be in flight)
+  SCHK(hipEventRecord(consumed, ctx_stream(c)));
+  keymap_mark_consumed(km);
   if (rc) return rc;
   W->maps = built; W->m_corner = m_corner; W->m_surf = m_surf; W->maps_epoch = ctx_cloud_epoch(c);
   W->have_maps = true; W->map_set = true;

@@ -1,0 +1,688 @@
+// The back end's sub-map assembly on gfx950: a device-resident key-frame store (rolo_keymap_*), extractCloud and pcl::VoxelGrid for clouds of any size.
+// Replaces (reference src/backMapping.cpp) extractNearby :575-614 (rolo_keyposes_select_nearby, host), extractCloud :617-658 with transformPointCloud :301-320
+// (rolo_keymap_extract), downsampleCurrentScan :666-678 (rolo_keymap_downsample) and the key-frame bookkeeping of saveKeyFramesAndFactor :1140-1181 /
+// correctPoses :1287-1320 (rolo_keymap_add_keyframe / rolo_keymap_set_pose).
+//
+// pcl::VoxelGrid<PointXYZI>::filter, bit-identical to the oracle's orc_voxelgrid (oracle/rolo_oracle_front.cpp): float min / max of the cloud, the integer
+// cell index as written there, cells in ascending index order, and per cell the four float sums taken SERIALLY IN ORIGINAL POINT ORDER, divided by the float
+// count. Float addition is not associative: a cell's sum is never split into partial sums and never made with atomics. Every point is stored once under its
+// cell by a STABLE sort of (cell, point index), then one lane per cell walks its points:
+//   vg_box_kernel / vg_box_final_kernel   min / max (exact in any order) and the non-finite flag -> host (div_b, min_b, the "too many cells" copy-through)
+//   vg_key_kernel                         the cell index of every point (at most 31 bits; 32 with the sign flipped if div_b's product wraps, as the int does)
+//   sort_hist / sort_scan / sort_scatter  LSD radix sort, 8 bits per pass, only the passes the largest index needs; stable: ranks by wavefront match, in point order
+//   run_heads_kernel<0>, scan_excl, <1>   a cell starts where the sorted index changes; the scan gives its output slot and the number of cells
+//   vg_runsum_kernel                      one lane per cell: the serial sums through the sorted point indices, the division, the output record
+// A clumped cell is one long serial chain in one lane; the summation order is the contract, so it stays that way.
+//
+// transformPointCloud: the oracle's float statement p0 + (p1 + (p2 + c3)) per row (orc_transform_cloud_f, the parity target of the tests), no contraction.
+#include "rolo_internal.hpp"
+#include <algorithm>
+#include <array>
+#include <cfloat>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace rolo {
+void ctx_set_error(const char* msg);
+
+namespace {
+
+constexpr int SM_THREADS = 256;
+constexpr int SORT_ITEMS = 16;                         // keys per lane of a sort tile
+constexpr int SORT_TILE = SM_THREADS * SORT_ITEMS;     // 4096 keys per workgroup, 1024 per wavefront
+constexpr int RUN_ITEMS = 4;
+constexpr int RUN_TILE = SM_THREADS * RUN_ITEMS;
+constexpr int BOX_BLOCKS_MAX = 1024;
+constexpr int KM_MAX_POINTS = ROLO_KEYMAP_MAX_POINTS;
+constexpr size_t CHUNK_POINTS = 1u << 20;              // the store grows in chunks of 16 MiB (or one cloud, if larger): nothing is ever moved or freed
+
+struct Seg { const float4* src; int n; int dst; float T[12]; };   // one key frame's cloud in the concatenation
+
+// *cloudOut = T * cloudIn of every listed key frame, written at its place in the concatenation (list order); intensity copied
+__global__ __launch_bounds__(SM_THREADS) void km_transform_kernel(const Seg* __restrict__ segs, float4* __restrict__ out) {
+  const Seg s = segs[blockIdx.y];
+  for (int i = blockIdx.x * SM_THREADS + threadIdx.x; i < s.n; i += gridDim.x * SM_THREADS) {
+    const float4 p = s.src[i];
+    float4 o;
+    o.x = s.T[0] * p.x + (s.T[1] * p.y + (s.T[2] * p.z + s.T[3]));
+    o.y = s.T[4] * p.x + (s.T[5] * p.y + (s.T[6] * p.z + s.T[7]));
+    o.z = s.T[8] * p.x + (s.T[9] * p.y + (s.T[10] * p.z + s.T[11]));
+    o.w = p.w;
+    out[(size_t)s.dst + i] = o;
+  }
+}
+
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+  return v;
+}
+
+// min / max of x, y, z and "a coordinate is not finite", per workgroup: part[8 * block + (0..2 min, 3..5 max, 6 flag)]
+__global__ __launch_bounds__(SM_THREADS) void vg_box_kernel(const float4* __restrict__ pts, int n, float* __restrict__ part) {
+  __shared__ float red[SM_THREADS / 64][8];
+  float v[7] = {FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX, 0.f};
+  for (int i = blockIdx.x * SM_THREADS + threadIdx.x; i < n; i += gridDim.x * SM_THREADS) {
+    const float4 p = pts[i];
+    if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) v[6] = 1.f;
+    v[0] = fminf(v[0], p.x); v[1] = fminf(v[1], p.y); v[2] = fminf(v[2], p.z);
+    v[3] = fmaxf(v[3], p.x); v[4] = fmaxf(v[4], p.y); v[5] = fmaxf(v[5], p.z);
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 7; k++) { const float r = k < 3 ? wave_min(v[k]) : wave_max(v[k]); if (lane == 0) red[wv][k] = r; }
+  __syncthreads();
+  if (threadIdx.x < 7) {
+    const int k = threadIdx.x;
+    float r = red[0][k];
+    for (int w = 1; w < SM_THREADS / 64; w++) r = k < 3 ? fminf(r, red[w][k]) : fmaxf(r, red[w][k]);
+    part[8 * (size_t)blockIdx.x + k] = r;
+  }
+}
+// the workgroups' rows -> out[0..6] (pinned host memory)
+__global__ __launch_bounds__(SM_THREADS) void vg_box_final_kernel(const float* __restrict__ part, int nparts, float* __restrict__ out) {
+  __shared__ float red[SM_THREADS / 64][8];
+  float v[7] = {FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX, 0.f};
+  for (int b = threadIdx.x; b < nparts; b += SM_THREADS) {
+#pragma unroll
+    for (int k = 0; k < 7; k++) { const float x = part[8 * (size_t)b + k]; v[k] = k < 3 ? fminf(v[k], x) : fmaxf(v[k], x); }
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 7; k++) { const float r = k < 3 ? wave_min(v[k]) : wave_max(v[k]); if (lane == 0) red[wv][k] = r; }
+  __syncthreads();
+  if (threadIdx.x < 7) {
+    const int k = threadIdx.x;
+    float r = red[0][k];
+    for (int w = 1; w < SM_THREADS / 64; w++) r = k < 3 ? fminf(r, red[w][k]) : fmaxf(r, red[w][k]);
+    out[k] = r;
+  }
+}
+
+struct VgGrid { float inv; int min_b[3]; unsigned mul[3]; unsigned flip; };
+
+// ijk = floor(p * inv) - min_b; idx = ijk0 * 1 + ijk1 * div_b0 + ijk2 * div_b0 * div_b1 (VoxelGrid::applyFilter), in wrapping 32-bit arithmetic
+__global__ __launch_bounds__(SM_THREADS) void vg_key_kernel(const float4* __restrict__ pts, int n, VgGrid G, unsigned* __restrict__ keys, int* __restrict__ vals) {
+  const int i = blockIdx.x * SM_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const float4 p = pts[i];
+  const int i0 = (int)floorf(p.x * G.inv) - G.min_b[0], i1 = (int)floorf(p.y * G.inv) - G.min_b[1], i2 = (int)floorf(p.z * G.inv) - G.min_b[2];
+  keys[i] = ((unsigned)i0 * G.mul[0] + (unsigned)i1 * G.mul[1] + (unsigned)i2 * G.mul[2]) ^ G.flip;
+  vals[i] = i;
+}
+
+// ---- stable LSD radix sort of (cell, point index), 8 bits per pass ---------------------------------------------------------------------------------------
+// digit counts of every tile: hist[digit * nblocks + block] (digit-major: its exclusive scan is where each tile's keys of each digit go)
+__global__ __launch_bounds__(SM_THREADS) void sort_hist_kernel(const unsigned* __restrict__ keys, int n, int shift, unsigned* __restrict__ hist, int nblocks,
+                                                               unsigned* __restrict__ dtot /* 256, zeroed: keys per digit */) {
+  __shared__ unsigned h[256];
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  const int base = blockIdx.x * SORT_TILE;
+#pragma unroll
+  for (int k = 0; k < SORT_ITEMS; k++) {
+    const int i = base + k * SM_THREADS + threadIdx.x;
+    if (i < n) atomicAdd(&h[(keys[i] >> shift) & 255u], 1u);   // integer counts: exact in any order
+  }
+  __syncthreads();
+  hist[(size_t)threadIdx.x * nblocks + blockIdx.x] = h[threadIdx.x];
+  if (h[threadIdx.x]) atomicAdd(&dtot[threadIdx.x], h[threadIdx.x]);
+}
+
+// exclusive scan of the digit-major table, one workgroup per digit: the keys of the digits below (dtot), then along the digit's row of tile counts
+__global__ __launch_bounds__(SM_THREADS) void sort_scan_kernel(unsigned* __restrict__ hist, int nblocks, const unsigned* __restrict__ dtot) {
+  __shared__ unsigned wsum[SM_THREADS / 64];
+  const int d = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  auto block_incl = [&](unsigned x, unsigned& total) {   // inclusive scan over the workgroup
+    unsigned incl = x;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const unsigned o = __shfl_up(incl, off, 64); if (lane >= off) incl += o; }
+    __syncthreads();   // wsum of the previous use has been read
+    if (lane == 63) wsum[wv] = incl;
+    __syncthreads();
+    unsigned before = 0; total = 0;
+#pragma unroll
+    for (int w = 0; w < SM_THREADS / 64; w++) { const unsigned t = wsum[w]; if (w < wv) before += t; total += t; }
+    return before + incl;
+  };
+  unsigned running;
+  block_incl((int)threadIdx.x < d ? dtot[threadIdx.x] : 0u, running);
+  unsigned* row = hist + (size_t)d * nblocks;
+  for (int b0 = 0; b0 < nblocks; b0 += SM_THREADS) {
+    const int i = b0 + threadIdx.x;
+    const unsigned x = i < nblocks ? row[i] : 0u;
+    unsigned total;
+    const unsigned incl = block_incl(x, total);
+    if (i < nblocks) row[i] = running + incl - x;
+    running += total;
+  }
+}
+
+// exclusive scan of a[0 .. N) in place by ONE workgroup; the total goes to total_dev / total_host when given
+__global__ __launch_bounds__(1024) void scan_excl_kernel(unsigned* __restrict__ a, int N, int* __restrict__ total_dev, int* __restrict__ total_host) {
+  __shared__ unsigned wsum[16];
+  const int chunk = (N + 1023) / 1024;
+  const int lo = min((int)threadIdx.x * chunk, N), hi = min(lo + chunk, N);
+  unsigned s = 0;
+  for (int i = lo; i < hi; i++) s += a[i];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  unsigned incl = s;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) { const unsigned o = __shfl_up(incl, off, 64); if (lane >= off) incl += o; }
+  if (lane == 63) wsum[wv] = incl;
+  __syncthreads();
+  unsigned before = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < 16; w++) { const unsigned x = wsum[w]; if (w < wv) before += x; total += x; }
+  unsigned run = before + incl - s;
+  for (int i = lo; i < hi; i++) { const unsigned t = a[i]; a[i] = run; run += t; }
+  if (threadIdx.x == 0) { if (total_dev) *total_dev = (int)total; if (total_host) *total_host = (int)total; }
+}
+
+// A wavefront takes 1024 consecutive keys in 16 rounds of 64, lane = position: a key's rank among the keys of its digit is the wavefront's running count of that
+// digit plus the number of lower lanes of this round that hold the same digit (eight ballots). Then digit d of wavefront w of tile b starts at
+// scanned hist[d][b] + the counts of the wavefronts before w: rounds, lanes, wavefronts and tiles all follow the input order, so the pass is stable.
+__global__ __launch_bounds__(SM_THREADS) void sort_scatter_kernel(const unsigned* __restrict__ kin, const int* __restrict__ vin, unsigned* __restrict__ kout,
+                                                                  int* __restrict__ vout, int n, int shift, const unsigned* __restrict__ hist, int nblocks) {
+  __shared__ unsigned cnt_[SM_THREADS / 64][256];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int w = 0; w < SM_THREADS / 64; w++) cnt_[w][threadIdx.x] = 0;
+  __syncthreads();
+  volatile unsigned* cnt = cnt_[wv];
+  const int base = blockIdx.x * SORT_TILE + wv * (64 * SORT_ITEMS);
+  unsigned key[SORT_ITEMS], rank[SORT_ITEMS];
+#pragma unroll
+  for (int r = 0; r < SORT_ITEMS; r++) {
+    const int i = base + r * 64 + lane;
+    const bool valid = i < n;
+    key[r] = valid ? kin[i] : 0xffffffffu;
+    const unsigned d = (key[r] >> shift) & 255u;
+    unsigned long long m = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < 8; b++) { const bool bit = (d >> b) & 1u; const unsigned long long bal = __ballot(bit); m &= bit ? bal : ~bal; }
+    const unsigned below = (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+    const unsigned prev = cnt[d];
+    __builtin_amdgcn_wave_barrier();
+    if (valid && below == 0) cnt[d] = prev + (unsigned)__popcll(m);   // the first lane of each digit of this round
+    __builtin_amdgcn_wave_barrier();
+    rank[r] = prev + below;
+  }
+  __syncthreads();
+  {   // thread = digit: where each wavefront's keys of this digit start
+    const int d = threadIdx.x;
+    unsigned g = hist[(size_t)d * nblocks + blockIdx.x];
+#pragma unroll
+    for (int w = 0; w < SM_THREADS / 64; w++) { const unsigned c = cnt_[w][d]; cnt_[w][d] = g; g += c; }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < SORT_ITEMS; r++) {
+    const int i = base + r * 64 + lane;
+    if (i < n) {
+      const unsigned pos = cnt_[wv][(key[r] >> shift) & 255u] + rank[r];   // < n: the scanned counts of all n keys
+      kout[pos] = key[r];
+      vout[pos] = vin[i];
+    }
+  }
+}
+
+// a cell starts at sorted position i when i = 0 or the index differs from its predecessor's. WRITE = 0: heads per tile -> bcnt[block];
+// WRITE = 1 (bcnt scanned): starts[slot] = i for every head
+template <int WRITE>
+__global__ __launch_bounds__(SM_THREADS) void run_heads_kernel(const unsigned* __restrict__ keys, int n, unsigned* __restrict__ bcnt, int* __restrict__ starts) {
+  __shared__ unsigned wsum[SM_THREADS / 64];
+  const int i0 = blockIdx.x * RUN_TILE + threadIdx.x * RUN_ITEMS;
+  bool head[RUN_ITEMS];
+  unsigned c = 0;
+  unsigned prev = (i0 > 0 && i0 - 1 < n) ? keys[i0 - 1] : 0u;
+#pragma unroll
+  for (int k = 0; k < RUN_ITEMS; k++) {
+    const int i = i0 + k;
+    const unsigned cur = i < n ? keys[i] : 0u;
+    head[k] = i < n && (i == 0 || cur != prev);
+    c += head[k] ? 1u : 0u;
+    prev = cur;
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  unsigned incl = c;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) { const unsigned o = __shfl_up(incl, off, 64); if (lane >= off) incl += o; }
+  if (lane == 63) wsum[wv] = incl;
+  __syncthreads();
+  unsigned before = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < SM_THREADS / 64; w++) { const unsigned x = wsum[w]; if (w < wv) before += x; total += x; }
+  if (!WRITE) { if (threadIdx.x == 0) bcnt[blockIdx.x] = total; return; }
+  unsigned pos = bcnt[blockIdx.x] + before + incl - c;   // < number of heads <= n
+#pragma unroll
+  for (int k = 0; k < RUN_ITEMS; k++) if (head[k]) starts[pos++] = i0 + k;
+}
+
+// one lane per cell: the centroid's four float sums in original point order (the stable sort keeps a cell's points in that order), then / float(count)
+__global__ __launch_bounds__(SM_THREADS) void vg_runsum_kernel(const float4* __restrict__ pts, const int* __restrict__ idx, const int* __restrict__ starts,
+                                                               const int* __restrict__ m_ptr, int n, float4* __restrict__ out) {
+  const int r = blockIdx.x * SM_THREADS + threadIdx.x;
+  const int m = *m_ptr;
+  if (r >= m) return;
+  const int s = starts[r], e = r + 1 < m ? starts[r + 1] : n;
+  float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;
+  for (int j = s; j < e; j++) { const float4 p = pts[idx[j]]; sx += p.x; sy += p.y; sz += p.z; si += p.w; }
+  const float cnt = (float)(e - s);
+  out[r] = make_float4(sx / cnt, sy / cnt, sz / cnt, si / cnt);
+}
+
+// ---- host restatement of the same filter (the key poses of extractNearby: a few hundred points) ------------------------------------------------------------
+int host_voxelgrid(const std::vector<std::array<float, 4>>& in, float leaf, std::vector<std::array<float, 4>>& out) {
+  out.clear();
+  const int n = (int)in.size();
+  if (n == 0) return 0;
+  const float inv = 1.0f / leaf;
+  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+  for (const auto& p : in) for (int d = 0; d < 3; d++) { mn[d] = std::min(mn[d], p[d]); mx[d] = std::max(mx[d], p[d]); }
+  long long ext[3];
+  for (int d = 0; d < 3; d++) { const float e = (mx[d] - mn[d]) * inv; ext[d] = e < 4e18f ? (long long)e + 1 : (long long)INT32_MAX + 1; }
+  if (ext[0] > INT32_MAX || ext[1] > INT32_MAX || ext[0] * ext[1] > INT32_MAX || ext[0] * ext[1] * ext[2] > INT32_MAX) { out = in; return n; }
+  int lo[3], div[3];
+  for (int d = 0; d < 3; d++) { lo[d] = (int)std::floor(mn[d] * inv); div[d] = (int)std::floor(mx[d] * inv) - lo[d] + 1; }
+  std::vector<std::pair<int, int>> cell(n);
+  for (int i = 0; i < n; i++) {
+    int c[3];
+    for (int d = 0; d < 3; d++) c[d] = (int)std::floor(in[i][d] * inv) - lo[d];
+    cell[i] = {(int)((unsigned)c[0] + (unsigned)c[1] * (unsigned)div[0] + (unsigned)c[2] * ((unsigned)div[0] * (unsigned)div[1])), i};
+  }
+  std::sort(cell.begin(), cell.end());
+  for (int a = 0; a < n;) {
+    int b = a;
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    while (b < n && cell[b].first == cell[a].first) { for (int d = 0; d < 4; d++) s[d] += in[cell[b].second][d]; b++; }
+    const float cnt = (float)(b - a);
+    out.push_back({s[0] / cnt, s[1] / cnt, s[2] / cnt, s[3] / cnt});
+    a = b;
+  }
+  return (int)out.size();
+}
+
+// pcl::getTransformation(x, y, z, roll, pitch, yaw) in float (pcl/common/impl/eigen.hpp), rows 0..2
+void pose_to_T(const float* pose6 /* roll pitch yaw x y z */, float* T) {
+  const float A = std::cos(pose6[2]), B = std::sin(pose6[2]), C = std::cos(pose6[1]), D = std::sin(pose6[1]), E = std::cos(pose6[0]), F = std::sin(pose6[0]);
+  const float DE = D * E, DF = D * F;
+  T[0] = A * C; T[1] = A * DF - B * E; T[2] = B * F + A * DE; T[3] = pose6[3];
+  T[4] = B * C; T[5] = A * E + B * DF; T[6] = B * DE - A * F; T[7] = pose6[4];
+  T[8] = -D; T[9] = C * F; T[10] = C * E; T[11] = pose6[5];
+}
+
+}  // namespace
+}  // namespace rolo
+
+using namespace rolo;
+
+#define KCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { ctx_set_error((std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); return ROLO_EHIP; } } while (0)
+
+struct rolo_keymap {
+  int device = 0;
+  hipStream_t stream = nullptr;      // a stream of its own: assembling a sub-map never queues behind a registration
+  hipEvent_t ready = nullptr;        // recorded after every extraction: what a consumer's stream waits for
+  hipEvent_t consumed = nullptr;     // recorded by the last consumer (rolo_scan2map_set_submap_keymap) after it has read the sub-map
+  bool consumer_pending = false;
+  // the store: chunks that are never moved or freed before rolo_keymap_destroy
+  struct Chunk { float4* p; size_t cap, used; };
+  std::vector<Chunk> chunks;
+  struct Frame { const float4* pts[2]; int n[2]; float pose[6]; double time; };
+  std::vector<Frame> frames;
+  // scratch and results: they only grow
+  float4* cat[2] = {nullptr, nullptr}; size_t cat_cap[2] = {0, 0};       // the concatenated, transformed clouds (corner, surface); cat[0] also stages rolo_keymap_downsample's input
+  float4* sub[2] = {nullptr, nullptr}; size_t sub_cap[2] = {0, 0};       // the sub-map (laserCloud*FromMapDS)
+  float4* ds_out = nullptr; size_t ds_cap = 0;                           // rolo_keymap_downsample's result
+  unsigned* keys[2] = {nullptr, nullptr}; size_t keys_cap[2] = {0, 0};
+  int* vals[2] = {nullptr, nullptr}; size_t vals_cap[2] = {0, 0};
+  unsigned* hist = nullptr; size_t hist_cap = 0;
+  unsigned* dtot = nullptr; size_t dtot_cap = 0;   // [4 passes][256 digits]
+  unsigned* bcnt = nullptr; size_t bcnt_cap = 0;
+  int* starts = nullptr; size_t starts_cap = 0;
+  float* box_part = nullptr; size_t box_part_cap = 0;
+  Seg* segs = nullptr; size_t segs_cap = 0;
+  int* d_m = nullptr;                // [2]
+  float* h_box = nullptr;            // pinned [2][8]
+  int* h_m = nullptr;                // pinned [2]
+  Seg* h_segs = nullptr; size_t h_segs_cap = 0;   // pinned staging of the segment table
+  std::vector<void*> retired, retired_host;   // outgrown scratch buffers (device, pinned host), freed by rolo_keymap_destroy
+  int m_sub[2] = {0, 0};
+  bool have_submap = false;
+};
+
+namespace {
+
+// elements; scratch only grows, and an outgrown buffer is kept until rolo_keymap_destroy: a hipFree is a device-wide synchronisation that would stall the frames
+// other contexts have in flight (scan2map.hip), and work queued on the key map's stream may still read the old buffer. Sizes grow by half: the retired ones
+// together stay below twice the live one.
+template <typename T>
+int km_grow(rolo_keymap* km, T*& p, size_t& cap, size_t need) {
+  if (need <= cap && p) return ROLO_OK;
+  if (p) { km->retired.push_back(p); p = nullptr; cap = 0; }
+  const size_t want = need + need / 2 + 256;
+  if (hipMalloc((void**)&p, want * sizeof(T)) != hipSuccess) { ctx_set_error("hipMalloc failed (keymap)"); return ROLO_EHIP; }
+  cap = want;
+  return ROLO_OK;
+}
+
+int km_sort_scratch(rolo_keymap* km, int n) {
+  const int nblocks = (n + SORT_TILE - 1) / SORT_TILE, nrun = (n + RUN_TILE - 1) / RUN_TILE;
+  int rc;
+  for (int b = 0; b < 2; b++) {
+    if ((rc = km_grow(km, km->keys[b], km->keys_cap[b], (size_t)n))) return rc;
+    if ((rc = km_grow(km, km->vals[b], km->vals_cap[b], (size_t)n))) return rc;
+  }
+  if ((rc = km_grow(km, km->hist, km->hist_cap, 256 * (size_t)nblocks))) return rc;
+  if ((rc = km_grow(km, km->dtot, km->dtot_cap, (size_t)4 * 256))) return rc;
+  if ((rc = km_grow(km, km->bcnt, km->bcnt_cap, (size_t)nrun))) return rc;
+  if ((rc = km_grow(km, km->starts, km->starts_cap, (size_t)n))) return rc;
+  if ((rc = km_grow(km, km->box_part, km->box_part_cap, 2 * 8 * (size_t)BOX_BLOCKS_MAX))) return rc;
+  return ROLO_OK;
+}
+
+// first half of the filter: the cloud's box into h_box[slot] (valid after the stream has been waited for)
+int vg_enqueue_box(rolo_keymap* km, const float4* pts, int n, int slot) {
+  if (n <= 0) return ROLO_OK;
+  const int blocks = std::min((n + SM_THREADS - 1) / SM_THREADS, BOX_BLOCKS_MAX);
+  vg_box_kernel<<<blocks, SM_THREADS, 0, km->stream>>>(pts, n, km->box_part + 8 * (size_t)BOX_BLOCKS_MAX * slot);
+  KCHK(hipGetLastError());
+  vg_box_final_kernel<<<1, SM_THREADS, 0, km->stream>>>(km->box_part + 8 * (size_t)BOX_BLOCKS_MAX * slot, blocks, km->h_box + 8 * slot);
+  KCHK(hipGetLastError());
+  return ROLO_OK;
+}
+
+// second half: keys, sort, cells, centroids into out; the number of cells lands in h_m[slot] (valid after the stream has been waited for).
+// *direct: the result is known without the device (n = 0, or PCL's "leaf size is too small": the input copied through)
+int vg_enqueue_filter(rolo_keymap* km, const float4* pts, int n, float leaf, int slot, float4* out, bool* direct, int* m_direct) {
+  *direct = false;
+  if (n <= 0) { *direct = true; *m_direct = 0; return ROLO_OK; }
+  const float* hb = km->h_box + 8 * slot;
+  if (hb[6] != 0.f) { ctx_set_error("a non-finite coordinate reached the voxel grid filter"); return ROLO_ENONFINITE; }
+  const float inv = 1.0f / leaf;
+  long long ext[3];
+  for (int d = 0; d < 3; d++) { const float e = (hb[3 + d] - hb[d]) * inv; ext[d] = e < 4e18f ? (long long)e + 1 : (long long)INT32_MAX + 1; }
+  if (ext[0] > INT32_MAX || ext[1] > INT32_MAX || ext[0] * ext[1] > INT32_MAX || ext[0] * ext[1] * ext[2] > INT32_MAX) {
+    KCHK(hipMemcpyAsync(out, pts, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, km->stream));
+    *direct = true; *m_direct = n;
+    return ROLO_OK;
+  }
+  VgGrid G{};
+  G.inv = inv;
+  int div[3];
+  for (int d = 0; d < 3; d++) { G.min_b[d] = (int)std::floor(hb[d] * inv); div[d] = (int)std::floor(hb[3 + d] * inv) - G.min_b[d] + 1; }
+  G.mul[0] = 1u; G.mul[1] = (unsigned)div[0]; G.mul[2] = (unsigned)div[0] * (unsigned)div[1];
+  const long long cells = (long long)div[0] * div[1] * div[2];
+  int bits = 32;
+  if (cells <= (long long)INT32_MAX) { bits = 1; while (bits < 31 && (1ll << bits) < cells) bits++; G.flip = 0u; }
+  else G.flip = 0x80000000u;   // div_b's product wraps the int (the extents' product did not): signed order through the flipped sign bit
+  hipStream_t s = km->stream;
+  const int nblocks = (n + SORT_TILE - 1) / SORT_TILE, nrun = (n + RUN_TILE - 1) / RUN_TILE;
+  vg_key_kernel<<<(n + SM_THREADS - 1) / SM_THREADS, SM_THREADS, 0, s>>>(pts, n, G, km->keys[0], km->vals[0]);
+  KCHK(hipGetLastError());
+  int cur = 0;
+  KCHK(hipMemsetAsync(km->dtot, 0, sizeof(unsigned) * 4 * 256, s));
+  for (int shift = 0; shift < bits; shift += 8) {
+    unsigned* dtot = km->dtot + 256 * (shift / 8);
+    sort_hist_kernel<<<nblocks, SM_THREADS, 0, s>>>(km->keys[cur], n, shift, km->hist, nblocks, dtot);
+    KCHK(hipGetLastError());
+    sort_scan_kernel<<<256, SM_THREADS, 0, s>>>(km->hist, nblocks, dtot);
+    KCHK(hipGetLastError());
+    sort_scatter_kernel<<<nblocks, SM_THREADS, 0, s>>>(km->keys[cur], km->vals[cur], km->keys[cur ^ 1], km->vals[cur ^ 1], n, shift, km->hist, nblocks);
+    KCHK(hipGetLastError());
+    cur ^= 1;
+  }
+  run_heads_kernel<0><<<nrun, SM_THREADS, 0, s>>>(km->keys[cur], n, km->bcnt, km->starts);
+  KCHK(hipGetLastError());
+  scan_excl_kernel<<<1, 1024, 0, s>>>(km->bcnt, nrun, km->d_m + slot, km->h_m + slot);
+  KCHK(hipGetLastError());
+  run_heads_kernel<1><<<nrun, SM_THREADS, 0, s>>>(km->keys[cur], n, km->bcnt, km->starts);
+  KCHK(hipGetLastError());
+  vg_runsum_kernel<<<(n + SM_THREADS - 1) / SM_THREADS, SM_THREADS, 0, s>>>(pts, km->vals[cur], km->starts, km->d_m + slot, n, out);
+  KCHK(hipGetLastError());
+  return ROLO_OK;
+}
+
+int km_alloc_points(rolo_keymap* km, size_t n, float4** out) {
+  *out = nullptr;
+  if (n == 0) return ROLO_OK;
+  if (km->chunks.empty() || km->chunks.back().cap - km->chunks.back().used < n) {
+    rolo_keymap::Chunk c{nullptr, std::max(CHUNK_POINTS, n), 0};
+    if (hipMalloc((void**)&c.p, c.cap * sizeof(float4)) != hipSuccess) { ctx_set_error("hipMalloc failed (key-frame store)"); return ROLO_EHIP; }
+    km->chunks.push_back(c);
+  }
+  rolo_keymap::Chunk& c = km->chunks.back();
+  *out = c.p + c.used;
+  c.used += n;
+  return ROLO_OK;
+}
+
+}  // namespace
+
+namespace rolo {
+// scan2map.hip: the resident sub-map as device clouds (n x 4 floats), the event a reader's stream waits for and the one it records when it has read them
+int keymap_device_submap(rolo_keymap* km, const float** d_corner, int* m_corner, const float** d_surf, int* m_surf, hipEvent_t* ready, hipEvent_t* consumed, int* device) {
+  if (!km->have_submap) { ctx_set_error("the key map holds no sub-map: call rolo_keymap_extract first"); return ROLO_ESTATE; }
+  *d_corner = reinterpret_cast<const float*>(km->sub[0]); *m_corner = km->m_sub[0];
+  *d_surf = reinterpret_cast<const float*>(km->sub[1]); *m_surf = km->m_sub[1];
+  *ready = km->ready; *consumed = km->consumed; *device = km->device;
+  return ROLO_OK;
+}
+void keymap_mark_consumed(rolo_keymap* km) { km->consumer_pending = true; }
+}  // namespace rolo
+
+extern "C" {
+
+int rolo_keymap_create(int device, rolo_keymap** out) {
+  if (!out) return ROLO_EINVAL;
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { ctx_set_error("no HIP device"); return ROLO_EHIP; }
+  if (device < 0 || device >= ndev) return ROLO_EINVAL;
+  KCHK(hipSetDevice(device));
+  rolo_keymap* km = new rolo_keymap();
+  km->device = device;
+  hipError_t e = hipStreamCreateWithFlags(&km->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&km->ready, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&km->consumed, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&km->h_box, sizeof(float) * 16);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&km->h_m, sizeof(int) * 2);
+  if (e == hipSuccess) e = hipMalloc((void**)&km->d_m, sizeof(int) * 2);
+  if (e != hipSuccess) { ctx_set_error((std::string("rolo_keymap_create: ") + hipGetErrorString(e)).c_str()); rolo_keymap_destroy(km); return ROLO_EHIP; }
+  *out = km;
+  return ROLO_OK;
+}
+
+void rolo_keymap_destroy(rolo_keymap* km) {
+  if (!km) return;
+  (void)hipSetDevice(km->device);
+  if (km->stream) (void)hipStreamSynchronize(km->stream);
+  if (km->consumer_pending && km->consumed) (void)hipEventSynchronize(km->consumed);
+  for (auto& c : km->chunks) (void)hipFree(c.p);
+  for (void* p : km->retired) (void)hipFree(p);
+  for (void* p : km->retired_host) (void)hipHostFree(p);
+  for (void* p : {(void*)km->cat[0], (void*)km->cat[1], (void*)km->sub[0], (void*)km->sub[1], (void*)km->ds_out, (void*)km->keys[0], (void*)km->keys[1], (void*)km->vals[0],
+                  (void*)km->vals[1], (void*)km->hist, (void*)km->dtot, (void*)km->bcnt, (void*)km->starts, (void*)km->box_part, (void*)km->segs, (void*)km->d_m})
+    if (p) (void)hipFree(p);
+  for (void* p : {(void*)km->h_box, (void*)km->h_m, (void*)km->h_segs}) if (p) (void)hipHostFree(p);
+  if (km->ready) (void)hipEventDestroy(km->ready);
+  if (km->consumed) (void)hipEventDestroy(km->consumed);
+  if (km->stream) (void)hipStreamDestroy(km->stream);
+  delete km;
+}
+
+int rolo_keymap_size(rolo_keymap* km) { return km ? (int)km->frames.size() : ROLO_EINVAL; }
+
+int rolo_keymap_add_keyframe(rolo_keymap* km, const float* corner, int n_corner, const float* surf, int n_surf, const float* pose6, double time) {
+  if (!km || !pose6 || n_corner < 0 || n_surf < 0 || (n_corner && !corner) || (n_surf && !surf) || n_corner > KM_MAX_POINTS || n_surf > KM_MAX_POINTS) return ROLO_EINVAL;
+  if (km->frames.size() >= (size_t)INT_MAX) return ROLO_EINVAL;
+  KCHK(hipSetDevice(km->device));
+  rolo_keymap::Frame f{};
+  const float* src[2] = {corner, surf};
+  const int n[2] = {n_corner, n_surf};
+  for (int t = 0; t < 2; t++) {
+    float4* d = nullptr;
+    const int rc = km_alloc_points(km, (size_t)n[t], &d);
+    if (rc) return rc;
+    if (n[t]) KCHK(hipMemcpyAsync(d, src[t], sizeof(float4) * (size_t)n[t], hipMemcpyHostToDevice, km->stream));
+    f.pts[t] = d; f.n[t] = n[t];
+  }
+  KCHK(hipStreamSynchronize(km->stream));   // the caller's arrays are free again
+  std::memcpy(f.pose, pose6, sizeof(f.pose));
+  f.time = time;
+  km->frames.push_back(f);
+  return (int)km->frames.size() - 1;
+}
+
+int rolo_keymap_set_pose(rolo_keymap* km, int index, const float* pose6) {
+  if (!km || !pose6 || index < 0 || index >= (int)km->frames.size()) return ROLO_EINVAL;
+  std::memcpy(km->frames[index].pose, pose6, sizeof(float) * 6);
+  return ROLO_OK;
+}
+
+int rolo_keymap_extract(rolo_keymap* km, const int32_t* indices, int n, float corner_leaf, float surf_leaf, int* m_corner, int* m_surf) {
+  if (!km || n < 0 || (n && !indices) || !(corner_leaf > 0.f) || !(surf_leaf > 0.f)) return ROLO_EINVAL;
+  long long total[2] = {0, 0};
+  int nseg[2] = {0, 0}, max_n = 1;
+  for (int i = 0; i < n; i++) {
+    if (indices[i] < 0 || indices[i] >= (int)km->frames.size()) { ctx_set_error("rolo_keymap_extract: key-frame index out of range"); return ROLO_EINVAL; }
+    for (int t = 0; t < 2; t++) { const int c = km->frames[indices[i]].n[t]; total[t] += c; if (c) nseg[t]++; max_n = std::max(max_n, c); }
+  }
+  if (total[0] > KM_MAX_POINTS || total[1] > KM_MAX_POINTS) { ctx_set_error("rolo_keymap_extract: more than ROLO_KEYMAP_MAX_POINTS points in one fused cloud"); return ROLO_EINVAL; }
+  KCHK(hipSetDevice(km->device));
+  hipStream_t s = km->stream;
+  if (km->consumer_pending) { KCHK(hipStreamWaitEvent(s, km->consumed, 0)); km->consumer_pending = false; }   // the last reader of the sub-map this call overwrites
+  km->have_submap = false;
+  int rc;
+  const int nmax = (int)std::max(total[0], total[1]);
+  if (nmax > 0 && (rc = km_sort_scratch(km, nmax))) return rc;
+  const size_t nsegs = (size_t)nseg[0] + nseg[1];
+  if (nsegs) {
+    if (nsegs > km->h_segs_cap) {
+      if (km->h_segs) { km->retired_host.push_back(km->h_segs); km->h_segs = nullptr; km->h_segs_cap = 0; }
+      const size_t want = nsegs + nsegs / 2 + 64;
+      KCHK(hipHostMalloc((void**)&km->h_segs, want * sizeof(Seg)));
+      km->h_segs_cap = want;
+    }
+    if ((rc = km_grow(km, km->segs, km->segs_cap, nsegs))) return rc;
+  }
+  for (int t = 0; t < 2; t++) {
+    if ((rc = km_grow(km, km->cat[t], km->cat_cap[t], (size_t)std::max<long long>(total[t], 1)))) return rc;
+    if ((rc = km_grow(km, km->sub[t], km->sub_cap[t], (size_t)std::max<long long>(total[t], 1)))) return rc;
+  }
+  // the segment table: corner segments, then surface segments, each in list order
+  size_t k = 0;
+  for (int t = 0; t < 2; t++) {
+    int dst = 0;
+    for (int i = 0; i < n; i++) {
+      const rolo_keymap::Frame& f = km->frames[indices[i]];
+      if (!f.n[t]) continue;
+      Seg& g = km->h_segs[k++];
+      g.src = f.pts[t]; g.n = f.n[t]; g.dst = dst;
+      pose_to_T(f.pose, g.T);
+      dst += f.n[t];
+    }
+  }
+  if (nsegs) KCHK(hipMemcpyAsync(km->segs, km->h_segs, nsegs * sizeof(Seg), hipMemcpyHostToDevice, s));
+  const int gx = std::min((max_n + SM_THREADS - 1) / SM_THREADS, 128);
+  for (int t = 0; t < 2; t++) {
+    const Seg* base = km->segs + (t ? nseg[0] : 0);
+    for (int y0 = 0; y0 < nseg[t]; y0 += 32768) {
+      km_transform_kernel<<<dim3(gx, std::min(nseg[t] - y0, 32768)), SM_THREADS, 0, s>>>(base + y0, km->cat[t]);
+      KCHK(hipGetLastError());
+    }
+    if ((rc = vg_enqueue_box(km, km->cat[t], (int)total[t], t))) return rc;
+  }
+  KCHK(hipStreamSynchronize(s));
+  bool direct[2]; int m_direct[2] = {0, 0};
+  const float leaf[2] = {corner_leaf, surf_leaf};
+  for (int t = 0; t < 2; t++)
+    if ((rc = vg_enqueue_filter(km, km->cat[t], (int)total[t], leaf[t], t, km->sub[t], &direct[t], &m_direct[t]))) return rc;
+  KCHK(hipEventRecord(km->ready, s));
+  KCHK(hipStreamSynchronize(s));
+  for (int t = 0; t < 2; t++) km->m_sub[t] = direct[t] ? m_direct[t] : km->h_m[t];
+  km->have_submap = true;
+  if (m_corner) *m_corner = km->m_sub[0];
+  if (m_surf) *m_surf = km->m_sub[1];
+  return ROLO_OK;
+}
+
+int rolo_keymap_get_submap(rolo_keymap* km, float* corner_out, int cap_corner, float* surf_out, int cap_surf) {
+  if (!km || cap_corner < 0 || cap_surf < 0) return ROLO_EINVAL;
+  if (!km->have_submap) { ctx_set_error("the key map holds no sub-map: call rolo_keymap_extract first"); return ROLO_ESTATE; }
+  if (km->m_sub[0] > cap_corner || km->m_sub[1] > cap_surf || (km->m_sub[0] && !corner_out) || (km->m_sub[1] && !surf_out)) return ROLO_EINVAL;
+  KCHK(hipSetDevice(km->device));
+  if (km->m_sub[0]) KCHK(hipMemcpyAsync(corner_out, km->sub[0], sizeof(float4) * (size_t)km->m_sub[0], hipMemcpyDeviceToHost, km->stream));
+  if (km->m_sub[1]) KCHK(hipMemcpyAsync(surf_out, km->sub[1], sizeof(float4) * (size_t)km->m_sub[1], hipMemcpyDeviceToHost, km->stream));
+  KCHK(hipStreamSynchronize(km->stream));
+  return ROLO_OK;
+}
+
+int rolo_keymap_downsample(rolo_keymap* km, const float* pts, int n, float leaf, float* out, int* m) {
+  if (!km || !m || n < 0 || (n && (!pts || !out)) || !(leaf > 0.f) || n > KM_MAX_POINTS) return ROLO_EINVAL;
+  *m = 0;
+  if (n == 0) return ROLO_OK;
+  KCHK(hipSetDevice(km->device));
+  hipStream_t s = km->stream;
+  int rc;
+  if ((rc = km_sort_scratch(km, n))) return rc;
+  if ((rc = km_grow(km, km->cat[0], km->cat_cap[0], (size_t)n))) return rc;
+  if ((rc = km_grow(km, km->ds_out, km->ds_cap, (size_t)n))) return rc;
+  KCHK(hipMemcpyAsync(km->cat[0], pts, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, s));
+  if ((rc = vg_enqueue_box(km, km->cat[0], n, 0))) return rc;
+  KCHK(hipStreamSynchronize(s));
+  bool direct; int m_direct = 0;
+  if ((rc = vg_enqueue_filter(km, km->cat[0], n, leaf, 0, km->ds_out, &direct, &m_direct))) return rc;
+  KCHK(hipStreamSynchronize(s));
+  const int mm = direct ? m_direct : km->h_m[0];
+  if (mm < 0 || mm > n) { ctx_set_error("rolo_keymap_downsample: inconsistent cell count"); return ROLO_ESTATE; }
+  if (mm) KCHK(hipMemcpy(out, km->ds_out, sizeof(float4) * (size_t)mm, hipMemcpyDeviceToHost));
+  *m = mm;
+  return ROLO_OK;
+}
+
+int rolo_keyposes_select_nearby(const float* xyz, const double* times, int n, float search_radius, float density, double time_cur, double recent_seconds,
+                                int32_t* out_indices, int cap) {
+  if (n < 0 || cap < 0 || (n && (!xyz || !times)) || (cap && !out_indices) || !(density > 0.f) || !(search_radius >= 0.f)) return ROLO_EINVAL;
+  if (n == 0) return 0;
+  auto d2 = [&](const float* a, const float* b) { const float dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2]; return dx * dx + dy * dy + dz * dz; };
+  const float* last = xyz + 3 * (size_t)(n - 1);
+  // radiusSearch(cloudKeyPoses3D->back(), radius) :585 — squared float distances below radius^2, nearest first
+  const float r2 = search_radius * search_radius;
+  std::vector<std::pair<float, int>> near;
+  for (int i = 0; i < n; i++) { const float d = d2(xyz + 3 * (size_t)i, last); if (d < r2) near.push_back({d, i}); }
+  std::sort(near.begin(), near.end());
+  // downSizeFilterSurroundingKeyPoses :592-593 (intensity = index of the key pose)
+  std::vector<std::array<float, 4>> poses, ds;
+  for (const auto& e : near) poses.push_back({xyz[3 * (size_t)e.second], xyz[3 * (size_t)e.second + 1], xyz[3 * (size_t)e.second + 2], (float)e.second});
+  host_voxelgrid(poses, density, ds);
+  // :595-600 — each down-sampled pose takes the index of the nearest key pose
+  for (auto& p : ds) {
+    int best = 0; float bd = d2(p.data(), xyz);
+    for (int i = 1; i < n; i++) { const float d = d2(p.data(), xyz + 3 * (size_t)i); if (d < bd) { bd = d; best = i; } }
+    p[3] = (float)best;
+  }
+  // :604-611 — the key poses of the last recent_seconds, newest first
+  for (int i = n - 1; i >= 0; --i) {
+    if (time_cur - times[i] < recent_seconds) ds.push_back({xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], (float)i});
+    else break;
+  }
+  // :626 — "if (pointDistance(cloudToExtract->points[i], cloudKeyPoses3D->back()) > surroundingKeyframeSearchRadius) continue"
+  int count = 0;
+  for (const auto& p : ds) {
+    if (std::sqrt(d2(p.data(), last)) > search_radius) continue;
+    if (count < cap) out_indices[count] = (int32_t)p[3];
+    count++;
+  }
+  return count;
+}
+
+}  // extern "C"
