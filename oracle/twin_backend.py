@@ -24,8 +24,9 @@ def associate(T, pts):   # pointAssociateToMap :293-299, float, left to right
 
 
 def knn5(tree_pts, tree, q):
-    """exact 5-NN with float squared distances ((dx*dx)+(dy*dy))+(dz*dz), ties by index"""
-    _, idx = tree.query(q.astype(np.float64), k=min(12, tree_pts.shape[0]))
+    """exact 5-NN with float squared distances ((dx*dx)+(dy*dy))+(dz*dz), ties by index (among the 32 nearest by cKDTree's own order: up to 28 points may tie
+    for the fifth place — tests/s2m_scenarios.py ties twelve)"""
+    _, idx = tree.query(q.astype(np.float64), k=min(32, tree_pts.shape[0]))
     d = q[:, None, :] - tree_pts[idx]                               # float32
     d2 = ((d[..., 0] * d[..., 0]) + (d[..., 1] * d[..., 1])) + (d[..., 2] * d[..., 2])
     order = np.lexsort((idx, d2), axis=1)[:, :5]

@@ -84,3 +84,117 @@ def test_restated_eigen_and_plane_fit_known_answers():
     assert np.abs(np.abs(n[:, 2]) - 1).max() < 1e-4                        # the ground's normal
     # Gauss-Newton pulls the scan onto the map: the translation offset is recovered, no rotation appears
     assert np.abs(tf[3:] - off).max() < 2e-3 and np.abs(tf[:3]).max() < 1e-3
+
+
+# ---- the constructed scenarios of tests/s2m_scenarios.py, pinned on the CPU: the GPU tier (tests/test_gpu_backend_cases.py) holds the kernels to the oracle on these arrays,
+# so what the oracle says about them is held here to the twin, to a float64 statement of the two fits and to what each case is there to reach ----
+import functools
+
+import s2m_scenarios as S
+
+_BUILDERS = {"table": S.table, "general_pose": S.table_general_pose, "ties": S.ties}
+
+
+@functools.lru_cache(maxsize=None)
+def _solved(which):
+    """(scenario, names, oracle result, twin result, float64 fit), computed once per scenario"""
+    scn, names = _BUILDERS[which]()
+    kw = dict(edge_min=scn[5], surf_min=scn[6])
+    return scn, names, pyorc.scan2map(*scn[:5], **kw), twin_backend.scan2map(*scn[:5], **kw), S.float64_fit(scn)
+
+
+def _one_association(scn, result):
+    """fewer than 50 selected: LMOptimization returned at once — one iteration, the pose exactly the guess"""
+    tf, st, sel, co = result
+    assert st["skipped"] == 0 and st["iterations"] == 1 and st["converged"] == 0 and st["degenerate"] == 0 and st["n_selected"] == int(sel.sum()) <= S.MAX_SELECTABLE, st
+    assert np.array_equal(tf, scn[4])
+    assert not co[~sel].any()
+
+
+@pytest.mark.parametrize("which", ["table", "general_pose"])
+def test_table_cases_reach_their_branches_and_agree_with_twin_and_float64(which):
+    scn, names, orc, twin, (fl64, co64, resid, nbrs) = _solved(which)
+    _one_association(scn, orc); _one_association(scn, twin)
+    assert len(names) == len(S.TABLE) - (sum(bool(c.get("exact")) for c in S.TABLE.values()) if which == "general_pose" else 0)
+    (_, _, sel, co), (_, _, sel_t, co_t) = orc, twin
+    wrong = [(n, bool(sel[i]), bool(sel_t[i]), bool(fl64[i])) for i, n in enumerate(names) if not (sel[i] == sel_t[i] == fl64[i] == S.TABLE[n]["select"])]
+    assert not wrong, f"(case, oracle, twin, float64) flags that miss what the case is there for: {wrong}"
+    well = np.array([not S.TABLE[n].get("oracle_only") for n in names])
+    dev64, dev_t = np.abs(co - co64).max(axis=1), np.abs(co - co_t).max(axis=1)
+    print(f"{which}: oracle vs float64 {dev64[well].max():.2e}, oracle vs twin {dev_t[well].max():.2e} on the well-conditioned cases")
+    off = [(n, dev64[i], dev_t[i]) for i, n in enumerate(names) if well[i] and not (dev64[i] <= S.FLOAT64_TOL and dev_t[i] <= S.FLOAT64_TOL)]
+    assert not off, f"(case, |oracle - float64|, |oracle - twin|) above {S.FLOAT64_TOL:.1e}: {off}"
+    # rank-deficient plane systems: Eigen's basic solution is A least-squares solution (ColPivHouseholderQR::solve), not the minimum-norm one numpy returns
+    corner, surf = scn[0], scn[1]
+    R, t = S.pose_matrix(scn[4])
+    n_checked = n_differ = 0
+    for i, n in enumerate(names):
+        if well[i] or not sel[i]:
+            continue
+        n_differ += np.abs(co[i] - co64[i]).max() > 1e-2
+        x = S.plane_from_coeff(co[i], R @ surf[i - corner.shape[0], :3].astype(np.float64) + t)
+        P = scn[3][nbrs[i], :3].astype(np.float64)
+        excess = np.linalg.norm(P @ x + 1) - resid[i]
+        print(f"{which}: {n}: residual excess over lstsq {excess:.2e}")
+        assert excess <= S.RANK_DEFICIENT_EXCESS_TOL, (n, excess)
+        n_checked += 1
+    assert n_checked >= 3 and n_differ >= 2   # (and the basic solution IS another one than numpy's minimum-norm solution: these cases can only be held to the oracle)
+
+
+def test_tie_cases_are_exact_ties_that_decide_the_fit():
+    scn, names, orc, twin, (fl64, co64, _, _) = _solved("ties")
+    _one_association(scn, orc); _one_association(scn, twin)
+    (_, _, sel, co), (_, _, sel_t, co_t) = orc, twin
+    assert np.array_equal(sel, sel_t) and np.array_equal(sel, fl64)
+    assert np.abs(co - co_t).max() <= S.FLOAT64_TOL and np.abs(co - co64).max() <= S.FLOAT64_TOL
+    assert {S.TIES[n]["kind"] for n in names} == {"corner", "surf"}
+    first = {"corner": 0, "surf": 0}
+    for i, n in enumerate(names):
+        c = S.TIES[n]
+        feat, m = (scn[0][i], scn[2]) if c["kind"] == "corner" else (scn[1][i - scn[0].shape[0]], scn[3])
+        d = feat[:3] - m[[first[c["kind"]] + j for j in c["tie"]], :3]                                   # float32, the kernels' and the oracle's expression
+        d2 = ((d[:, 0] * d[:, 0]) + (d[:, 1] * d[:, 1])) + (d[:, 2] * d[:, 2])
+        assert d2.dtype == np.float32 and d2[0] == d2[1], (n, d2)
+        first[c["kind"]] += len(c["pts"])
+        # the other candidate first in the array: another fit for this feature, the same bits for every other one
+        _, _, sel_s, co_s = pyorc.scan2map(*S.swap_tie(scn, names, n)[:5], edge_min=0, surf_min=0)
+        assert sel_s[i] != sel[i] or np.abs(co_s[i] - co[i]).max() > 0.1, f"{n}: taking the other candidate changes nothing — the case cannot see a broken tie order"
+        others = np.arange(len(names)) != i
+        assert np.array_equal(sel_s[others], sel[others]) and np.array_equal(co_s[others], co[others])
+
+
+def test_sweep_scenarios_select_near_structure_only():
+    for m in S.TREE_SIZES:
+        scn, names = S.tree_sweep(m)
+        orc, twin = pyorc.scan2map(*scn[:5], edge_min=0, surf_min=0), twin_backend.scan2map(*scn[:5], edge_min=0, surf_min=0)
+        _one_association(scn, orc)
+        assert scn[2].shape[0] == scn[3].shape[0] == m and np.array_equal(orc[2], twin[2]), m
+        nc = scn[0].shape[0]
+        assert orc[2][:nc].sum() >= 12 and orc[2][nc:].sum() >= 12, (m, orc[1])                       # the fits ARE selected: the sweep compares coefficients, not zeros
+    for n_corner, n_surf in S.COUNT_PAIRS:
+        scn, names = S.count_sweep(n_corner, n_surf)
+        orc, twin = pyorc.scan2map(*scn[:5], edge_min=0, surf_min=0), twin_backend.scan2map(*scn[:5], edge_min=0, surf_min=0)
+        _one_association(scn, orc)
+        assert (scn[0].shape[0], scn[1].shape[0]) == (n_corner, n_surf) and np.array_equal(orc[2], twin[2])
+        near = np.array([n.endswith("near") for n in names])
+        assert not orc[2][~near].any() and orc[2][near].sum() >= 0.8 * near.sum(), (n_corner, n_surf, orc[1])
+        if near.sum() < len(names):   # interleaved, not at the head: selected features follow unselected ones
+            assert np.flatnonzero(near).max() > np.flatnonzero(~near).min()
+        feats = np.concatenate([scn[0], scn[1]])[:, :3].astype(np.float64); maps = np.concatenate([scn[2], scn[3]])[:, :3].astype(np.float64)
+        assert all(np.linalg.norm(maps - f, axis=1).min() >= 3.0 for f in feats[~near])
+    assert sorted({a for a, _ in S.COUNT_PAIRS}) == sorted({b for _, b in S.COUNT_PAIRS}) == sorted(S.FEATURE_COUNTS) and all(a != b for a, b in S.COUNT_PAIRS)
+
+
+@pytest.mark.parametrize("variant", list(S.SCENES))
+def test_scenes_reach_their_exits_and_are_stable_targets(variant):
+    corner, surf, mc, ms, guess, e, s = S.corridor(variant)
+    tf, st, sel, co = pyorc.scan2map(corner, surf, mc, ms, guess, edge_min=e, surf_min=s)
+    tf_t, st_t, sel_t, _ = twin_backend.scan2map(corner, surf, mc, ms, guess, edge_min=e, surf_min=s)
+    assert st == S.SCENES[variant] and st_t == S.SCENES[variant]
+    assert np.array_equal(sel, sel_t) and np.abs(tf - tf_t).max() <= 1e-6
+    assert S.scene_pose_problems(variant, tf, guess) == [] and S.scene_pose_problems(variant, tf_t, guess) == []
+    # a GPU that sums J^T J in another order perturbs the iterates in their last bits: such a perturbation must flip nothing and move the pose by less than half the
+    # 2e-6 the GPU tier allows
+    for d in (1e-7, -1e-7, 3e-7):
+        tf_p, st_p, sel_p, _ = pyorc.scan2map(corner, surf, mc, ms, (guess + np.float32(d)).astype(np.float32), edge_min=e, surf_min=s)
+        assert st_p == st and np.array_equal(sel_p, sel) and np.abs(tf_p - tf).max() <= 1e-6, (d, st_p, np.abs(tf_p - tf).max())
