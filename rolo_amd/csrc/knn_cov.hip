@@ -16,6 +16,7 @@
 #include <cstring>
 #include <string.h>
 #include "rolo_internal.hpp"
+#include "switches.hpp"
 #include "dev_math.hpp"
 #include "voxel_dev.hpp"
 #ifdef ROLO_KNN_ROCPRIM_SORT
@@ -690,7 +691,7 @@ constexpr int KNN_SUB_MAX_PACKETS = 1792;   // (the pipeline's pair launch is 14
 // Round 5: above the limit the choice follows the DEVICE'S LOAD. Alone on the chip the two-lane walk finishes sooner (0.175 against 0.22 ms: single-frame latency 0.71
 // against 0.76 ms); with other contexts' frames in flight the packets — half the wavefronts, the same instructions — leave the other frames' short LM kernels more of
 // every SIMD's issue slots: 3.04 against 2.98 k scans/s, and 3.17 against 3.01 k once those kernels run at raised priority (ROLO_SHORT_PRIO). The caller says which
-// case it is (frames in flight on the device when this one is enqueued, api.hip); a captured hipGraph is keyed on it.
+// case it is (frames in flight on the device when this one is enqueued, schedule.hip); a captured hipGraph is keyed on it.
 hipError_t launch_knn_walk(const KnnPair& A, int k, hipStream_t s, int* lanes_out, bool device_busy, bool moments) {
   if (lanes_out) *lanes_out = 1;
   constexpr int QPB = 256;   // queries per workgroup of the plain walk: four wavefronts of 64
@@ -711,15 +712,8 @@ hipError_t launch_knn_walk(const KnnPair& A, int k, hipStream_t s, int* lanes_ou
   if (k == 20) {
     // small clouds: 16 queries x 4 lanes per wavefront (knn_walk_sub_kernel) — below ~2 packets of 64 per SIMD the walk is a chain of fetches, not
     // inserts. ROLO_KNN_SUB (an A/B switch): 0 = the 64-query packets at every size, 2 = two lanes per query always, 4 (or 1) = four lanes always; unset = by size.
-    // Any other value is ignored with a warning instead of silently picking a kernel (advisor, round 4).
-    static const int sub_env = [] {
-      const char* e = getenv("ROLO_KNN_SUB");
-      if (!e) return -1;
-      const int v = atoi(e);
-      if (v == 0 || v == 1 || v == 2 || v == 4) return v;
-      fprintf(stderr, "librolo_hip: ROLO_KNN_SUB=%s is not one of 0 / 1 / 2 / 4: ignored (the walk is picked by size)\n", e);
-      return -1;
-    }();
+    // Any other value is ignored with a warning instead of silently picking a kernel (advisor, round 4; switches.hpp warns when it parses the table).
+    const int sub_env = switches().knn_sub;
     const int packets = (n0 + 63) / 64 + (n1 + 63) / 64;
     const int lanes = sub_env < 0 ? (packets <= KNN_SUB_MAX_PACKETS ? 4 : (device_busy ? 0 : 2)) : (sub_env == 2 ? 2 : (sub_env ? 4 : 0));
     if (lanes_out) *lanes_out = lanes ? lanes : 1;

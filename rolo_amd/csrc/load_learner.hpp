@@ -1,5 +1,5 @@
 // What the per-process count of frames in flight cannot see — another PROCESS (or a foreign workload) on the same GPU — learned from the device's own signal: how long a
-// context's frames take on the device (round 5's verdict, item 7). Pure host logic, no HIP: api.hip feeds it the event-timed duration of every frame that was sized by it
+// context's frames take on the device (round 5's verdict, item 7). Pure host logic, no HIP: schedule.hip feeds it the event-timed duration of every frame that was sized by it
 // (rolo_set_load_hint -1, no other frame of this process in flight, not sharded); tests/cpp/learner_test.cpp drives it with synthetic durations on the CPU tier.
 //
 // While the context believes the device idle (mode 0) it remembers the shortest frame it has seen at the current sizes. Frames that last a quarter longer than that for a

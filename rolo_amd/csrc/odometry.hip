@@ -6,6 +6,7 @@
 // The fp32 pose algebra restates pcl::getTransformation / getTranslationAndEulerAngles / Eigen::Affine3f products
 // (PCL, Eigen: not vendored by the reference).
 #include "rolo_internal.hpp"
+#include "switches.hpp"
 #include "polar_f32.hpp"
 #include <cmath>
 #include <cstdlib>
@@ -126,7 +127,7 @@ int rolo_odom_create(rolo_ctx* ctx, float ct_lambda, rolo_odom** out) {
   if (!ctx || !out) return ROLO_EINVAL;
   rolo_odom* o = new rolo_odom();
   o->ctx = ctx; o->ct_lambda = ct_lambda;
-  if (const char* e = getenv("ROLO_ODOM_EARLY_SOURCE")) o->early_source_enabled = atoi(e) != 0;   // A/B runs
+  o->early_source_enabled = rolo::odom_early_source_now(o->early_source_enabled);   // A/B runs (ROLO_ODOM_EARLY_SOURCE, read per driver)
   // (rolo_params.fused_lm is NOT switched behind the caller's back here: the driver asserts its own option right before every registration it
   // enqueues — a later rolo_set_params with the caller's own parameter block cannot silently revert it, nor does creating a driver change
   // what a plain rolo_register_async on the same context does afterwards beyond the frames the driver itself runs)
@@ -156,7 +157,7 @@ void rolo_odom_increment(const float* front6, const float* back6, float* incre6)
 
 static int ensure_front_ctx(rolo_odom* o) {
   if (o->fctx) return ROLO_OK;
-  static const bool plain = [] { const char* e = getenv("ROLO_ODOM_FRONT_PRIORITY"); return e && atoi(e) == 0; }();   // A/B: 0 = a normal-priority front-end stream (round 2)
+  const bool plain = !rolo::switches().odom_front_priority;   // A/B: 0 = a normal-priority front-end stream (round 2)
   int rc = plain ? rolo_ctx_create(rolo::ctx_device(o->ctx), &o->fctx) : rolo::ctx_create_high_priority(rolo::ctx_device(o->ctx), &o->fctx);
   if (rc) return rc;
   for (auto& sl : o->q) {

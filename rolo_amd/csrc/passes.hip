@@ -18,6 +18,7 @@
 // are predicated on the device-side state, so a fixed schedule of launches can be enqueued (or graph-captured)
 // without knowing how many trials the data will need.
 #include "rolo_internal.hpp"
+#include "switches.hpp"
 #include <atomic>
 #include "lm_begin.hpp"
 #include "dev_math.hpp"
@@ -1757,12 +1758,12 @@ hipError_t lmp_launch(int nrows, int threads, size_t lds, hipStream_t s, Args...
 }
 LmpForm lm_persist_form(int dof, int threads, int ppt, int n_off, int nrows) {
   // the interleaved bodies (1, 2 or 4 points per thread in registers) for the reference's own configuration — SO(3) optimiser, DIRECT1; everything else one point after the other
-  static const bool interleave = [] { const char* e = getenv("ROLO_LM_PERSIST_INTERLEAVE"); return !(e && atoi(e) == 0); }();
+  const bool interleave = switches().lm_persist_interleave;
   // ROLO_LM_PERSIST_MCACHE=0 (A/B): no Mahalanobis cache in LDS — every trial inverts again, as the pass kernels do
-  static const int mcache_on = [] { const char* e = getenv("ROLO_LM_PERSIST_MCACHE"); return (e && atoi(e) == 0) ? 0 : 1; }();
+  const int mcache_on = switches().lm_persist_mcache;
   // (builds for four wavefronts per SIMD — 128 registers, so that a walk's wavefronts could share the SIMDs — spill 85 / 159 / 270 registers at 1 / 2 / 4 points per thread and are
   // not instantiated: lm_persist_kernel<3, 512, PPT, 1, 4>, profiles/DEAD_ENDS.md round 6)
-  static const int batch4 = [] { const char* e = getenv("ROLO_LM_PERSIST_BATCH"); const int v = e ? atoi(e) : 2; return (v == 1 || v == 4) ? v : 2; }();   // four points per thread go through the bodies in batches of 2 (default: 4 087 scans/s with four contexts, final kernels) / 1 (4 046: twice the dependent round trips and the same 6.6 us per linearising body — the bodies are bound by their fp64 issue at two wavefronts per SIMD, not by their fetches) / 4 (3 761: 144 spilled registers)
+  const int batch4 = switches().lm_persist_batch;   // four points per thread go through the bodies in batches of 2 (default: 4 087 scans/s with four contexts, final kernels) / 1 (4 046: twice the dependent round trips and the same 6.6 us per linearising body — the bodies are bound by their fp64 issue at two wavefronts per SIMD, not by their fetches) / 4 (3 761: 144 spilled registers)
   LmpForm f;
   f.rows = nrows; f.threads = threads; f.ppt = ppt;
   f.sp = (interleave && dof == 3 && n_off == 1 && (ppt == 1 || ppt == 2 || ppt == 4)) ? ppt : 0;
@@ -1802,7 +1803,7 @@ hipError_t launch_reduce(const double* partials, int nblocks, double* sums, cons
 }
 hipError_t launch_ctrl(LmState* st, const double* partials, int nblocks, const double* sums, rolo_trace_rec* trace, int stage, hipStream_t s, LmState* pub,
                        const PeerArgs* peer, int dof) {
-  static const bool generic = [] { const char* e = getenv("ROLO_CTRL_GENERIC"); return e && atoi(e) != 0; }();   // A/B: the one-size-fits-all kernel of round 2
+  const bool generic = switches().ctrl_generic;   // A/B: the one-size-fits-all kernel of round 2
   const int mode = generic ? -1 : (stage == 2 ? 2 : (dof == 3 ? 0 : (dof == 6 ? 1 : -1)));
   const bool p = peer && peer->world > 1 && partials;
   switch (mode) {

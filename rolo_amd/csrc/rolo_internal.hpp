@@ -123,7 +123,7 @@ struct LmState {
   int lin_skip, spec_lin;
   int rot_cost_only, trans_cost_only;   // passes of rot_passes / trans_passes that ran with lin_skip set (counted by the step that consumes them): rolo_stats::n_cost_only
   int lmp_bailed;   // the resident LM kernel (fused_lm = 2) did not get all its workgroups resident within the admission time and left WITHOUT touching the stage: the host
-                    // finishes the frame with pass + controller launches (passes.hip lm_persist_kernel, api.hip run_stage)
+                    // finishes the frame with pass + controller launches (passes.hip lm_persist_kernel, schedule.hip run_stage)
   // parameters
   int optimizer, max_iterations, fixed_iterations, lm_max, q2_intended;
   double rot_eps, trans_eps, lm_init;

@@ -15,6 +15,7 @@
 // colPivHouseholderQr().solve of the 5 x 3 plane system = Eigen's column-pivoted Householder QR. The C++ oracle (oracle/rolo_oracle_backend.cpp)
 // restates the same algorithms independently: selection flags bit-identical, coefficients to float rounding (tests/test_gpu_backend.py).
 #include "rolo_internal.hpp"
+#include "switches.hpp"
 #include "dev_math.hpp"
 #include "knn_packet.hpp"
 #include <cfloat>
@@ -830,11 +831,11 @@ extern "C" int rolo_scan2map_optimize(rolo_ctx* c, const float* corner, int n_co
   const int n = n_corner + n_surf;
   // ROLO_S2M_PACKETS=0: one tree walk per lane in the caller's order (rounds 2-3, the A/B); default: the features sorted along the curve once per call,
   // 64 consecutive ones walk the sub-map's tree as one packet (s2m_packet_kernel)
-  static const bool use_packets = [] { const char* e = getenv("ROLO_S2M_PACKETS"); return !(e && atoi(e) == 0); }();
-  static const int qpp = [] { const char* e = getenv("ROLO_S2M_QPP"); const int v = e ? atoi(e) : 64; return v == 8 || v == 16 || v == 32 ? v : 64; }();
+  const bool use_packets = switches().s2m_packets;
+  const int qpp = switches().s2m_qpp;
   // ROLO_S2M_SUB = 2 / 4 / 8 lanes per feature (s2m_sub_kernel); 1 = the 64-feature packets (s2m_packet_kernel, the A/B)
-  static const int sub = [] { const char* e = getenv("ROLO_S2M_SUB"); const int v = e ? atoi(e) : 4; return v == 1 || v == 2 || v == 8 ? v : 4; }();
-  static const int wide = [] { const char* e = getenv("ROLO_S2M_WIDE"); const int v = e ? atoi(e) : 4; return v == 0 || v == 6 ? v : 4; }();
+  const int sub = switches().s2m_sub;
+  const int wide = switches().s2m_wide;
   const int fpw = sub > 1 ? 64 / sub : qpp;   // features per wavefront
   KnnPair qp{};
   int grid = (n + S2M_THREADS - 1) / S2M_THREADS, split = 0;
@@ -869,9 +870,9 @@ extern "C" int rolo_scan2map_optimize(rolo_ctx* c, const float* corner, int n_co
   S2mArgs A{};
   A.feat = d_feat; A.n_corner = n_corner; A.n_surf = n_surf; A.map[0] = maps.c[0]; A.map[1] = maps.c[1]; A.partials = d_part; A.selected = d_sel; A.coeff = d_coeff;
   A.qry[0] = qp.c[0]; A.qry[1] = qp.c[1]; A.qpp = qpp;
-  { static const int xr = [] { const char* e = getenv("ROLO_S2M_XCD"); return e ? atoi(e) : 1; }(); A.xcd_remap = xr; }
-  { static const int cp = [] { const char* e = getenv("ROLO_S2M_CAP"); return e ? atoi(e) : 1; }(); A.cap = cp; }
-  static const char* stats_path = getenv("ROLO_S2M_STATS");
+  A.xcd_remap = switches().s2m_xcd;
+  A.cap = switches().s2m_cap;
+  const char* stats_path = switches().s2m_stats;
   int4* d_wstats = nullptr;
   if (stats_path && use_packets && sub > 1) { SCHK(hipMalloc((void**)&d_wstats, sizeof(int4) * 4 * (size_t)grid)); SCHK(hipMemsetAsync(d_wstats, 0, sizeof(int4) * 4 * (size_t)grid, s)); A.wstats = d_wstats; }
   float* tf = transformTobeMapped;
