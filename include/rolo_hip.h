@@ -465,6 +465,57 @@ int rolo_keymap_downsample(rolo_keymap* km, const float* pts, int n, float leaf,
 /* kdtree*FromMap->setInputCloud (:690-691) without the host round trip: rolo_scan2map_set_submap on the key map's last extraction (same device) */
 int rolo_scan2map_set_submap_keymap(rolo_ctx* ctx, rolo_keymap* km);
 
+/* ---- back end: Scan Context place recognition from the resident key frames ------------------------------------------------------------
+ * SCManager (src/scancontext/Scancontext.cpp, include/scancontext/Scancontext.h) as the back end uses it: saveKeyFramesAndFactor (src/backMapping.cpp:1183-1216)
+ * turns every key frame into a descriptor, performSCLoopClosure (:2399-2479) asks for a loop candidate and a yaw offset. The descriptors live in the key map,
+ * on its stream and under its rules (the store only grows, nothing is freed before rolo_keymap_destroy). Per descriptor: the num_ring x num_sector matrix of
+ * maximum heights (float values, as the reference's MatrixXd only widens them), the fp64 column norms, the sector key (column means, fp64) and the ring key (row
+ * means, fp64 rounded to float as eig2stdvec :62-66 does).
+ * The arithmetic is the reference's statement by statement (rolo_amd/csrc/scancontext.hip lists it); every sum is taken serially in index order.
+ * Parity unpinned, stated once: the order in which Eigen's norm(), mean() and dot() add; the order in which the kd-tree returns keys at equal distance (here
+ * the lower index first; the candidate SET is the exact K nearest, which nanoflann's tree also returns); which atan overload the reference's build selects
+ * for xy2theta's float quotient (here the fp64 one, correctly rounded). The tests hold the kernels bit for bit to the numpy statement tests/sc_twin.py.
+ * Limits (ROLO_EINVAL): num_ring * num_sector <= ROLO_SC_MAX_BINS (the bins and the query's matrix sit in one workgroup's LDS), num_sector <=
+ * ROLO_SC_MAX_SECTORS, num_candidates <= ROLO_SC_MAX_CANDIDATES or 0 = every searched descriptor is a candidate (the exhaustive form of the original paper,
+ * with search_ratio = 1.0 for all shifts). A zero maximum height is stored as +0.0. */
+#define ROLO_SC_MAX_BINS 4096
+#define ROLO_SC_MAX_SECTORS 1024
+#define ROLO_SC_MAX_CANDIDATES 64
+typedef struct rolo_sc_params { int num_ring, num_sector; double max_radius, lidar_height;
+                                int num_exclude_recent, num_candidates; double search_ratio, dist_thres; } rolo_sc_params;
+/* Scancontext.h:80-95: PC_NUM_RING 20, PC_NUM_SECTOR 60, PC_MAX_RADIUS 80.0, LIDAR_HEIGHT 2.0, NUM_EXCLUDE_RECENT 30, NUM_CANDIDATES_FROM_TREE 3,
+ * SEARCH_RATIO 0.1, SC_DIST_THRES 0.4; host only (no device needed). num_exclude_recent is carried for the caller (ScanContextManager); the library does not read it. */
+void rolo_sc_default_params(rolo_sc_params* p);
+/* the geometry (num_ring, num_sector, max_radius, lidar_height) can change only while no descriptor is stored (ROLO_ESTATE otherwise;
+ * arrays an earlier, failed add has sized for the old geometry are retired); the rest at any time */
+int rolo_keymap_sc_set_params(rolo_keymap* km, const rolo_sc_params* p);
+/* the parameters in force (the defaults before the first rolo_keymap_sc_set_params): what sizes rolo_keymap_sc_get's outputs */
+int rolo_keymap_sc_get_params(rolo_keymap* km, rolo_sc_params* out);
+/* makeAndSaveScancontextAndKeys (:236-250) with makeScancontext :151-195 and the two keys :198-227; both return the new descriptor's index (>= 0). A non-finite
+ * coordinate is ROLO_ENONFINITE and an empty cloud ROLO_EINVAL (the reference skips it with a warning): nothing is stored.
+ * scInputType scan_feat (src/backMapping.cpp:1213): the key frame's RESIDENT surface cloud, device to device */
+int rolo_keymap_sc_add_surface(rolo_keymap* km, int keyframe);
+/* scInputType scan_raw (:1186-1196): n x 4 floats from the host; leaf > 0: downSizeFilterSC (0.5) first, on the device with the key map's voxel filter, no
+ * round trip; leaf = 0: the cloud as it is */
+int rolo_keymap_sc_add_cloud(rolo_keymap* km, const float* pts, int n, float leaf);
+int rolo_keymap_sc_size(rolo_keymap* km);
+/* download of one descriptor, each part optional: desc[num_ring * num_sector] ring-major (desc[r * num_sector + s], the reference's desc(r, s)),
+ * ringkey[num_ring], sectorkey[num_sector], colnorm[num_sector] */
+int rolo_keymap_sc_get(rolo_keymap* km, int index, double* desc, float* ringkey, double* sectorkey, double* colnorm);
+/* detectLoopClosureID (:253-344) for descriptor `query` against descriptors 0 .. n_search - 1. The caller passes n_search because the reference searches a stale
+ * set: its tree is rebuilt every TREE_MAKING_PERIOD_ = 10 calls from all keys but the newest NUM_EXCLUDE_RECENT (:263-282). n_search <= 0 is the early return
+ * (loop_id -1, yaw 0). Candidates: the min(num_candidates, n_search) smallest float squared ring-key distances (nanoflann.hpp:383-408: groups of four, left to
+ * right), ascending by (distance, index). Per candidate distanceBtnScanContext :116-148: the sector-key alignment over all shifts (first strict minimum), the
+ * window of round(0.5 * search_ratio * num_sector) shifts either side of it modulo num_sector, each shift once in ascending order, and the column-wise cosine
+ * distance at each (columns with a zero norm on either side not counted; none counted: NaN, never a minimum, so the pair keeps 10 000 000 and shift 0).
+ * nn_idx / nn_align / min_dist: the first strict minimum in candidate order (:302-317); loop_id = nn_idx if min_dist < dist_thres, else -1; yaw_diff_rad =
+ * deg2rad(nn_align * 360.0 / num_sector) with the reference's float / double mix (:17-20, :339).
+ * cand_idx / cand_dist / cand_align (optional, cap entries each): the first min(n_candidates, cap) candidates in candidate order. */
+typedef struct rolo_sc_result { int loop_id; float yaw_diff_rad; int nn_idx, nn_align; double min_dist; int n_candidates; } rolo_sc_result;
+int rolo_keymap_sc_detect(rolo_keymap* km, int query, int n_search, rolo_sc_result* out, int32_t* cand_idx, double* cand_dist, int32_t* cand_align, int cap);
+/* device time of the last rolo_keymap_sc_add_* / rolo_keymap_sc_detect call in milliseconds, between two events on the key map's stream (profiles/tools/sc_time.py) */
+float rolo_keymap_sc_last_ms(rolo_keymap* km);
+
 #ifdef __cplusplus
 }
 #endif

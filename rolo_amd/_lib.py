@@ -57,6 +57,16 @@ class Scan2MapStats(C.Structure):
     _fields_ = [("skipped", C.c_int), ("iterations", C.c_int), ("converged", C.c_int), ("degenerate", C.c_int), ("n_selected", C.c_int)]
 
 
+class ScParams(C.Structure):
+    _fields_ = [("num_ring", C.c_int), ("num_sector", C.c_int), ("max_radius", C.c_double), ("lidar_height", C.c_double),
+                ("num_exclude_recent", C.c_int), ("num_candidates", C.c_int), ("search_ratio", C.c_double), ("dist_thres", C.c_double)]
+
+
+class ScResult(C.Structure):
+    _fields_ = [("loop_id", C.c_int), ("yaw_diff_rad", C.c_float), ("nn_idx", C.c_int), ("nn_align", C.c_int), ("min_dist", C.c_double),
+                ("n_candidates", C.c_int)]
+
+
 class EskfOptions(C.Structure):   # include/rolo_fusion.h
     _fields_ = [(k, C.c_double) for k in ("max_dt", "q_linear_jerk_std", "q_angular_jerk_std", "r_position_std", "r_rotation_std", "init_position_std",
                                           "init_rotation_std", "init_velocity_std", "init_angular_velocity_std", "init_acceleration_std",
@@ -138,6 +148,15 @@ SYMBOLS = {
     "rolo_keymap_extract": (C.c_int, [vp, ip, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rolo_keymap_get_submap": (C.c_int, [vp, fp, C.c_int, fp, C.c_int]),
     "rolo_keymap_downsample": (C.c_int, [vp, fp, C.c_int, C.c_float, fp, C.POINTER(C.c_int)]),
+    "rolo_sc_default_params": (None, [C.POINTER(ScParams)]),
+    "rolo_keymap_sc_set_params": (C.c_int, [vp, C.POINTER(ScParams)]),
+    "rolo_keymap_sc_get_params": (C.c_int, [vp, C.POINTER(ScParams)]),
+    "rolo_keymap_sc_add_surface": (C.c_int, [vp, C.c_int]),
+    "rolo_keymap_sc_add_cloud": (C.c_int, [vp, fp, C.c_int, C.c_float]),
+    "rolo_keymap_sc_size": (C.c_int, [vp]),
+    "rolo_keymap_sc_get": (C.c_int, [vp, C.c_int, dp, fp, dp, dp]),
+    "rolo_keymap_sc_detect": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(ScResult), ip, dp, ip, C.c_int]),
+    "rolo_keymap_sc_last_ms": (C.c_float, [vp]),
     "rolo_num_voxels": (C.c_int, [vp]),
     "rolo_num_edge_points": (C.c_int, [vp]),
     "rolo_get_voxels": (C.c_int, [vp, ip, ip, dp, dp]),

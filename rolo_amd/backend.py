@@ -1,12 +1,13 @@
-"""Host mirrors of the back end: the scan-to-submap optimisation (reference src/backMapping.cpp:681-1058) over rolo_scan2map_optimize and the
-device-resident key frames with sub-map assembly (:558-678) over rolo_keymap_*."""
+"""Host mirrors of the back end: the scan-to-submap optimisation (reference src/backMapping.cpp:681-1058) over rolo_scan2map_optimize, the
+device-resident key frames with sub-map assembly (:558-678) over rolo_keymap_* and Scan Context loop detection (src/scancontext/Scancontext.cpp) over
+rolo_keymap_sc_*."""
 from __future__ import annotations
 
 import ctypes as C
 
 import numpy as np
 
-from ._lib import lib, check, Scan2MapStats
+from ._lib import lib, check, Scan2MapStats, ScParams, ScResult
 from .rotvgicp import RotVGICP
 
 
@@ -128,3 +129,92 @@ class KeyFrameMap:
         m = C.c_int(0)
         check(lib().rolo_keymap_downsample(self._h, a.ctypes.data_as(fp), a.shape[0], leaf, out.ctypes.data_as(fp), C.byref(m)), "rolo_keymap_downsample")
         return out[:m.value].copy()
+
+    # ---- Scan Context (src/scancontext/Scancontext.cpp): descriptors of the key frames, resident beside their clouds ----
+    def scParams(self) -> ScParams:
+        """the defaults of Scancontext.h:80-95; change fields and hand the struct to scSetParams"""
+        p = ScParams()
+        lib().rolo_sc_default_params(C.byref(p))
+        return p
+
+    def scSetParams(self, p: ScParams):
+        check(lib().rolo_keymap_sc_set_params(self._h, C.byref(p)), "rolo_keymap_sc_set_params")
+
+    def scGetParams(self) -> ScParams:
+        """the parameters the key map holds now"""
+        p = ScParams()
+        check(lib().rolo_keymap_sc_get_params(self._h, C.byref(p)), "rolo_keymap_sc_get_params")
+        return p
+
+    def scAddSurface(self, index: int) -> int:
+        """scInputType scan_feat (backMapping.cpp:1213): the descriptor of key frame `index`'s resident surface cloud; returns the descriptor's index"""
+        return check(lib().rolo_keymap_sc_add_surface(self._h, index), "rolo_keymap_sc_add_surface")
+
+    def scAddCloud(self, pts, leaf: float = 0.5) -> int:
+        """scInputType scan_raw (:1186-1196): downSizeFilterSC at `leaf` (0: none), then the descriptor; returns its index"""
+        a = np.ascontiguousarray(pts, np.float32).reshape(-1, 4)
+        return check(lib().rolo_keymap_sc_add_cloud(self._h, a.ctypes.data_as(C.POINTER(C.c_float)), a.shape[0], leaf), "rolo_keymap_sc_add_cloud")
+
+    def scSize(self) -> int:
+        return check(lib().rolo_keymap_sc_size(self._h), "rolo_keymap_sc_size")
+
+    def scDescriptor(self, i: int):
+        """(desc num_ring x num_sector float64, ring key float32, sector key float64, column norms float64) of descriptor i"""
+        p = self.scGetParams()   # the library's own geometry sizes the buffers it fills
+        R, S = p.num_ring, p.num_sector
+        desc = np.zeros((R, S), np.float64); ring = np.zeros(R, np.float32); sector = np.zeros(S, np.float64); norm = np.zeros(S, np.float64)
+        dp, fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
+        check(lib().rolo_keymap_sc_get(self._h, i, desc.ctypes.data_as(dp), ring.ctypes.data_as(fp), sector.ctypes.data_as(dp), norm.ctypes.data_as(dp)), "rolo_keymap_sc_get")
+        return desc, ring, sector, norm
+
+    def scDetect(self, query: int, n_search: int, want_candidates: bool = False):
+        """detectLoopClosureID (:253-344) for descriptor `query` against descriptors 0 .. n_search-1 -> ScResult [, candidate indices, distances, alignments]"""
+        res = ScResult()
+        if not want_candidates:
+            check(lib().rolo_keymap_sc_detect(self._h, query, n_search, C.byref(res), None, None, None, 0), "rolo_keymap_sc_detect")
+            return res
+        cap = max(n_search, 1)
+        idx = np.zeros(cap, np.int32); dist = np.zeros(cap, np.float64); align = np.zeros(cap, np.int32)
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        check(lib().rolo_keymap_sc_detect(self._h, query, n_search, C.byref(res), idx.ctypes.data_as(ip), dist.ctypes.data_as(dp), align.ctypes.data_as(ip), cap), "rolo_keymap_sc_detect")
+        m = res.n_candidates
+        return res, idx[:m].copy(), dist[:m].copy(), align[:m].copy()
+
+    def scLastMs(self) -> float:
+        return float(lib().rolo_keymap_sc_last_ms(self._h))
+
+
+class ScanContextManager:
+    """SCManager's two user calls over a key map's descriptor store. detectLoopClosureID keeps the reference's rebuild-period counter and its stale searched set
+    (Scancontext.cpp:263-282): the set is re-taken (all descriptors but the newest NUM_EXCLUDE_RECENT) only on every TREE_MAKING_PERIOD_-th call that gets past the
+    early return, and calls in between search the set as it was."""
+    TREE_MAKING_PERIOD = 10   # Scancontext.h:99
+
+    def __init__(self, keymap: KeyFrameMap, params: ScParams = None, leaf: float = 0.0):
+        self.km = keymap
+        self.params = params if params is not None else keymap.scParams()
+        keymap.scSetParams(self.params)
+        self.leaf = leaf
+        self.tree_making_period_counter = 0
+        self.n_search = 0
+        self.last = None
+
+    def makeAndSaveScancontextAndKeys(self, scan_down) -> int:
+        """:236-250 on a host cloud (n x 4 floats), already down-sampled as the reference's caller hands it over (leaf = 0) or filtered here at `leaf`"""
+        return self.km.scAddCloud(scan_down, self.leaf)
+
+    def makeAndSaveFromKeyFrame(self, index: int) -> int:
+        """the same on key frame `index`'s resident surface cloud"""
+        return self.km.scAddSurface(index)
+
+    def detectLoopClosureID(self):
+        """:253-344 -> (loop_id, yaw_diff_rad as np.float32); the query is the newest descriptor"""
+        n = self.km.scSize()
+        if n < self.params.num_exclude_recent + 1:   # :263-267
+            self.last = None
+            return -1, np.float32(0.0)
+        if self.tree_making_period_counter % self.TREE_MAKING_PERIOD == 0:   # :270-281
+            self.n_search = n - self.params.num_exclude_recent
+        self.tree_making_period_counter += 1
+        self.last = self.km.scDetect(n - 1, self.n_search)
+        return self.last.loop_id, np.float32(self.last.yaw_diff_rad)

@@ -1,0 +1,71 @@
+// The key map's state, shared by the units that work on it: submap.hip (key-frame store, sub-map assembly, voxel filter) and scancontext.hip (Scan Context
+// descriptors of the same key frames). One rule for both: the key map's own stream, buffers that only grow, nothing freed before rolo_keymap_destroy.
+#pragma once
+#include "rolo_internal.hpp"
+#include <string>
+#include <vector>
+
+namespace rolo {
+void ctx_set_error(const char* msg);
+
+struct Seg { const float4* src; int n; int dst; float T[12]; };   // one key frame's cloud in the concatenation
+struct ScStore;                                                    // scancontext.hip
+void sc_store_destroy(ScStore* sc);                                // frees what the descriptor store holds (rolo_keymap_destroy, after the stream has drained)
+}  // namespace rolo
+
+#define KCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { rolo::ctx_set_error((std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); return ROLO_EHIP; } } while (0)
+
+struct rolo_keymap {
+  int device = 0;
+  hipStream_t stream = nullptr;      // a stream of its own: assembling a sub-map never queues behind a registration
+  hipEvent_t ready = nullptr;        // recorded after every extraction: what a consumer's stream waits for
+  hipEvent_t consumed = nullptr;     // recorded by the last consumer (rolo_scan2map_set_submap_keymap) after it has read the sub-map
+  bool consumer_pending = false;
+  // the store: chunks that are never moved or freed before rolo_keymap_destroy
+  struct Chunk { float4* p; size_t cap, used; };
+  std::vector<Chunk> chunks;
+  struct Frame { const float4* pts[2]; int n[2]; float pose[6]; double time; };
+  std::vector<Frame> frames;
+  // scratch and results: they only grow
+  float4* cat[2] = {nullptr, nullptr}; size_t cat_cap[2] = {0, 0};       // the concatenated, transformed clouds (corner, surface); cat[0] also stages rolo_keymap_downsample's input
+  float4* sub[2] = {nullptr, nullptr}; size_t sub_cap[2] = {0, 0};       // the sub-map (laserCloud*FromMapDS)
+  float4* ds_out = nullptr; size_t ds_cap = 0;                           // rolo_keymap_downsample's result
+  unsigned* keys[2] = {nullptr, nullptr}; size_t keys_cap[2] = {0, 0};
+  int* vals[2] = {nullptr, nullptr}; size_t vals_cap[2] = {0, 0};
+  unsigned* hist = nullptr; size_t hist_cap = 0;
+  unsigned* dtot = nullptr; size_t dtot_cap = 0;   // [4 passes][256 digits]
+  unsigned* bcnt = nullptr; size_t bcnt_cap = 0;
+  int* starts = nullptr; size_t starts_cap = 0;
+  float* box_part = nullptr; size_t box_part_cap = 0;
+  rolo::Seg* segs = nullptr; size_t segs_cap = 0;
+  int* d_m = nullptr;                // [2]
+  float* h_box = nullptr;            // pinned [2][8]
+  int* h_m = nullptr;                // pinned [2]
+  rolo::Seg* h_segs = nullptr; size_t h_segs_cap = 0;   // pinned staging of the segment table
+  std::vector<void*> retired, retired_host;   // outgrown scratch buffers (device, pinned host), freed by rolo_keymap_destroy
+  int m_sub[2] = {0, 0};
+  bool have_submap = false;
+  rolo::ScStore* sc = nullptr;       // the Scan Context descriptors (scancontext.hip), created by the first rolo_keymap_sc_* call
+};
+
+namespace rolo {
+
+// elements; scratch only grows, and an outgrown buffer is kept until rolo_keymap_destroy: a hipFree is a device-wide synchronisation that would stall the frames
+// other contexts have in flight (scan2map.hip), and work queued on the key map's stream may still read the old buffer. Sizes grow by half: the retired ones
+// together stay below twice the live one.
+template <typename T>
+int km_grow(rolo_keymap* km, T*& p, size_t& cap, size_t need) {
+  if (need <= cap && p) return ROLO_OK;
+  if (p) { km->retired.push_back(p); p = nullptr; cap = 0; }
+  const size_t want = need + need / 2 + 256;
+  if (hipMalloc((void**)&p, want * sizeof(T)) != hipSuccess) { ctx_set_error("hipMalloc failed (keymap)"); return ROLO_EHIP; }
+  cap = want;
+  return ROLO_OK;
+}
+
+// submap.hip: a host cloud (n x 4 floats, 0 < n <= ROLO_KEYMAP_MAX_POINTS) onto the device through the key map's scratch and, with leaf > 0, through the voxel
+// filter (vg_enqueue_box / vg_enqueue_filter) without leaving the device. *d_out (n_out points) is valid on the key map's stream until the next call that
+// uses the scratch. The stream has been waited for when this returns: the caller's array is free again.
+int keymap_stage_cloud(rolo_keymap* km, const float* pts, int n, float leaf, const float4** d_out, int* n_out);
+
+}  // namespace rolo

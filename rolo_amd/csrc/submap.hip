@@ -15,7 +15,7 @@
 // A clumped cell is one long serial chain in one lane; the summation order is the contract, so it stays that way.
 //
 // transformPointCloud: the oracle's float statement p0 + (p1 + (p2 + c3)) per row (orc_transform_cloud_f, the parity target of the tests), no contraction.
-#include "rolo_internal.hpp"
+#include "keymap.hpp"
 #include <algorithm>
 #include <array>
 #include <cfloat>
@@ -26,8 +26,6 @@
 #include <vector>
 
 namespace rolo {
-void ctx_set_error(const char* msg);
-
 namespace {
 
 constexpr int SM_THREADS = 256;
@@ -38,8 +36,6 @@ constexpr int RUN_TILE = SM_THREADS * RUN_ITEMS;
 constexpr int BOX_BLOCKS_MAX = 1024;
 constexpr int KM_MAX_POINTS = ROLO_KEYMAP_MAX_POINTS;
 constexpr size_t CHUNK_POINTS = 1u << 20;              // the store grows in chunks of 16 MiB (or one cloud, if larger): nothing is ever moved or freed
-
-struct Seg { const float4* src; int n; int dst; float T[12]; };   // one key frame's cloud in the concatenation
 
 // *cloudOut = T * cloudIn of every listed key frame, written at its place in the concatenation (list order); intensity copied
 __global__ __launch_bounds__(SM_THREADS) void km_transform_kernel(const Seg* __restrict__ segs, float4* __restrict__ out) {
@@ -325,54 +321,7 @@ void pose_to_T(const float* pose6 /* roll pitch yaw x y z */, float* T) {
 
 using namespace rolo;
 
-#define KCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { ctx_set_error((std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); return ROLO_EHIP; } } while (0)
-
-struct rolo_keymap {
-  int device = 0;
-  hipStream_t stream = nullptr;      // a stream of its own: assembling a sub-map never queues behind a registration
-  hipEvent_t ready = nullptr;        // recorded after every extraction: what a consumer's stream waits for
-  hipEvent_t consumed = nullptr;     // recorded by the last consumer (rolo_scan2map_set_submap_keymap) after it has read the sub-map
-  bool consumer_pending = false;
-  // the store: chunks that are never moved or freed before rolo_keymap_destroy
-  struct Chunk { float4* p; size_t cap, used; };
-  std::vector<Chunk> chunks;
-  struct Frame { const float4* pts[2]; int n[2]; float pose[6]; double time; };
-  std::vector<Frame> frames;
-  // scratch and results: they only grow
-  float4* cat[2] = {nullptr, nullptr}; size_t cat_cap[2] = {0, 0};       // the concatenated, transformed clouds (corner, surface); cat[0] also stages rolo_keymap_downsample's input
-  float4* sub[2] = {nullptr, nullptr}; size_t sub_cap[2] = {0, 0};       // the sub-map (laserCloud*FromMapDS)
-  float4* ds_out = nullptr; size_t ds_cap = 0;                           // rolo_keymap_downsample's result
-  unsigned* keys[2] = {nullptr, nullptr}; size_t keys_cap[2] = {0, 0};
-  int* vals[2] = {nullptr, nullptr}; size_t vals_cap[2] = {0, 0};
-  unsigned* hist = nullptr; size_t hist_cap = 0;
-  unsigned* dtot = nullptr; size_t dtot_cap = 0;   // [4 passes][256 digits]
-  unsigned* bcnt = nullptr; size_t bcnt_cap = 0;
-  int* starts = nullptr; size_t starts_cap = 0;
-  float* box_part = nullptr; size_t box_part_cap = 0;
-  Seg* segs = nullptr; size_t segs_cap = 0;
-  int* d_m = nullptr;                // [2]
-  float* h_box = nullptr;            // pinned [2][8]
-  int* h_m = nullptr;                // pinned [2]
-  Seg* h_segs = nullptr; size_t h_segs_cap = 0;   // pinned staging of the segment table
-  std::vector<void*> retired, retired_host;   // outgrown scratch buffers (device, pinned host), freed by rolo_keymap_destroy
-  int m_sub[2] = {0, 0};
-  bool have_submap = false;
-};
-
 namespace {
-
-// elements; scratch only grows, and an outgrown buffer is kept until rolo_keymap_destroy: a hipFree is a device-wide synchronisation that would stall the frames
-// other contexts have in flight (scan2map.hip), and work queued on the key map's stream may still read the old buffer. Sizes grow by half: the retired ones
-// together stay below twice the live one.
-template <typename T>
-int km_grow(rolo_keymap* km, T*& p, size_t& cap, size_t need) {
-  if (need <= cap && p) return ROLO_OK;
-  if (p) { km->retired.push_back(p); p = nullptr; cap = 0; }
-  const size_t want = need + need / 2 + 256;
-  if (hipMalloc((void**)&p, want * sizeof(T)) != hipSuccess) { ctx_set_error("hipMalloc failed (keymap)"); return ROLO_EHIP; }
-  cap = want;
-  return ROLO_OK;
-}
 
 int km_sort_scratch(rolo_keymap* km, int n) {
   const int nblocks = (n + SORT_TILE - 1) / SORT_TILE, nrun = (n + RUN_TILE - 1) / RUN_TILE;
@@ -477,6 +426,31 @@ int keymap_device_submap(rolo_keymap* km, const float** d_corner, int* m_corner,
   return ROLO_OK;
 }
 void keymap_mark_consumed(rolo_keymap* km) { km->consumer_pending = true; }
+
+int keymap_stage_cloud(rolo_keymap* km, const float* pts, int n, float leaf, const float4** d_out, int* n_out) {
+  KCHK(hipSetDevice(km->device));
+  hipStream_t s = km->stream;
+  int rc;
+  if ((rc = km_grow(km, km->cat[0], km->cat_cap[0], (size_t)n))) return rc;
+  if (!(leaf > 0.f)) {
+    KCHK(hipMemcpyAsync(km->cat[0], pts, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, s));
+    KCHK(hipStreamSynchronize(s));
+    *d_out = km->cat[0]; *n_out = n;
+    return ROLO_OK;
+  }
+  if ((rc = km_sort_scratch(km, n))) return rc;
+  if ((rc = km_grow(km, km->ds_out, km->ds_cap, (size_t)n))) return rc;
+  KCHK(hipMemcpyAsync(km->cat[0], pts, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, s));
+  if ((rc = vg_enqueue_box(km, km->cat[0], n, 0))) return rc;
+  KCHK(hipStreamSynchronize(s));
+  bool direct; int m_direct = 0;
+  if ((rc = vg_enqueue_filter(km, km->cat[0], n, leaf, 0, km->ds_out, &direct, &m_direct))) return rc;
+  KCHK(hipStreamSynchronize(s));
+  const int mm = direct ? m_direct : km->h_m[0];
+  if (mm < 0 || mm > n) { ctx_set_error("the key map's voxel filter returned an inconsistent cell count"); return ROLO_ESTATE; }
+  *d_out = km->ds_out; *n_out = mm;
+  return ROLO_OK;
+}
 }  // namespace rolo
 
 extern "C" {
@@ -506,6 +480,7 @@ void rolo_keymap_destroy(rolo_keymap* km) {
   (void)hipSetDevice(km->device);
   if (km->stream) (void)hipStreamSynchronize(km->stream);
   if (km->consumer_pending && km->consumed) (void)hipEventSynchronize(km->consumed);
+  if (km->sc) { sc_store_destroy(km->sc); km->sc = nullptr; }
   for (auto& c : km->chunks) (void)hipFree(c.p);
   for (void* p : km->retired) (void)hipFree(p);
   for (void* p : km->retired_host) (void)hipHostFree(p);
@@ -630,21 +605,10 @@ int rolo_keymap_downsample(rolo_keymap* km, const float* pts, int n, float leaf,
   if (!km || !m || n < 0 || (n && (!pts || !out)) || !(leaf > 0.f) || n > KM_MAX_POINTS) return ROLO_EINVAL;
   *m = 0;
   if (n == 0) return ROLO_OK;
-  KCHK(hipSetDevice(km->device));
-  hipStream_t s = km->stream;
-  int rc;
-  if ((rc = km_sort_scratch(km, n))) return rc;
-  if ((rc = km_grow(km, km->cat[0], km->cat_cap[0], (size_t)n))) return rc;
-  if ((rc = km_grow(km, km->ds_out, km->ds_cap, (size_t)n))) return rc;
-  KCHK(hipMemcpyAsync(km->cat[0], pts, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, s));
-  if ((rc = vg_enqueue_box(km, km->cat[0], n, 0))) return rc;
-  KCHK(hipStreamSynchronize(s));
-  bool direct; int m_direct = 0;
-  if ((rc = vg_enqueue_filter(km, km->cat[0], n, leaf, 0, km->ds_out, &direct, &m_direct))) return rc;
-  KCHK(hipStreamSynchronize(s));
-  const int mm = direct ? m_direct : km->h_m[0];
-  if (mm < 0 || mm > n) { ctx_set_error("rolo_keymap_downsample: inconsistent cell count"); return ROLO_ESTATE; }
-  if (mm) KCHK(hipMemcpy(out, km->ds_out, sizeof(float4) * (size_t)mm, hipMemcpyDeviceToHost));
+  const float4* d = nullptr; int mm = 0;
+  const int rc = keymap_stage_cloud(km, pts, n, leaf, &d, &mm);
+  if (rc) return rc;
+  if (mm) KCHK(hipMemcpy(out, d, sizeof(float4) * (size_t)mm, hipMemcpyDeviceToHost));
   *m = mm;
   return ROLO_OK;
 }
