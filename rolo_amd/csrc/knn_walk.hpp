@@ -4,8 +4,8 @@
 // Why a packet: with one independent walk per lane the wavefront executes the union of 64 divergent walks and
 // pays the sorted-insert (the expensive part) on almost every visited point because *some* lane accepts it;
 // measured 2.45 ms per 131k-point cloud, vs 0.59 ms for the packet. Here every control decision is wave-uniform:
-//   * seed: the wavefront's own 64 points (64 / KNN_LEAF = 4 consecutive leaves of 16) are scored first, so every lane starts the walk
-//     with a finite search radius;
+//   * seed: the wavefront's own 64 points (64 / KNN_LEAF = 4 consecutive leaves of 16) and a leaf on either side are scored first, so every lane starts the walk
+//     with a finite search radius (k = 20: by sorting / merging networks, knn_seed_net.hpp — nearly every seed candidate is accepted by some lane);
 //   * a node is expanded if ANY lane's search sphere reaches its box (ballot); of two live children the one
 //     nearer to the majority of interested lanes goes first, the other is pushed on ONE small per-wave stack in LDS;
 //   * node boxes and leaf points are fetched through wave-uniform addresses, so a leaf's 16 points are loaded
@@ -44,6 +44,7 @@ ROLO_DEV double* stage_area(const KnnCloud& cl, unsigned add) {
 #ifdef ROLO_KNN_STATS
 __device__ unsigned g_knn_wave_rec[16384][8];   // nodes, leaves, insert executions, pushes, start, end (100 MHz wall clock), lanes live summed over the
                                                  // insert executions, per-leaf maximum over the lanes of the candidates accepted at leaf entry (summed)
+                                                 // (k = 20: the seed leaves go through the networks and count as leaves only — inserts, live lanes and accepted candidates are the tree phase's)
 #endif
 
 // neighbour lists of one finished packet -> the debug lists (rolo_get_knn), the next round's lower bound (k > 64), the slot-major index array for knn_tail_kernel
@@ -115,14 +116,20 @@ static_assert(ROLO_KNN_PACKET == 64, "one query per lane");
 
 // the seeds of a packet: its own 64 / KNN_LEAF leaves first, then ROLO_KNN_SEED_EXTRA leaves on either side (the own points are the nearer ones, so
 // fewer keys are inserted only to be pushed out again: walk 0.1763 -> 0.1725 ms at 2 x 131 072 points, 0.1486 -> 0.1470 at 2 x 43 776)
+// k = 20 without a lower bound (the headline's walk): the seed leaves go through the sort-and-merge networks (knn_seed_leaf) with no bound and no compare, and
+// the lane's bound is taken from the list once, after the last seed — the order of the seeds then changes nothing. Every other form keeps one insert per candidate.
 template <int KMAX, bool LOWER>
-ROLO_DEV void walk_seeds(const float4* __restrict__ sorted, int g_mine0, int g_own0, int g_own1, int n_leaves, const float4& q, double (&K)[KMAX], int kk, double& bkey, float& bd, double lo,
+ROLO_DEV void walk_seeds(const float4* __restrict__ sorted, int g_mine0, int g_own0, int g_own1, int n_leaves, const float4& q, bool active, double (&K)[KMAX], int kk, double& bkey, float& bd, double lo,
                          unsigned& st_leaves, unsigned& st_ins, unsigned& st_lane, unsigned& st_rounds) {
   const int n_own = min(g_mine0 + 64 / KNN_LEAF, n_leaves) - g_mine0, n_before = g_mine0 - g_own0;
   for (int i = 0; i < g_own1 - g_own0; i++) {
     const int g = i < n_own ? g_mine0 + i : (i - n_own < n_before ? g_own0 + (i - n_own) : g_mine0 + (i - n_before));
-    knn_score_leaf<KMAX, LOWER>(sorted, g, q, K, kk, bkey, bd, st_ins, st_lane, st_rounds, lo);
+    if constexpr (KMAX == 20 && !LOWER) knn_seed_leaf(sorted, g, q, K);
+    else knn_score_leaf<KMAX, LOWER>(sorted, g, q, K, kk, bkey, bd, st_ins, st_lane, st_rounds, lo);
     st_leaves++;
+  }
+  if constexpr (KMAX == 20 && !LOWER) {
+    if (active) { bkey = K[KMAX - 1]; bd = key_d2(bkey); }   // (padding lanes keep bd = -1 and the key nothing is below)
   }
 }
 
@@ -165,7 +172,7 @@ __global__ __launch_bounds__(256, KMAX > 32 ? 2 : (MOMENTS ? 6 : ROLO_KNN_WALK_O
   double lo = 0.0;
   if (LOWER && active) lo = A.c[which].lower[j];
   (void)lo;
-  walk_seeds<KMAX, LOWER>(sorted, g_mine0, g_own0, g_own1, n_leaves, q, K, kk, bkey, bd, lo, st_leaves, st_ins, st_lane, st_rounds);
+  walk_seeds<KMAX, LOWER>(sorted, g_mine0, g_own0, g_own1, n_leaves, q, active, K, kk, bkey, bd, lo, st_leaves, st_ins, st_lane, st_rounds);
 
   // ---- packet walk ----
   // (a stack in one vector register — slot i in lane i, v_writelane / v_readlane — measured the same as this LDS stack: 0.202 vs 0.200 ms;
@@ -223,18 +230,7 @@ template <int ST> ROLO_DEV void merge20(double (&K)[20]) {
     K[j] = vmin_f64(K[j], o1);
     K[19 - j] = vmin_f64(K[19 - j], o2);
   }
-#pragma unroll
-  for (int d = 16; d >= 1; d >>= 1) {
-#pragma unroll
-    for (int p = 12; p < 32; p++) {
-      if ((p & d) == 0) {
-        const int x = p - 12, y = p + d - 12;
-        const double lo = vmin_f64(K[x], K[y]);
-        K[y] = vmax_f64(K[x], K[y]);
-        K[x] = lo;
-      }
-    }
-  }
+  seednet::bitonic_clean<20, 0, false>(K, KeyMin(), KeyMax());
 }
 
 template <int SUB, bool MOMENTS = false>
@@ -288,8 +284,10 @@ __global__ __launch_bounds__(256, MOMENTS ? 6 : ROLO_KNN_WALK_OCC) void knn_walk
   // ---- seeds: the wavefront's own leaves, then ROLO_KNN_SEED_EXTRA leaves on either side along the curve ----
   const int g_mine = min(j0 / KNN_LEAF, n_leaves - 1);
   const int g_own0 = max(g_mine - ROLO_KNN_SEED_EXTRA, 0), g_own1 = min(g_mine + OWN + ROLO_KNN_SEED_EXTRA, n_leaves);
-  for (int g = g_mine; g < min(g_mine + OWN, n_leaves); g++) score(g);
-  for (int g = g_own0; g < g_own1; g++) if (g < g_mine || g >= g_mine + OWN) score(g);
+  // (through the networks, as the packets' seeds: a lane's share of a leaf is one chunk of PPL = 8 or 4 candidates; the shared bound is taken once, after the last seed)
+  for (int g = g_own0; g < g_own1; g++) seed_chunk<PPL, SUB>(sorted + KNN_LEAF * (size_t)g, sub, q, K);
+  B = vmin_f64(vmin_f64(B, sub_min<SUB>(K[KMAX - 1])), sub_max<SUB>(K[KMAX / SUB - 1]));
+  if (active) bd = key_d2(B);   // (an idle query keeps bd = -1 and reaches no box)
   // ---- the walk ----
   {
     lds_int* stk = (lds_int*)&stk_[wv][0];
