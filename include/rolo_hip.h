@@ -516,6 +516,67 @@ int rolo_keymap_sc_detect(rolo_keymap* km, int query, int n_search, rolo_sc_resu
 /* device time of the last rolo_keymap_sc_add_* / rolo_keymap_sc_detect call in milliseconds, between two events on the key map's stream (profiles/tools/sc_time.py) */
 float rolo_keymap_sc_last_ms(rolo_keymap* km);
 
+/* ---- back end: loop-closure ICP from the resident key frames ----------------------------------------------------------------------------
+ * performRSLoopClosure / performSCLoopClosure (src/backMapping.cpp:2307-2479) without the factor graph: two clouds built from key frames
+ * (loopFindNearKeyframes[WithRespectTo] :2572-2624) are aligned with pcl::IterativeClosestPoint as the reference configures it (SVD estimation, no rejectors,
+ * no RANSAC) and accepted or rejected on getFitnessScore. PCL is not in the reference tree: the contract is this statement (tests/icp_twin.py restates it in
+ * numpy; parity with a PCL build is unpinned).
+ *   setup      the source is moved by the guess (each row T0 x + (T1 y + (T2 z + T3)) in float, no contraction; NULL or the identity: not at all), the target gets
+ *              the neighbour search's curve-sorted implicit BVH, the moved source is sorted along the same curve once and stays on the device
+ *   iteration  every source point's exact nearest target point in float, d2 = ((dx dx) + (dy dy)) + (dz dz) with dx = source - target, ties to the smallest
+ *              target index; the pair is kept when (double)d2 <= max_correspondence_distance^2. Over the kept pairs n, sum d2, sum p, sum q and sum p q^T in fp64,
+ *              per workgroup and then over the workgroups in a fixed order (no floating-point atomics: the same bits on every run).
+ *              n < min_correspondences: state NO_CORRESPONDENCES, not converged, stop. Otherwise Umeyama without scaling in double on the host:
+ *              Sigma = sum q p^T / n - mean(q) mean(p)^T, Sigma = U S V^T, R = U diag(1, 1, s) V^T with s = -1 when det U det V < 0 (for a rank-2 Sigma this is
+ *              Eigen's rank rule), t = mean(q) - R mean(p); the increment is rounded to float, the moved source is multiplied by it in float (PCL's
+ *              progressive form) and final = increment * final in float (each entry a0 b0 + a1 b1 + a2 b2 + a3 b3, left to right).
+ *   exit       in this order, with the count of finished iterations: iterations >= max_iterations -> ITERATIONS; cos = 0.5 (tr R - 1) >= rot_thr and |t|^2 <=
+ *              transformation_epsilon (R, t of the float increment, in double; rot_thr = rotation_epsilon if > 0, else 1 - transformation_epsilon) -> TRANSFORM;
+ *              mse = sum d2 / n < 1e-12 -> ABS_MSE; |mse - prev| / prev < euclidean_fitness_epsilon -> REL_MSE; else prev = mse (prev starts at DBL_MAX).
+ *   fitness    getFitnessScore(): one more association of the moved source without a cap; the mean of d2 over the pairs (DBL_MAX without one). */
+#define ROLO_ICP_NOT_CONVERGED 0
+#define ROLO_ICP_ITERATIONS 1
+#define ROLO_ICP_TRANSFORM 2
+#define ROLO_ICP_ABS_MSE 3
+#define ROLO_ICP_REL_MSE 4
+#define ROLO_ICP_NO_CORRESPONDENCES 5
+typedef struct rolo_loopicp_params { int max_iterations; double transformation_epsilon, euclidean_fitness_epsilon, rotation_epsilon /* <= 0: not given */;
+                                     double max_correspondence_distance; int min_correspondences; } rolo_loopicp_params;
+typedef struct rolo_loopicp_result { float T[16]; double fitness; int converged, iterations, state, n_source, n_target, n_last; } rolo_loopicp_result;
+/* one association of an alignment: the kept pairs, their mean d2, the 17 sums (n, sum d2, sum p [3], sum q [3], sum p q^T [9] row-major) and the float increment
+ * estimated from them (zeros where the alignment stopped before estimating) */
+typedef struct rolo_loopicp_trace_rec { int n; double mse; double sums[17]; float increment[16]; } rolo_loopicp_trace_rec;
+/* 100 iterations, transformation epsilon 1e-6, fitness epsilon 1e-6 (:2343-2345, :2432-2434), no rotation epsilon, min_correspondences 3; the cap
+ * (setMaxCorrespondenceDistance) is the caller's: 2 * historyKeyframeSearchRadius or 150 m in the reference, +infinity here */
+void rolo_loopicp_default_params(rolo_loopicp_params* p);
+/* loopFindNearKeyframes (wrt_key < 0) / loopFindNearKeyframesWithRespectTo (wrt_key >= 0) into the key map's resident loop cloud `slot` (0: source, 1: target):
+ * for keyNear = key - search_num .. key + search_num inside the store, the corner and then the surface cloud of keyNear moved by keyNear's own pose (by wrt_key's
+ * pose in the second form), all concatenated in that order, then ONE pcl::VoxelGrid of `leaf` (downSizeFilterICP, mappingSurfLeafSize) over the whole cloud.
+ * *m receives the size; 0 is a valid result (an empty store, empty frames). key or a non-negative wrt_key outside the store is ROLO_EINVAL (an empty store
+ * takes any key). The clouds stay on the device under the key map's rules: its stream, buffers that only grow. */
+int rolo_keymap_loop_cloud(rolo_keymap* km, int slot, int key, int search_num, int wrt_key, float leaf, int* m);
+int rolo_keymap_get_loop_cloud(rolo_keymap* km, int slot, float* out, int cap);
+/* detectLoopClosureDistance (:2481-2515), host only: radius search around the LAST key pose under rolo_keyposes_select_nearby's rule (squared float distance below
+ * radius^2, ascending by (distance, index)); the first hit with |time - time_cur| > time_diff is the candidate. *loop_key_pre receives its index, or -1 when no
+ * hit qualifies or the candidate is the last key itself (the "already has a loop" map stays with the caller). */
+int rolo_keyposes_detect_loop_distance(const float* xyz, const double* times, int n, float search_radius, double time_diff, double time_cur, int32_t* loop_key_pre);
+/* icp.align + getFitnessScore on the key map's two loop clouds (slot 0 onto slot 1); guess16: row-major 4 x 4 or NULL. An empty cloud gives state NO_CORRESPONDENCES.
+ * The tree and the walk run in a registration context the key map takes from the pool (rolo_ctx_acquire) and keeps until rolo_keymap_destroy. */
+int rolo_keymap_loop_icp(rolo_keymap* km, const rolo_loopicp_params* params, const float* guess16, rolo_loopicp_result* out);
+/* the same on two host clouds (n x 4 floats) in a caller's context, whose source / target clouds it overwrites */
+int rolo_loopicp_align(rolo_ctx* ctx, const float* source, int n_source, const float* target, int n_target, const rolo_loopicp_params* params, const float* guess16,
+                       rolo_loopicp_result* out);
+/* the associations of the last alignment in order, the fitness pass last; returns their number and writes the first min(number, cap) */
+int rolo_loopicp_get_trace(rolo_ctx* ctx, rolo_loopicp_trace_rec* out, int cap);
+int rolo_keymap_loop_trace(rolo_keymap* km, rolo_loopicp_trace_rec* out, int cap);
+/* test hook: one association of T16 * source (NULL: source as it is) against target; per source point the target index and d2, or -1 and +infinity beyond the cap */
+int rolo_loopicp_associate(rolo_ctx* ctx, const float* source, int n_source, const float* target, int n_target, const float* T16, double max_correspondence_distance,
+                           int32_t* index_out, float* d2_out);
+/* device time of the last alignment in milliseconds between HIP events: ms4[0] set-up (guess, sort, tree), [1] all iterations, [2] the fitness pass, [3] the whole call;
+ * rolo_keymap_loop_last_ms adds ms6[4] / ms6[5]: the last rolo_keymap_loop_cloud of slot 0 / slot 1 */
+int rolo_loopicp_last_ms(rolo_ctx* ctx, float* ms4);
+int rolo_keymap_loop_last_ms(rolo_keymap* km, float* ms6);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,20 @@ class ScResult(C.Structure):
                 ("n_candidates", C.c_int)]
 
 
+class LoopIcpParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int), ("transformation_epsilon", C.c_double), ("euclidean_fitness_epsilon", C.c_double), ("rotation_epsilon", C.c_double),
+                ("max_correspondence_distance", C.c_double), ("min_correspondences", C.c_int)]
+
+
+class LoopIcpResult(C.Structure):
+    _fields_ = [("T", C.c_float * 16), ("fitness", C.c_double), ("converged", C.c_int), ("iterations", C.c_int), ("state", C.c_int), ("n_source", C.c_int),
+                ("n_target", C.c_int), ("n_last", C.c_int)]
+
+
+class LoopIcpTraceRec(C.Structure):
+    _fields_ = [("n", C.c_int), ("mse", C.c_double), ("sums", C.c_double * 17), ("increment", C.c_float * 16)]
+
+
 class EskfOptions(C.Structure):   # include/rolo_fusion.h
     _fields_ = [(k, C.c_double) for k in ("max_dt", "q_linear_jerk_std", "q_angular_jerk_std", "r_position_std", "r_rotation_std", "init_position_std",
                                           "init_rotation_std", "init_velocity_std", "init_angular_velocity_std", "init_acceleration_std",
@@ -157,6 +171,17 @@ SYMBOLS = {
     "rolo_keymap_sc_get": (C.c_int, [vp, C.c_int, dp, fp, dp, dp]),
     "rolo_keymap_sc_detect": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(ScResult), ip, dp, ip, C.c_int]),
     "rolo_keymap_sc_last_ms": (C.c_float, [vp]),
+    "rolo_loopicp_default_params": (None, [C.POINTER(LoopIcpParams)]),
+    "rolo_keymap_loop_cloud": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int)]),
+    "rolo_keymap_get_loop_cloud": (C.c_int, [vp, C.c_int, fp, C.c_int]),
+    "rolo_keyposes_detect_loop_distance": (C.c_int, [fp, dp, C.c_int, C.c_float, C.c_double, C.c_double, ip]),
+    "rolo_keymap_loop_icp": (C.c_int, [vp, C.POINTER(LoopIcpParams), fp, C.POINTER(LoopIcpResult)]),
+    "rolo_loopicp_align": (C.c_int, [vp, fp, C.c_int, fp, C.c_int, C.POINTER(LoopIcpParams), fp, C.POINTER(LoopIcpResult)]),
+    "rolo_loopicp_get_trace": (C.c_int, [vp, C.POINTER(LoopIcpTraceRec), C.c_int]),
+    "rolo_keymap_loop_trace": (C.c_int, [vp, C.POINTER(LoopIcpTraceRec), C.c_int]),
+    "rolo_loopicp_associate": (C.c_int, [vp, fp, C.c_int, fp, C.c_int, fp, C.c_double, ip, fp]),
+    "rolo_loopicp_last_ms": (C.c_int, [vp, fp]),
+    "rolo_keymap_loop_last_ms": (C.c_int, [vp, fp]),
     "rolo_num_voxels": (C.c_int, [vp]),
     "rolo_num_edge_points": (C.c_int, [vp]),
     "rolo_get_voxels": (C.c_int, [vp, ip, ip, dp, dp]),

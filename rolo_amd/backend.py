@@ -1,13 +1,13 @@
 """Host mirrors of the back end: the scan-to-submap optimisation (reference src/backMapping.cpp:681-1058) over rolo_scan2map_optimize, the
-device-resident key frames with sub-map assembly (:558-678) over rolo_keymap_* and Scan Context loop detection (src/scancontext/Scancontext.cpp) over
-rolo_keymap_sc_*."""
+device-resident key frames with sub-map assembly (:558-678) over rolo_keymap_*, Scan Context loop detection (src/scancontext/Scancontext.cpp) over
+rolo_keymap_sc_* and the loop closure's clouds, radius-search detector and ICP (:2307-2624) over rolo_keymap_loop_* / rolo_loopicp_*."""
 from __future__ import annotations
 
 import ctypes as C
 
 import numpy as np
 
-from ._lib import lib, check, Scan2MapStats, ScParams, ScResult
+from ._lib import lib, check, Scan2MapStats, ScParams, ScResult, LoopIcpParams, LoopIcpResult, LoopIcpTraceRec
 from .rotvgicp import RotVGICP
 
 
@@ -64,6 +64,88 @@ def select_nearby(xyz, times, time_cur, search_radius=50.0, density=2.0, recent_
                                                 out.ctypes.data_as(ip), out.shape[0]), "rolo_keyposes_select_nearby")
     assert m <= out.shape[0]
     return out[:m].copy()
+
+
+def detect_loop_distance(xyz, times, time_cur, search_radius=30.0, time_diff=30.0) -> int:
+    """detectLoopClosureDistance (:2481-2515) without its loopIndexContainer test: the nearest key pose within search_radius of the last one that is more than
+    time_diff away from time_cur, or -1 (none, or the last key itself); host only"""
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    times = np.ascontiguousarray(times, np.float64).reshape(-1)
+    assert times.shape[0] == xyz.shape[0]
+    pre = C.c_int32(-1)
+    check(lib().rolo_keyposes_detect_loop_distance(xyz.ctypes.data_as(C.POINTER(C.c_float)), times.ctypes.data_as(C.POINTER(C.c_double)), xyz.shape[0],
+                                                   search_radius, time_diff, time_cur, C.byref(pre)), "rolo_keyposes_detect_loop_distance")
+    return pre.value
+
+
+def loop_icp_params(max_correspondence_distance=np.inf, **kw) -> LoopIcpParams:
+    """the reference's ICP settings (:2342-2346): 100 iterations, both epsilons 1e-6; fields of rolo_loopicp_params by keyword"""
+    p = LoopIcpParams()
+    lib().rolo_loopicp_default_params(C.byref(p))
+    p.max_correspondence_distance = max_correspondence_distance
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def _icp_result(res: LoopIcpResult) -> dict:
+    return dict(T=np.array(res.T, np.float32).reshape(4, 4), fitness=res.fitness, converged=bool(res.converged), iterations=res.iterations, state=res.state,
+                n_source=res.n_source, n_target=res.n_target, n_last=res.n_last)
+
+
+def _icp_trace(fn, handle):
+    n = check(fn(handle, None, 0), "loop ICP trace")
+    recs = (LoopIcpTraceRec * max(n, 1))()
+    check(fn(handle, recs, n), "loop ICP trace")
+    return [dict(n=r.n, mse=r.mse, sums=np.array(r.sums, np.float64), increment=np.array(r.increment, np.float32).reshape(4, 4)) for r in recs[:n]]
+
+
+def _guess_ptr(guess):
+    if guess is None:
+        return None, None
+    g = np.ascontiguousarray(guess, np.float32).reshape(16)
+    return g, g.ctypes.data_as(C.POINTER(C.c_float))
+
+
+class LoopIcp:
+    """pcl::IterativeClosestPoint as the loop closure configures it, on two host clouds (n x 4 floats): the route for users without a key map, and the tests'"""
+    STATES = ("NOT_CONVERGED", "ITERATIONS", "TRANSFORM", "ABS_MSE", "REL_MSE", "NO_CORRESPONDENCES")
+
+    def __init__(self, device: int = 0):
+        self.reg = RotVGICP(device)   # a context of its own: its clouds hold the target's tree
+
+    def close(self):
+        self.reg.close()
+
+    def align(self, source, target, params: LoopIcpParams = None, guess=None) -> dict:
+        fp = C.POINTER(C.c_float)
+        a = [np.ascontiguousarray(x, np.float32).reshape(-1, 4) for x in (source, target)]
+        res = LoopIcpResult()
+        keep, g = _guess_ptr(guess)
+        check(lib().rolo_loopicp_align(self.reg._h, a[0].ctypes.data_as(fp), a[0].shape[0], a[1].ctypes.data_as(fp), a[1].shape[0],
+                                       C.byref(params if params is not None else loop_icp_params()), g, C.byref(res)), "rolo_loopicp_align")
+        return _icp_result(res)
+
+    def trace(self):
+        """one record per association of the last align, the fitness pass last"""
+        return _icp_trace(lib().rolo_loopicp_get_trace, self.reg._h)
+
+    def associate(self, source, target, T=None, max_correspondence_distance=np.inf):
+        """test hook: (target index, d2) of every source point moved by T, -1 / inf beyond the cap"""
+        fp = C.POINTER(C.c_float)
+        a = [np.ascontiguousarray(x, np.float32).reshape(-1, 4) for x in (source, target)]
+        idx = np.zeros(a[0].shape[0], np.int32); d2 = np.zeros(a[0].shape[0], np.float32)
+        keep, g = _guess_ptr(T)
+        check(lib().rolo_loopicp_associate(self.reg._h, a[0].ctypes.data_as(fp), a[0].shape[0], a[1].ctypes.data_as(fp), a[1].shape[0], g, max_correspondence_distance,
+                                           idx.ctypes.data_as(C.POINTER(C.c_int32)), d2.ctypes.data_as(fp)), "rolo_loopicp_associate")
+        return idx, d2
+
+    def lastMs(self):
+        """device milliseconds of the last align: set-up, iterations, fitness pass, whole call"""
+        ms = np.zeros(4, np.float32)
+        check(lib().rolo_loopicp_last_ms(self.reg._h, ms.ctypes.data_as(C.POINTER(C.c_float))), "rolo_loopicp_last_ms")
+        return ms
 
 
 class KeyFrameMap:
@@ -183,6 +265,41 @@ class KeyFrameMap:
     def scLastMs(self) -> float:
         return float(lib().rolo_keymap_sc_last_ms(self._h))
 
+    # ---- loop closure (:2307-2624): the two loop clouds and their ICP, resident beside the key frames ----
+    def loopCloud(self, slot: int, key: int, search_num: int, wrt_key: int = None, leaf: float = None) -> int:
+        """loopFindNearKeyframes (:2572-2596), or ...WithRespectTo (:2598-2624) with wrt_key, into slot 0 (source) or 1 (target); returns the cloud's size"""
+        m = C.c_int(0)
+        check(lib().rolo_keymap_loop_cloud(self._h, slot, key, search_num, -1 if wrt_key is None else wrt_key, self.surf_leaf if leaf is None else leaf, C.byref(m)),
+              "rolo_keymap_loop_cloud")
+        return m.value
+
+    def loopCloudPoints(self, slot: int, m: int):
+        """download of a loop cloud (m: the size loopCloud returned)"""
+        out = np.zeros((m, 4), np.float32)
+        got = check(lib().rolo_keymap_get_loop_cloud(self._h, slot, out.ctypes.data_as(C.POINTER(C.c_float)), m), "rolo_keymap_get_loop_cloud")
+        return out[:got].copy()
+
+    def loopIcp(self, params: LoopIcpParams = None, guess=None) -> dict:
+        """icp.align + getFitnessScore of slot 0 onto slot 1"""
+        res = LoopIcpResult()
+        keep, g = _guess_ptr(guess)
+        check(lib().rolo_keymap_loop_icp(self._h, C.byref(params if params is not None else loop_icp_params()), g, C.byref(res)), "rolo_keymap_loop_icp")
+        return _icp_result(res)
+
+    def loopTrace(self):
+        return _icp_trace(lib().rolo_keymap_loop_trace, self._h)
+
+    def loopLastMs(self):
+        """device milliseconds: ICP set-up, iterations, fitness pass, whole ICP call, assembly of slot 0, assembly of slot 1"""
+        ms = np.zeros(6, np.float32)
+        check(lib().rolo_keymap_loop_last_ms(self._h, ms.ctypes.data_as(C.POINTER(C.c_float))), "rolo_keymap_loop_last_ms")
+        return ms
+
+    def detect_loop_distance(self, time_cur: float, search_radius: float = 30.0, time_diff: float = 30.0) -> int:
+        """detectLoopClosureDistance (:2481-2515) on the stored key poses"""
+        xyz = np.array([p[3:6] for p in self.poses], np.float32).reshape(-1, 3)
+        return detect_loop_distance(xyz, self.times, time_cur, search_radius, time_diff)
+
 
 class ScanContextManager:
     """SCManager's two user calls over a key map's descriptor store. detectLoopClosureID keeps the reference's rebuild-period counter and its stale searched set
@@ -218,3 +335,71 @@ class ScanContextManager:
         self.tree_making_period_counter += 1
         self.last = self.km.scDetect(n - 1, self.n_search)
         return self.last.loop_id, np.float32(self.last.yaw_diff_rad)
+
+
+def pose6_to_T(pose6, dtype=np.float32):
+    """pcl::getTransformation(x, y, z, roll, pitch, yaw) of a transformTobeMapped-order pose (roll, pitch, yaw, x, y, z), 4 x 4 in `dtype` arithmetic"""
+    r, p, y, tx, ty, tz = (dtype(v) for v in pose6)
+    A, B, Cc, D, E, F = np.cos(y), np.sin(y), np.cos(p), np.sin(p), np.cos(r), np.sin(r)
+    DE, DF = D * E, D * F
+    return np.array([[A * Cc, A * DF - B * E, B * F + A * DE, tx], [B * Cc, A * E + B * DF, B * DE - A * F, ty], [-D, Cc * F, Cc * E, tz], [0, 0, 0, 1]], dtype)
+
+
+class LoopCloser:
+    """performRSLoopClosure (:2307-2397) and performSCLoopClosure (:2399-2479) over a key map, up to the factor graph: each call returns
+    (loopKeyCur, loopKeyPre, poseFrom 4 x 4, poseTo 4 x 4, noise) — the constraint is poseFrom.between(poseTo) with the variance `noise` on all six axes — or None."""
+    MIN_CUR, MIN_PREV = 300, 1000   # :2333, :2424
+    SC_CAP = 150.0                  # :2431
+
+    def __init__(self, keymap: KeyFrameMap, historyKeyframeSearchRadius: float = 30.0, historyKeyframeSearchTimeDiff: float = 30.0, historyKeyframeSearchNum: int = 25,
+                 historyKeyframeFitnessScore: float = 0.3, sc_yaw_guess: float = 0.0):
+        """sc_yaw_guess: the SC form's ICP starts from pcl::getTransformation(0, 0, 0, 0, 0, sc_yaw_guess * yawDiffRad). 0 (default) is the reference as written: it
+        computes the guess and aligns without it (:2437-2443); +1 is its commented-out line; -1 turns the current scan onto the loop scan when key 0's pose is the
+        origin (yawDiffRad is the turn from the loop scan to the current one)."""
+        self.km = keymap
+        self.sc_yaw_guess = sc_yaw_guess
+        self.radius, self.time_diff, self.search_num, self.fitness_score = historyKeyframeSearchRadius, historyKeyframeSearchTimeDiff, historyKeyframeSearchNum, historyKeyframeFitnessScore
+        self.loopIndexContainer = {}
+        self.last = None   # the last ICP result, also of a rejected loop
+
+    def _align(self, cur, pre, wrt_key, cap, guess=None):
+        self.last = None
+        n_cur = self.km.loopCloud(0, cur, 0, wrt_key)
+        n_pre = self.km.loopCloud(1, pre, self.search_num, wrt_key)
+        if n_cur < self.MIN_CUR or n_pre < self.MIN_PREV:
+            return None
+        self.last = self.km.loopIcp(loop_icp_params(cap), guess)
+        if not self.last["converged"] or self.last["fitness"] > self.fitness_score:   # :2354, :2445
+            return None
+        return self.last
+
+    def performRSLoopClosure(self, time_cur: float):
+        if len(self.km.poses) == 0:
+            return None
+        cur = len(self.km.poses) - 1
+        if cur in self.loopIndexContainer:   # :2487-2489
+            return None
+        pre = self.km.detect_loop_distance(time_cur, self.radius, self.time_diff)
+        if pre < 0:
+            return None
+        res = self._align(cur, pre, None, 2.0 * self.radius)   # :2342
+        if res is None:
+            return None
+        t_wrong = pose6_to_T(self.km.poses[cur])
+        t_correct = (res["T"].astype(np.float32) @ t_wrong).astype(np.float64)   # :2377
+        self.loopIndexContainer[cur] = pre
+        return cur, pre, t_correct, pose6_to_T(self.km.poses[pre], np.float64), np.float32(res["fitness"])
+
+    def performSCLoopClosure(self, sc_manager: "ScanContextManager"):
+        if len(self.km.poses) == 0:
+            return None
+        pre, yaw = sc_manager.detectLoopClosureID()
+        cur = len(self.km.poses) - 1
+        if pre == -1 or cur == pre:
+            return None
+        guess = pose6_to_T([0.0, 0.0, np.float32(self.sc_yaw_guess) * np.float32(yaw), 0.0, 0.0, 0.0]) if self.sc_yaw_guess != 0.0 else None
+        res = self._align(cur, pre, 0, self.SC_CAP, guess)   # baseKey 0, :2421-2423
+        if res is None:
+            return None
+        self.loopIndexContainer[cur] = pre
+        return cur, pre, res["T"].astype(np.float64), np.eye(4), np.float32(res["fitness"])

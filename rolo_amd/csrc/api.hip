@@ -237,9 +237,10 @@ int fetch_state(rolo_ctx* c) {
   return ROLO_OK;
 }
 
-// accessors for front.hip / odometry.hip / scan2map.hip / submap.hip (the context layout is private to the host units that share ctx.hpp)
+// accessors for front.hip / odometry.hip / scan2map.hip / submap.hip / loopicp.hip (the context layout is private to the host units that share ctx.hpp)
 void** ctx_front_slot(rolo_ctx* c) { return &c->front; }
 void** ctx_s2m_slot(rolo_ctx* c) { return &c->s2m; }
+void** ctx_loop_slot(rolo_ctx* c) { return &c->loop; }
 unsigned long long ctx_cloud_epoch(rolo_ctx* c) { return c->cloud_epoch; }
 hipStream_t ctx_stream(rolo_ctx* c) { return c->stream; }
 int ctx_device(rolo_ctx* c) { return c->device; }
@@ -398,6 +399,7 @@ static int ctx_create_impl(int device, bool high_priority, rolo_ctx** out) {
 
 void rolo_front_destroy(rolo_ctx* c);  // front.hip
 void rolo_s2m_destroy(rolo_ctx* c);    // scan2map.hip
+void rolo_loopicp_destroy(rolo_ctx* c);   // loopicp.hip
 void rolo_s2m_forget(rolo_ctx* c);     // scan2map.hip: a context going back to the pool forgets its resident sub-map and gives its helper context back
 }
 namespace rolo { void front_reset_object_state(rolo_ctx* c); }   // front.hip
@@ -410,6 +412,7 @@ void rolo_ctx_destroy(rolo_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   rolo_front_destroy(c);
   rolo_s2m_destroy(c);
+  rolo_loopicp_destroy(c);
   peer_release(c);
   if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
   void* bufs[] = {c->src.nrm, c->tgt.nrm, c->src.bbox_part, c->tgt.bbox_part, c->src.xyz, c->src.cov, c->src.sorted, c->src.boxes, c->src.knn_idx, c->src.knn_d2, c->tgt.xyz, c->tgt.cov, c->tgt.sorted,

@@ -184,6 +184,7 @@ struct rolo_ctx {
   // front end (front.hip)
   void* front = nullptr;
   void* s2m = nullptr;   // scan2map.hip scratch
+  void* loop = nullptr;  // loopicp.hip scratch
   unsigned long long cloud_epoch = 0;   // bumped whenever the source / target clouds (or their buffers) change hands: the resident sub-map of rolo_scan2map_set_submap lives in them
 };
 

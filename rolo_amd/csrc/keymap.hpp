@@ -46,6 +46,14 @@ struct rolo_keymap {
   int m_sub[2] = {0, 0};
   bool have_submap = false;
   rolo::ScStore* sc = nullptr;       // the Scan Context descriptors (scancontext.hip), created by the first rolo_keymap_sc_* call
+  // loop closure (rolo_keymap_loop_cloud in submap.hip, rolo_keymap_loop_icp in loopicp.hip): the two resident loop clouds, 0 source, 1 target. Both calls wait for
+  // their streams before they return, so neither needs an event to order the other
+  float4* loop[2] = {nullptr, nullptr}; size_t loop_cap[2] = {0, 0};
+  int m_loop[2] = {0, 0};
+  bool have_loop[2] = {false, false};
+  float loop_ms[2] = {0.f, 0.f};     // device time of the last assembly per slot
+  hipEvent_t loop_t0 = nullptr, loop_t1 = nullptr;   // with timing, created by the first assembly
+  rolo_ctx* loop_ctx = nullptr;      // the pooled registration context whose tree builder and stream the ICP uses; given back by rolo_keymap_destroy
 };
 
 namespace rolo {

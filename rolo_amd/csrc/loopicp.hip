@@ -1,0 +1,532 @@
+// The loop closure's ICP on gfx950: pcl::IterativeClosestPoint as performRSLoopClosure / performSCLoopClosure configure it (reference src/backMapping.cpp:2339-2354,
+// :2430-2446: SVD estimation, no rejectors, no RANSAC) and getFitnessScore, on two clouds that are on the device already (the key map's loop clouds, submap.hip
+// rolo_keymap_loop_cloud) or come from the host (rolo_loopicp_align). PCL is not in the reference tree: the contract is the statement in include/rolo_hip.h, which
+// tests/icp_twin.py restates in numpy.
+//
+// MI355X design: the target gets the Hilbert-sorted implicit BVH of the neighbour search (knn_cov.hip, through ctx_build_map_trees) once per call, and the same build
+// sorts the source, moved by the guess, along the same curve. A rigid motion keeps neighbours neighbours, so 64 consecutive source points stay one blob over all
+// iterations: one wavefront walks the target's tree once for its 64 queries (ballot-driven descent, node boxes and leaves through wave-uniform fetches, as
+// knn_packet.hpp's walk) with ONE best key per lane, (d2, index) packed so that an integer minimum is the nearest point with the smallest index. The search starts
+// at the correspondence cap, so a source point beyond it leaves the tree at the root. The same kernel forms the 17 fp64 sums of the kept pairs and reduces them per
+// workgroup; icp_sum_kernel adds the workgroups' rows in a fixed order into pinned host memory (one 136-byte read-back per iteration, the precedent of scan2map.hip).
+// The 3 x 3 SVD and the convergence tests run on the host in double; icp_transform_kernel multiplies the resident source by the float increment.
+// The tree and the walk live in a registration context (its stream, its builder); the scratch hangs off that context, only grows and is freed with it.
+#include "keymap.hpp"
+#include "knn_packet.hpp"
+#include <cfloat>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+namespace rolo {
+int ctx_build_map_trees(rolo_ctx* c, const float* corner, int nc, const float* surf, int ns, int stride, KnnPair* out, bool on_device = false);   // api.hip
+void** ctx_loop_slot(rolo_ctx* c);
+hipStream_t ctx_stream(rolo_ctx* c);
+int ctx_device(rolo_ctx* c);
+
+namespace {
+
+constexpr int ICP_THREADS = 256;
+constexpr int ICP_NV = 17;   // n, sum d2, sum p (3), sum q (3), sum p q^T (9, row = p, column = q)
+
+struct IcpArgs {
+  const float4* cur;       // the moved source in curve order: x, y, z, bits(index in the caller's order); padding: index INT_MAX
+  int n_sorted;
+  const float4* tsorted;   // the target's tree
+  const float4* tboxes;
+  const float4* txyz;      // the target in the caller's order
+  int P, n_leaves;
+  float cap2;              // the largest float whose double is <= max_correspondence_distance^2
+  double* partials;        // grid x ICP_NV
+  int32_t* idx_out;        // per source point in the caller's order (tests), or nullptr
+  float* d2_out;
+};
+
+ROLO_DEV unsigned long long icp_key(float d2, int idx) { return ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)idx; }
+
+__global__ __launch_bounds__(ICP_THREADS) void icp_assoc_kernel(IcpArgs A) {
+  __shared__ int stk_[ICP_THREADS / 64][WALK_STACK];
+  __shared__ double red[ICP_THREADS / 64][ICP_NV];
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int j = blockIdx.x * ICP_THREADS + threadIdx.x;
+  float4 qs = make_float4(0.f, 0.f, 0.f, __int_as_float(INT_MAX));
+  if (j < A.n_sorted) qs = A.cur[j];
+  const int qidx = __float_as_int(qs.w);
+  const bool active = qidx != INT_MAX;
+  const float4 q = make_float4(active ? qs.x : 0.f, active ? qs.y : 0.f, active ? qs.z : 0.f, 0.f);
+  // a real candidate's index is below INT_MAX: a pair at exactly the cap sorts below this key and is kept; an idle lane accepts nothing
+  unsigned long long best = active ? icp_key(A.cap2, INT_MAX) : 0ull;
+  float bd = active ? A.cap2 : -1.0f;
+  {
+    const float4* __restrict__ sorted = A.tsorted;
+    const float4* __restrict__ boxes = A.tboxes;
+    const int P = A.P, n_leaves = A.n_leaves;
+    lds_int* stk = (lds_int*)&stk_[wv][0];
+    int sp = 0, h = 1;
+    while (true) {   // (no store ahead of or inside this loop: the node and leaf fetches stay scalar, knn_packet.hpp's clobber rule)
+      h = __builtin_amdgcn_readfirstlane(h);
+      if (h < P) {
+        float4 llo, lhi, rlo, rhi;
+        sload_node(boxes + 4 * (size_t)h, llo, lhi, rlo, rhi);
+        const float bl = box_d2(llo, lhi, q), br = box_d2(rlo, rhi, q);
+        const bool okl = (bl <= bd) && (bl < INFINITY), okr = (br <= bd) && (br < INFINITY);   // "<=": an equal distance may hide a smaller index
+        const unsigned long long ml = __ballot(okl), mr = __ballot(okr);
+        if (ml != 0ull && mr != 0ull) {
+          const unsigned long long pref = __ballot((okl || okr) && (bl <= br));
+          const bool left_first = 2 * __popcll(pref) >= __popcll(ml | mr);
+          if (sp < WALK_STACK) { stk[sp] = left_first ? 2 * h + 1 : 2 * h; sp++; }
+          h = left_first ? 2 * h : 2 * h + 1;
+          continue;
+        }
+        if (ml != 0ull) { h = 2 * h; continue; }
+        if (mr != 0ull) { h = 2 * h + 1; continue; }
+      } else if (h - P < n_leaves) {
+        float4 pts[KNN_LEAF];
+        sload_leaf(sorted + KNN_LEAF * (size_t)(h - P), pts);
+#pragma unroll
+        for (int u = 0; u < KNN_LEAF; u++) {
+          const float4 c = pts[u];
+          const float dx = q.x - c.x, dy = q.y - c.y, dz = q.z - c.z;
+          const float cd = ((dx * dx) + (dy * dy)) + (dz * dz);   // (-ffp-contract=off)
+          const unsigned long long ck = icp_key(cd, __float_as_int(c.w));   // (a padding point: +infinity, INT_MAX — never below the start key)
+          best = ck < best ? ck : best;
+        }
+        bd = active ? __uint_as_float((unsigned)(best >> 32)) : -1.0f;
+      }
+      if (sp == 0) break;
+      sp--;
+      h = stk[sp];
+    }
+  }
+  const int ti = (int)(unsigned)(best & 0xffffffffull);
+  const bool kept = active && ti != INT_MAX;
+  const float d2 = __uint_as_float((unsigned)(best >> 32));
+  double acc[ICP_NV];
+#pragma unroll
+  for (int v = 0; v < ICP_NV; v++) acc[v] = 0.0;
+  if (kept) {
+    const float4 t = A.txyz[ti];
+    const double p[3] = {(double)qs.x, (double)qs.y, (double)qs.z}, qq[3] = {(double)t.x, (double)t.y, (double)t.z};
+    acc[0] = 1.0; acc[1] = (double)d2;
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      acc[2 + r] = p[r]; acc[5 + r] = qq[r];
+#pragma unroll
+      for (int c = 0; c < 3; c++) acc[8 + 3 * r + c] = p[r] * qq[c];
+    }
+  }
+  if (active && A.idx_out) { A.idx_out[qidx] = kept ? ti : -1; A.d2_out[qidx] = kept ? d2 : INFINITY; }
+  // workgroup sum, fixed order
+#pragma unroll
+  for (int v = 0; v < ICP_NV; v++) {
+    double x = acc[v];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    if (lane == 0) red[wv][v] = x;
+  }
+  __syncthreads();
+  if (threadIdx.x < ICP_NV) {
+    double s = 0;
+#pragma unroll
+    for (int w = 0; w < ICP_THREADS / 64; w++) s += red[w][threadIdx.x];
+    A.partials[(size_t)blockIdx.x * ICP_NV + threadIdx.x] = s;
+  }
+}
+
+// the workgroups' rows summed in a fixed order (the scheme of s2m_sum_kernel: 8 strided groups of 32 lanes, then the groups in order); the 17 sums go straight
+// to pinned host memory
+__global__ __launch_bounds__(256) void icp_sum_kernel(const double* __restrict__ partials, int nblocks, double* __restrict__ out) {
+  __shared__ double part[8][32];
+  const int v = threadIdx.x & 31, q = threadIdx.x >> 5;
+  double s = 0;
+  if (v < ICP_NV) for (int b = q; b < nblocks; b += 8) s += partials[(size_t)b * ICP_NV + v];
+  part[q][v] = s;
+  __syncthreads();
+  if (threadIdx.x < ICP_NV) {
+    double t = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) t += part[k][threadIdx.x];
+    out[threadIdx.x] = t;
+  }
+}
+
+struct Rows12 { float T[12]; };
+// out = T * in, each row T0 x + (T1 y + (T2 z + T3)) in float (km_transform_kernel's statement); w is carried; a padding slot (KEEP_PAD, index INT_MAX) stays as it is
+template <bool KEEP_PAD>
+__global__ __launch_bounds__(256) void icp_transform_kernel(const float4* in, float4* out /* may be in */, int n, Rows12 R) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float4 p = in[i];
+  if (KEEP_PAD && __float_as_int(p.w) == INT_MAX) { out[i] = p; return; }
+  float4 o;
+  o.x = R.T[0] * p.x + (R.T[1] * p.y + (R.T[2] * p.z + R.T[3]));
+  o.y = R.T[4] * p.x + (R.T[5] * p.y + (R.T[6] * p.z + R.T[7]));
+  o.z = R.T[8] * p.x + (R.T[9] * p.y + (R.T[10] * p.z + R.T[11]));
+  o.w = p.w;
+  out[i] = o;
+}
+
+// ---- host: Umeyama without scaling, in double ------------------------------------------------------------------------------------------------
+inline double det3(const double* M) {
+  return M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
+}
+
+// A = U diag(S) V^T of a 3 x 3 matrix (row-major), singular values descending, U and V orthogonal whatever A's rank: one-sided Jacobi on the columns of A; U's first
+// column is the largest column normalised, the second the next one made orthogonal to it, the third their cross product with the sign of the third column
+void svd3(const double* Ain, double* U, double* S, double* V) {
+  double A[9], Vv[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  std::memcpy(A, Ain, sizeof(A));
+  for (int sweep = 0; sweep < 60; sweep++) {
+    bool rotated = false;
+    for (int p = 0; p < 2; p++)
+      for (int q = p + 1; q < 3; q++) {
+        double a = 0, b = 0, g = 0;
+        for (int r = 0; r < 3; r++) { a += A[3 * r + p] * A[3 * r + p]; b += A[3 * r + q] * A[3 * r + q]; g += A[3 * r + p] * A[3 * r + q]; }
+        if (g == 0.0 || std::fabs(g) <= 1e-17 * std::sqrt(a * b)) continue;
+        rotated = true;
+        const double zeta = (b - a) / (2.0 * g);
+        const double t = (zeta >= 0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
+        const double c = 1.0 / std::sqrt(1.0 + t * t), s = c * t;
+        for (int r = 0; r < 3; r++) {
+          const double x = A[3 * r + p], y = A[3 * r + q];
+          A[3 * r + p] = c * x - s * y; A[3 * r + q] = s * x + c * y;
+          const double vx = Vv[3 * r + p], vy = Vv[3 * r + q];
+          Vv[3 * r + p] = c * vx - s * vy; Vv[3 * r + q] = s * vx + c * vy;
+        }
+      }
+    if (!rotated) break;
+  }
+  double nrm[3]; int ord[3] = {0, 1, 2};
+  for (int k = 0; k < 3; k++) nrm[k] = std::sqrt(A[k] * A[k] + A[3 + k] * A[3 + k] + A[6 + k] * A[6 + k]);
+  for (int a = 0; a < 2; a++) for (int b = a + 1; b < 3; b++) if (nrm[ord[b]] > nrm[ord[a]]) std::swap(ord[a], ord[b]);
+  double col[3][3];
+  for (int k = 0; k < 3; k++) { S[k] = nrm[ord[k]]; for (int r = 0; r < 3; r++) { col[k][r] = A[3 * r + ord[k]]; V[3 * r + k] = Vv[3 * r + ord[k]]; } }
+  double u[3][3];
+  auto unit_perp = [](const double* a, double* o) {   // a unit vector orthogonal to the unit vector a
+    const int k = std::fabs(a[0]) <= std::fabs(a[1]) && std::fabs(a[0]) <= std::fabs(a[2]) ? 0 : (std::fabs(a[1]) <= std::fabs(a[2]) ? 1 : 2);
+    double e[3] = {0, 0, 0}; e[k] = 1.0;
+    const double d = a[k];
+    double n = 0;
+    for (int r = 0; r < 3; r++) { o[r] = e[r] - d * a[r]; n += o[r] * o[r]; }
+    n = std::sqrt(n);
+    for (int r = 0; r < 3; r++) o[r] /= n;
+  };
+  if (S[0] > 0) for (int r = 0; r < 3; r++) u[0][r] = col[0][r] / S[0]; else { u[0][0] = 1; u[0][1] = 0; u[0][2] = 0; }
+  {
+    double d = 0, w[3], n = 0;
+    for (int r = 0; r < 3; r++) d += col[1][r] * u[0][r];
+    for (int r = 0; r < 3; r++) { w[r] = col[1][r] - d * u[0][r]; n += w[r] * w[r]; }
+    n = std::sqrt(n);
+    if (n > 1e-14 * S[0] && n > 0) for (int r = 0; r < 3; r++) u[1][r] = w[r] / n; else unit_perp(u[0], u[1]);
+  }
+  u[2][0] = u[0][1] * u[1][2] - u[0][2] * u[1][1]; u[2][1] = u[0][2] * u[1][0] - u[0][0] * u[1][2]; u[2][2] = u[0][0] * u[1][1] - u[0][1] * u[1][0];
+  if (u[2][0] * col[2][0] + u[2][1] * col[2][1] + u[2][2] * col[2][2] < 0) for (int r = 0; r < 3; r++) u[2][r] = -u[2][r];
+  for (int k = 0; k < 3; k++) for (int r = 0; r < 3; r++) U[3 * r + k] = u[k][r];
+}
+
+// the 17 sums -> R (row-major) and t with q ~ R p + t
+void umeyama(const double* h, double* R, double* t) {
+  const double n = h[0];
+  double mp[3], mq[3], Sg[9], U[9], S[3], V[9];
+  for (int r = 0; r < 3; r++) { mp[r] = h[2 + r] / n; mq[r] = h[5 + r] / n; }
+  for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Sg[3 * r + c] = h[8 + 3 * c + r] / n - mq[r] * mp[c];   // row = q, column = p
+  svd3(Sg, U, S, V);
+  const double s = det3(U) * det3(V) < 0 ? -1.0 : 1.0;
+  for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) R[3 * r + c] = U[3 * r] * V[3 * c] + U[3 * r + 1] * V[3 * c + 1] + s * U[3 * r + 2] * V[3 * c + 2];
+  for (int r = 0; r < 3; r++) t[r] = mq[r] - (R[3 * r] * mp[0] + R[3 * r + 1] * mp[1] + R[3 * r + 2] * mp[2]);
+}
+
+inline float cap2_float(double max_dist) {   // the largest float f with (double)f <= max_dist^2: "(double)d2 <= max_dist^2" as a float comparison
+  const double c2 = max_dist * max_dist;
+  if (!(c2 < (double)FLT_MAX)) return INFINITY;
+  float f = (float)c2;
+  if ((double)f > c2) f = std::nextafterf(f, 0.f);
+  return f;
+}
+
+struct LoopIcp {
+  float4 *src = nullptr, *tgt = nullptr, *srcg = nullptr, *cur = nullptr; size_t src_cap = 0, tgt_cap = 0, srcg_cap = 0, cur_cap = 0;
+  double* part = nullptr; size_t part_cap = 0;
+  int32_t* idx = nullptr; size_t idx_cap = 0;
+  float* d2 = nullptr; size_t d2_cap = 0;
+  double* h_sum = nullptr;          // pinned: the 17 sums of an association, written by icp_sum_kernel
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  float ms[4] = {0.f, 0.f, 0.f, 0.f};
+  std::vector<void*> retired;       // outgrown buffers: freed with the context (a hipFree would stall every context's frames in flight)
+  std::vector<rolo_loopicp_trace_rec> trace;
+};
+
+#define LCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { rolo::ctx_set_error((std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); return ROLO_EHIP; } } while (0)
+
+template <typename T>
+int loop_grow(LoopIcp* W, T*& p, size_t& cap, size_t need) {
+  if (need <= cap && p) return ROLO_OK;
+  if (p) { W->retired.push_back(p); p = nullptr; cap = 0; }
+  const size_t want = need + need / 2 + 256;
+  if (hipMalloc((void**)&p, want * sizeof(T)) != hipSuccess) { ctx_set_error("hipMalloc failed (loop ICP)"); return ROLO_EHIP; }
+  cap = want;
+  return ROLO_OK;
+}
+
+int loop_state(rolo_ctx* c, LoopIcp** out) {
+  LoopIcp* W = static_cast<LoopIcp*>(*ctx_loop_slot(c));
+  if (!W) {
+    W = new LoopIcp();
+    *ctx_loop_slot(c) = W;
+    LCHK(hipSetDevice(ctx_device(c)));
+    LCHK(hipHostMalloc((void**)&W->h_sum, sizeof(double) * ICP_NV));
+    for (int i = 0; i < 4; i++) LCHK(hipEventCreate(&W->ev[i]));
+  }
+  *out = W;
+  return ROLO_OK;
+}
+
+bool is_identity16(const float* T) {
+  for (int i = 0; i < 16; i++) if (T[i] != ((i % 5 == 0) ? 1.f : 0.f)) return false;
+  return true;
+}
+
+// the moved source sorted along the target's curve and the target's tree; d_src / d_tgt: device clouds of float4
+int loop_setup(rolo_ctx* c, LoopIcp* W, const float4* d_src, int ns, const float4* d_tgt, int nt, const float* T16, IcpArgs* A, int* grid) {
+  hipStream_t s = ctx_stream(c);
+  int rc;
+  const float4* moved = d_src;
+  if (T16 && !is_identity16(T16)) {
+    if ((rc = loop_grow(W, W->srcg, W->srcg_cap, (size_t)ns))) return rc;
+    Rows12 R; std::memcpy(R.T, T16, sizeof(R.T));
+    icp_transform_kernel<false><<<(ns + 255) / 256, 256, 0, s>>>(d_src, W->srcg, ns, R);
+    LCHK(hipGetLastError());
+    moved = W->srcg;
+  }
+  KnnPair pair{};
+  if ((rc = ctx_build_map_trees(c, reinterpret_cast<const float*>(d_tgt), nt, reinterpret_cast<const float*>(moved), ns, 4, &pair, true))) return rc;
+  const int n_sorted = pair.c[1].n_sorted;
+  *grid = (n_sorted + ICP_THREADS - 1) / ICP_THREADS;
+  if ((rc = loop_grow(W, W->cur, W->cur_cap, (size_t)n_sorted))) return rc;
+  if ((rc = loop_grow(W, W->part, W->part_cap, (size_t)*grid * ICP_NV))) return rc;
+  LCHK(hipMemcpyAsync(W->cur, pair.c[1].sorted, sizeof(float4) * (size_t)n_sorted, hipMemcpyDeviceToDevice, s));
+  *A = IcpArgs{};
+  A->cur = W->cur; A->n_sorted = n_sorted; A->tsorted = pair.c[0].sorted; A->tboxes = pair.c[0].boxes; A->txyz = pair.c[0].xyz; A->P = pair.c[0].P;
+  A->n_leaves = pair.c[0].n_leaves; A->partials = W->part;
+  return ROLO_OK;
+}
+
+// one association on the stream, its 17 sums in W->h_sum when this returns
+int loop_associate(rolo_ctx* c, LoopIcp* W, const IcpArgs& A, int grid) {
+  hipStream_t s = ctx_stream(c);
+  icp_assoc_kernel<<<grid, ICP_THREADS, 0, s>>>(A);
+  LCHK(hipGetLastError());
+  icp_sum_kernel<<<1, 256, 0, s>>>(A.partials, grid, W->h_sum);
+  LCHK(hipGetLastError());
+  LCHK(hipStreamSynchronize(s));
+  return ROLO_OK;
+}
+
+void matmul4f(const float* a, const float* b, float* o) {   // o = a b, each entry a0 b0 + a1 b1 + a2 b2 + a3 b3 left to right
+  float r[16];
+  for (int i = 0; i < 4; i++)
+    for (int j = 0; j < 4; j++) {
+      float x = a[4 * i] * b[j];
+      for (int k = 1; k < 4; k++) x = x + a[4 * i + k] * b[4 * k + j];
+      r[4 * i + j] = x;
+    }
+  std::memcpy(o, r, sizeof(r));
+}
+
+int loop_align(rolo_ctx* c, const float4* d_src, int ns, const float4* d_tgt, int nt, const rolo_loopicp_params* P, const float* guess16, rolo_loopicp_result* out) {
+  LoopIcp* W = nullptr;
+  int rc = loop_state(c, &W);
+  if (rc) return rc;
+  if (!(P->max_correspondence_distance >= 0.0) || P->max_iterations < 0) { ctx_set_error("loop ICP: bad parameters"); return ROLO_EINVAL; }
+  LCHK(hipSetDevice(ctx_device(c)));
+  hipStream_t s = ctx_stream(c);
+  rolo_loopicp_result res{};
+  for (int i = 0; i < 16; i++) res.T[i] = guess16 ? guess16[i] : ((i % 5 == 0) ? 1.f : 0.f);
+  res.n_source = ns; res.n_target = nt; res.fitness = DBL_MAX; res.state = ROLO_ICP_NOT_CONVERGED;
+  W->trace.clear();
+  for (float& m : W->ms) m = 0.f;
+  if (ns <= 0 || nt <= 0) { res.state = ROLO_ICP_NO_CORRESPONDENCES; *out = res; return ROLO_OK; }
+  LCHK(hipEventRecord(W->ev[0], s));
+  IcpArgs A{};
+  int grid = 0;
+  if ((rc = loop_setup(c, W, d_src, ns, d_tgt, nt, guess16, &A, &grid))) return rc;
+  LCHK(hipEventRecord(W->ev[1], s));
+  A.cap2 = cap2_float(P->max_correspondence_distance);
+  const double rot_thr = P->rotation_epsilon > 0 ? P->rotation_epsilon : 1.0 - P->transformation_epsilon;
+  double prev = DBL_MAX;
+  const double* h = W->h_sum;
+  while (true) {
+    if ((rc = loop_associate(c, W, A, grid))) return rc;
+    rolo_loopicp_trace_rec tr{};
+    const int n = (int)(h[0] + 0.5);
+    tr.n = n; tr.mse = n > 0 ? h[1] / n : 0.0;
+    std::memcpy(tr.sums, h, sizeof(tr.sums));
+    res.n_last = n;
+    if (n < P->min_correspondences || n < 1) { W->trace.push_back(tr); res.state = ROLO_ICP_NO_CORRESPONDENCES; res.converged = 0; break; }
+    double R[9], t[3];
+    umeyama(h, R, t);
+    float inc[16] = {(float)R[0], (float)R[1], (float)R[2], (float)t[0], (float)R[3], (float)R[4], (float)R[5], (float)t[1],
+                     (float)R[6], (float)R[7], (float)R[8], (float)t[2], 0.f, 0.f, 0.f, 1.f};
+    std::memcpy(tr.increment, inc, sizeof(inc));
+    W->trace.push_back(tr);
+    Rows12 Rw; std::memcpy(Rw.T, inc, sizeof(Rw.T));
+    icp_transform_kernel<true><<<(A.n_sorted + 255) / 256, 256, 0, s>>>(W->cur, W->cur, A.n_sorted, Rw);
+    LCHK(hipGetLastError());
+    matmul4f(inc, res.T, res.T);
+    res.iterations++;
+    const double cosa = 0.5 * ((double)inc[0] + (double)inc[5] + (double)inc[10] - 1.0);
+    const double tsq = (double)inc[3] * (double)inc[3] + (double)inc[7] * (double)inc[7] + (double)inc[11] * (double)inc[11];
+    const double mse = tr.mse;
+    if (res.iterations >= P->max_iterations) { res.state = ROLO_ICP_ITERATIONS; res.converged = 1; break; }
+    if (cosa >= rot_thr && tsq <= P->transformation_epsilon) { res.state = ROLO_ICP_TRANSFORM; res.converged = 1; break; }
+    if (mse < 1e-12) { res.state = ROLO_ICP_ABS_MSE; res.converged = 1; break; }
+    if (std::fabs(mse - prev) / prev < P->euclidean_fitness_epsilon) { res.state = ROLO_ICP_REL_MSE; res.converged = 1; break; }
+    prev = mse;
+  }
+  LCHK(hipEventRecord(W->ev[2], s));
+  {   // getFitnessScore(): the moved source as it stands, no cap
+    A.cap2 = INFINITY;
+    if ((rc = loop_associate(c, W, A, grid))) return rc;
+    rolo_loopicp_trace_rec tr{};
+    tr.n = (int)(h[0] + 0.5); tr.mse = tr.n > 0 ? h[1] / tr.n : 0.0;
+    std::memcpy(tr.sums, h, sizeof(tr.sums));
+    W->trace.push_back(tr);
+    res.fitness = tr.n > 0 ? tr.mse : DBL_MAX;
+  }
+  LCHK(hipEventRecord(W->ev[3], s));
+  LCHK(hipEventSynchronize(W->ev[3]));
+  (void)hipEventElapsedTime(&W->ms[0], W->ev[0], W->ev[1]);
+  (void)hipEventElapsedTime(&W->ms[1], W->ev[1], W->ev[2]);
+  (void)hipEventElapsedTime(&W->ms[2], W->ev[2], W->ev[3]);
+  (void)hipEventElapsedTime(&W->ms[3], W->ev[0], W->ev[3]);
+  *out = res;
+  return ROLO_OK;
+}
+
+int loop_upload(rolo_ctx* c, LoopIcp* W, const float* src, int ns, const float* tgt, int nt) {
+  int rc;
+  if ((rc = loop_grow(W, W->src, W->src_cap, (size_t)std::max(ns, 1)))) return rc;
+  if ((rc = loop_grow(W, W->tgt, W->tgt_cap, (size_t)std::max(nt, 1)))) return rc;
+  hipStream_t s = ctx_stream(c);
+  if (ns > 0) LCHK(hipMemcpyAsync(W->src, src, sizeof(float4) * (size_t)ns, hipMemcpyHostToDevice, s));
+  if (nt > 0) LCHK(hipMemcpyAsync(W->tgt, tgt, sizeof(float4) * (size_t)nt, hipMemcpyHostToDevice, s));
+  return ROLO_OK;
+}
+
+int copy_trace(rolo_ctx* c, rolo_loopicp_trace_rec* out, int cap) {
+  LoopIcp* W = static_cast<LoopIcp*>(*ctx_loop_slot(c));
+  if (!W) return 0;
+  const int m = (int)W->trace.size();
+  for (int i = 0; i < std::min(m, cap); i++) out[i] = W->trace[i];
+  return m;
+}
+
+}  // namespace
+}  // namespace rolo
+
+using namespace rolo;
+
+extern "C" {
+
+void rolo_loopicp_destroy(rolo_ctx* c) {   // called by rolo_ctx_destroy
+  LoopIcp* W = static_cast<LoopIcp*>(*ctx_loop_slot(c));
+  if (!W) return;
+  for (void* p : {(void*)W->src, (void*)W->tgt, (void*)W->srcg, (void*)W->cur, (void*)W->part, (void*)W->idx, (void*)W->d2}) if (p) (void)hipFree(p);
+  for (void* p : W->retired) (void)hipFree(p);
+  if (W->h_sum) (void)hipHostFree(W->h_sum);
+  for (hipEvent_t e : W->ev) if (e) (void)hipEventDestroy(e);
+  delete W;
+  *ctx_loop_slot(c) = nullptr;
+}
+
+void rolo_loopicp_default_params(rolo_loopicp_params* p) {
+  if (!p) return;
+  p->max_iterations = 100;
+  p->transformation_epsilon = 1e-6;
+  p->euclidean_fitness_epsilon = 1e-6;
+  p->rotation_epsilon = 0.0;
+  p->max_correspondence_distance = INFINITY;
+  p->min_correspondences = 3;
+}
+
+int rolo_loopicp_align(rolo_ctx* c, const float* source, int n_source, const float* target, int n_target, const rolo_loopicp_params* params, const float* guess16,
+                       rolo_loopicp_result* out) {
+  if (!c || !params || !out || n_source < 0 || n_target < 0 || (n_source && !source) || (n_target && !target) || n_source > ROLO_KEYMAP_MAX_POINTS ||
+      n_target > ROLO_KEYMAP_MAX_POINTS)
+    return ROLO_EINVAL;
+  LoopIcp* W = nullptr;
+  int rc = loop_state(c, &W);
+  if (rc) return rc;
+  LCHK(hipSetDevice(ctx_device(c)));
+  if ((rc = loop_upload(c, W, source, n_source, target, n_target))) return rc;
+  rc = loop_align(c, W->src, n_source, W->tgt, n_target, params, guess16, out);
+  if (rc) (void)hipStreamSynchronize(ctx_stream(c));   // the caller's arrays are free again, whatever happened
+  return rc;
+}
+
+int rolo_keymap_loop_icp(rolo_keymap* km, const rolo_loopicp_params* params, const float* guess16, rolo_loopicp_result* out) {
+  if (!km || !params || !out) return ROLO_EINVAL;
+  if (!km->have_loop[0] || !km->have_loop[1]) { ctx_set_error("rolo_keymap_loop_icp: build both loop clouds first (rolo_keymap_loop_cloud, slots 0 and 1)"); return ROLO_ESTATE; }
+  if (!km->loop_ctx) { const int rc = rolo_ctx_acquire(km->device, &km->loop_ctx); if (rc) return rc; }
+  // (rolo_keymap_loop_cloud waited for the key map's stream before it returned: the clouds are complete, and this call waits for the context's stream before it returns)
+  return loop_align(km->loop_ctx, km->loop[0], km->m_loop[0], km->loop[1], km->m_loop[1], params, guess16, out);
+}
+
+int rolo_loopicp_get_trace(rolo_ctx* c, rolo_loopicp_trace_rec* out, int cap) {
+  if (!c || cap < 0 || (cap && !out)) return ROLO_EINVAL;
+  return copy_trace(c, out, cap);
+}
+
+int rolo_keymap_loop_trace(rolo_keymap* km, rolo_loopicp_trace_rec* out, int cap) {
+  if (!km || cap < 0 || (cap && !out)) return ROLO_EINVAL;
+  return km->loop_ctx ? copy_trace(km->loop_ctx, out, cap) : 0;
+}
+
+int rolo_loopicp_associate(rolo_ctx* c, const float* source, int n_source, const float* target, int n_target, const float* T16, double max_correspondence_distance,
+                           int32_t* index_out, float* d2_out) {
+  if (!c || n_source <= 0 || n_target <= 0 || !source || !target || !index_out || !d2_out || !(max_correspondence_distance >= 0.0) ||
+      n_source > ROLO_KEYMAP_MAX_POINTS || n_target > ROLO_KEYMAP_MAX_POINTS)
+    return ROLO_EINVAL;
+  LoopIcp* W = nullptr;
+  int rc = loop_state(c, &W);
+  if (rc) return rc;
+  LCHK(hipSetDevice(ctx_device(c)));
+  hipStream_t s = ctx_stream(c);
+  if ((rc = loop_upload(c, W, source, n_source, target, n_target))) return rc;
+  if ((rc = loop_grow(W, W->idx, W->idx_cap, (size_t)n_source))) return rc;
+  if ((rc = loop_grow(W, W->d2, W->d2_cap, (size_t)n_source))) return rc;
+  IcpArgs A{};
+  int grid = 0;
+  W->trace.clear();
+  rc = loop_setup(c, W, W->src, n_source, W->tgt, n_target, T16, &A, &grid);
+  if (rc) { (void)hipStreamSynchronize(s); return rc; }
+  A.cap2 = cap2_float(max_correspondence_distance);
+  A.idx_out = W->idx; A.d2_out = W->d2;
+  if ((rc = loop_associate(c, W, A, grid))) return rc;
+  rolo_loopicp_trace_rec tr{};
+  tr.n = (int)(W->h_sum[0] + 0.5); tr.mse = tr.n > 0 ? W->h_sum[1] / tr.n : 0.0;
+  std::memcpy(tr.sums, W->h_sum, sizeof(tr.sums));
+  W->trace.push_back(tr);
+  LCHK(hipMemcpyAsync(index_out, W->idx, sizeof(int32_t) * (size_t)n_source, hipMemcpyDeviceToHost, s));
+  LCHK(hipMemcpyAsync(d2_out, W->d2, sizeof(float) * (size_t)n_source, hipMemcpyDeviceToHost, s));
+  LCHK(hipStreamSynchronize(s));
+  return ROLO_OK;
+}
+
+int rolo_loopicp_last_ms(rolo_ctx* c, float* ms4) {
+  if (!c || !ms4) return ROLO_EINVAL;
+  LoopIcp* W = static_cast<LoopIcp*>(*ctx_loop_slot(c));
+  for (int i = 0; i < 4; i++) ms4[i] = W ? W->ms[i] : 0.f;
+  return ROLO_OK;
+}
+
+int rolo_keymap_loop_last_ms(rolo_keymap* km, float* ms6) {
+  if (!km || !ms6) return ROLO_EINVAL;
+  for (int i = 0; i < 4; i++) ms6[i] = 0.f;
+  if (km->loop_ctx) rolo_loopicp_last_ms(km->loop_ctx, ms6);
+  ms6[4] = km->loop_ms[0]; ms6[5] = km->loop_ms[1];
+  return ROLO_OK;
+}
+
+}  // extern "C"

@@ -400,6 +400,23 @@ int vg_enqueue_filter(rolo_keymap* km, const float4* pts, int n, float leaf, int
   return ROLO_OK;
 }
 
+// kdtree->radiusSearch(cloud->back(), radius) over the key poses, the one statement of its rule (extractNearby :585, detectLoopClosureDistance :2496): the poses whose
+// squared float distance to the LAST one is below radius^2, ascending by (distance, index)
+std::vector<std::pair<float, int>> radius_hits_last(const float* xyz, int n, float radius) {
+  std::vector<std::pair<float, int>> near;
+  if (n <= 0) return near;
+  const float* last = xyz + 3 * (size_t)(n - 1);
+  const float r2 = radius * radius;
+  for (int i = 0; i < n; i++) {
+    const float* a = xyz + 3 * (size_t)i;
+    const float dx = a[0] - last[0], dy = a[1] - last[1], dz = a[2] - last[2];
+    const float d = dx * dx + dy * dy + dz * dz;
+    if (d < r2) near.push_back({d, i});
+  }
+  std::sort(near.begin(), near.end());
+  return near;
+}
+
 int km_alloc_points(rolo_keymap* km, size_t n, float4** out) {
   *out = nullptr;
   if (n == 0) return ROLO_OK;
@@ -481,15 +498,18 @@ void rolo_keymap_destroy(rolo_keymap* km) {
   if (km->stream) (void)hipStreamSynchronize(km->stream);
   if (km->consumer_pending && km->consumed) (void)hipEventSynchronize(km->consumed);
   if (km->sc) { sc_store_destroy(km->sc); km->sc = nullptr; }
+  if (km->loop_ctx) { rolo_ctx_release(km->loop_ctx); km->loop_ctx = nullptr; }
   for (auto& c : km->chunks) (void)hipFree(c.p);
   for (void* p : km->retired) (void)hipFree(p);
   for (void* p : km->retired_host) (void)hipHostFree(p);
   for (void* p : {(void*)km->cat[0], (void*)km->cat[1], (void*)km->sub[0], (void*)km->sub[1], (void*)km->ds_out, (void*)km->keys[0], (void*)km->keys[1], (void*)km->vals[0],
-                  (void*)km->vals[1], (void*)km->hist, (void*)km->dtot, (void*)km->bcnt, (void*)km->starts, (void*)km->box_part, (void*)km->segs, (void*)km->d_m})
+                  (void*)km->vals[1], (void*)km->hist, (void*)km->dtot, (void*)km->bcnt, (void*)km->starts, (void*)km->box_part, (void*)km->segs, (void*)km->d_m, (void*)km->loop[0], (void*)km->loop[1]})
     if (p) (void)hipFree(p);
   for (void* p : {(void*)km->h_box, (void*)km->h_m, (void*)km->h_segs}) if (p) (void)hipHostFree(p);
   if (km->ready) (void)hipEventDestroy(km->ready);
   if (km->consumed) (void)hipEventDestroy(km->consumed);
+  if (km->loop_t0) (void)hipEventDestroy(km->loop_t0);
+  if (km->loop_t1) (void)hipEventDestroy(km->loop_t1);
   if (km->stream) (void)hipStreamDestroy(km->stream);
   delete km;
 }
@@ -619,11 +639,8 @@ int rolo_keyposes_select_nearby(const float* xyz, const double* times, int n, fl
   if (n == 0) return 0;
   auto d2 = [&](const float* a, const float* b) { const float dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2]; return dx * dx + dy * dy + dz * dz; };
   const float* last = xyz + 3 * (size_t)(n - 1);
-  // radiusSearch(cloudKeyPoses3D->back(), radius) :585 — squared float distances below radius^2, nearest first
-  const float r2 = search_radius * search_radius;
-  std::vector<std::pair<float, int>> near;
-  for (int i = 0; i < n; i++) { const float d = d2(xyz + 3 * (size_t)i, last); if (d < r2) near.push_back({d, i}); }
-  std::sort(near.begin(), near.end());
+  // radiusSearch(cloudKeyPoses3D->back(), radius) :585
+  const std::vector<std::pair<float, int>> near = radius_hits_last(xyz, n, search_radius);
   // downSizeFilterSurroundingKeyPoses :592-593 (intensity = index of the key pose)
   std::vector<std::array<float, 4>> poses, ds;
   for (const auto& e : near) poses.push_back({xyz[3 * (size_t)e.second], xyz[3 * (size_t)e.second + 1], xyz[3 * (size_t)e.second + 2], (float)e.second});
@@ -647,6 +664,90 @@ int rolo_keyposes_select_nearby(const float* xyz, const double* times, int n, fl
     count++;
   }
   return count;
+}
+
+int rolo_keyposes_detect_loop_distance(const float* xyz, const double* times, int n, float search_radius, double time_diff, double time_cur, int32_t* loop_key_pre) {
+  if (!loop_key_pre || n < 0 || (n && (!xyz || !times)) || !(search_radius >= 0.f)) return ROLO_EINVAL;
+  *loop_key_pre = -1;
+  // :2498-2506 — the first hit, nearest first, that is old enough; :2508 — none, or the last key itself
+  for (const auto& e : radius_hits_last(xyz, n, search_radius))
+    if (std::fabs(times[e.second] - time_cur) > time_diff) { if (e.second != n - 1) *loop_key_pre = e.second; break; }
+  return ROLO_OK;
+}
+
+int rolo_keymap_loop_cloud(rolo_keymap* km, int slot, int key, int search_num, int wrt_key, float leaf, int* m) {
+  if (!km || slot < 0 || slot > 1 || search_num < 0 || !(leaf > 0.f)) return ROLO_EINVAL;
+  const int size = (int)km->frames.size();
+  if (size > 0 && (key < 0 || key >= size)) { ctx_set_error("rolo_keymap_loop_cloud: key outside the store"); return ROLO_EINVAL; }
+  if (wrt_key >= size) { ctx_set_error("rolo_keymap_loop_cloud: wrt_key outside the store"); return ROLO_EINVAL; }
+  km->have_loop[slot] = false; km->m_loop[slot] = 0;
+  // :2577-2585 / :2605-2611 — keyNear = key - searchNum .. key + searchNum inside the store; corner, then surface, of each
+  const int lo = size ? (int)std::max<long long>((long long)key - search_num, 0) : 0, hi = size ? (int)std::min<long long>((long long)key + search_num, size - 1) : -1;
+  long long total = 0;
+  size_t nsegs = 0;
+  int max_n = 1;
+  for (int k = lo; k <= hi; k++) for (int t = 0; t < 2; t++) { const int c = km->frames[k].n[t]; total += c; if (c) nsegs++; max_n = std::max(max_n, c); }
+  if (total > KM_MAX_POINTS) { ctx_set_error("rolo_keymap_loop_cloud: more than ROLO_KEYMAP_MAX_POINTS points in one loop cloud"); return ROLO_EINVAL; }
+  KCHK(hipSetDevice(km->device));
+  hipStream_t s = km->stream;
+  if (!km->loop_t0) { KCHK(hipEventCreate(&km->loop_t0)); KCHK(hipEventCreate(&km->loop_t1)); }
+  km->loop_ms[slot] = 0.f;
+  if (total == 0) { km->have_loop[slot] = true; if (m) *m = 0; return ROLO_OK; }   // :2587 — "if (nearKeyframes->empty()) return"
+  int rc;
+  const int n = (int)total;
+  if ((rc = km_sort_scratch(km, n))) return rc;
+  if (nsegs > km->h_segs_cap) {
+    if (km->h_segs) { km->retired_host.push_back(km->h_segs); km->h_segs = nullptr; km->h_segs_cap = 0; }
+    const size_t want = nsegs + nsegs / 2 + 64;
+    KCHK(hipHostMalloc((void**)&km->h_segs, want * sizeof(Seg)));
+    km->h_segs_cap = want;
+  }
+  if ((rc = km_grow(km, km->segs, km->segs_cap, nsegs))) return rc;
+  if ((rc = km_grow(km, km->cat[0], km->cat_cap[0], (size_t)n))) return rc;
+  if ((rc = km_grow(km, km->loop[slot], km->loop_cap[slot], (size_t)n))) return rc;
+  size_t q = 0;
+  int dst = 0;
+  for (int k = lo; k <= hi; k++) {
+    const rolo_keymap::Frame& f = km->frames[k];
+    for (int t = 0; t < 2; t++) {
+      if (!f.n[t]) continue;
+      Seg& g = km->h_segs[q++];
+      g.src = f.pts[t]; g.n = f.n[t]; g.dst = dst;
+      pose_to_T(wrt_key >= 0 ? km->frames[wrt_key].pose : f.pose, g.T);
+      dst += f.n[t];
+    }
+  }
+  KCHK(hipEventRecord(km->loop_t0, s));
+  KCHK(hipMemcpyAsync(km->segs, km->h_segs, nsegs * sizeof(Seg), hipMemcpyHostToDevice, s));
+  const int gx = std::min((max_n + SM_THREADS - 1) / SM_THREADS, 128);
+  for (size_t y0 = 0; y0 < nsegs; y0 += 32768) {
+    km_transform_kernel<<<dim3(gx, (unsigned)std::min<size_t>(nsegs - y0, 32768)), SM_THREADS, 0, s>>>(km->segs + y0, km->cat[0]);
+    KCHK(hipGetLastError());
+  }
+  if ((rc = vg_enqueue_box(km, km->cat[0], n, 0))) return rc;
+  KCHK(hipStreamSynchronize(s));
+  // :2593-2595 — ONE downSizeFilterICP over corner and surface together
+  bool direct; int m_direct = 0;
+  if ((rc = vg_enqueue_filter(km, km->cat[0], n, leaf, 0, km->loop[slot], &direct, &m_direct))) return rc;
+  KCHK(hipEventRecord(km->loop_t1, s));
+  KCHK(hipStreamSynchronize(s));
+  const int mm = direct ? m_direct : km->h_m[0];
+  if (mm < 0 || mm > n) { ctx_set_error("the key map's voxel filter returned an inconsistent cell count"); return ROLO_ESTATE; }
+  (void)hipEventElapsedTime(&km->loop_ms[slot], km->loop_t0, km->loop_t1);
+  km->m_loop[slot] = mm; km->have_loop[slot] = true;
+  if (m) *m = mm;
+  return ROLO_OK;
+}
+
+int rolo_keymap_get_loop_cloud(rolo_keymap* km, int slot, float* out, int cap) {
+  if (!km || slot < 0 || slot > 1 || cap < 0) return ROLO_EINVAL;
+  if (!km->have_loop[slot]) { ctx_set_error("the key map holds no loop cloud in this slot: call rolo_keymap_loop_cloud first"); return ROLO_ESTATE; }
+  const int mm = km->m_loop[slot];
+  if (mm > cap || (mm && !out)) return ROLO_EINVAL;
+  KCHK(hipSetDevice(km->device));
+  if (mm) KCHK(hipMemcpyAsync(out, km->loop[slot], sizeof(float4) * (size_t)mm, hipMemcpyDeviceToHost, km->stream));
+  KCHK(hipStreamSynchronize(km->stream));
+  return mm;
 }
 
 }  // extern "C"
