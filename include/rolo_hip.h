@@ -577,6 +577,62 @@ int rolo_loopicp_associate(rolo_ctx* ctx, const float* source, int n_source, con
 int rolo_loopicp_last_ms(rolo_ctx* ctx, float* ms4);
 int rolo_keymap_loop_last_ms(rolo_keymap* km, float* ms6);
 
+/* ---- back end: pose-graph optimisation for the loop closures ----------------------------------------------------------------------------
+ * saveKeyFramesAndFactor / addOdomFactor / addLoopFactor / addPriorFactor / correctPoses (src/backMapping.cpp:1094-1320) as a BATCH minimiser of the objective
+ * the reference hands to iSAM2, built from the same factors and the same noise models. GTSAM is not in the reference tree and iSAM2 is incremental: this is not a
+ * restatement of it, and parity with GTSAM is unpinned. The contract is this statement; tests/pgo_twin.py restates it in numpy.
+ *   poses      X_k = (R_k, t_k), fp64 everywhere; T16 is a row-major 4 x 4 double matrix (its last row is not read)
+ *   factors    prior(i, Z, var6): e = Log(Z^-1 X_i); between(i, j, Z, var6): e = Log(Z^-1 X_i^-1 X_j), i != j in either order. Log is the full SE(3) logarithm,
+ *              tangent order [omega, v] (rotation first, as GTSAM's Pose3), coefficient series below an angle of 1e-2; an angle within 1e-6 of pi is outside the
+ *              statement. var6: variances in that order (noiseModel::Diagonal::Variances). Objective 1/2 sum |e / sigma|^2.
+ *   linearise  retraction X <- X Exp(delta); J_j = Jr^-1(e), J_i = -Jr^-1(e) Ad((X_i^-1 X_j)^-1), prior J_i = Jr^-1(e), with Jr^-1 by its series
+ *              I + ad/2 + ad^2/12 - ad^4/720; rows whitened by 1 / sigma. H and g are summed per pose over its factors in factor order (no atomics).
+ *   step       (H + lambda I) delta = -g by conjugate gradients preconditioned with T, the block-tridiagonal part of H + lambda I (diagonal blocks and the blocks
+ *              between poses k and k + 1; a factor on such a pair in either direction lands there). Everything else, the chords, enters through the
+ *              matrix-vector product only. T^-1 by block cyclic reduction (6 x 6 blocks, identity padding to a power of two), factored once per lambda.
+ *              Exit when sqrt(r z) <= pcg_tol sqrt(r0 z0), at the cap (pcg_max_iterations, or 0 = automatic: min(12 chords + 2, 1000) since H - T has rank
+ *              <= 12 chords; without chords T is the matrix and the cap is 1), or when r z or p A p stops being positive; r0 z0 == 0 returns delta = 0 at once.
+ *   outer      Levenberg-Marquardt, GTSAM's LevenbergMarquardtParams defaults. Per trial: iterations >= max_iterations -> ITERATIONS; lambda > lambda_upper ->
+ *              LAMBDA; solve, retract, cost. A trial that lowers the cost is accepted: lambda /= factor, iterations += 1, and CONVERGED when the decrease is
+ *              <= absolute_error_tol or <= relative_error_tol * cost before; else relinearise. A trial that does not lower it but raises it by less than
+ *              absolute_error_tol ends as CONVERGED without moving (a zero gradient ends here: the every-key-frame case). Otherwise lambda *= factor and the
+ *              step is retried without relinearising.
+ * pose6 (transformTobeMapped order) is taken from R as pcl::getTranslationAndEulerAngles does; GTSAM's rotation().roll()/pitch()/yaw() agree away from gimbal
+ * lock (parity unpinned). A graph is single-threaded like a key map, works on a stream of its own and waits for it before returning; its device store only grows.
+ * ROLO_EINVAL: an index out of range, i == j, a variance <= 0 or non-finite, a non-finite pose, more than ROLO_PGO_MAX_POSES poses, a solve whose H + lambda I is
+ * not positive definite. ROLO_ESTATE: optimise or linearise with no pose or no factor; solve_linear without a linearisation of the graph as it stands. */
+#define ROLO_PGO_MAX_POSES (1 << 16)
+#define ROLO_PGO_CONVERGED 1
+#define ROLO_PGO_ITERATIONS 2
+#define ROLO_PGO_LAMBDA 3
+typedef struct rolo_pgo rolo_pgo;
+typedef struct rolo_pgo_params { int max_iterations; double absolute_error_tol, relative_error_tol, lambda_initial, lambda_factor, lambda_upper, pcg_tol;
+                                 int pcg_max_iterations; } rolo_pgo_params;
+typedef struct rolo_pgo_result { int state, iterations, trials; double initial_cost, final_cost, lambda; int pcg_iterations; } rolo_pgo_result;
+/* one record per trial: its lambda, the trial's cost, whether it was accepted, the PCG iterations and sqrt(r z) / sqrt(r0 z0) of its solve */
+typedef struct rolo_pgo_trace_rec { double lambda, cost; int accepted, pcg_iterations; double residual; } rolo_pgo_trace_rec;
+int rolo_pgo_create(int device, rolo_pgo** out);
+void rolo_pgo_destroy(rolo_pgo* g);
+void rolo_pgo_default_params(rolo_pgo_params* p);
+/* initialEstimate.insert; returns the pose's index (>= 0) */
+int rolo_pgo_add_pose(rolo_pgo* g, const double* T16);
+int rolo_pgo_add_prior(rolo_pgo* g, int i, const double* T16, const double* var6);
+int rolo_pgo_add_between(rolo_pgo* g, int i, int j, const double* T16, const double* var6);
+int rolo_pgo_size(rolo_pgo* g, int* n_poses, int* n_factors, int* n_chords);
+int rolo_pgo_optimize(rolo_pgo* g, const rolo_pgo_params* params, rolo_pgo_result* out);
+/* the current poses: T16_out (n x 16 doubles) and / or pose6_out (n x 6 floats), the first min(n, cap); returns n */
+int rolo_pgo_get_poses(rolo_pgo* g, double* T16_out, float* pose6_out, int cap);
+int rolo_pgo_get_trace(rolo_pgo* g, rolo_pgo_trace_rec* out, int cap);
+/* test hooks. linearise at the current poses: cost, grad[6N], diag[N x 36], chain[(N - 1) x 36] (the blocks H[k, k+1]), chord[chords x 36] (H[i, j] of the
+ * factor as given) and chord_ij[chords x 2], each optional; solve_linear: the step a trial would take on the last linearisation */
+int rolo_pgo_linearize(rolo_pgo* g, double* cost, double* grad, double* diag, double* chain, double* chord, int32_t* chord_ij);
+int rolo_pgo_solve_linear(rolo_pgo* g, double lambda, double pcg_tol, int pcg_max, double* delta, int* pcg_iterations, double* residual);
+/* device milliseconds of the last optimise, summed over its trials: ms4[0] linearise + assemble and [3] retract + cost between HIP events; [1] the cyclic
+ * reduction's factorisation and [2] the PCG loop, which share one launch, by the device's wall clock inside it */
+int rolo_pgo_last_ms(rolo_pgo* g, float* ms4);
+/* correctPoses (:1301-1314) in one call: poses 0 .. n - 1 of the key map (n x 6 floats); n above the key map's size is ROLO_EINVAL */
+int rolo_keymap_set_poses(rolo_keymap* km, const float* pose6, int n);
+
 #ifdef __cplusplus
 }
 #endif

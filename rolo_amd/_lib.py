@@ -77,6 +77,20 @@ class LoopIcpResult(C.Structure):
                 ("n_target", C.c_int), ("n_last", C.c_int)]
 
 
+class PgoParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int), ("absolute_error_tol", C.c_double), ("relative_error_tol", C.c_double), ("lambda_initial", C.c_double),
+                ("lambda_factor", C.c_double), ("lambda_upper", C.c_double), ("pcg_tol", C.c_double), ("pcg_max_iterations", C.c_int)]
+
+
+class PgoResult(C.Structure):
+    _fields_ = [("state", C.c_int), ("iterations", C.c_int), ("trials", C.c_int), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("lambda_", C.c_double), ("pcg_iterations", C.c_int)]
+
+
+class PgoTraceRec(C.Structure):
+    _fields_ = [("lambda_", C.c_double), ("cost", C.c_double), ("accepted", C.c_int), ("pcg_iterations", C.c_int), ("residual", C.c_double)]
+
+
 class LoopIcpTraceRec(C.Structure):
     _fields_ = [("n", C.c_int), ("mse", C.c_double), ("sums", C.c_double * 17), ("increment", C.c_float * 16)]
 
@@ -181,6 +195,20 @@ SYMBOLS = {
     "rolo_keymap_loop_trace": (C.c_int, [vp, C.POINTER(LoopIcpTraceRec), C.c_int]),
     "rolo_loopicp_associate": (C.c_int, [vp, fp, C.c_int, fp, C.c_int, fp, C.c_double, ip, fp]),
     "rolo_loopicp_last_ms": (C.c_int, [vp, fp]),
+    "rolo_pgo_create": (C.c_int, [C.c_int, C.POINTER(vp)]),
+    "rolo_pgo_destroy": (None, [vp]),
+    "rolo_pgo_default_params": (None, [C.POINTER(PgoParams)]),
+    "rolo_pgo_add_pose": (C.c_int, [vp, dp]),
+    "rolo_pgo_add_prior": (C.c_int, [vp, C.c_int, dp, dp]),
+    "rolo_pgo_add_between": (C.c_int, [vp, C.c_int, C.c_int, dp, dp]),
+    "rolo_pgo_size": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rolo_pgo_optimize": (C.c_int, [vp, C.POINTER(PgoParams), C.POINTER(PgoResult)]),
+    "rolo_pgo_get_poses": (C.c_int, [vp, dp, fp, C.c_int]),
+    "rolo_pgo_get_trace": (C.c_int, [vp, C.POINTER(PgoTraceRec), C.c_int]),
+    "rolo_pgo_linearize": (C.c_int, [vp, dp, dp, dp, dp, dp, ip]),
+    "rolo_pgo_solve_linear": (C.c_int, [vp, C.c_double, C.c_double, C.c_int, dp, C.POINTER(C.c_int), dp]),
+    "rolo_pgo_last_ms": (C.c_int, [vp, fp]),
+    "rolo_keymap_set_poses": (C.c_int, [vp, fp, C.c_int]),
     "rolo_keymap_loop_last_ms": (C.c_int, [vp, fp]),
     "rolo_num_voxels": (C.c_int, [vp]),
     "rolo_num_edge_points": (C.c_int, [vp]),

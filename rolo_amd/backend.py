@@ -1,13 +1,14 @@
 """Host mirrors of the back end: the scan-to-submap optimisation (reference src/backMapping.cpp:681-1058) over rolo_scan2map_optimize, the
 device-resident key frames with sub-map assembly (:558-678) over rolo_keymap_*, Scan Context loop detection (src/scancontext/Scancontext.cpp) over
-rolo_keymap_sc_* and the loop closure's clouds, radius-search detector and ICP (:2307-2624) over rolo_keymap_loop_* / rolo_loopicp_*."""
+rolo_keymap_sc_*, the loop closure's clouds, radius-search detector and ICP (:2307-2624) over rolo_keymap_loop_* / rolo_loopicp_*, and the factor graph
+(:1222-1320) as a batch pose-graph optimisation over rolo_pgo_*."""
 from __future__ import annotations
 
 import ctypes as C
 
 import numpy as np
 
-from ._lib import lib, check, Scan2MapStats, ScParams, ScResult, LoopIcpParams, LoopIcpResult, LoopIcpTraceRec
+from ._lib import lib, check, Scan2MapStats, ScParams, ScResult, LoopIcpParams, LoopIcpResult, LoopIcpTraceRec, PgoParams, PgoResult, PgoTraceRec
 from .rotvgicp import RotVGICP
 
 
@@ -182,6 +183,13 @@ class KeyFrameMap:
         check(lib().rolo_keymap_set_pose(self._h, index, p.ctypes.data_as(C.POINTER(C.c_float))), "rolo_keymap_set_pose")
         self.poses[index] = p.copy()
 
+    def setPoses(self, poses6):
+        """correctPoses (:1301-1314) for key frames 0 .. n - 1 in one call"""
+        p = np.ascontiguousarray(poses6, np.float32).reshape(-1, 6)
+        check(lib().rolo_keymap_set_poses(self._h, p.ctypes.data_as(C.POINTER(C.c_float)), p.shape[0]), "rolo_keymap_set_poses")
+        for k in range(p.shape[0]):
+            self.poses[k] = p[k].copy()
+
     def selectNearby(self, time_cur: float, search_radius: float = 50.0, density: float = 2.0, recent_seconds: float = 10.0):
         """extractNearby (:575-614) on the stored key poses"""
         xyz = np.array([p[3:6] for p in self.poses], np.float32).reshape(-1, 3)
@@ -347,7 +355,8 @@ def pose6_to_T(pose6, dtype=np.float32):
 
 class LoopCloser:
     """performRSLoopClosure (:2307-2397) and performSCLoopClosure (:2399-2479) over a key map, up to the factor graph: each call returns
-    (loopKeyCur, loopKeyPre, poseFrom 4 x 4, poseTo 4 x 4, noise) — the constraint is poseFrom.between(poseTo) with the variance `noise` on all six axes — or None."""
+    (loopKeyCur, loopKeyPre, poseFrom 4 x 4, poseTo 4 x 4, noise) — the constraint is poseFrom.between(poseTo) with the variance `noise` on all six axes — or None.
+    PoseGraph.addLoopFactor takes that tuple as it is."""
     MIN_CUR, MIN_PREV = 300, 1000   # :2333, :2424
     SC_CAP = 150.0                  # :2431
 
@@ -403,3 +412,139 @@ class LoopCloser:
             return None
         self.loopIndexContainer[cur] = pre
         return cur, pre, res["T"].astype(np.float64), np.eye(4), np.float32(res["fitness"])
+
+
+
+def pgo_params(**kw) -> PgoParams:
+    """GTSAM's LevenbergMarquardtParams defaults (rolo_pgo_default_params); fields of rolo_pgo_params by keyword"""
+    p = PgoParams()
+    lib().rolo_pgo_default_params(C.byref(p))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+class PoseGraph:
+    """gtSAMgraph + initialEstimate + isam->update + correctPoses (:1094-1320) as a batch minimiser of the same objective on the device (include/rolo_hip.h,
+    "pose-graph optimisation"): the same factors and noise models; iSAM2's incremental bookkeeping and its marginal covariance are not restated, and parity with
+    GTSAM is unpinned. Poses are 4 x 4 doubles; pose6 is transformTobeMapped order (roll, pitch, yaw, x, y, z)."""
+    STATES = ("NONE", "CONVERGED", "ITERATIONS", "LAMBDA")
+    PRIOR_VARIANCES = (1e-2, 1e-2, np.pi * np.pi, 1e8, 1e8, 1e8)   # :1229
+    ODOM_VARIANCES = (1e-6, 1e-6, 1e-6, 1e-4, 1e-4, 1e-4)          # :1235
+
+    def __init__(self, device: int = 0):
+        self._h = C.c_void_p()
+        check(lib().rolo_pgo_create(device, C.byref(self._h)), "rolo_pgo_create")
+        self._last = None   # the graph's last pose (4 x 4), kept on the host between optimisations
+        self.last = None    # the last optimise's result
+
+    def close(self):
+        if self._h:
+            lib().rolo_pgo_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def size(self):
+        """(poses, factors, chords)"""
+        a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+        check(lib().rolo_pgo_size(self._h, C.byref(a), C.byref(b), C.byref(c)), "rolo_pgo_size")
+        return a.value, b.value, c.value
+
+    def __len__(self):
+        return self.size()[0]
+
+    @staticmethod
+    def _dp(a, n):
+        a = np.ascontiguousarray(a, np.float64).reshape(n)
+        return a, a.ctypes.data_as(C.POINTER(C.c_double))
+
+    def addPose(self, T) -> int:
+        keep, p = self._dp(T, 16)
+        k = check(lib().rolo_pgo_add_pose(self._h, p), "rolo_pgo_add_pose")
+        self._last = keep.reshape(4, 4).copy()
+        return k
+
+    def addPrior(self, i: int, T, variances):
+        kt, t = self._dp(T, 16); kv, v = self._dp(variances, 6)
+        check(lib().rolo_pgo_add_prior(self._h, i, t, v), "rolo_pgo_add_prior")
+
+    def addBetween(self, i: int, j: int, T, variances):
+        """BetweenFactor<Pose3>(i, j, T, Diagonal::Variances(variances)); the reference's ground-prior factors (:1266-1284) come through here"""
+        kt, t = self._dp(T, 16); kv, v = self._dp(variances, 6)
+        check(lib().rolo_pgo_add_between(self._h, i, j, t, v), "rolo_pgo_add_between")
+
+    def addOdomFactor(self, pose6) -> int:
+        """addOdomFactor (:1224-1243): the first call adds the prior, later ones poseFrom.between(poseTo) from the graph's last pose; returns the new pose's index"""
+        T = pose6_to_T(pose6, np.float64)
+        if self._last is None:
+            k = self.addPose(T)
+            self.addPrior(k, T, self.PRIOR_VARIANCES)
+            return k
+        prev = self._last
+        k = self.addPose(T)
+        self.addBetween(k - 1, k, np.linalg.inv(prev) @ T, self.ODOM_VARIANCES)
+        return k
+
+    def addLoopFactor(self, loop):
+        """addLoopFactor (:1245-1264) for one (cur, pre, poseFrom, poseTo, noise) of LoopCloser: between(cur, pre, poseFrom^-1 poseTo, noise on all six)"""
+        cur, pre, pose_from, pose_to, noise = loop
+        Z = np.linalg.inv(np.asarray(pose_from, np.float64)) @ np.asarray(pose_to, np.float64)
+        self.addBetween(int(cur), int(pre), Z, np.full(6, float(noise)))
+
+    def optimize(self, params: PgoParams = None) -> dict:
+        res = PgoResult()
+        check(lib().rolo_pgo_optimize(self._h, C.byref(params if params is not None else pgo_params()), C.byref(res)), "rolo_pgo_optimize")
+        self.last = dict(state=res.state, iterations=res.iterations, trials=res.trials, initial_cost=res.initial_cost, final_cost=res.final_cost, lambda_=res.lambda_,
+                         pcg_iterations=res.pcg_iterations)
+        if res.iterations > 0:   # the poses moved: the host's copy of the last one is stale
+            n = len(self)
+            self._last = self.poses()[n - 1].copy()
+        return self.last
+
+    def poses(self):
+        """n x 4 x 4 doubles"""
+        n = len(self)
+        T = np.zeros((max(n, 1), 16), np.float64)
+        check(lib().rolo_pgo_get_poses(self._h, T.ctypes.data_as(C.POINTER(C.c_double)), None, n), "rolo_pgo_get_poses")
+        return T[:n].reshape(n, 4, 4)
+
+    def poses6(self):
+        """n x 6 floats, transformTobeMapped order"""
+        n = len(self)
+        p = np.zeros((max(n, 1), 6), np.float32)
+        check(lib().rolo_pgo_get_poses(self._h, None, p.ctypes.data_as(C.POINTER(C.c_float)), n), "rolo_pgo_get_poses")
+        return p[:n]
+
+    def trace(self):
+        """one record per trial of the last optimise"""
+        n = check(lib().rolo_pgo_get_trace(self._h, None, 0), "rolo_pgo_get_trace")
+        recs = (PgoTraceRec * max(n, 1))()
+        check(lib().rolo_pgo_get_trace(self._h, recs, n), "rolo_pgo_get_trace")
+        return [dict(lambda_=r.lambda_, cost=r.cost, accepted=bool(r.accepted), pcg_iterations=r.pcg_iterations, residual=r.residual) for r in recs[:n]]
+
+    def lastMs(self):
+        """device milliseconds of the last optimise: linearise + assemble, factorisation, PCG, retract + cost"""
+        ms = np.zeros(4, np.float32)
+        check(lib().rolo_pgo_last_ms(self._h, ms.ctypes.data_as(C.POINTER(C.c_float))), "rolo_pgo_last_ms")
+        return ms
+
+    def correctPoses(self, keymap: KeyFrameMap):
+        """correctPoses (:1287-1320): the graph's poses into the key map (the first len(graph) key frames); the next extraction uses them"""
+        keymap.setPoses(self.poses6())
+
+    def linearize(self):
+        """test hook -> cost, grad (6N), diag (N x 6 x 6), chain ((N - 1) x 6 x 6), chord (C x 6 x 6), chord_ij (C x 2)"""
+        n, _, nc = self.size()
+        dp = C.POINTER(C.c_double)
+        cost = C.c_double(0.0)
+        g = np.zeros(6 * n); D = np.zeros((n, 6, 6)); Ch = np.zeros((max(n - 1, 1), 6, 6)); H = np.zeros((max(nc, 1), 6, 6)); ij = np.zeros((max(nc, 1), 2), np.int32)
+        check(lib().rolo_pgo_linearize(self._h, C.byref(cost), g.ctypes.data_as(dp), D.ctypes.data_as(dp), Ch.ctypes.data_as(dp), H.ctypes.data_as(dp),
+                                       ij.ctypes.data_as(C.POINTER(C.c_int32))), "rolo_pgo_linearize")
+        return cost.value, g, D, Ch[:max(n - 1, 0)], H[:nc], ij[:nc]
+
+    def solveLinear(self, lambda_: float = 0.0, pcg_tol: float = 1e-10, pcg_max: int = 0):
+        """test hook -> delta (6N), PCG iterations, sqrt(r z) / sqrt(r0 z0): the step a trial would take on the last linearize()"""
+        n = len(self)
+        d = np.zeros(6 * max(n, 1)); its = C.c_int(0); res = C.c_double(0.0)
+        check(lib().rolo_pgo_solve_linear(self._h, lambda_, pcg_tol, pcg_max, d.ctypes.data_as(C.POINTER(C.c_double)), C.byref(its), C.byref(res)), "rolo_pgo_solve_linear")
+        return d[:6 * n], its.value, res.value

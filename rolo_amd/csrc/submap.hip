@@ -543,6 +543,12 @@ int rolo_keymap_set_pose(rolo_keymap* km, int index, const float* pose6) {
   return ROLO_OK;
 }
 
+int rolo_keymap_set_poses(rolo_keymap* km, const float* pose6, int n) {
+  if (!km || n < 0 || (n && !pose6) || n > (int)km->frames.size()) return ROLO_EINVAL;
+  for (int k = 0; k < n; k++) std::memcpy(km->frames[k].pose, pose6 + 6 * (size_t)k, sizeof(float) * 6);
+  return ROLO_OK;
+}
+
 int rolo_keymap_extract(rolo_keymap* km, const int32_t* indices, int n, float corner_leaf, float surf_leaf, int* m_corner, int* m_surf) {
   if (!km || n < 0 || (n && !indices) || !(corner_leaf > 0.f) || !(surf_leaf > 0.f)) return ROLO_EINVAL;
   long long total[2] = {0, 0};

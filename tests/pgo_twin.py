@@ -1,0 +1,423 @@
+"""Pose-graph optimisation as include/rolo_hip.h states it, in numpy / scipy: the statement the device code (rolo_amd/csrc/posegraph.hip) is held to.
+
+Poses X = (R, t) in fp64; tangent order [omega, v]; prior error Log(Z^-1 X_i), between error Log(Z^-1 X_i^-1 X_j); objective 1/2 sum |e / sigma|^2; retraction
+X <- X Exp(delta); Jr^-1 by its series I + ad/2 + ad^2/12 - ad^4/720; Levenberg-Marquardt with lambda I damping; the step either by a sparse direct solve
+(`optimize(..., solver="direct")`) or by conjugate gradients preconditioned with the block-tridiagonal part of H + lambda I, solved exactly (`solver="pcg"`)."""
+import numpy as np
+import scipy.sparse as sp
+import scipy.sparse.linalg as spl
+
+SMALL = 1e-2   # below this angle the coefficient series are used (their next terms are below 1e-18 there)
+
+CONVERGED, ITERATIONS, LAMBDA = 1, 2, 3
+STATES = {0: "NONE", 1: "CONVERGED", 2: "ITERATIONS", 3: "LAMBDA"}
+
+DEFAULTS = dict(max_iterations=100, absolute_error_tol=1e-5, relative_error_tol=1e-5, lambda_initial=1e-5, lambda_factor=10.0, lambda_upper=1e5, pcg_tol=1e-10,
+                pcg_max_iterations=0)
+MAX_TRIALS = 10000
+
+
+def hat(w):
+    return np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+
+
+def coeffs(th):
+    """A = sin th / th, B = (1 - cos th) / th^2, C = (th - sin th) / th^3, D = (1 - (th/2) cot(th/2)) / th^2"""
+    t2 = th * th
+    if th < SMALL:
+        A = 1.0 - t2 / 6.0 * (1.0 - t2 / 20.0 * (1.0 - t2 / 42.0))
+        B = 0.5 - t2 / 24.0 * (1.0 - t2 / 30.0 * (1.0 - t2 / 56.0))
+        C = 1.0 / 6.0 - t2 / 120.0 * (1.0 - t2 / 42.0 * (1.0 - t2 / 72.0))
+        D = 1.0 / 12.0 + t2 / 720.0 * (1.0 + t2 / 42.0 * (1.0 + t2 / 40.0))
+        return A, B, C, D
+    s, c = np.sin(th), np.cos(th)
+    sh, ch = np.sin(0.5 * th), np.cos(0.5 * th)
+    return s / th, 2.0 * sh * sh / t2, (th - s) / (t2 * th), (1.0 - 0.5 * th * ch / sh) / t2
+
+
+def exp_se3(xi):
+    w, v = xi[:3], xi[3:]
+    th = np.sqrt(w @ w)
+    A, B, C, _ = coeffs(th)
+    W = hat(w)
+    W2 = W @ W
+    return np.eye(3) + A * W + B * W2, (np.eye(3) + B * W + C * W2) @ v
+
+
+def log_so3(R):
+    w = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s = np.sqrt(w @ w)
+    c = 0.5 * (R[0, 0] + R[1, 1] + R[2, 2] - 1.0)
+    if s < 1e-6 and c > 0.0:
+        return w * (1.0 + s * s / 6.0)
+    return w * (np.arctan2(s, c) / s)   # (an angle within 1e-6 of pi is outside the statement)
+
+
+def log_se3(R, t):
+    w = log_so3(R)
+    th = np.sqrt(w @ w)
+    D = coeffs(th)[3]
+    W = hat(w)
+    return np.concatenate([w, (np.eye(3) - 0.5 * W + D * (W @ W)) @ t])
+
+
+def ad(xi):
+    M = np.zeros((6, 6))
+    M[:3, :3] = hat(xi[:3]); M[3:, 3:] = M[:3, :3]; M[3:, :3] = hat(xi[3:])
+    return M
+
+
+def jr_inv(xi):
+    a = ad(xi)
+    a2 = a @ a
+    return np.eye(6) + 0.5 * a + a2 / 12.0 - (a2 @ a2) / 720.0
+
+
+def Ad(R, t):
+    M = np.zeros((6, 6))
+    M[:3, :3] = R; M[3:, 3:] = R; M[3:, :3] = hat(t) @ R
+    return M
+
+
+def inv(R, t):
+    return R.T, -(R.T @ t)
+
+
+def mul(a, b):
+    return a[0] @ b[0], a[0] @ b[1] + a[1]
+
+
+def T_of(X):
+    T = np.eye(4); T[:3, :3] = X[0]; T[:3, 3] = X[1]
+    return T
+
+
+def X_of(T):
+    T = np.asarray(T, np.float64).reshape(4, 4)
+    return T[:3, :3].copy(), T[:3, 3].copy()
+
+
+def pose6_of(X):
+    """pcl::getTranslationAndEulerAngles, transformTobeMapped order"""
+    R, t = X
+    return np.array([np.arctan2(R[2, 1], R[2, 2]), np.arcsin(min(1.0, max(-1.0, -R[2, 0]))), np.arctan2(R[1, 0], R[0, 0]), t[0], t[1], t[2]])
+
+
+class Graph:
+    def __init__(self):
+        self.poses = []      # (R, t)
+        self.factors = []    # (i, j or -1, (Rz, tz), 1 / sigma)
+
+    def add_pose(self, T):
+        self.poses.append(X_of(T)); return len(self.poses) - 1
+
+    def add_prior(self, i, T, var6):
+        self.factors.append((i, -1, X_of(T), 1.0 / np.sqrt(np.asarray(var6, np.float64))))
+
+    def add_between(self, i, j, T, var6):
+        assert i != j
+        self.factors.append((i, j, X_of(T), 1.0 / np.sqrt(np.asarray(var6, np.float64))))
+
+    def chords(self):
+        return [f for f in range(len(self.factors)) if self.factors[f][1] >= 0 and abs(self.factors[f][0] - self.factors[f][1]) != 1]
+
+    # ---- one factor: whitened error and Jacobians ----
+    def factor(self, f, poses=None):
+        poses = self.poses if poses is None else poses
+        i, j, Z, isig = self.factors[f]
+        Zi = inv(*Z)
+        if j < 0:
+            e = log_se3(*mul(Zi, poses[i]))
+            return e * isig, jr_inv(e) * isig[:, None], None
+        D = mul(inv(*poses[i]), poses[j])
+        e = log_se3(*mul(Zi, D))
+        J = jr_inv(e)
+        return e * isig, (-J @ Ad(*inv(*D))) * isig[:, None], J * isig[:, None]
+
+    def cost(self, poses=None):
+        c = 0.0
+        for f in range(len(self.factors)):
+            e = self.factor(f, poses)[0]
+            c += 0.5 * (e @ e)
+        return c
+
+    def linearize(self):
+        """cost, grad (6N), diag (N x 6 x 6), chain ((N-1) x 6 x 6, the block H[k, k+1]), chord (C x 6 x 6, the block H[i, j]), chord_ij (C x 2); sums in factor order"""
+        N = len(self.poses)
+        g = np.zeros((N, 6)); Dg = np.zeros((N, 6, 6)); Ch = np.zeros((max(N - 1, 0), 6, 6)); chord = []; chord_ij = []
+        cost = 0.0
+        for f, (i, j, _, _) in enumerate(self.factors):
+            e, Ji, Jj = self.factor(f)
+            cost += 0.5 * (e @ e)
+            g[i] += Ji.T @ e; Dg[i] += Ji.T @ Ji
+            if j >= 0:
+                g[j] += Jj.T @ e; Dg[j] += Jj.T @ Jj
+                Hij = Ji.T @ Jj
+                if j == i + 1: Ch[i] += Hij
+                elif i == j + 1: Ch[j] += Hij.T
+                else: chord.append(Hij); chord_ij.append((i, j))
+        return cost, g.reshape(-1), Dg, Ch, np.array(chord).reshape(-1, 6, 6), np.array(chord_ij, np.int32).reshape(-1, 2)
+
+    # ---- the linear step ----
+    @staticmethod
+    def tri_matrix(Dg, Ch, lam):
+        N = Dg.shape[0]
+        rows, cols, vals = [], [], []
+        r6, c6 = np.meshgrid(np.arange(6), np.arange(6), indexing="ij")
+        for k in range(N):
+            rows.append(6 * k + r6); cols.append(6 * k + c6); vals.append(Dg[k] + lam * np.eye(6))
+        for k in range(N - 1):
+            rows.append(6 * k + r6); cols.append(6 * (k + 1) + c6); vals.append(Ch[k])
+            rows.append(6 * (k + 1) + r6); cols.append(6 * k + c6); vals.append(Ch[k].T)
+        cat = lambda a: np.concatenate([x.reshape(-1) for x in a])
+        return sp.csc_matrix((cat(vals), (cat(rows), cat(cols))), shape=(6 * N, 6 * N))
+
+    @staticmethod
+    def chord_matrix(N, chord, chord_ij):
+        rows, cols, vals = [], [], []
+        r6, c6 = np.meshgrid(np.arange(6), np.arange(6), indexing="ij")
+        for H, (i, j) in zip(chord, chord_ij):
+            rows.append(6 * i + r6); cols.append(6 * j + c6); vals.append(H)
+            rows.append(6 * j + r6); cols.append(6 * i + c6); vals.append(H.T)
+        if not rows:
+            return sp.csc_matrix((6 * N, 6 * N))
+        cat = lambda a: np.concatenate([x.reshape(-1) for x in a])
+        return sp.csc_matrix((cat(vals), (cat(rows), cat(cols))), shape=(6 * N, 6 * N))
+
+    @staticmethod
+    def solve_direct(lin, lam):
+        _, g, Dg, Ch, chord, chord_ij = lin
+        A = Graph.tri_matrix(Dg, Ch, lam) + Graph.chord_matrix(Dg.shape[0], chord, chord_ij)
+        return spl.spsolve(A.tocsc(), -g)
+
+    @staticmethod
+    def pcg_cap(n_chords, pcg_max=0):
+        if pcg_max > 0:
+            return pcg_max
+        return min(12 * n_chords + 2, 1000) if n_chords else 1   # without chords the preconditioner is the matrix: one application is the solve
+
+    @staticmethod
+    def solve_pcg(lin, lam, tol=1e-10, pcg_max=0):
+        """-> delta, iterations, sqrt(r z) / sqrt(r0 z0)"""
+        _, g, Dg, Ch, chord, chord_ij = lin
+        T = Graph.tri_matrix(Dg, Ch, lam)
+        A = T + Graph.chord_matrix(Dg.shape[0], chord, chord_ij)
+        lu = spl.splu(T.tocsc())
+        x = np.zeros_like(g)
+        r = -g
+        z = lu.solve(r)
+        rz = r @ z
+        rz0 = rz
+        if rz0 == 0.0:
+            return x, 0, 0.0
+        p = z.copy()
+        it = 0
+        for it in range(1, Graph.pcg_cap(len(chord), pcg_max) + 1):
+            q = A @ p
+            pq = p @ q
+            if not pq > 0.0:
+                it -= 1
+                break
+            a = rz / pq
+            x += a * p; r -= a * q
+            z = lu.solve(r)
+            rzn = r @ z
+            if not rzn > 0.0:
+                rz = 0.0
+                break
+            done = np.sqrt(rzn) <= tol * np.sqrt(rz0)
+            p = z + (rzn / rz) * p
+            rz = rzn
+            if done:
+                break
+        return x, it, np.sqrt(rz) / np.sqrt(rz0)
+
+    def retract(self, delta):
+        d = delta.reshape(-1, 6)
+        return [mul(X, exp_se3(d[k])) for k, X in enumerate(self.poses)]
+
+    # ---- Levenberg-Marquardt ----
+    def optimize(self, solver="direct", **kw):
+        """-> dict(state, iterations, trials, initial_cost, final_cost, lambda_, pcg_iterations, trace=[(lambda, cost, accepted, pcg iterations)])"""
+        P = dict(DEFAULTS); P.update(kw)
+        lin = self.linearize()
+        cost = lin[0]
+        res = dict(state=0, iterations=0, trials=0, initial_cost=cost, pcg_iterations=0, trace=[])
+        lam = P["lambda_initial"]
+        while True:
+            if res["iterations"] >= P["max_iterations"] or res["trials"] >= MAX_TRIALS:
+                res["state"] = ITERATIONS; break
+            if lam > P["lambda_upper"]:
+                res["state"] = LAMBDA; break
+            if solver == "direct":
+                delta, its = self.solve_direct(lin, lam), 0
+            else:
+                delta, its, _ = self.solve_pcg(lin, lam, P["pcg_tol"], P["pcg_max_iterations"])
+            trial = self.retract(delta)
+            new = self.cost(trial)
+            res["trials"] += 1; res["pcg_iterations"] += its
+            change = cost - new
+            res["trace"].append((lam, new, change > 0.0, its))
+            if change > 0.0:
+                self.poses = trial
+                lam /= P["lambda_factor"]
+                res["iterations"] += 1
+                old = cost
+                cost = new
+                if change <= P["absolute_error_tol"] or change <= P["relative_error_tol"] * old:
+                    res["state"] = CONVERGED; break
+                lin = self.linearize()
+            elif -change < P["absolute_error_tol"]:   # not lowered, and not raised by a resolvable amount: nothing left to gain (a zero gradient ends here)
+                res["state"] = CONVERGED; break
+            else:
+                lam *= P["lambda_factor"]
+        res["final_cost"] = cost; res["lambda_"] = lam
+        return res
+
+
+# ---- a seeded generator: a closed circuit driven `laps` times, drifting odometry, loop factors from truth plus small noise ----
+def circuit(N, n_loops, seed=0, laps=2, radius=20.0, odo_sigma=(2e-3, 2e-2), loop_sigma=(1e-3, 1e-2), prior_var=(1e-4,) * 6, odo_var=(1e-6, 1e-6, 1e-6, 1e-4, 1e-4, 1e-4),
+            loop_var=0.3):
+    """-> dict(truth, initial, priors=[(i, T, var6)], betweens=[(i, j, T, var6)]): the odometry chain first, then the loops (newer key to older key)"""
+    rng = np.random.default_rng(seed)
+    per_lap = max(N // laps, 1)
+    truth = []
+    for k in range(N):
+        a = 2.0 * np.pi * k / per_lap
+        R = exp_se3(np.array([0.02 * np.sin(3 * a), 0.03 * np.cos(2 * a), a + 0.5 * np.pi, 0, 0, 0]))[0]
+        truth.append((R, np.array([radius * np.cos(a), radius * np.sin(a), 0.5 * np.sin(a)])))
+    noise = lambda s: np.concatenate([rng.normal(0, s[0], 3), rng.normal(0, s[1], 3)])
+    initial = [truth[0]]
+    betweens = []
+    for k in range(1, N):
+        Z = mul(mul(inv(*truth[k - 1]), truth[k]), exp_se3(noise(odo_sigma)))
+        betweens.append((k - 1, k, T_of(Z), np.array(odo_var)))
+        initial.append(mul(initial[-1], Z))
+    for c in range(n_loops):
+        pre = int(rng.integers(0, max(N - per_lap, 1) if N > per_lap else max(N // 2, 1)))
+        cur = min(pre + per_lap, N - 1) if N > per_lap else N - 1
+        if cur - pre < 2:
+            continue
+        Z = mul(mul(inv(*truth[cur]), truth[pre]), exp_se3(noise(loop_sigma)))
+        betweens.append((cur, pre, T_of(Z), np.full(6, loop_var)))
+    return dict(truth=truth, initial=initial, priors=[(0, T_of(truth[0]), np.array(prior_var))], betweens=betweens)
+
+
+def build(spec, graph=None):
+    g = Graph() if graph is None else graph
+    for X in spec["initial"]:
+        g.add_pose(T_of(X))
+    for i, T, v in spec["priors"]:
+        g.add_prior(i, T, v)
+    for i, j, T, v in spec["betweens"]:
+        g.add_between(i, j, T, v)
+    return g
+
+
+# ---- the small graphs the linearisation and the solve are checked on ----
+SIZES = (1, 2, 3, 4, 5, 63, 64, 65, 1000)
+KINDS = ("none", "one", "skip2", "reversed", "pair2", "chain2", "prior_other", "prior2")
+MIN_N = dict(none=1, one=3, skip2=3, reversed=3, pair2=3, chain2=2, prior_other=2, prior2=1)
+CASES = [(n, k) for n in SIZES for k in KINDS if n >= MIN_N[k]]
+
+
+def case_spec(N, kind, seed=0, perturb=(1e-2, 5e-2)):
+    """a circuit's odometry chain with prior variances 1e-4, every initial pose moved off it by Exp(noise) so that no residual is trivial, plus the extra
+    factors of `kind`: one chord 0 -> N-1; a chord (k, k+2); a reversed chord N-1 -> 0; two chords on one pair; a second factor on a chain pair in reversed
+    direction (no chord); a prior on the last pose; two priors on pose 0"""
+    spec = circuit(N, 0, seed=seed + 7 * N, laps=2 if N >= 8 else 1)
+    rng = np.random.default_rng(1000 + seed + N)
+    noise = lambda s: np.concatenate([rng.normal(0, s[0], 3), rng.normal(0, s[1], 3)])
+    spec["initial"] = [mul(X, exp_se3(noise(perturb))) for X in spec["initial"]]
+    tr = spec["truth"]
+    meas = lambda i, j: T_of(mul(mul(inv(*tr[i]), tr[j]), exp_se3(noise((1e-3, 1e-2)))))
+    lv = np.full(6, 0.3)
+    if kind == "one": spec["betweens"].append((0, N - 1, meas(0, N - 1), lv))
+    elif kind == "skip2": k = max(N // 2 - 1, 0); spec["betweens"].append((k, k + 2, meas(k, k + 2), lv))
+    elif kind == "reversed": spec["betweens"].append((N - 1, 0, meas(N - 1, 0), lv))
+    elif kind == "pair2": spec["betweens"] += [(0, N - 1, meas(0, N - 1), lv), (0, N - 1, meas(0, N - 1), 0.5 * lv)]
+    elif kind == "chain2": k = N // 2 - 1 if N > 2 else 0; spec["betweens"].append((k + 1, k, meas(k + 1, k), np.array([1e-6] * 3 + [1e-4] * 3)))
+    elif kind == "prior_other": spec["priors"].append((N - 1, T_of(tr[N - 1]), np.full(6, 1e-2)))
+    elif kind == "prior2": spec["priors"].append((0, T_of(mul(tr[0], exp_se3(noise((1e-3, 1e-2))))), np.full(6, 1e-3)))
+    return spec
+
+
+def exact_chain(N):
+    """a chain whose every product is exact in binary floating point (quarter turns about z, dyadic translations), composed from its own measurements:
+    every residual, and so the gradient, is exactly zero"""
+    Rq = np.array([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]])
+    poses = [(np.eye(3), np.array([0.5, -0.25, 1.0]))]
+    betweens = []
+    for k in range(1, N):
+        Z = (Rq if k % 3 == 0 else np.eye(3), np.array([1.0, 0.5 * (k % 2), 0.25]))
+        betweens.append((k - 1, k, T_of(Z), np.array([1e-6] * 3 + [1e-4] * 3)))
+        poses.append(mul(poses[-1], Z))
+    return dict(truth=poses, initial=poses, priors=[(0, T_of(poses[0]), np.full(6, 1e-4))], betweens=betweens)
+
+
+def drift_spec():
+    """the graph of the truth test: 200 poses, two laps, odometry drifting by 2 mrad / 2 cm per step, 12 loops of variance 1e-3 from truth plus 1 mrad / 1 cm"""
+    return circuit(200, 12, seed=5, loop_var=1e-3)
+
+
+def max_position_error(poses, truth):
+    return max(float(np.linalg.norm((p if isinstance(p, tuple) else X_of(p))[1] - t[1])) for p, t in zip(poses, truth))
+
+
+def pose_distance(A, B):
+    """largest translation distance (m) and rotation angle (rad) between two pose lists; entries are (R, t) or 4 x 4"""
+    X = lambda P: P if isinstance(P, tuple) else X_of(P)
+    dt = dr = 0.0
+    for a, b in zip(A, B):
+        (Ra, ta), (Rb, tb) = X(a), X(b)
+        dt = max(dt, float(np.linalg.norm(ta - tb)))
+        w = log_so3(Ra.T @ Rb)
+        dr = max(dr, float(np.sqrt(w @ w)))
+    return dt, dr
+
+
+def relative_to_first(P):
+    X = [p if isinstance(p, tuple) else X_of(p) for p in P]
+    return [mul(inv(*X[0]), x) for x in X]
+
+
+WHOLE = ((65, 1), (200, 8), (1000, 20))   # (poses, loops) of the whole optimisations, seed = poses
+STRICT = dict(absolute_error_tol=0.0, relative_error_tol=0.0, max_iterations=50)
+
+
+def reference_spec(N=120, n_loops=4, seed=120):
+    """the reference's own calls: pose6 per key frame for addOdomFactor and LoopCloser-style tuples (cur, pre, poseFrom, poseTo, noise) for addLoopFactor"""
+    c = circuit(N, n_loops, seed=seed)
+    poses6 = [pose6_of(X).astype(np.float32) for X in c["initial"]]
+    loops = []
+    for i, j, T, v in c["betweens"][N - 1:]:     # Z = poseFrom^-1 poseTo with poseTo = truth[j]
+        pose_to = T_of(c["truth"][j])
+        loops.append((i, j, pose_to @ np.linalg.inv(T), pose_to, np.float32(v[0])))
+    return dict(poses6=poses6, loops=loops, truth=c["truth"])
+
+
+def pose6_to_T(p):
+    """pcl::getTransformation of a transformTobeMapped-order pose in double (rolo_amd.backend.pose6_to_T)"""
+    r, pt, y, tx, ty, tz = (np.float64(v) for v in p)
+    A, B, Cc, D, E, F = np.cos(y), np.sin(y), np.cos(pt), np.sin(pt), np.cos(r), np.sin(r)
+    DE, DF = D * E, D * F
+    return np.array([[A * Cc, A * DF - B * E, B * F + A * DE, tx], [B * Cc, A * E + B * DF, B * DE - A * F, ty], [-D, Cc * F, Cc * E, tz], [0, 0, 0, 1]], np.float64)
+
+
+PRIOR_VARIANCES = (1e-2, 1e-2, np.pi * np.pi, 1e8, 1e8, 1e8)
+ODOM_VARIANCES = (1e-6, 1e-6, 1e-6, 1e-4, 1e-4, 1e-4)
+
+
+def build_reference(ref):
+    """the twin's side of PoseGraph.addOdomFactor / addLoopFactor"""
+    g = Graph()
+    last = None
+    for p in ref["poses6"]:
+        T = pose6_to_T(p)
+        k = g.add_pose(T)
+        if last is None: g.add_prior(0, T, PRIOR_VARIANCES)
+        else: g.add_between(k - 1, k, np.linalg.inv(last) @ T, ODOM_VARIANCES)
+        last = T
+    for cur, pre, pf, pt, noise in ref["loops"]:
+        g.add_between(cur, pre, np.linalg.inv(pf) @ pt, np.full(6, float(noise)))
+    return g
