@@ -339,7 +339,8 @@ void rolo_affine3f_rotation(const float* T16, float* R9);
 /* The input of FeatureExtraction::laserCloudInfoHandler (src/featureExtraction.cpp:71-85) when that node runs as its own process: the arrays
  * of the received rolo/cloud_info — extracted[n_valid*4] = fromROSMsg(cloud_projected) as x, y, z, intensity; pointColInd, pointRange
  * (first n_valid entries), startRingIndex / endRingIndex [n_scan] — go where rolo_project_frame would have left them on the device;
- * rolo_extract_features then runs as usual. */
+ * rolo_extract_features then runs as usual. The index arrays are used as array indices on the device, so a malformed message is ROLO_EINVAL:
+ * start / end indices that are not the running counts of n_valid points, a ring of more than Horizon_SCAN points, a column outside the image. */
 int rolo_front_load_projection(rolo_ctx* ctx, const rolo_front_params* P, const float* extracted, const int32_t* point_col_ind,
                                const float* point_range, const int32_t* start_ring, const int32_t* end_ring, int n_valid);
 /* FeatureExtraction::calculateSmoothness + markOccludedPoints + extractFeatures (src/featureExtraction.cpp:87-266)
@@ -347,6 +348,21 @@ int rolo_front_load_projection(rolo_ctx* ctx, const rolo_front_params* P, const 
  * out (host): corner[nc*4], surface[ns*4] (sized for N points each); optional curvature/picked/label [N]. */
 int rolo_extract_features(rolo_ctx* ctx, const rolo_front_params* P, float* corner, int* n_corner, float* surface,
                           int* n_surface, float* curvature, int32_t* neighbor_picked, int32_t* label);
+/* Test hook: which way the last rolo_extract_features on `ctx` made the greedy corner / surface picks of every ring — out[n_scan], one
+ * word per ring, n_scan as in the parameters of the rolo_project_frame / rolo_front_load_projection it ran on. The choice depends on the data only
+ * (ring population, thresholds, position of the ring in the cloud, number of corner picks), never on the result.
+ *   bits 1..0, the ring:       ROLO_XPATH_RING_NONE     the whole-ring fixed point (all twelve pick stages at once) was not attempted
+ *                              ROLO_XPATH_RING_CAPPED   attempted and discarded: a sector had more than 20 corner picks, the ring was redone stage by stage
+ *                              ROLO_XPATH_RING_APPLIED  attempted and applied; every sector field below is ROLO_XPATH_SECTOR_NOT_STAGED
+ *   bits 3+2j..2+2j, sector j = 0..5 of a ring that went stage by stage:
+ *                              ROLO_XPATH_SECTOR_EMPTY     skipped (sp >= ep)
+ *                              ROLO_XPATH_SECTOR_PARALLEL  corner and surface picks as parallel fixed points
+ *                              ROLO_XPATH_SECTOR_SERIAL    the reference's serial walk on one lane
+ * A build with -DROLO_XT_STAGED never attempts the whole-ring fixed point: the ring field is always ROLO_XPATH_RING_NONE.
+ * ROLO_ESTATE if no extraction has run since the last projection or load, ROLO_EINVAL if n_scan is not that projection's. */
+enum { ROLO_XPATH_RING_NONE = 0, ROLO_XPATH_RING_CAPPED = 1, ROLO_XPATH_RING_APPLIED = 2 };
+enum { ROLO_XPATH_SECTOR_NOT_STAGED = 0, ROLO_XPATH_SECTOR_EMPTY = 1, ROLO_XPATH_SECTOR_PARALLEL = 2, ROLO_XPATH_SECTOR_SERIAL = 3 };
+int rolo_debug_extract_paths(rolo_ctx* ctx, int32_t* out, int n_scan);
 
 /* ---- per-frame odometry driver -------------------------------------------------------------------------------
  * LidarOdometry (src/lidarOdometry.cpp:325-713) between fromROSMsg and publish, on feature clouds (n x 4 floats:

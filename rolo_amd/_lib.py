@@ -274,6 +274,7 @@ SYMBOLS = {
     "rolo_front_load_projection": (C.c_int, [vp, C.POINTER(FrontParams), fp, ip, fp, ip, ip, C.c_int]),
     "rolo_extract_features": (C.c_int, [vp, C.POINTER(FrontParams), fp, C.POINTER(C.c_int), fp, C.POINTER(C.c_int), fp,
                                         ip, ip]),
+    "rolo_debug_extract_paths": (C.c_int, [vp, ip, C.c_int]),
 }
 
 _lib = None

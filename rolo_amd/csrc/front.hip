@@ -263,6 +263,7 @@ struct FeatArgs {
   float4* corner_stage; int* corner_cnt;  // [n_scan][6][20], [n_scan][6]
   float4* surf_stage; int* surf_cnt;      // [n_scan][MAXH], [n_scan]
   unsigned char* big;                     // Horizon_SCAN > 2048: front_ring_bytes(MAXH) of scratch per ring
+  int* paths;                             // [n_scan]: which way the ring's picks were made (ROLO_XPATH_*, rolo_hip.h) — one lane's store per ring
 };
 
 // One workgroup of XT = 1024 threads per ring: 128 rings are only 128 workgroups, so the parallelism has to come from inside —
@@ -411,6 +412,7 @@ __global__ __launch_bounds__(XT) void extract_kernel(FeatArgs A) {
   // thresholds that let a cell be corner AND surface candidate, and the cap — the corner walk stops after its 20th pick
   // (largestPickedNum, :186-193), so a sector with more corner picks than that is redone stage by stage (checked before anything is applied).
   bool global_done = false;
+  int path = ROLO_XPATH_RING_NONE;   // uniform: every branch below that sets it is taken by the whole workgroup
 #ifndef ROLO_XT_STAGED
   {
     constexpr int UPG = (6 * SEGMAX + XT - 1) / XT;   // entries (sector, position) per thread
@@ -527,6 +529,7 @@ __global__ __launch_bounds__(XT) void extract_kernel(FeatArgs A) {
         if (j < 6 && lane == 0 && (i0 - j * SEGMAX) == 0) A.corner_cnt[ring * 6 + j] = total;   // (rewritten by the staged code if the cap strikes)
       }
       __syncthreads();
+      path = s_gbad == 0 ? ROLO_XPATH_RING_APPLIED : ROLO_XPATH_RING_CAPPED;
       if (s_gbad == 0) {
 #pragma unroll
         for (int u = 0; u < UPG; u++) {
@@ -577,7 +580,7 @@ __global__ __launch_bounds__(XT) void extract_kernel(FeatArgs A) {
   for (int j = 0; j < 6; j++) {
     const int sp = (s * (6 - j) + e * j) / 6;
     const int ep = (s * (5 - j) + e * (j + 1)) / 6 - 1;
-    if (sp >= ep) { if (t == 0) A.corner_cnt[ring * 6 + j] = 0; continue; }  // uniform
+    if (sp >= ep) { if (t == 0) A.corner_cnt[ring * 6 + j] = 0; path |= ROLO_XPATH_SECTOR_EMPTY << (2 + 2 * j); continue; }  // uniform
     const unsigned long long* skeys = keys + j * seg;
     const int len = ep - sp;  // sorted range [sp, ep); positions sp..ep take part in the picks
     // Sectors at the two ends of the cloud hold the reference's stale {0, 0} smoothness entries: entries that all name POINT 0,
@@ -590,7 +593,9 @@ __global__ __launch_bounds__(XT) void extract_kernel(FeatArgs A) {
     const bool thr_ok = A.surf_threshold > 0.f && A.edge_threshold >= 0.f;
     const bool head_ok = !head_sp || (thr_ok && !tail_sp && ep >= 5 && w0 <= 0 && -w0 < wlen);
     const bool tail_ok = !tail_sp || (thr_ok && !head_sp && n >= 64 && A.start_ring[0] == 4 && A.end_ring[0] >= 30);   // ring 0 starts at 0 - 1 + 5 and its stale entry marked point 0
-    if (head_ok && tail_ok && len < SEGMAX) {
+    const bool parallel = head_ok && tail_ok && len < SEGMAX;
+    path |= (parallel ? ROLO_XPATH_SECTOR_PARALLEL : ROLO_XPATH_SECTOR_SERIAL) << (2 + 2 * j);
+    if (parallel) {
       // ---- parallel greedy picks ----
       // The reference walks the sector in curvature order and a pick marks its +-5 neighbours (up to a column break) as
       // taken. Equivalent fixed point: a candidate is picked iff no better-ranked candidate that reaches it is picked.
@@ -785,6 +790,7 @@ __global__ __launch_bounds__(XT) void extract_kernel(FeatArgs A) {
     }
   }
   XT_STAMP(3);
+  if (t == 0) A.paths[ring] = path;
   // write the ring's picked / label window back (the oracle's arrays after extraction)
   for (int i = t; i < wlen; i += XT) {
     const int gi = w0 + i;
@@ -952,6 +958,7 @@ struct Front {
   float* curv = nullptr; int *picked = nullptr, *label = nullptr;
   float4 *corner_stage = nullptr, *surf_stage = nullptr, *corner_out = nullptr, *surf_out = nullptr;
   int *corner_cnt = nullptr, *surf_cnt = nullptr;
+  int* paths = nullptr; bool paths_valid = false;   // per-ring path words of the last extraction (rolo_debug_extract_paths)
   unsigned char* big = nullptr; int maxh = FRONT_MAX_H, cap_maxh = 0;   // Horizon_SCAN > 2048: per-ring scratch of the extract kernel, staging pitch
   int n_valid = 0; int n_scan = 0, H = 0;
   bool projected = false;
@@ -978,7 +985,7 @@ bool dev_alloc(T*& p, size_t count) {
 
 void front_free(Front* f) {
   void* bufs[] = {f->raw, f->ring, f->owner, f->local_idx, f->ring_count, f->start_ring, f->end_ring, f->counters, f->extracted, f->col, f->range,
-                  f->range_mat, f->curv, f->picked, f->label, f->corner_stage, f->surf_stage, f->corner_out, f->surf_out, f->corner_cnt, f->surf_cnt, f->big, f->rel_time, f->msg_raw, f->msg_xyz, f->msg_ring, f->msg_time};
+                  f->range_mat, f->curv, f->picked, f->label, f->corner_stage, f->surf_stage, f->corner_out, f->surf_out, f->corner_cnt, f->surf_cnt, f->paths, f->big, f->rel_time, f->msg_raw, f->msg_xyz, f->msg_ring, f->msg_time};
   for (void* b : bufs) if (b) (void)hipFree(b);
 }
 
@@ -1027,13 +1034,13 @@ int front_prepare(rolo_ctx* c, const rolo_front_params* P, int n_raw, int stride
   if ((size_t)NS > f->cap_scan || !f->ring_count || maxh > f->cap_maxh) {
     ok = ok && dev_alloc(f->ring_count, NS) && dev_alloc(f->start_ring, NS) && dev_alloc(f->end_ring, NS) && dev_alloc(f->counters, 8) &&
          dev_alloc(f->corner_stage, (size_t)NS * 6 * 20) && dev_alloc(f->corner_cnt, (size_t)NS * 6) && dev_alloc(f->surf_stage, (size_t)NS * maxh) &&
-         dev_alloc(f->surf_cnt, NS);
+         dev_alloc(f->surf_cnt, NS) && dev_alloc(f->paths, NS);
     if (maxh > FRONT_MAX_H) ok = ok && dev_alloc(f->big, (size_t)NS * front_ring_bytes(FRONT_MAX_H_BIG));
     f->cap_scan = ok ? NS : 0; f->cap_maxh = ok ? maxh : 0;
   }
   f->maxh = maxh;
   if (!ok) { ctx_set_error("hipMalloc failed (front end)"); return ROLO_EHIP; }
-  f->n_scan = NS; f->H = H; f->projected = false;
+  f->n_scan = NS; f->H = H; f->projected = false; f->paths_valid = false;
   *out = f;
   return ROLO_OK;
 }
@@ -1095,7 +1102,7 @@ int front_extract_enqueue(Front* f, const rolo_front_params* P, hipStream_t s, f
   A.label = f->label + FRONT_GUARD; A.start_ring = f->start_ring; A.end_ring = f->end_ring; A.n_ptr = f->counters; A.n_scan = NS;
   A.edge_threshold = P->edge_threshold; A.surf_threshold = P->surf_threshold; A.leaf = P->odometry_surf_leaf_size;
   A.corner_stage = f->corner_stage; A.corner_cnt = f->corner_cnt; A.surf_stage = f->surf_stage; A.surf_cnt = f->surf_cnt;
-  A.big = reinterpret_cast<unsigned char*>(f->big);
+  A.big = reinterpret_cast<unsigned char*>(f->big); A.paths = f->paths;
   if (f->maxh > FRONT_MAX_H) {
     extract_kernel<FRONT_MAX_H_BIG, true><<<NS, XT, 0, s>>>(A);   // the ring's working set in HBM scratch
   } else {
@@ -1112,6 +1119,7 @@ int front_extract_enqueue(Front* f, const rolo_front_params* P, hipStream_t s, f
     concat_kernel<<<NS, 256, 0, s>>>(f->surf_stage, f->surf_cnt, NS, f->maxh, f->surf_out, f->counters + 2);
   }
   FCHK(hipGetLastError());
+  f->paths_valid = true;
   return ROLO_OK;
 }
 
@@ -1197,7 +1205,7 @@ void front_reset_object_state(rolo_ctx* c) {
   Front* f = static_cast<Front*>(*slot);
   f->projected = false; f->extract_cleared = false; f->precleared_np = 0;
   f->deskew_armed = false; f->deskew_from_msg = false; f->deskew_n = 0;
-  f->n_valid = 0;
+  f->n_valid = 0; f->paths_valid = false;
 }
 }  // namespace rolo
 
@@ -1288,6 +1296,8 @@ int rolo_front_load_projection(rolo_ctx* c, const rolo_front_params* P, const fl
     for (int i = 0; i < P->n_scan; i++) {
       const long long before = (long long)start_ring[i] - 4, after = (long long)end_ring[i] + 6;
       if (before < prev || after < before || after > n_valid) { ctx_set_error("startRingIndex / endRingIndex are not the running counts of a projection of n_valid points"); return ROLO_EINVAL; }
+      // extract_kernel sizes its ring window and its sector sort for a ring of at most Horizon_SCAN points (one per column)
+      if (after - before > P->horizon_scan) { ctx_set_error("a ring holds more than Horizon_SCAN points"); return ROLO_EINVAL; }
       prev = (int)after;
     }
     for (int i = 0; i < n_valid; i++)
@@ -1337,6 +1347,20 @@ int rolo_extract_features(rolo_ctx* c, const rolo_front_params* P, float* corner
   if (curvature && n) FCHK(hipMemcpyAsync(curvature, f->curv + FRONT_GUARD, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, s));
   if (neighbor_picked && n) FCHK(hipMemcpyAsync(neighbor_picked, f->picked + FRONT_GUARD, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s));
   if (label && n) FCHK(hipMemcpyAsync(label, f->label + FRONT_GUARD, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s));
+  FCHK(hipStreamSynchronize(s));
+  return ROLO_OK;
+}
+
+// the path word of every ring (ROLO_XPATH_*, rolo_hip.h) as the last rolo_extract_features on this context left it
+int rolo_debug_extract_paths(rolo_ctx* c, int32_t* out, int n_scan) {
+  if (!c || !out || n_scan <= 0) return ROLO_EINVAL;
+  void** slot = ctx_front_slot(c);
+  Front* f = static_cast<Front*>(*slot);
+  if (!f || !f->paths_valid) { ctx_set_error("rolo_debug_extract_paths needs a preceding extraction"); return ROLO_ESTATE; }
+  if (n_scan != f->n_scan) { ctx_set_error("rolo_debug_extract_paths: n_scan is not the last projection's"); return ROLO_EINVAL; }
+  FCHK(hipSetDevice(ctx_device(c)));
+  hipStream_t s = ctx_stream(c);
+  FCHK(hipMemcpyAsync(out, f->paths, sizeof(int) * (size_t)n_scan, hipMemcpyDeviceToHost, s));
   FCHK(hipStreamSynchronize(s));
   return ROLO_OK;
 }

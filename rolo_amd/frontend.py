@@ -78,6 +78,24 @@ class FrontEnd:
             out["range_mat"] = rm.reshape(NS, H)
         return out
 
+    def loadProjection(self, proj):
+        """The feature node's input when it runs as its own process (rolo_front_load_projection): the dict project() / pyorc.project return goes
+        where project() would have left it on the device; extract() then runs as usual. Returns n."""
+        n = int(proj["n"])
+        ext = np.ascontiguousarray(proj["extracted"], np.float32).reshape(-1, 4)
+        col = np.ascontiguousarray(proj["point_col_ind"], np.int32); rng = np.ascontiguousarray(proj["point_range"], np.float32)
+        sr = np.ascontiguousarray(proj["start_ring"], np.int32); er = np.ascontiguousarray(proj["end_ring"], np.int32)
+        if ext.shape[0] < n or col.shape[0] < n or rng.shape[0] < n or sr.shape[0] != self.p.n_scan or er.shape[0] != self.p.n_scan:
+            raise ValueError("projection arrays shorter than n points / not n_scan rings")
+        check(lib().rolo_front_load_projection(self.ctx._h, C.byref(self.p), _f(ext), _i(col), _f(rng), _i(sr), _i(er), n), "rolo_front_load_projection")
+        return n
+
+    def extractPaths(self):
+        """Test hook (rolo_debug_extract_paths): the path word of every ring of the last extract() — ROLO_XPATH_* in include/rolo_hip.h."""
+        out = np.zeros(self.p.n_scan, np.int32)
+        check(lib().rolo_debug_extract_paths(self.ctx._h, _i(out), self.p.n_scan), "rolo_debug_extract_paths")
+        return out
+
     def extract(self, n, debug=False):
         corner = np.zeros((max(n, 1), 4), np.float32); surf = np.zeros((max(n, 1), 4), np.float32)
         nc = C.c_int(0); ns = C.c_int(0)

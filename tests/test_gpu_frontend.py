@@ -224,6 +224,14 @@ def test_load_projection_refuses_indices_that_would_leave_the_arrays():
     assert call(start, end, bad) == -1
     bad = col.copy(); bad[0] = -1
     assert call(start, end, bad) == -1
+    # a ring of more than Horizon_SCAN points: extract_kernel sizes its window and its sector sort for at most one point per column. (The load alone: an
+    # extraction must never follow a refused load.)
+    P.n_scan = 2; P.horizon_scan = 600
+    col6 = (np.arange(n) % 600).astype(np.int32)
+    rings = lambda first: (np.array([4, first + 4], np.int32), np.array([first - 6, n - 6], np.int32))   # noqa: E731 — rings of `first` and n - first points
+    assert call(*rings(601), col6) == -1 and b"more than Horizon_SCAN points" in lib().rolo_last_error()
+    assert call(*rings(399), col6) == -1 and b"more than Horizon_SCAN points" in lib().rolo_last_error()      # ... the second ring: 601
+    assert call(*rings(600), col6) == 0
     g.close()
 
 
