@@ -601,6 +601,14 @@ int rolo_keymap_loop_last_ms(rolo_keymap* km, float* ms6);
  *   factors    prior(i, Z, var6): e = Log(Z^-1 X_i); between(i, j, Z, var6): e = Log(Z^-1 X_i^-1 X_j), i != j in either order. Log is the full SE(3) logarithm,
  *              tangent order [omega, v] (rotation first, as GTSAM's Pose3), coefficient series below an angle of 1e-2; an angle within 1e-6 of pi is outside the
  *              statement. var6: variances in that order (noiseModel::Diagonal::Variances). Objective 1/2 sum |e / sigma|^2.
+ *   loss       a between factor may carry a Cauchy loss with constant k > 0, as performSCLoopClosure adds its loop (noiseModel::Robust::Create(
+ *              mEstimator::Cauchy::Create(1.0), Diagonal::Variances(v6)), :2464-2470). With e_w = e / sigma and r^2 = |e_w|^2 its cost term is
+ *              rho = k^2 / 2 log1p(r^2 / k^2) in place of r^2 / 2 and its weight w = k^2 / (k^2 + r^2): mEstimator::Cauchy::loss and ::weight at distance r.
+ *              In the linearisation the whitened error and both whitened Jacobians are scaled by sqrt(w) before the products, as
+ *              noiseModel::Robust::WhitenSystem does: the factor's blocks are w J^T J and its gradient parts w J^T e_w, the exact gradient of rho. The outer loop
+ *              is unchanged: accept, reject and convergence read the robust cost. w > 0 always, so H + lambda I keeps its definiteness rule. A factor without
+ *              loss is computed as before, and a graph without a robust factor gives the results it gave. Priors carry no loss, and Cauchy is the only
+ *              M-estimator (the reference configures no other). tests/pgo_robust_twin.py restates this in numpy; parity with GTSAM is unpinned here too.
  *   linearise  retraction X <- X Exp(delta); J_j = Jr^-1(e), J_i = -Jr^-1(e) Ad((X_i^-1 X_j)^-1), prior J_i = Jr^-1(e), with Jr^-1 by its series
  *              I + ad/2 + ad^2/12 - ad^4/720; rows whitened by 1 / sigma. H and g are summed per pose over its factors in factor order (no atomics).
  *   step       (H + lambda I) delta = -g by conjugate gradients preconditioned with T, the block-tridiagonal part of H + lambda I (diagonal blocks and the blocks
@@ -616,11 +624,14 @@ int rolo_keymap_loop_last_ms(rolo_keymap* km, float* ms6);
  * pose6 (transformTobeMapped order) is taken from R as pcl::getTranslationAndEulerAngles does; GTSAM's rotation().roll()/pitch()/yaw() agree away from gimbal
  * lock (parity unpinned). A graph is single-threaded like a key map, works on a stream of its own and waits for it before returning; its device store only grows.
  * ROLO_EINVAL: an index out of range, i == j, a variance <= 0 or non-finite, a non-finite pose, more than ROLO_PGO_MAX_POSES poses, a solve whose H + lambda I is
- * not positive definite. ROLO_ESTATE: optimise or linearise with no pose or no factor; solve_linear without a linearisation of the graph as it stands. */
+ * not positive definite, a loss constant k that is not finite and positive (or whose square is not). ROLO_EUNSUPPORTED: a loss other than
+ * ROLO_PGO_LOSS_CAUCHY. ROLO_ESTATE: optimise, linearise or get_factor_errors with no pose or no factor; solve_linear without a linearisation of the graph as
+ * it stands. */
 #define ROLO_PGO_MAX_POSES (1 << 16)
 #define ROLO_PGO_CONVERGED 1
 #define ROLO_PGO_ITERATIONS 2
 #define ROLO_PGO_LAMBDA 3
+#define ROLO_PGO_LOSS_CAUCHY 1
 typedef struct rolo_pgo rolo_pgo;
 typedef struct rolo_pgo_params { int max_iterations; double absolute_error_tol, relative_error_tol, lambda_initial, lambda_factor, lambda_upper, pcg_tol;
                                  int pcg_max_iterations; } rolo_pgo_params;
@@ -634,10 +645,16 @@ void rolo_pgo_default_params(rolo_pgo_params* p);
 int rolo_pgo_add_pose(rolo_pgo* g, const double* T16);
 int rolo_pgo_add_prior(rolo_pgo* g, int i, const double* T16, const double* var6);
 int rolo_pgo_add_between(rolo_pgo* g, int i, int j, const double* T16, const double* var6);
+/* the same factor under a loss: everything rolo_pgo_add_between checks, and loss == ROLO_PGO_LOSS_CAUCHY with its constant k. A factor on a chain pair
+ * (|i - j| == 1) may be robust: it lands in the chain block like any other */
+int rolo_pgo_add_between_robust(rolo_pgo* g, int i, int j, const double* T16, const double* var6, int loss, double k);
 int rolo_pgo_size(rolo_pgo* g, int* n_poses, int* n_factors, int* n_chords);
 int rolo_pgo_optimize(rolo_pgo* g, const rolo_pgo_params* params, rolo_pgo_result* out);
 /* the current poses: T16_out (n x 16 doubles) and / or pose6_out (n x 6 floats), the first min(n, cap); returns n */
 int rolo_pgo_get_poses(rolo_pgo* g, double* T16_out, float* pose6_out, int cap);
+/* every factor's r^2 = |e / sigma|^2 and weight w at the current poses, in the order the factors were added, the first min(F, cap); each output is optional;
+ * returns F. w is exactly 1.0 for a factor without loss: after an optimise, a robust loop whose w is near 0 is one the optimum outvoted */
+int rolo_pgo_get_factor_errors(rolo_pgo* g, double* r2, double* weight, int cap);
 int rolo_pgo_get_trace(rolo_pgo* g, rolo_pgo_trace_rec* out, int cap);
 /* test hooks. linearise at the current poses: cost, grad[6N], diag[N x 36], chain[(N - 1) x 36] (the blocks H[k, k+1]), chord[chords x 36] (H[i, j] of the
  * factor as given) and chord_ij[chords x 2], each optional; solve_linear: the step a trial would take on the last linearisation */

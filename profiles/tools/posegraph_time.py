@@ -6,7 +6,8 @@ GTSAM's default tolerances. Recorded into --out (profiles/r10/posegraph.json): t
 HIP events; the cyclic reduction's factorisation and the PCG loop, which share one launch, by the device's wall clock inside it), the host clock around the call,
 the exit, iterations, trials and PCG iterations. `keyframe_call`: the zero-loop per-key-frame use, the median of --reps addOdomFactor + optimise calls on a graph of
 N - reps poses without loops. `host_direct_solve_s`: scipy's sparse direct solve (spsolve, SuperLU on the host cores) of the SAME first linear system, taken from
-the device's linearisation, wall clock: for scale, NOT a baseline (the reference's iSAM2 is incremental and cannot be built here)."""
+the device's linearisation, wall clock: for scale, NOT a baseline (the reference's iSAM2 is incremental and cannot be built here). --cauchy K adds every loop
+under a Cauchy(K) loss, as performSCLoopClosure does with K = 1 (profiles/r11/posegraph_robust.json); without it every factor is plain."""
 import argparse
 import json
 import os
@@ -22,12 +23,16 @@ import pgo_twin as tw  # noqa: E402
 from rolo_amd.backend import PoseGraph  # noqa: E402
 
 
-def fill(g, spec, n_between=None):
+def fill(g, spec, n_between=None, cauchy=None):
+    n = len(spec["initial"])
     for X in spec["initial"]:
         g.addPose(tw.T_of(X))
     g.addPrior(0, tw.T_of(spec["initial"][0]), tw.PRIOR_VARIANCES)
-    for i, j, T, v in spec["betweens"][:n_between]:
-        g.addBetween(i, j, T, v)
+    for f, (i, j, T, v) in enumerate(spec["betweens"][:n_between]):
+        if cauchy is None or f < n - 1:     # the odometry chain comes first and is always plain
+            g.addBetween(i, j, T, v)
+        else:
+            g.addBetween(i, j, T, v, cauchy=cauchy)
 
 
 def main():
@@ -37,6 +42,7 @@ def main():
     ap.add_argument("--loops", default="1,10,100")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--host-solve-max", type=int, default=60000, help="largest N whose first system is also solved on the host")
+    ap.add_argument("--cauchy", type=float, default=None, help="every loop under a Cauchy loss with this constant")
     a = ap.parse_args()
     rows = []
     for N in [int(x) for x in a.sizes.split(",")]:
@@ -63,7 +69,7 @@ def main():
         for loops in [int(x) for x in a.loops.split(",")]:
             spec = tw.circuit(N, loops, seed=N)
             g = PoseGraph()
-            fill(g, spec)
+            fill(g, spec, cauchy=a.cauchy)
             n, f, c = g.size()
             host = None
             if N <= a.host_solve_max:
@@ -76,7 +82,7 @@ def main():
             wall_ms = 1e3 * (time.perf_counter() - t0)
             row = dict(poses=n, factors=f, chords=c, state=PoseGraph.STATES[r["state"]], iterations=r["iterations"], trials=r["trials"], pcg_iterations=r["pcg_iterations"],
                        initial_cost=r["initial_cost"], final_cost=r["final_cost"], ms_linearise_factor_pcg_retract=[float(x) for x in g.lastMs()], wall_ms=wall_ms,
-                       pcg_per_trial=[t["pcg_iterations"] for t in g.trace()], host_direct_solve_s=host, keyframe_call=key)
+                       pcg_per_trial=[t["pcg_iterations"] for t in g.trace()], host_direct_solve_s=host, keyframe_call=key, cauchy=a.cauchy)
             g.close()
             rows.append(row)
             print(row, flush=True)

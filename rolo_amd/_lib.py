@@ -201,6 +201,8 @@ SYMBOLS = {
     "rolo_pgo_add_pose": (C.c_int, [vp, dp]),
     "rolo_pgo_add_prior": (C.c_int, [vp, C.c_int, dp, dp]),
     "rolo_pgo_add_between": (C.c_int, [vp, C.c_int, C.c_int, dp, dp]),
+    "rolo_pgo_add_between_robust": (C.c_int, [vp, C.c_int, C.c_int, dp, dp, C.c_int, C.c_double]),
+    "rolo_pgo_get_factor_errors": (C.c_int, [vp, dp, dp, C.c_int]),
     "rolo_pgo_size": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rolo_pgo_optimize": (C.c_int, [vp, C.POINTER(PgoParams), C.POINTER(PgoResult)]),
     "rolo_pgo_get_poses": (C.c_int, [vp, dp, fp, C.c_int]),

@@ -353,10 +353,24 @@ def pose6_to_T(pose6, dtype=np.float32):
     return np.array([[A * Cc, A * DF - B * E, B * F + A * DE, tx], [B * Cc, A * E + B * DF, B * DE - A * F, ty], [-D, Cc * F, Cc * E, tz], [0, 0, 0, 1]], dtype)
 
 
+PGO_LOSS_CAUCHY = 1   # ROLO_PGO_LOSS_CAUCHY
+
+
+class LoopFactor(tuple):
+    """(loopKeyCur, loopKeyPre, poseFrom, poseTo, noise) as LoopCloser returns it, with the loss the reference wraps that noise in: `robust` is None (the plain
+    diagonal of performRSLoopClosure, :2382-2385) or the Cauchy constant k (performSCLoopClosure's Robust noise with Cauchy(1), :2468-2470). It unpacks into the
+    same five entries as the plain tuple."""
+    def __new__(cls, entries, robust=None):
+        self = super().__new__(cls, entries)
+        self.robust = None if robust is None else float(robust)
+        return self
+
+
 class LoopCloser:
-    """performRSLoopClosure (:2307-2397) and performSCLoopClosure (:2399-2479) over a key map, up to the factor graph: each call returns
+    """performRSLoopClosure (:2307-2397) and performSCLoopClosure (:2399-2479) over a key map, up to the factor graph: each call returns a LoopFactor
     (loopKeyCur, loopKeyPre, poseFrom 4 x 4, poseTo 4 x 4, noise) — the constraint is poseFrom.between(poseTo) with the variance `noise` on all six axes — or None.
-    PoseGraph.addLoopFactor takes that tuple as it is."""
+    Its `robust` is None for the RS form and 1.0 for the SC form, whose noise the reference puts under a Cauchy(1) M-estimator because Scan Context can propose a
+    wrong place. PoseGraph.addLoopFactor takes it as it is."""
     MIN_CUR, MIN_PREV = 300, 1000   # :2333, :2424
     SC_CAP = 150.0                  # :2431
 
@@ -397,7 +411,7 @@ class LoopCloser:
         t_wrong = pose6_to_T(self.km.poses[cur])
         t_correct = (res["T"].astype(np.float32) @ t_wrong).astype(np.float64)   # :2377
         self.loopIndexContainer[cur] = pre
-        return cur, pre, t_correct, pose6_to_T(self.km.poses[pre], np.float64), np.float32(res["fitness"])
+        return LoopFactor((cur, pre, t_correct, pose6_to_T(self.km.poses[pre], np.float64), np.float32(res["fitness"])), robust=None)   # :2382-2385
 
     def performSCLoopClosure(self, sc_manager: "ScanContextManager"):
         if len(self.km.poses) == 0:
@@ -411,7 +425,7 @@ class LoopCloser:
         if res is None:
             return None
         self.loopIndexContainer[cur] = pre
-        return cur, pre, res["T"].astype(np.float64), np.eye(4), np.float32(res["fitness"])
+        return LoopFactor((cur, pre, res["T"].astype(np.float64), np.eye(4), np.float32(res["fitness"])), robust=1.0)   # :2468-2470
 
 
 
@@ -427,8 +441,8 @@ def pgo_params(**kw) -> PgoParams:
 
 class PoseGraph:
     """gtSAMgraph + initialEstimate + isam->update + correctPoses (:1094-1320) as a batch minimiser of the same objective on the device (include/rolo_hip.h,
-    "pose-graph optimisation"): the same factors and noise models; iSAM2's incremental bookkeeping and its marginal covariance are not restated, and parity with
-    GTSAM is unpinned. Poses are 4 x 4 doubles; pose6 is transformTobeMapped order (roll, pitch, yaw, x, y, z)."""
+    "pose-graph optimisation"): the same factors and noise models, the SC loop's Cauchy-robust noise included; iSAM2's incremental bookkeeping and its marginal
+    covariance are not restated, and parity with GTSAM is unpinned. Poses are 4 x 4 doubles; pose6 is transformTobeMapped order (roll, pitch, yaw, x, y, z)."""
     STATES = ("NONE", "CONVERGED", "ITERATIONS", "LAMBDA")
     PRIOR_VARIANCES = (1e-2, 1e-2, np.pi * np.pi, 1e8, 1e8, 1e8)   # :1229
     ODOM_VARIANCES = (1e-6, 1e-6, 1e-6, 1e-4, 1e-4, 1e-4)          # :1235
@@ -468,10 +482,14 @@ class PoseGraph:
         kt, t = self._dp(T, 16); kv, v = self._dp(variances, 6)
         check(lib().rolo_pgo_add_prior(self._h, i, t, v), "rolo_pgo_add_prior")
 
-    def addBetween(self, i: int, j: int, T, variances):
-        """BetweenFactor<Pose3>(i, j, T, Diagonal::Variances(variances)); the reference's ground-prior factors (:1266-1284) come through here"""
+    def addBetween(self, i: int, j: int, T, variances, cauchy=None):
+        """BetweenFactor<Pose3>(i, j, T, Diagonal::Variances(variances)); the reference's ground-prior factors (:1266-1284) come through here. cauchy = k puts the
+        noise under Robust::Create(mEstimator::Cauchy::Create(k), ...) as the SC loop closure does (:2464-2470); None is the plain diagonal"""
         kt, t = self._dp(T, 16); kv, v = self._dp(variances, 6)
-        check(lib().rolo_pgo_add_between(self._h, i, j, t, v), "rolo_pgo_add_between")
+        if cauchy is None:
+            check(lib().rolo_pgo_add_between(self._h, i, j, t, v), "rolo_pgo_add_between")
+        else:
+            check(lib().rolo_pgo_add_between_robust(self._h, i, j, t, v, PGO_LOSS_CAUCHY, float(cauchy)), "rolo_pgo_add_between_robust")
 
     def addOdomFactor(self, pose6) -> int:
         """addOdomFactor (:1224-1243): the first call adds the prior, later ones poseFrom.between(poseTo) from the graph's last pose; returns the new pose's index"""
@@ -486,10 +504,11 @@ class PoseGraph:
         return k
 
     def addLoopFactor(self, loop):
-        """addLoopFactor (:1245-1264) for one (cur, pre, poseFrom, poseTo, noise) of LoopCloser: between(cur, pre, poseFrom^-1 poseTo, noise on all six)"""
+        """addLoopFactor (:1245-1264) for one (cur, pre, poseFrom, poseTo, noise) of LoopCloser: between(cur, pre, poseFrom^-1 poseTo, noise on all six). A
+        LoopFactor whose `robust` is k, as performSCLoopClosure returns it, becomes a factor under Cauchy(k); a plain tuple or robust = None a plain one"""
         cur, pre, pose_from, pose_to, noise = loop
         Z = np.linalg.inv(np.asarray(pose_from, np.float64)) @ np.asarray(pose_to, np.float64)
-        self.addBetween(int(cur), int(pre), Z, np.full(6, float(noise)))
+        self.addBetween(int(cur), int(pre), Z, np.full(6, float(noise)), cauchy=getattr(loop, "robust", None))
 
     def optimize(self, params: PgoParams = None) -> dict:
         res = PgoResult()
@@ -521,6 +540,15 @@ class PoseGraph:
         recs = (PgoTraceRec * max(n, 1))()
         check(lib().rolo_pgo_get_trace(self._h, recs, n), "rolo_pgo_get_trace")
         return [dict(lambda_=r.lambda_, cost=r.cost, accepted=bool(r.accepted), pcg_iterations=r.pcg_iterations, residual=r.residual) for r in recs[:n]]
+
+    def factorErrors(self):
+        """(r2, w): every factor's r^2 = |e / sigma|^2 and weight at the current poses, in the order the factors were added; w is 1.0 for a factor without
+        loss, and near 0 for a robust loop that the optimum outvoted"""
+        f = self.size()[1]
+        r2 = np.zeros(max(f, 1), np.float64); w = np.zeros(max(f, 1), np.float64)
+        dp = C.POINTER(C.c_double)
+        check(lib().rolo_pgo_get_factor_errors(self._h, r2.ctypes.data_as(dp), w.ctypes.data_as(dp), f), "rolo_pgo_get_factor_errors")
+        return r2[:f], w[:f]
 
     def lastMs(self):
         """device milliseconds of the last optimise: linearise + assemble, factorisation, PCG, retract + cost"""

@@ -3,13 +3,15 @@
 // which is not in its tree: the contract is the statement in include/rolo_hip.h, which tests/pgo_twin.py restates in numpy; parity with GTSAM is unpinned.
 //
 // MI355X design, everything in fp64 and every sum in a fixed order (no atomics: the same bits on every run):
-//   pgo_linearize_kernel     one factor per thread: error, whitened Jacobians, the factor's five blocks and its cost term into the factor's own slot
+//   pgo_linearize_kernel     one factor per thread: error, whitened Jacobians, the factor's five blocks and its cost term into the factor's own slot; a between
+//                            factor under a Cauchy loss (performSCLoopClosure's Robust noise, :2464-2470) scales all three by sqrt(w) first and its cost term is rho
 //   pgo_assemble_kernel      36 lanes per pose gather the slots of its incident factors in factor order (CSR incidence list kept by the host, the changed tail
 //                            uploaded): diagonal block, chain block H[k, k+1], gradient; pgo_chord_kernel packs the off-chain blocks
 //   pgo_solve_kernel         ONE workgroup of 1024 threads, __syncthreads only: block cyclic reduction of the block-tridiagonal part T of H + lambda I (6 x 6 blocks,
 //                            padded with identity blocks to a power of two, every level's inverses and couplings kept), then the whole conjugate-gradient loop
 //                            preconditioned with T^-1 (depth O(log N) per application), its dot products included: no host read-back inside a solve
 //   pgo_retract_cost_kernel  trial poses X Exp(delta) and the trial cost; per-workgroup sums, added in a fixed order by pgo_sum_kernel
+//   pgo_factor_error_kernel  one factor per thread: r^2 = |e / sigma|^2 and the loss's weight at the current poses, for rolo_pgo_get_factor_errors
 // The Levenberg-Marquardt controller runs on the host in double with one small read-back per trial (cost, PCG iterations, residual) through pinned memory.
 // Every loop is bounded: PCG by its cap, the trials by PGO_MAX_TRIALS and the lambda bound. A graph works on a stream of its own; its device store only grows.
 #include "rolo_internal.hpp"
@@ -30,7 +32,7 @@ constexpr int PGO_FACTOR_THREADS = 128;  // one factor per thread: the Jacobians
 constexpr int PGO_MAX_TRIALS = 10000;
 constexpr double PGO_SMALL = 1e-2;   // below this angle the coefficient series (their next terms are below 1e-18 there)
 
-struct PgoFactor { int i, j; double Zi[12]; double isig[6]; };   // j < 0: a prior; Zi = Z^-1 (R row-major, t); isig = 1 / sigma
+struct PgoFactor { int i, j; double Zi[12]; double isig[6]; double k2; };   // j < 0: a prior; Zi = Z^-1 (R row-major, t); isig = 1 / sigma; k2 = k^2 of the Cauchy loss, 0: no loss
 struct Pose { double R[9], t[3]; };
 
 #define PGO_DEV __device__ __forceinline__
@@ -157,6 +159,10 @@ PGO_DEV void factor_error(const PgoFactor& F, const Pose& Xi, const Pose& Xj, do
   for (int k = 0; k < 6; k++) ew[k] = e[k] * F.isig[k];
 }
 
+// mEstimator::Cauchy at distance r: weight k^2 / (k^2 + r^2) and loss k^2 / 2 log1p(r^2 / k^2)
+PGO_DEV double cauchy_weight(double k2, double r2) { return k2 / (k2 + r2); }
+PGO_DEV double cauchy_rho(double k2, double r2) { return 0.5 * k2 * log1p(r2 / k2); }
+
 PGO_DEV void load_pose(const double* p, Pose& X) {
 #pragma unroll
   for (int k = 0; k < 9; k++) X.R[k] = p[k];
@@ -183,16 +189,39 @@ PGO_DEV void atv6(const double* a, const double* v, double* o) {
   }
 }
 
+// a between factor under a loss, as noiseModel::Robust::WhitenSystem leaves it: error and Jacobians by sqrt(w), so the blocks are w J^T J and the gradient
+// w J^T e_w, that of rho. Kept out of line: inlined next to the path of a factor without loss it moved that path's Jacobians out of the registers (its scratch
+// accesses tripled and linearise + assemble of a graph without any loss took 1.6 x the time), and as a call that path compiles as it did. It loads the factor
+// and the poses itself, so that the caller keeps nothing in memory for it
+__device__ __noinline__ void linearize_robust(const PgoFactor* __restrict__ factors, int f, const double* __restrict__ poses, double* __restrict__ s) {
+  const PgoFactor Fa = factors[f];
+  Pose Xi, Xj;
+  load_pose(poses + 12 * (size_t)Fa.i, Xi);
+  load_pose(poses + 12 * (size_t)Fa.j, Xj);
+  double ew[6], Ji[36], Jj[36], r2 = 0;
+  factor_error(Fa, Xi, Xj, ew, Ji, Jj);
+#pragma unroll
+  for (int k = 0; k < 6; k++) r2 += ew[k] * ew[k];
+  const double sw = sqrt(cauchy_weight(Fa.k2, r2));
+#pragma unroll
+  for (int k = 0; k < 6; k++) ew[k] *= sw;
+  for (int k = 0; k < 36; k++) { Ji[k] *= sw; Jj[k] *= sw; }
+  atv6(Ji, ew, s); atb6(Ji, Ji, s + 12);
+  atv6(Jj, ew, s + 6); atb6(Jj, Jj, s + 48); atb6(Ji, Jj, s + 84);   // (a loss is on a between factor only)
+  s[120] = cauchy_rho(Fa.k2, r2);
+}
+
 __global__ __launch_bounds__(PGO_FACTOR_THREADS) void pgo_linearize_kernel(const PgoFactor* __restrict__ factors, int F, const double* __restrict__ poses, double* __restrict__ slots) {
   const int f = blockIdx.x * PGO_FACTOR_THREADS + threadIdx.x;
   if (f >= F) return;
+  double* s = slots + (size_t)PGO_SLOT * f;
+  if (factors[f].k2 > 0.0) { linearize_robust(factors, f, poses, s); return; }
   const PgoFactor Fa = factors[f];
   Pose Xi, Xj;
   load_pose(poses + 12 * (size_t)Fa.i, Xi);
   load_pose(poses + 12 * (size_t)(Fa.j < 0 ? Fa.i : Fa.j), Xj);
   double ew[6], Ji[36], Jj[36];
   factor_error(Fa, Xi, Xj, ew, Ji, Jj);
-  double* s = slots + (size_t)PGO_SLOT * f;
   atv6(Ji, ew, s);
   atb6(Ji, Ji, s + 12);
   if (Fa.j >= 0) { atv6(Jj, ew, s + 6); atb6(Jj, Jj, s + 48); atb6(Ji, Jj, s + 84); }
@@ -266,13 +295,30 @@ __global__ __launch_bounds__(PGO_FACTOR_THREADS) void pgo_retract_cost_kernel(co
     double ew[6];
     factor_error(Fa, Xi, Xj, ew, nullptr, nullptr);
     for (int k = 0; k < 6; k++) term += ew[k] * ew[k];
-    term *= 0.5;
+    term = Fa.k2 > 0.0 ? cauchy_rho(Fa.k2, term) : 0.5 * term;
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) term += __shfl_xor(term, off, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = term;
   __syncthreads();
   if (threadIdx.x == 0) { double t = 0; for (int w = 0; w < (PGO_FACTOR_THREADS + 63) / 64; w++) t += red[w]; partials[blockIdx.x] = t; }
+}
+
+// r^2 and the weight of every factor at the poses: error only, plain stores
+__global__ __launch_bounds__(PGO_FACTOR_THREADS) void pgo_factor_error_kernel(const PgoFactor* __restrict__ factors, int F, const double* __restrict__ poses,
+                                                                              double* __restrict__ r2_out, double* __restrict__ w_out) {
+  const int f = blockIdx.x * PGO_FACTOR_THREADS + threadIdx.x;
+  if (f >= F) return;
+  const PgoFactor Fa = factors[f];
+  Pose Xi, Xj;
+  load_pose(poses + 12 * (size_t)Fa.i, Xi);
+  load_pose(poses + 12 * (size_t)(Fa.j < 0 ? Fa.i : Fa.j), Xj);
+  double ew[6], r2 = 0;
+  factor_error(Fa, Xi, Xj, ew, nullptr, nullptr);
+#pragma unroll
+  for (int k = 0; k < 6; k++) r2 += ew[k] * ew[k];
+  r2_out[f] = r2;
+  w_out[f] = Fa.k2 > 0.0 ? cauchy_weight(Fa.k2, r2) : 1.0;
 }
 
 // ---- the solve -------------------------------------------------------------------------------------------------------------------------------
@@ -594,6 +640,7 @@ struct rolo_pgo {
   double *LD = nullptr, *LU = nullptr, *LW = nullptr, *B = nullptr, *X = nullptr; size_t LD_cap = 0, LU_cap = 0, LW_cap = 0, B_cap = 0, X_cap = 0;
   double* vec[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; size_t vec_cap[5] = {0, 0, 0, 0, 0};
   double *cscr = nullptr, *delta = nullptr, *partials = nullptr; size_t cscr_cap = 0, delta_cap = 0, partials_cap = 0;
+  double* ferr = nullptr; size_t ferr_cap = 0;   // rolo_pgo_get_factor_errors: F x r^2, then F x w
   double* h_info = nullptr;                // pinned: [0] cost, [1..5] the solve's info
   std::vector<void*> retired;
   float ms[4] = {0.f, 0.f, 0.f, 0.f};
@@ -782,7 +829,7 @@ void rolo_pgo_destroy(rolo_pgo* g) {
   for (void* p : {(void*)g->poses, (void*)g->trial, (void*)g->d_factors, (void*)g->slots, (void*)g->rowptr, (void*)g->entries, (void*)g->diag, (void*)g->chain, (void*)g->grad,
                   (void*)g->chordH, (void*)g->d_chord_factor, (void*)g->d_chord_ij, (void*)g->touched, (void*)g->touched_ptr, (void*)g->touched_ent, (void*)g->LD, (void*)g->LU,
                   (void*)g->LW, (void*)g->B, (void*)g->X, (void*)g->vec[0], (void*)g->vec[1], (void*)g->vec[2], (void*)g->vec[3], (void*)g->vec[4], (void*)g->cscr, (void*)g->delta,
-                  (void*)g->partials})
+                  (void*)g->partials, (void*)g->ferr})
     if (p) (void)hipFree(p);
   for (void* p : g->retired) (void)hipFree(p);
   if (g->h_info) (void)hipHostFree(g->h_info);
@@ -829,13 +876,15 @@ int rolo_pgo_add_prior(rolo_pgo* g, int i, const double* T16, const double* var6
   return ROLO_OK;
 }
 
-int rolo_pgo_add_between(rolo_pgo* g, int i, int j, const double* T16, const double* var6) {
+// k2: k^2 of the Cauchy loss, 0 for none
+static int pgo_add_between(rolo_pgo* g, int i, int j, const double* T16, const double* var6, double k2) {
   if (!g || !T16 || !var6 || i < 0 || i >= g->N || j < 0 || j >= g->N || i == j) return ROLO_EINVAL;
   if (!pgo_finite_T(T16)) { ctx_set_error("rolo_pgo_add_between: a non-finite pose"); return ROLO_EINVAL; }
   if (pgo_check_var(var6)) return ROLO_EINVAL;
   if (g->factors.size() >= (size_t)(1 << 28)) return ROLO_EINVAL;
   PgoFactor f{};
   pgo_fill_factor(f, i, j, T16, var6);
+  f.k2 = k2;
   const int id = (int)g->factors.size();
   g->factors.push_back(f);
   g->inc[i].push_back((id << 2) | (j == i + 1 ? 2 : 0));
@@ -844,6 +893,15 @@ int rolo_pgo_add_between(rolo_pgo* g, int i, int j, const double* T16, const dou
   g->dirty_from = std::min(g->dirty_from, std::min(i, j));
   g->linearized = false;
   return ROLO_OK;
+}
+
+int rolo_pgo_add_between(rolo_pgo* g, int i, int j, const double* T16, const double* var6) { return pgo_add_between(g, i, j, T16, var6, 0.0); }
+
+int rolo_pgo_add_between_robust(rolo_pgo* g, int i, int j, const double* T16, const double* var6, int loss, double k) {
+  if (!g) return ROLO_EINVAL;
+  if (loss != ROLO_PGO_LOSS_CAUCHY) { ctx_set_error("rolo_pgo_add_between_robust: only ROLO_PGO_LOSS_CAUCHY (the reference configures no other)"); return ROLO_EUNSUPPORTED; }
+  if (!std::isfinite(k) || !(k > 0.0) || !std::isfinite(k * k) || !(k * k > 0.0)) { ctx_set_error("rolo_pgo_add_between_robust: k must be finite and positive"); return ROLO_EINVAL; }
+  return pgo_add_between(g, i, j, T16, var6, k * k);
 }
 
 int rolo_pgo_size(rolo_pgo* g, int* n_poses, int* n_factors, int* n_chords) {
@@ -975,6 +1033,22 @@ int rolo_pgo_get_poses(rolo_pgo* g, double* T16_out, float* pose6_out, int cap) 
     if (pose6_out) pose6_of(p, pose6_out + 6 * (size_t)k);
   }
   return g->N;
+}
+
+int rolo_pgo_get_factor_errors(rolo_pgo* g, double* r2, double* weight, int cap) {
+  if (!g || cap < 0) return ROLO_EINVAL;
+  if (g->N == 0 || g->factors.empty()) { ctx_set_error("rolo_pgo_get_factor_errors: the graph has no pose or no factor"); return ROLO_ESTATE; }
+  const int F = (int)g->factors.size(), n = std::min(F, cap);
+  if (n == 0 || (!r2 && !weight)) return F;
+  int rc;
+  if ((rc = pgo_sync_graph(g))) return rc;
+  if ((rc = pgo_grow(g, g->ferr, g->ferr_cap, 2 * (size_t)F))) return rc;
+  pgo_factor_error_kernel<<<(F + PGO_FACTOR_THREADS - 1) / PGO_FACTOR_THREADS, PGO_FACTOR_THREADS, 0, g->stream>>>(g->d_factors, F, g->poses, g->ferr, g->ferr + F);
+  PCHK(hipGetLastError());
+  if (r2) PCHK(hipMemcpyAsync(r2, g->ferr, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
+  if (weight) PCHK(hipMemcpyAsync(weight, g->ferr + F, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
+  PCHK(hipStreamSynchronize(g->stream));
+  return F;
 }
 
 int rolo_pgo_get_trace(rolo_pgo* g, rolo_pgo_trace_rec* out, int cap) {
