@@ -1,6 +1,6 @@
 // The packet walk of the exact k-nearest-neighbour search, as device functions: packed (d2, index) keys and their min / max sorted insert, wave-uniform
-// fetches, leaf scoring and the walk itself. Included by knn_walk.hpp (K5: the queries are the cloud's own points) and by scan2map.hip (8f.4: foreign
-// queries — the scan's features against the sub-map's tree). Design notes: knn_walk.hpp.
+// fetches, leaf scoring and the walk itself. Included by knn_walk.hpp (K5: the queries are the cloud's own points) and by scan2map.hip (8f.4: its own walk for foreign
+// queries takes the keys, insert_slot, sub_*, sload_node, box_d2, xcd_contiguous_block and WALK_STACK from here, not packet_walk). Design notes: knn_walk.hpp.
 #pragma once
 #include "rolo_internal.hpp"
 #include "dev_math.hpp"
@@ -9,7 +9,7 @@
 #include <climits>
 
 #ifndef KNN_STAT
-#ifdef ROLO_KNN_STATS   // (the instrumented build: every includer sees the same definition — scan2map.hip includes this file without knn_walk.hpp)
+#ifdef ROLO_KNN_STATS   // (the instrumented build: every includer sees the same definition — scan2map.hip includes this file without knn_walk.hpp, and calls none of the counted functions)
 #define KNN_STAT(x) x
 #else
 #define KNN_STAT(x)

@@ -6,8 +6,8 @@
 // Gauss-Newton step; up to 30 iterations.
 //
 // MI355X design: the two sub-maps get the Hilbert-sorted implicit BVH of the neighbour search (knn_cov.hip) once per call; ONE kernel per
-// iteration does association + fit + Jacobian row per point (a per-lane exact 5-NN walk: the queries are foreign to the tree, so there is
-// no packet to share) and reduces J^T J (21 values), J^T r (6) and the number of selected points per workgroup; a second tiny kernel sums the
+// iteration does association + fit + Jacobian row per point (an exact 5-NN walk, s2m_assoc_kernel: the scan's features sorted along the curve,
+// four lanes per feature; s2m_kernel, one walk per lane, is its cross-check) and reduces J^T J (21 values), J^T r (6) and the number of selected points per workgroup; a second tiny kernel sums the
 // rows in a fixed order. The 6 x 6 solve, the degeneracy projection and the convergence test run on the host in float, as the reference's
 // cv::solve / cv::eigen do (one 232-byte read-back per iteration; the back end runs at <= 1 / 0.15 s).
 // Third-party numerics restated, not copied (OpenCV / Eigen are not in the reference tree), in FLOAT with the operation order of their published
@@ -40,19 +40,18 @@ namespace {
 constexpr int S2M_THREADS = 128;
 constexpr int S2M_STACK = 40;
 constexpr int S2M_NV = 28;   // 21 (lower triangle of A^T A) + 6 (A^T b) + 1 (selected points)
+constexpr int S2M_SUB = 4;   // lanes per feature of s2m_assoc_kernel
+constexpr int S2M_FPW = 64 / S2M_SUB;   // its features per wavefront
 
 struct S2mArgs {
   const float4* feat;      // n_corner corner points, then n_surf surface points (x, y, z, intensity)
   int n_corner, n_surf;
-  KnnCloud qry[2];         // the same features in CURVE order (sorted: x, y, z, bits(index in its cloud); padded to whole leaves): 64 consecutive ones form a packet
+  KnnCloud qry[2];         // the same features in CURVE order (sorted: x, y, z, bits(index in its cloud); padded to whole leaves): S2M_FPW consecutive ones share a wavefront
   KnnCloud map[2];         // corner / surface sub-map trees
   float T[12];             // transPointAssociateToMap rows (float Affine3f of pcl::getTransformation)
   float srx, crx, sry, cry, srz, crz;   // LMOptimization :942-947
   double* partials;        // grid x S2M_NV
-  int xcd_remap;
-  int cap;                 // 1: the search is capped at the radius the fits accept (d2 < 1.0)
   int4* wstats;            // ROLO_S2M_STATS: per wavefront (nodes, leaves, clock ticks of the walk, block) of the LAST iteration
-  int qpp;                 // features per packet (wavefront) of s2m_packet_kernel: 64, or fewer (the remaining lanes idle) for more wavefronts in flight
   unsigned char* selected; // per feature point: 1 = laserCloudOri*Flag (debug / tests)
   float4* coeff;           // per feature point: coeffSel (debug / tests)
 };
@@ -332,38 +331,32 @@ ROLO_DEV void s2m_row(const S2mArgs& A, const float4& po, const float4& coeff, d
   acc[27] = 1.0;
 }
 
-__global__ __launch_bounds__(S2M_THREADS) void s2m_kernel(S2mArgs A) {
-  __shared__ int stk[S2M_STACK * S2M_THREADS];
-  __shared__ double red[S2M_THREADS / 64][S2M_NV];
-  const int i = blockIdx.x * S2M_THREADS + threadIdx.x;
-  const int n = A.n_corner + A.n_surf;
-  double acc[S2M_NV];
-#pragma unroll
-  for (int v = 0; v < S2M_NV; v++) acc[v] = 0.0;
+// pointAssociateToMap :293-299 (float, left to right)
+ROLO_DEV void pointAssociateToMap(const float* T, const float4& pi, float& sx, float& sy, float& sz) {
+  sx = T[0] * pi.x + T[1] * pi.y + T[2] * pi.z + T[3];
+  sy = T[4] * pi.x + T[5] * pi.y + T[6] * pi.z + T[7];
+  sz = T[8] * pi.x + T[9] * pi.y + T[10] * pi.z + T[11];
+}
+
+// one feature after its search: po = pointOri, (sx, sy, sz) = pointSel, (bd, bi) = its five nearest points of the sub-map M in (d2, index) order, gi = its position
+// in the caller's order. "if (pointSearchSqDis[4] < 1.0)" (:745, :852; a list that was never filled keeps its INT_MAX indices), the fit, the debug outputs, its row.
+ROLO_DEV void s2m_feature(const S2mArgs& A, bool corner, const KnnCloud& M, const float4& po, float sx, float sy, float sz, const float (&bd)[5], const int (&bi)[5], int gi,
+                          double (&acc)[S2M_NV]) {
   bool sel = false;
   float4 coeff = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (i < n) {
-    const float4 po = A.feat[i];
-    const float* T = A.T;
-    // pointAssociateToMap :293-299 (float, left to right)
-    const float sx = T[0] * po.x + T[1] * po.y + T[2] * po.z + T[3];
-    const float sy = T[4] * po.x + T[5] * po.y + T[6] * po.z + T[7];
-    const float sz = T[8] * po.x + T[9] * po.y + T[10] * po.z + T[11];
-    const bool corner = i < A.n_corner;
-    const KnnCloud& M = A.map[corner ? 0 : 1];
-    float bd[5]; int bi[5];
-    knn5(M, sx, sy, sz, stk + threadIdx.x, bd, bi);
-    if (bi[4] != INT_MAX && bd[4] < 1.0f) {
-      float px[5], py[5], pz[5];
+  if (bi[4] != INT_MAX && bd[4] < 1.0f) {
+    float px[5], py[5], pz[5];
 #pragma unroll
-      for (int j = 0; j < 5; j++) { const float4 p = M.xyz[bi[j]]; px[j] = p.x; py[j] = p.y; pz[j] = p.z; }
-      s2m_fit(corner, sx, sy, sz, po, px, py, pz, sel, coeff);
-    }
-    if (A.selected) A.selected[i] = sel ? 1 : 0;
-    if (A.coeff) A.coeff[i] = sel ? coeff : make_float4(0.f, 0.f, 0.f, 0.f);
-    if (sel) s2m_row(A, po, coeff, acc);
+    for (int j = 0; j < 5; j++) { const float4 p = M.xyz[bi[j]]; px[j] = p.x; py[j] = p.y; pz[j] = p.z; }
+    s2m_fit(corner, sx, sy, sz, po, px, py, pz, sel, coeff);
   }
-  // workgroup sum, fixed order
+  if (A.selected) A.selected[gi] = sel ? 1 : 0;
+  if (A.coeff) A.coeff[gi] = sel ? coeff : make_float4(0.f, 0.f, 0.f, 0.f);
+  if (sel) s2m_row(A, po, coeff, acc);
+}
+
+// workgroup sum of the S2M_NV accumulators in a fixed order: the 64 lanes of a wavefront as a butterfly, then the wavefronts in index order
+template <int WAVES> ROLO_DEV void s2m_block_sum(const double (&acc)[S2M_NV], double (&red)[WAVES][S2M_NV], double* partials /* grid x S2M_NV */, int blk) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
   for (int v = 0; v < S2M_NV; v++) {
@@ -376,93 +369,50 @@ __global__ __launch_bounds__(S2M_THREADS) void s2m_kernel(S2mArgs A) {
   if (threadIdx.x < S2M_NV) {
     double s = 0;
 #pragma unroll
-    for (int w = 0; w < S2M_THREADS / 64; w++) s += red[w][threadIdx.x];
-    A.partials[(size_t)blockIdx.x * S2M_NV + threadIdx.x] = s;
+    for (int w = 0; w < WAVES; w++) s += red[w][threadIdx.x];
+    partials[(size_t)blk * S2M_NV + threadIdx.x] = s;
   }
 }
 
-// ---- the same with PACKETS (round 4) ------------------------------------------------------------------------------------------------------------
-// The per-lane walk above takes ~1 ms for 48.7 k features against a 252 k-point sub-map: every lane descends the tree on its own, the wavefront executes
-// the union of 64 divergent walks. But the features are a point cloud too: sorted along the same Hilbert curve (a rigid motion keeps neighbours
-// neighbours, so they are sorted once per call, before the first pose), 64 consecutive ones are one blob — one wavefront walks the sub-map's tree ONCE
-// for its 64 queries with the packet walk of the K5 search (knn_packet.hpp: ballot-driven descent, leaves fetched once per wave, packed-key min / max
-// insert, k = 5). Same neighbours in the same (d2, index) order, so everything downstream — fits, flags, rows — is the same floats.
-__global__ __launch_bounds__(256) void s2m_packet_kernel(S2mArgs A, int split /* first block of the surface features */) {
-  __shared__ int stk[4][WALK_STACK];
-  __shared__ double red[4][S2M_NV];
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const bool corner = (int)blockIdx.x < split;   // workgroup-uniform
-  const KnnCloud& Q = A.qry[corner ? 0 : 1];
-  const KnnCloud& M = A.map[corner ? 0 : 1];
-  const int j = lane < A.qpp ? (((int)blockIdx.x - (corner ? 0 : split)) * 4 + wv) * A.qpp + lane : INT_MAX;
+// ---- the cross-check (ROLO_S2M_PACKETS=0; rounds 2-3): one walk per lane, features in the caller's order -----------------------------------------------
+// Shares no search code with the product kernel below: its own knn5 and box_d2f, no knn_packet.hpp, no curve sort, no helper context. ~1 ms per iteration for 48.7 k
+// features against a 252 k-point sub-map: every lane descends the tree on its own, the wavefront executes the union of 64 divergent walks.
+__global__ __launch_bounds__(S2M_THREADS) void s2m_kernel(S2mArgs A) {
+  __shared__ int stk[S2M_STACK * S2M_THREADS];
+  __shared__ double red[S2M_THREADS / 64][S2M_NV];
+  const int i = blockIdx.x * S2M_THREADS + threadIdx.x;
+  const int n = A.n_corner + A.n_surf;
   double acc[S2M_NV];
 #pragma unroll
   for (int v = 0; v < S2M_NV; v++) acc[v] = 0.0;
-  float4 qs = make_float4(0.f, 0.f, 0.f, __int_as_float(INT_MAX));
-  if (j < Q.n_sorted) qs = Q.sorted[j];
-  const int qidx = __float_as_int(qs.w);
-  const bool active = qidx != INT_MAX;
-  const float* T = A.T;
-  // pointAssociateToMap :293-299 (float, left to right)
-  const float sx = T[0] * qs.x + T[1] * qs.y + T[2] * qs.z + T[3];
-  const float sy = T[4] * qs.x + T[5] * qs.y + T[6] * qs.z + T[7];
-  const float sz = T[8] * qs.x + T[9] * qs.y + T[10] * qs.z + T[11];
-  const float4 q = make_float4(active ? sx : 0.f, active ? sy : 0.f, active ? sz : 0.f, 0.f);
-  const double sentinel = key_pack(INFINITY, INT_MAX);
-  double K[5] = {sentinel, sentinel, sentinel, sentinel, sentinel};
-  float bd = active ? INFINITY : -1.0f;
-  double bkey = active ? sentinel : key_pack(0.f, 0);
-  {
-    unsigned s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0;
-    int sp = 0;
-    packet_walk<5, false>(M.sorted, M.boxes, M.P, 0, 0, q, K, 5, bkey, bd, 0.0, (lds_int*)&stk[wv][0], sp, 1, s0, s1, s2, s3, s4, s5);
+  if (i < n) {
+    const float4 po = A.feat[i];
+    float sx, sy, sz;
+    pointAssociateToMap(A.T, po, sx, sy, sz);
+    const bool corner = i < A.n_corner;
+    const KnnCloud& M = A.map[corner ? 0 : 1];
+    float bd[5]; int bi[5];
+    knn5(M, sx, sy, sz, stk + threadIdx.x, bd, bi);
+    s2m_feature(A, corner, M, po, sx, sy, sz, bd, bi, i, acc);
   }
-  bool sel = false;
-  float4 coeff = make_float4(0.f, 0.f, 0.f, 0.f);
-  const int gi = (corner ? 0 : A.n_corner) + qidx;   // position in the caller's order
-  if (active) {
-    float bdv[5]; int bi[5];
-#pragma unroll
-    for (int u = 0; u < 5; u++) { bdv[u] = key_d2(K[u]); bi[u] = key_idx(K[u]); }
-    const float4 po = qs;
-    if (bi[4] != INT_MAX && bdv[4] < 1.0f) {
-      float px[5], py[5], pz[5];
-#pragma unroll
-      for (int u = 0; u < 5; u++) { const float4 p = M.xyz[bi[u]]; px[u] = p.x; py[u] = p.y; pz[u] = p.z; }
-      s2m_fit(corner, sx, sy, sz, po, px, py, pz, sel, coeff);
-    }
-    if (A.selected) A.selected[gi] = sel ? 1 : 0;
-    if (A.coeff) A.coeff[gi] = sel ? coeff : make_float4(0.f, 0.f, 0.f, 0.f);
-    if (sel) s2m_row(A, po, coeff, acc);
-  }
-  // workgroup sum, fixed order
-#pragma unroll
-  for (int v = 0; v < S2M_NV; v++) {
-    double x = acc[v];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    if (lane == 0) red[wv][v] = x;
-  }
-  __syncthreads();
-  if (threadIdx.x < S2M_NV) {
-    double s = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) s += red[w][threadIdx.x];
-    A.partials[(size_t)blockIdx.x * S2M_NV + threadIdx.x] = s;
-  }
+  s2m_block_sum<S2M_THREADS / 64>(acc, red, A.partials, blockIdx.x);
 }
 
-// ---- the same with SUB lanes per feature (round 4, second step) -----------------------------------------------------------------------------------------
-// Measured on the packet kernel above (profiles/r04/s2m_kernel_stats.txt): 0.30 ms per iteration for 48.7 k features — 764 wavefronts, not even one
-// per SIMD, each scoring all 16 points of ~160 leaves in every lane: the scan's features are thinned to 0.4 m (64 of them along the curve span metres)
-// while the sub-map is five key frames dense, so a 64-feature packet's frontier is wide and every lane pays for the union. Here a wavefront carries
-// 64 / SUB features, SUB adjacent lanes per feature: the frontier shrinks with the packet, there are SUB times as many wavefronts to hide the fetch
-// latency, and a visited leaf costs each lane 16 / SUB candidates (point u of the leaf goes to sub-lane u % SUB: every sub-lane sees an even sample
-// of the neighbourhood). Each sub-lane keeps the 5 best of ITS candidates; the feature's pruning bound is shared by its SUB lanes:
-//     B = min( min_s K_s[4],  max_s K_s[ceil(5 / SUB) - 1] )          (SUB = 4: the second term is max( max_s K_s[0], min_s K_s[1] ))
-// — all are keys with at least five real candidates at or below them (five in one sub-lane's list; ceil(5/SUB) in each of SUB lists; two in one list and
-// the best of each other one), so a candidate or a box beyond B cannot belong to the five nearest: the walk stays exact. After the walk the SUB lists are merged (sorted inserts of the partners'
-// keys): the same five (d2, index) keys in the same order as the one-lane search, and the fits, flags and rows downstream are the same floats.
+// ---- the product form (round 4): features sorted along the curve, four lanes per feature ----------------------------------------------------------------------
+// The features are a point cloud too: sorted along the same Hilbert curve as the sub-map (a rigid motion keeps neighbours neighbours, so they are sorted once
+// per call, before the first pose), consecutive ones are one blob and can walk the sub-map's tree TOGETHER (ballot-driven descent, leaves fetched once per wave,
+// packed-key min / max insert: the pieces of knn_packet.hpp). A wavefront carries S2M_FPW = 16 features, S2M_SUB = 4 adjacent lanes per feature: the scan's
+// features are thinned to 0.4 m while the sub-map is five key frames dense, so a wider packet's frontier is wide and every lane pays for the union (64 features
+// per wavefront, one lane each: 0.30 ms per iteration for 48.7 k features, 764 wavefronts, not even one per SIMD — profiles/r04/s2m_kernel_stats.txt). With four
+// lanes per feature there are four times as many wavefronts to hide the fetch latency, and a visited leaf costs each lane 16 / 4 candidates (point u of the leaf
+// goes to sub-lane u % 4: every sub-lane sees an even sample of the neighbourhood). Each sub-lane keeps the 5 best of ITS candidates; the feature's pruning bound
+// is shared by its four lanes:
+//     B = min( B, min_s K_s[4],  max( max_s K_s[0], min_s K_s[1] ) )
+// — all are keys with at least five real candidates at or below them (five in one sub-lane's list; two in one list and the best of each other one), so a
+// candidate or a box beyond B cannot belong to the five nearest: the walk stays exact. After the walk the four lists are merged (sorted inserts of the partners'
+// keys): the same five (d2, index) keys in the same order as the one-lane search, so everything downstream — fits, flags, rows — is the same floats.
+// (The forms this one was measured against — 64 / 32 / 16 / 8-feature packets of one lane per feature, 2 and 8 lanes, binary steps only, paired leaf fetches,
+// no radius cap, no XCD mapping — are in profiles/DEAD_ENDS.md.)
 ROLO_DEV void insert5(double (&K)[5], double ck) {
 #pragma unroll
   for (int s = 4; s >= 1; s--) insert_slot(K[s], K[s - 1], ck);
@@ -476,18 +426,17 @@ template <int ST> ROLO_DEV void merge5(double (&K)[5]) {   // K <- the five smal
   for (int u = 0; u < 5; u++) insert5(K, o[u]);
 }
 
-template <int SUB, int MODE /* 4: two tree levels per step (SUB = 4); + 2: two leaves per fetch */>
-__global__ __launch_bounds__(256) void s2m_sub_kernel(S2mArgs A, int split /* first block of the surface features */) {
-  constexpr int QPW = 64 / SUB, PPL = KNN_LEAF / SUB, SH = SUB == 2 ? 1 : SUB == 4 ? 2 : 3, NEED = (5 + SUB - 1) / SUB;
-  static_assert(SUB == 2 || SUB == 4 || SUB == 8, "sub-lanes per feature");
+__global__ __launch_bounds__(256) void s2m_assoc_kernel(S2mArgs A, int split /* first block of the surface features */) {
+  constexpr int SUB = S2M_SUB, PPL = KNN_LEAF / SUB;
+  static_assert(SUB == 4, "the two-level step tests one grandchild per sub-lane");
   __shared__ int stk_[4][WALK_STACK];
   __shared__ double red[4][S2M_NV];
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, sub = lane & (SUB - 1), ql = lane >> SH;
-  const int blk = A.xcd_remap ? xcd_contiguous_block((int)blockIdx.x, (int)gridDim.x, 4) : (int)blockIdx.x;   // curve-adjacent features on one XCD: they read the same boxes and leaves
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, sub = lane & (SUB - 1), ql = lane >> 2;
+  const int blk = xcd_contiguous_block((int)blockIdx.x, (int)gridDim.x, 4);   // curve-adjacent features on one XCD: they read the same boxes and leaves
   const bool corner = blk < split;   // workgroup-uniform
   const KnnCloud& Q = A.qry[corner ? 0 : 1];
   const KnnCloud& M = A.map[corner ? 0 : 1];
-  const int j = ((blk - (corner ? 0 : split)) * 4 + wv) * QPW + ql;
+  const int j = ((blk - (corner ? 0 : split)) * 4 + wv) * S2M_FPW + ql;
   double acc[S2M_NV];
 #pragma unroll
   for (int v = 0; v < S2M_NV; v++) acc[v] = 0.0;
@@ -495,20 +444,17 @@ __global__ __launch_bounds__(256) void s2m_sub_kernel(S2mArgs A, int split /* fi
   if (j < Q.n_sorted) qs = Q.sorted[j];
   const int qidx = __float_as_int(qs.w);
   const bool active = qidx != INT_MAX;
-  const float* T = A.T;
-  // pointAssociateToMap :293-299 (float, left to right)
-  const float sx = T[0] * qs.x + T[1] * qs.y + T[2] * qs.z + T[3];
-  const float sy = T[4] * qs.x + T[5] * qs.y + T[6] * qs.z + T[7];
-  const float sz = T[8] * qs.x + T[9] * qs.y + T[10] * qs.z + T[11];
+  float sx, sy, sz;
+  pointAssociateToMap(A.T, qs, sx, sy, sz);
   const float4 q = make_float4(active ? sx : 0.f, active ? sy : 0.f, active ? sz : 0.f, 0.f);
   const double sentinel = key_pack(INFINITY, INT_MAX);
   double K[5] = {sentinel, sentinel, sentinel, sentinel, sentinel};
   // The fits use a feature's neighbours only "if (pointSearchSqDis[4] < 1.0)" (:745, :852): a neighbour at d2 >= 1 can never matter — either the fifth
   // nearest is closer than 1 m, and so are the other four, or the feature is dropped. The search therefore starts with the bound (1.0f, index 0): every
   // key it accepts is below it, a feature without five neighbours inside the ball keeps sentinels in its list and is dropped by the same test as before.
-  // Without the cap a feature far from the sub-map walks until it has ANY five points: those were the launch's heaviest wavefronts (A.cap = 0: the A/B).
-  double B = active ? (A.cap ? key_pack(1.0f, 0) : sentinel) : key_pack(0.f, 0);   // (no key is below (0, 0): an idle feature accepts nothing)
-  float bd = active ? (A.cap ? 1.0f : INFINITY) : -1.0f;
+  // Without the cap a feature far from the sub-map walks until it has ANY five points: those were the launch's heaviest wavefronts.
+  double B = active ? key_pack(1.0f, 0) : key_pack(0.f, 0);   // (no key is below (0, 0): an idle feature accepts nothing)
+  float bd = active ? 1.0f : -1.0f;
   int n_nodes = 0, n_leaves = 0;
   const long long t_walk0 = A.wstats ? wall_clock64() : 0;
   {
@@ -517,12 +463,11 @@ __global__ __launch_bounds__(256) void s2m_sub_kernel(S2mArgs A, int split /* fi
     const int P = M.P;
     lds_int* stk = (lds_int*)&stk_[wv][0];
     int sp = 0, h = 1;
-    // Per-wavefront counters (ROLO_S2M_STATS, profiles/r04/s2m_wave_stats.txt): 123 nodes + 40 leaves per wavefront on average, 353 + 107 in the worst one,
-    // ~0.4 us per step whichever it is — the launch (every wavefront resident at once) lasts as long as its heaviest wavefront, and a step costs what it
-    // ISSUES. So (MODE 4) where the tree allows it a step takes TWO levels: the four grandchild boxes of h (nodes 4h .. 4h + 3, 128 contiguous bytes) are
-    // tested one per sub-lane, the grandchild most features are nearest to is entered, the other live ones are pushed, best on top — one box test per
-    // lane where two binary steps cost four (nodes per wavefront 123 -> 63, heaviest wavefront 167 -> 136 us). (+2) fetches a leaf together with the
-    // entry on top of the stack when that is a leaf too: no further gain, kept as the A/B.
+    // Per-wavefront counters (ROLO_S2M_STATS, profiles/r04/s2m_wave_stats.txt): with binary steps only 123 nodes + 40 leaves per wavefront on average, 353 + 107 in
+    // the worst one, ~0.4 us per step whichever it is — the launch (every wavefront resident at once) lasts as long as its heaviest wavefront, and a step costs what
+    // it ISSUES. So where the tree allows it a step takes TWO levels: the four grandchild boxes of h (nodes 4h .. 4h + 3, 128 contiguous bytes) are tested one per
+    // sub-lane, the grandchild most features are nearest to is entered, the other live ones are pushed, best on top — one box test per lane where two binary steps
+    // cost four (nodes per wavefront 123 -> 63, heaviest wavefront 167 -> 136 us).
     auto score = [&](const float4 (&c)[PPL]) {
       bool changed = false;
 #pragma unroll
@@ -533,19 +478,15 @@ __global__ __launch_bounds__(256) void s2m_sub_kernel(S2mArgs A, int split /* fi
         if (ck < B) { insert5(K, ck); changed = true; }
       }
       if (__any(changed)) {
-        if (SUB == 4) {
-          // exactly five candidates instead of eight: two from the sub-lane whose second key is smallest, the best key of each of the other three
-          // (max_s K_s[0] also covers that sub-lane's own first key) — never above max_s K_s[1], the bound of two from each
-          B = vmin_f64(vmin_f64(B, sub_min<SUB>(K[4])), vmax_f64(sub_max<SUB>(K[0]), sub_min<SUB>(K[1])));
-        } else {
-          B = vmin_f64(vmin_f64(B, sub_min<SUB>(K[4])), sub_max<SUB>(K[NEED - 1]));
-        }
+        // exactly five candidates instead of eight: two from the sub-lane whose second key is smallest, the best key of each of the other three
+        // (max_s K_s[0] also covers that sub-lane's own first key) — never above max_s K_s[1], the bound of two from each
+        B = vmin_f64(vmin_f64(B, sub_min<SUB>(K[4])), vmax_f64(sub_max<SUB>(K[0]), sub_min<SUB>(K[1])));
         bd = key_d2(B);
       }
     };
     while (true) {
       h = __builtin_amdgcn_readfirstlane(h);
-      if ((MODE & 4) && SUB == 4 && 2 * h < P) {
+      if (2 * h < P) {
         // two levels per step with the four box tests SPREAD over the feature's four lanes: sub-lane c tests grandchild c (the walk is bound by the
         // instructions it issues, not by its fetches: this step costs one box test per lane where two binary steps cost four)
         n_nodes++;
@@ -589,24 +530,11 @@ __global__ __launch_bounds__(256) void s2m_sub_kernel(S2mArgs A, int split /* fi
         if (mr != 0ull) { h = 2 * h + 1; continue; }
       } else {
         const float4* __restrict__ leaf = sorted + KNN_LEAF * (size_t)(h - P);
-        int h2 = -1;
-        if ((MODE & 2) && sp > 0) { h2 = __builtin_amdgcn_readfirstlane(stk[sp - 1]); if (h2 < P) h2 = -1; }
         float4 c[PPL];
 #pragma unroll
         for (int t = 0; t < PPL; t++) c[t] = leaf[t * SUB + sub];
-        if ((MODE & 2) && h2 >= 0) {
-          const float4* __restrict__ leaf2 = sorted + KNN_LEAF * (size_t)(h2 - P);
-          float4 c2[PPL];
-#pragma unroll
-          for (int t = 0; t < PPL; t++) c2[t] = leaf2[t * SUB + sub];
-          score(c);
-          score(c2);
-          sp--;
-          n_leaves += 2;
-        } else {
-          score(c);
-          n_leaves++;
-        }
+        score(c);
+        n_leaves++;
       }
       if (sp == 0) break;
       sp--;
@@ -615,41 +543,14 @@ __global__ __launch_bounds__(256) void s2m_sub_kernel(S2mArgs A, int split /* fi
   }
   if (A.wstats && lane == 0) A.wstats[blk * 4 + wv] = make_int4(n_nodes, n_leaves, (int)(wall_clock64() - t_walk0), blk);
   merge5<0>(K);
-  if (SUB >= 4) merge5<1>(K);
-  if (SUB >= 8) merge5<2>(K);
-  bool sel = false;
-  float4 coeff = make_float4(0.f, 0.f, 0.f, 0.f);
-  const int gi = (corner ? 0 : A.n_corner) + qidx;   // position in the caller's order
+  merge5<1>(K);
   if (active && sub == 0) {
     float bdv[5]; int bi[5];
 #pragma unroll
     for (int u = 0; u < 5; u++) { bdv[u] = key_d2(K[u]); bi[u] = key_idx(K[u]); }
-    const float4 po = qs;
-    if (bi[4] != INT_MAX && bdv[4] < 1.0f) {
-      float px[5], py[5], pz[5];
-#pragma unroll
-      for (int u = 0; u < 5; u++) { const float4 p = M.xyz[bi[u]]; px[u] = p.x; py[u] = p.y; pz[u] = p.z; }
-      s2m_fit(corner, sx, sy, sz, po, px, py, pz, sel, coeff);
-    }
-    if (A.selected) A.selected[gi] = sel ? 1 : 0;
-    if (A.coeff) A.coeff[gi] = sel ? coeff : make_float4(0.f, 0.f, 0.f, 0.f);
-    if (sel) s2m_row(A, po, coeff, acc);
+    s2m_feature(A, corner, M, qs, sx, sy, sz, bdv, bi, (corner ? 0 : A.n_corner) + qidx, acc);
   }
-  // workgroup sum, fixed order
-#pragma unroll
-  for (int v = 0; v < S2M_NV; v++) {
-    double x = acc[v];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    if (lane == 0) red[wv][v] = x;
-  }
-  __syncthreads();
-  if (threadIdx.x < S2M_NV) {
-    double s = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) s += red[w][threadIdx.x];
-    A.partials[(size_t)blk * S2M_NV + threadIdx.x] = s;
-  }
+  s2m_block_sum<4>(acc, red, A.partials, blk);
 }
 
 // the rows of the workgroups summed in a fixed order (deterministic for a given grid): 8 strided groups of 32 lanes with eight loads in flight each, then
@@ -829,14 +730,9 @@ extern "C" int rolo_scan2map_optimize(rolo_ctx* c, const float* corner, int n_co
   const KnnPair maps = static_cast<S2mScratch*>(*ctx_s2m_slot(c))->maps;
   hipStream_t s = ctx_stream(c);
   const int n = n_corner + n_surf;
-  // ROLO_S2M_PACKETS=0: one tree walk per lane in the caller's order (rounds 2-3, the A/B); default: the features sorted along the curve once per call,
-  // 64 consecutive ones walk the sub-map's tree as one packet (s2m_packet_kernel)
+  // ROLO_S2M_PACKETS=0: one tree walk per lane in the caller's order (s2m_kernel, the cross-check); default: the features sorted along the curve once per call,
+  // S2M_FPW consecutive ones walk the sub-map's tree as one packet (s2m_assoc_kernel)
   const bool use_packets = switches().s2m_packets;
-  const int qpp = switches().s2m_qpp;
-  // ROLO_S2M_SUB = 2 / 4 / 8 lanes per feature (s2m_sub_kernel); 1 = the 64-feature packets (s2m_packet_kernel, the A/B)
-  const int sub = switches().s2m_sub;
-  const int wide = switches().s2m_wide;
-  const int fpw = sub > 1 ? 64 / sub : qpp;   // features per wavefront
   KnnPair qp{};
   int grid = (n + S2M_THREADS - 1) / S2M_THREADS, split = 0;
   if (use_packets) {
@@ -846,8 +742,8 @@ extern "C" int rolo_scan2map_optimize(rolo_ctx* c, const float* corner, int n_co
     if (rq) return rq;
     SCHK(hipEventRecord(Wq->qev, ctx_stream(Wq->qctx)));
     SCHK(hipStreamWaitEvent(s, Wq->qev, 0));
-    split = (qp.c[0].n_sorted + 4 * fpw - 1) / (4 * fpw);
-    grid = split + (qp.c[1].n_sorted + 4 * fpw - 1) / (4 * fpw);
+    split = (qp.c[0].n_sorted + 4 * S2M_FPW - 1) / (4 * S2M_FPW);
+    grid = split + (qp.c[1].n_sorted + 4 * S2M_FPW - 1) / (4 * S2M_FPW);
   }
   // scratch lives with the context and only grows: hipFree is a device-wide synchronisation that would stall the frames other contexts have in flight
   S2mScratch* W = static_cast<S2mScratch*>(*ctx_s2m_slot(c));
@@ -863,18 +759,15 @@ extern "C" int rolo_scan2map_optimize(rolo_ctx* c, const float* corner, int n_co
       !grow((void**)&W->sum, W->sum_cap, sizeof(double) * S2M_NV) || (selected_out && !grow((void**)&W->sel, W->sel_cap, (size_t)n)) ||
       (coeff_out && !grow((void**)&W->coeff, W->coeff_cap, sizeof(float4) * (size_t)n))) { ctx_set_error("hipMalloc failed (scan2map)"); return ROLO_EHIP; }
   float4* d_feat = W->feat; double* d_part = W->part; unsigned char* d_sel = selected_out ? W->sel : nullptr; float4* d_coeff = coeff_out ? W->coeff : nullptr;
-  auto cleanup = [&]() {};
-  if (!use_packets &&   // (the packet kernel reads the features from the helper context's sorted clouds)
+  if (!use_packets &&   // (s2m_assoc_kernel reads the features from the helper context's sorted clouds)
       (hipMemcpyAsync(d_feat, corner, sizeof(float4) * (size_t)n_corner, hipMemcpyHostToDevice, s) != hipSuccess ||
-       hipMemcpyAsync(d_feat + n_corner, surf, sizeof(float4) * (size_t)n_surf, hipMemcpyHostToDevice, s) != hipSuccess)) { cleanup(); ctx_set_error("upload failed (scan2map)"); return ROLO_EHIP; }
+       hipMemcpyAsync(d_feat + n_corner, surf, sizeof(float4) * (size_t)n_surf, hipMemcpyHostToDevice, s) != hipSuccess)) { ctx_set_error("upload failed (scan2map)"); return ROLO_EHIP; }
   S2mArgs A{};
   A.feat = d_feat; A.n_corner = n_corner; A.n_surf = n_surf; A.map[0] = maps.c[0]; A.map[1] = maps.c[1]; A.partials = d_part; A.selected = d_sel; A.coeff = d_coeff;
-  A.qry[0] = qp.c[0]; A.qry[1] = qp.c[1]; A.qpp = qpp;
-  A.xcd_remap = switches().s2m_xcd;
-  A.cap = switches().s2m_cap;
+  A.qry[0] = qp.c[0]; A.qry[1] = qp.c[1];
   const char* stats_path = switches().s2m_stats;
   int4* d_wstats = nullptr;
-  if (stats_path && use_packets && sub > 1) { SCHK(hipMalloc((void**)&d_wstats, sizeof(int4) * 4 * (size_t)grid)); SCHK(hipMemsetAsync(d_wstats, 0, sizeof(int4) * 4 * (size_t)grid, s)); A.wstats = d_wstats; }
+  if (stats_path && use_packets) { SCHK(hipMalloc((void**)&d_wstats, sizeof(int4) * 4 * (size_t)grid)); SCHK(hipMemsetAsync(d_wstats, 0, sizeof(int4) * 4 * (size_t)grid, s)); A.wstats = d_wstats; }
   float* tf = transformTobeMapped;
   bool isDegenerate = false;
   float matP[36]; for (int i = 0; i < 36; i++) matP[i] = (i % 7 == 0) ? 1.f : 0.f;
@@ -890,17 +783,12 @@ extern "C" int rolo_scan2map_optimize(rolo_ctx* c, const float* corner, int n_co
       A.T[8] = -Dx; A.T[9] = Cx * Fx; A.T[10] = Cx * Ex; A.T[11] = tf[5];
     }
     A.srx = std::sin(tf[1]); A.crx = std::cos(tf[1]); A.sry = std::sin(tf[2]); A.cry = std::cos(tf[2]); A.srz = std::sin(tf[0]); A.crz = std::cos(tf[0]);
-    if (use_packets && sub == 4 && wide == 4) s2m_sub_kernel<4, 4><<<grid, 256, 0, s>>>(A, split);
-    else if (use_packets && sub == 4 && wide == 6) s2m_sub_kernel<4, 6><<<grid, 256, 0, s>>>(A, split);
-    else if (use_packets && sub == 4) s2m_sub_kernel<4, 0><<<grid, 256, 0, s>>>(A, split);
-    else if (use_packets && sub == 2) s2m_sub_kernel<2, 0><<<grid, 256, 0, s>>>(A, split);
-    else if (use_packets && sub == 8) s2m_sub_kernel<8, 0><<<grid, 256, 0, s>>>(A, split);
-    else if (use_packets) s2m_packet_kernel<<<grid, 256, 0, s>>>(A, split);
+    if (use_packets) s2m_assoc_kernel<<<grid, 256, 0, s>>>(A, split);
     else s2m_kernel<<<grid, S2M_THREADS, 0, s>>>(A);
     SCHK(hipGetLastError());
     s2m_sum_kernel<<<1, 256, 0, s>>>(d_part, grid, h_sum);
     SCHK(hipGetLastError());
-    if (hipStreamSynchronize(s) != hipSuccess) { cleanup(); ctx_set_error("scan2map iteration failed"); return ROLO_EHIP; }
+    if (hipStreamSynchronize(s) != hipSuccess) { ctx_set_error("scan2map iteration failed"); return ROLO_EHIP; }
     st.iterations = iterCount + 1;
     st.n_selected = (int)(h_sum[27] + 0.5);
     if (st.n_selected < 50) break;   // LMOptimization returns false without touching the pose: the remaining iterations would repeat this one

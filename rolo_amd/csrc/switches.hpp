@@ -57,13 +57,8 @@ struct Switches {
   int cu_partition = env::one_of("ROLO_CU_PARTITION", {2, 4, 8}, 0);                // groups: the k-th context's main stream is confined to XCD group k % groups (0 = off)
   bool odom_front_priority = env::unless_zero("ROLO_ODOM_FRONT_PRIORITY");          // =0: the odometry driver's front-end stream at normal priority
   // ---- scan-to-submap association (scan2map.hip) ----
-  bool s2m_packets = env::unless_zero("ROLO_S2M_PACKETS");       // =0: one tree walk per lane in the caller's order, features not sorted along the curve
-  int s2m_qpp = env::one_of("ROLO_S2M_QPP", {8, 16, 32}, 64);    // features per packet of s2m_packet_kernel
-  int s2m_sub = env::one_of("ROLO_S2M_SUB", {1, 2, 8}, 4);       // lanes per feature of s2m_sub_kernel; 1 = the 64-feature packets (s2m_packet_kernel)
-  int s2m_wide = env::one_of("ROLO_S2M_WIDE", {0, 6}, 4);        // the wide-walk form of s2m_sub_kernel
-  int s2m_xcd = (int)env::num("ROLO_S2M_XCD", 1);                // S2mArgs::xcd_remap, as given
-  int s2m_cap = (int)env::num("ROLO_S2M_CAP", 1);                // S2mArgs::cap, as given
-  const char* s2m_stats = env::str("ROLO_S2M_STATS");            // =<path>: per-wavefront walk statistics are written there
+  bool s2m_packets = env::unless_zero("ROLO_S2M_PACKETS");       // =0: the cross-check s2m_kernel, one tree walk per lane in the caller's order, features not sorted along the curve
+  const char* s2m_stats = env::str("ROLO_S2M_STATS");            // =<path>: per-wavefront walk statistics of s2m_assoc_kernel are written there
 };
 
 inline const Switches& switches() {

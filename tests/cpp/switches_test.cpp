@@ -14,8 +14,7 @@ int main() {
   std::printf("ROLO_LM_PERSIST_INTERLEAVE %d\nROLO_LM_PERSIST_MCACHE %d\nROLO_LM_PERSIST_BATCH %d\nROLO_CTRL_GENERIC %d\n", s.lm_persist_interleave, s.lm_persist_mcache, s.lm_persist_batch,
               s.ctrl_generic);
   std::printf("ROLO_CU_PARTITION %d\nROLO_ODOM_FRONT_PRIORITY %d\n", s.cu_partition, s.odom_front_priority);
-  std::printf("ROLO_S2M_PACKETS %d\nROLO_S2M_QPP %d\nROLO_S2M_SUB %d\nROLO_S2M_WIDE %d\nROLO_S2M_XCD %d\nROLO_S2M_CAP %d\nROLO_S2M_STATS %s\n", s.s2m_packets, s.s2m_qpp, s.s2m_sub, s.s2m_wide,
-              s.s2m_xcd, s.s2m_cap, s.s2m_stats ? s.s2m_stats : "-");
+  std::printf("ROLO_S2M_PACKETS %d\nROLO_S2M_STATS %s\n", s.s2m_packets, s.s2m_stats ? s.s2m_stats : "-");
   // the three that are read on every call
   std::printf("ROLO_PEER_TIMEOUT_MS %g\nROLO_PEER_MEM %s\nROLO_ODOM_EARLY_SOURCE %d/%d\n", rolo::peer_timeout_ms_now(), rolo::peer_mem_now() ? rolo::peer_mem_now() : "-",
               rolo::odom_early_source_now(false), rolo::odom_early_source_now(true));

@@ -138,11 +138,11 @@ def test_resident_submap_goes_stale_with_the_contexts_clouds():
     g.close()
 
 
-@pytest.mark.parametrize("switch", ["ROLO_S2M_SUB=1", "ROLO_S2M_SUB=8", "ROLO_S2M_CAP=0", "ROLO_S2M_WIDE=0", "ROLO_S2M_WIDE=6", "ROLO_S2M_PACKETS=0"])
+@pytest.mark.parametrize("switch", ["ROLO_S2M_PACKETS=0"])
 def test_association_kernel_variants_keep_the_oracles_flags(switch):
-    """the association kernel's earlier forms and A/B switches (64-feature packets, 8 lanes per feature, no radius cap, binary steps, paired leaf fetches, one walk
-    per lane) are all exact searches: the parity test above — selection flags bit-identical to the C++ oracle's, same iterations, same pose — must pass with
-    each of them (own process: the switches are read once)"""
+    """the association kernel's cross-check form (s2m_kernel, one walk per lane; the default is s2m_assoc_kernel, four lanes per feature) is an exact search
+    too: the parity test above — selection flags bit-identical to the C++ oracle's, same iterations, same pose — must pass with it as well (own process: the
+    switches are read once)"""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     k, v = switch.split("=")

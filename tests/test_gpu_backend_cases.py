@@ -1,7 +1,7 @@
 """GPU: rolo_scan2map_optimize on the constructed scenarios of tests/s2m_scenarios.py against the C++ oracle (pyorc.scan2map) on the same arrays — the branches whole lidar
 scans never reach (tests/test_gpu_backend.py): rank-deficient and inconsistent plane fits, the fifth neighbour at d2 == 1 exactly and fewer than five points in the
 ball, equal distances, one-leaf and few-leaf trees, partial wavefronts and workgroups, the scatter back to the caller's order, the n_selected < 50 exit, a degenerate
-first linearisation with its projected step — and every launch form of the association kernel on all of them. What the oracle says about these arrays is itself pinned
+first linearisation with its projected step — and both forms of the association kernel (s2m_assoc_kernel, the product; s2m_kernel, its cross-check) on all of them. What the oracle says about these arrays is itself pinned
 on the CPU (tests/test_oracle_backend.py: the twin, a float64 statement of the fits, what each case is there to reach).
 
 Bars: flags bit-identical, coefficients <= 1e-6 and poses <= 2e-6 to the oracle (the bars of tests/test_gpu_backend.py); well-conditioned cases also <= FLOAT64_TOL to
@@ -110,15 +110,15 @@ def test_scenes_iterate_project_and_exit_like_the_oracle(s2m, variant):
     assert S.scene_pose_problems(variant, tf, scn[4]) == []
 
 
-SWITCHES = ["ROLO_S2M_SUB=1", "ROLO_S2M_SUB=2", "ROLO_S2M_SUB=8", "ROLO_S2M_SUB=1 ROLO_S2M_QPP=8", "ROLO_S2M_SUB=1 ROLO_S2M_QPP=16", "ROLO_S2M_SUB=1 ROLO_S2M_QPP=32",
-            "ROLO_S2M_WIDE=0", "ROLO_S2M_WIDE=6", "ROLO_S2M_CAP=0", "ROLO_S2M_XCD=0", "ROLO_S2M_PACKETS=0"]
+SWITCHES = ["ROLO_S2M_PACKETS=0"]
 _child_died = []   # a child that ended on a signal, faulted the GPU or ran out of time: nothing more is started on that GPU
 
 
 @pytest.mark.parametrize("switch", SWITCHES)
 def test_every_kernel_form_passes_this_module(switch):
-    """the association kernel's other forms (64-, 32-, 16-, 8-feature packets, 2 / 8 lanes per feature, binary steps, paired leaf fetches, no radius cap, no XCD
-    remap, one walk per lane) are all exact searches in front of the same fits: every test above must pass with each (own process: the switches are read once)"""
+    """the association kernel has two forms — s2m_assoc_kernel (the default: features sorted along the curve, four lanes per feature, the search capped at the
+    radius the fits accept) and s2m_kernel (ROLO_S2M_PACKETS=0: one uncapped walk per lane in the caller's order, no search code in common with the other) —, both
+    exact searches in front of the same fits: every test above must pass with the second as well (own process: the switches are read once)"""
     assert not _child_died, f"not started: the child for {_child_died[0]} ended on a signal or a timeout"
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, **dict(kv.split("=") for kv in switch.split()))
@@ -134,3 +134,42 @@ def test_every_kernel_form_passes_this_module(switch):
         _child_died.append(switch)
     n_tests = len(TABLES) + len(S.TREE_SIZES) + len(S.COUNT_PAIRS) + 1 + len(S.SCENES)
     assert r.returncode == 0 and f"{n_tests} passed" in r.stdout, r.stdout[-3000:] + r.stderr[-1500:]
+
+
+def _dump_tables_main(out_dir):
+    """body of the child of test_every_kernel_form_gives_the_same_flag_and_coefficient_bits (own process: ROLO_S2M_PACKETS is read once per process)"""
+    g = Scan2Map(edgeFeatureMinValidNum=0, surfFeatureMinValidNum=0)
+    for which in TABLES:
+        _, st, sel, co = _run(g, TABLES[which][0]()[0])
+        np.savez(os.path.join(out_dir, which + ".npz"), sel=sel, coeff=co, stats=np.array([st[k] for k in STAT_FIELDS]))
+    g.close()
+    print("DUMPED", len(TABLES))
+
+
+def test_every_kernel_form_gives_the_same_flag_and_coefficient_bits(s2m, tmp_path):
+    """both forms find the same five neighbours in the same (d2, index) order, so flags and coefficients are the same FLOATS, not only both within the oracle's bar:
+    a child with ROLO_S2M_PACKETS=0 writes them for the three case tables (ties, the d2 == 1 edge, rank-deficient fits), this process runs the default form —
+    byte-identical, equal stats. The poses are not compared in bits: the two forms sum their rows over different grids. (The name keeps this test, like the one
+    above, out of that test's child runs: a child would compare s2m_kernel with itself.)"""
+    assert not _child_died, f"not started: the child for {_child_died[0]} ended on a signal or a timeout"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = "import sys; sys.path[:0] = [%r, %r]; from tests.test_gpu_backend_cases import _dump_tables_main; _dump_tables_main(%r)" % (root, os.path.join(root, "tests"), str(tmp_path))
+    try:
+        r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, ROLO_S2M_PACKETS="0"), capture_output=True, text=True, timeout=240, cwd=root)
+    except subprocess.TimeoutExpired as e:
+        _child_died.append("ROLO_S2M_PACKETS=0 (tables)")
+        pytest.fail(f"no result after {e.timeout} s: {(e.stdout or b'')[-2000:]}")
+    if r.returncode < 0 or "illegal memory access" in r.stdout + r.stderr:
+        _child_died.append("ROLO_S2M_PACKETS=0 (tables)")
+    assert r.returncode == 0 and f"DUMPED {len(TABLES)}" in r.stdout, r.stdout[-3000:] + r.stderr[-1500:]
+    for which in TABLES:
+        scn, names = _table(which)[:2]
+        _, st, sel, co = _run(s2m, scn)
+        ref = np.load(os.path.join(str(tmp_path), which + ".npz"))
+        assert st == dict(zip(STAT_FIELDS, ref["stats"].tolist())), (which, st, ref["stats"])
+        assert sel.dtype == ref["sel"].dtype and co.dtype == ref["coeff"].dtype == np.float32 and co.shape == ref["coeff"].shape
+        flags = [n for i, n in enumerate(names) if sel[i] != ref["sel"][i]]
+        assert not flags and sel.tobytes() == ref["sel"].tobytes(), f"{which}: flags differ between the forms: {flags}"
+        bits, ref_bits = np.ascontiguousarray(co).view(np.uint32), np.ascontiguousarray(ref["coeff"]).view(np.uint32)
+        diff = [(n, co[i], ref["coeff"][i]) for i, n in enumerate(names) if not np.array_equal(bits[i], ref_bits[i])]
+        assert not diff, f"{which}: (case, default form's coefficients, one-walk-per-lane form's) differ in bits: {diff}"

@@ -12,7 +12,7 @@ DEFAULTS = {
     "ROLO_LM_PERSIST_WGS": "0", "ROLO_LM_PERSIST_BUSY_THREADS": "512", "ROLO_LM_PERSIST_ADMIT_US": "1000", "ROLO_LM_PERSIST_TIMEOUT_MS": "200",
     "ROLO_LM_PERSIST_INTERLEAVE": "1", "ROLO_LM_PERSIST_MCACHE": "1", "ROLO_LM_PERSIST_BATCH": "2", "ROLO_CTRL_GENERIC": "0",
     "ROLO_CU_PARTITION": "0", "ROLO_ODOM_FRONT_PRIORITY": "1",
-    "ROLO_S2M_PACKETS": "1", "ROLO_S2M_QPP": "64", "ROLO_S2M_SUB": "4", "ROLO_S2M_WIDE": "4", "ROLO_S2M_XCD": "1", "ROLO_S2M_CAP": "1", "ROLO_S2M_STATS": "-",
+    "ROLO_S2M_PACKETS": "1", "ROLO_S2M_STATS": "-",
     "ROLO_PEER_TIMEOUT_MS": "10000", "ROLO_PEER_MEM": "-", "ROLO_ODOM_EARLY_SOURCE": "0/1",   # (the last: unset leaves the caller's default, whichever it is)
 }
 # switch -> (value set, value read): one accepted non-default value each
@@ -23,16 +23,15 @@ ACCEPTED = {
     "ROLO_LM_PERSIST_WGS": ("64", "64"), "ROLO_LM_PERSIST_BUSY_THREADS": ("256", "256"), "ROLO_LM_PERSIST_ADMIT_US": ("0", "0"), "ROLO_LM_PERSIST_TIMEOUT_MS": ("50", "50"),
     "ROLO_LM_PERSIST_INTERLEAVE": ("0", "0"), "ROLO_LM_PERSIST_MCACHE": ("0", "0"), "ROLO_LM_PERSIST_BATCH": ("4", "4"), "ROLO_CTRL_GENERIC": ("1", "1"),
     "ROLO_CU_PARTITION": ("4", "4"), "ROLO_ODOM_FRONT_PRIORITY": ("0", "0"),
-    "ROLO_S2M_PACKETS": ("0", "0"), "ROLO_S2M_QPP": ("16", "16"), "ROLO_S2M_SUB": ("8", "8"), "ROLO_S2M_WIDE": ("6", "6"), "ROLO_S2M_XCD": ("0", "0"), "ROLO_S2M_CAP": ("7", "7"),
-    "ROLO_S2M_STATS": ("/tmp/walk.csv", "/tmp/walk.csv"),
+    "ROLO_S2M_PACKETS": ("0", "0"), "ROLO_S2M_STATS": ("/tmp/walk.csv", "/tmp/walk.csv"),
     "ROLO_PEER_TIMEOUT_MS": ("250.5", "250.5"), "ROLO_PEER_MEM": ("coarse", "coarse"), "ROLO_ODOM_EARLY_SOURCE": ("1", "1/1"),
 }
 # values outside what a switch accepts, in two rounds (two of the switches have a rejected value on either side)
 REJECTED = [
-    {"ROLO_LM_THREADS": ("768", "512"), "ROLO_S2M_SUB": ("3", "4"), "ROLO_S2M_QPP": ("64", "64"), "ROLO_S2M_WIDE": ("5", "4"), "ROLO_LM_PPT": ("0", "1"),
+    {"ROLO_LM_THREADS": ("768", "512"), "ROLO_LM_PPT": ("0", "1"),
      "ROLO_LM_PERSIST_BATCH": ("3", "2"), "ROLO_LM_PERSIST_BUSY_THREADS": ("128", "512"), "ROLO_CU_PARTITION": ("3", "0"), "ROLO_LM_PERSIST_ADMIT_US": ("-5", "1000"),
      "ROLO_LM_PERSIST_TIMEOUT_MS": ("0", "200"), "ROLO_LM_PERSIST_WGS": ("7", "0"), "ROLO_KNN_SUB": ("3", "-1"), "ROLO_ODOM_EARLY_SOURCE": ("0", "0/0")},
-    {"ROLO_S2M_QPP": ("12", "64"), "ROLO_LM_PPT": ("17", "1"), "ROLO_LM_PERSIST_WGS": ("257", "0"), "ROLO_LM_PERSIST_TIMEOUT_MS": ("-3", "200"), "ROLO_LM_FUSED": ("-4", "-4")},
+    {"ROLO_LM_PPT": ("17", "1"), "ROLO_LM_PERSIST_WGS": ("257", "0"), "ROLO_LM_PERSIST_TIMEOUT_MS": ("-3", "200"), "ROLO_LM_FUSED": ("-4", "-4")},
 ]
 
 
