@@ -119,3 +119,67 @@ def outlier_spec(N, k=1.0, outliers=True):
     spec["true_loops"] = list(range(first, first + n_true))
     spec["false_loops"] = list(range(first + n_true, first + n_true + len(fl)))
     return spec
+
+
+# ---- a graph grown as the back end grows it: one key pose per step, events arriving while it grows ----
+LIFE_POSES = 200
+
+
+def life_script(N=LIFE_POSES, seed=9):
+    """-> (steps, spec). steps: one list of operations per call of optimize, ("pose", k, Z) (key pose k, its odometry measurement Z from k - 1; for k = 0 its
+    prior follows), ("prior", i, T, var6), ("between", i, j, T, var6, k or None); steps named in `events` carry more than the key pose. spec: the whole graph
+    in the form of pgo_twin.circuit plus `loss`, its `factors` in the order the steps add them, starting from the composed odometry. Measurements are truth
+    plus 1 mrad / 1 cm. The events: a loop from the newest pose to an old one; two loops in one step; a loop between two old poses in a step without a pose;
+    a loop under Cauchy(1); a second factor on an old consecutive pair (it lands in that pose's chain block, reversed); a prior on an old pose; a loop to pose 0;
+    and a second factor on the newest pair (N - 2, N - 1) in a step without a pose"""
+    c = tw.circuit(N, 0, seed=seed)
+    rng = np.random.default_rng(900 + seed)
+    tr = c["truth"]
+    noise = lambda: np.concatenate([rng.normal(0, 1e-3, 3), rng.normal(0, 1e-2, 3)])
+    meas = lambda i, j: tw.T_of(tw.mul(tw.mul(tw.inv(*tr[i]), tr[j]), tw.exp_se3(noise())))
+    lv, ov = np.full(6, 1e-2), np.array(tw.ODOM_VARIANCES)
+    loop = lambda i, j, k=None: ("between", i, j, meas(i, j), lv, k)
+    at = {40: [loop(40, 5)], 60: [loop(60, 20), loop(60, 33)], 90: [loop(90, 30, 1.0)], 110: [("between", 71, 70, meas(71, 70), ov, None)],
+          130: [("prior", 100, tw.T_of(tr[100]), np.full(6, 1e-2))], 150: [loop(150, 0)]}
+    alone = {75: [loop(50, 10)], 170: [("between", 170, 169, meas(170, 169), ov, None)]}      # after key pose 75 (170): a step that adds no pose
+    steps, events = [], []
+    for k in range(N):
+        ops = [("pose", k, None if k == 0 else c["betweens"][k - 1][2])]
+        if k == 0:
+            ops.append(("prior", 0, c["priors"][0][1], c["priors"][0][2]))
+        if k in at:
+            ops += at[k]; events.append(len(steps))
+        steps.append(ops)
+        if k in alone:
+            events.append(len(steps)); steps.append(list(alone[k]))
+    factors = []
+    for ops in steps:
+        for op in ops:
+            if op[0] == "pose" and op[1] > 0: factors.append(("between", op[1] - 1, op[1], op[2], ov, None))
+            elif op[0] != "pose": factors.append(op)
+    return steps, dict(truth=tr, initial=c["initial"], factors=factors, events=events)
+
+
+def build_life(spec):
+    """the twin's graph of life_script's whole graph, the factors in the order the steps added them"""
+    g = Graph()
+    for X in spec["initial"]:
+        g.add_pose(tw.T_of(X))
+    for f in spec["factors"]:
+        if f[0] == "prior": g.add_prior(f[1], f[2], f[3])
+        else: g.add_between(f[1], f[2], f[3], f[4], f[5])
+    return g
+
+
+def grow_life(steps, first_pose, add_pose, add_prior, add_between, last_pose, after_step):
+    """drives a graph through life_script's steps: a new key pose starts at the graph's last pose times its odometry measurement, as the back end's does"""
+    for n, ops in enumerate(steps):
+        for op in ops:
+            if op[0] == "pose":
+                if op[1] == 0:
+                    add_pose(first_pose)
+                else:
+                    add_pose(last_pose() @ op[2]); add_between(op[1] - 1, op[1], op[2], np.array(tw.ODOM_VARIANCES), None)
+            elif op[0] == "prior": add_prior(*op[1:])
+            else: add_between(*op[1:])
+        after_step(n, ops)

@@ -1,12 +1,17 @@
-"""CPU: tests/pgo_twin.py, the numpy statement of the pose-graph optimisation (include/rolo_hip.h), against finite differences, known answers and itself
-(its direct solve against its preconditioned conjugate gradients). The figures the GPU test's bars are derived from are measured here and asserted to stay
+"""CPU: tests/pgo_twin.py, the numpy statement of the pose-graph optimisation (include/rolo_hip.h), against finite differences, known answers, mpmath
+(tests/se3_mp.py: Exp and Log written from the mathematics, at every angle where the statement changes form) and itself (its direct solve against its
+preconditioned conjugate gradients). The figures the GPU test's bars are derived from are measured here and asserted to stay
 below the constants recorded at the top of tests/test_gpu_posegraph.py."""
 import numpy as np
 import pytest
 
+import pgo_robust_twin as rt
 import pgo_twin as tw
+import se3_cases as sc
+import se3_mp as sm
 
-from test_gpu_posegraph import TWIN_REFERENCE as RECORDED_REFERENCE, TWIN_STEP as RECORDED_STEP, TWIN_WHOLE as RECORDED_WHOLE   # the recorded figures live there
+from test_gpu_posegraph import (TWIN_LIFE as RECORDED_LIFE, TWIN_REFERENCE as RECORDED_REFERENCE, TWIN_RETRACT as RECORDED_RETRACT, TWIN_STEP as RECORDED_STEP,
+                                TWIN_WHOLE as RECORDED_WHOLE)   # the recorded figures live there
 
 
 def rand_xi(rng, th, tscale=1.0):
@@ -29,6 +34,43 @@ def test_exp_log_round_trip(th):
 def test_coefficient_series_meet_the_closed_forms():
     lo, hi = np.array(tw.coeffs(tw.SMALL * (1 - 1e-9))), np.array(tw.coeffs(tw.SMALL * (1 + 1e-9)))
     assert np.abs(lo - hi).max() < 1e-11   # (C and D lose eps / th^2 in the closed form: 1e-12 at the switch)
+
+
+def test_exp_and_log_against_mpmath():
+    """the statement's Exp and Log against tests/se3_mp.py on the same doubles: every angle of se3_cases.ANGLES (both sides of each switch of form, and up to
+    pi - 1e-5), 20 random axes and the exact and near-yaw ones, translations up to 20 m. Relative to the largest entry of mpmath's vector (for R: to 1)"""
+    rng = np.random.default_rng(3)
+    worst_exp = worst_log = 0.0
+    for th in sc.ANGLES:
+        for axis in sc.axes(20, seed=5):
+            xi = np.concatenate([th * axis, rng.uniform(-20.0, 20.0, 3)])
+            R, t = tw.exp_se3(xi)
+            Rm, tm = sm.exp_se3(xi)
+            tm = sm.floats(tm)
+            worst_exp = max(worst_exp, np.abs(R - sm.floats(Rm)).max(), np.abs(t - tm).max() / np.abs(tm).max())
+            want = sm.floats(sm.log_se3(R, t))      # Log of the statement's own doubles: the same input on both sides
+            worst_log = max(worst_log, np.abs(tw.log_se3(R, t) - want).max() / np.abs(want).max())
+    print(f"the statement against mpmath, worst relative difference: Exp {worst_exp:.2e}, Log {worst_log:.2e}")
+    assert worst_exp <= 1e-14 and worst_log <= 1e-14
+
+
+@pytest.mark.parametrize("kind", sc.KINDS)
+def test_one_gauss_newton_step_lands_on_the_zero_error_poses(kind):
+    """lambda = 0 on the planted graphs of tests/se3_cases.py: Jr^-1 e = e, so the step is -e and X Exp(-e) the zero-error pose at every angle; the distance
+    left is the figure the bar of tests/test_gpu_posegraph_se3.py is 10 x of"""
+    worst = {}
+    for th in sc.RETRACT_ANGLES:
+        wt = wr = 0.0
+        for axis in sc.axes():
+            spec, _, rest = sc.planted(kind, th, axis)
+            g = rt.build(spec)
+            r = g.optimize("direct", max_iterations=1, lambda_initial=0.0, absolute_error_tol=0.0, relative_error_tol=0.0)
+            assert (r["state"], r["iterations"], r["trials"]) == (tw.ITERATIONS, 1, 1), (th, axis, r)
+            dt, dr = sm.pose_distance(g.poses, rest)
+            wt, wr = max(wt, dt), max(wr, dr)
+        worst[th] = (wt, wr)
+    print(kind, "after one step, (m, rad) from the zero-error poses by angle:", {f"{th:.6g}": (f"{a:.1e}", f"{b:.1e}") for th, (a, b) in worst.items()})
+    assert max(v[0] for v in worst.values()) <= RECORDED_RETRACT[kind][0] and max(v[1] for v in worst.values()) <= RECORDED_RETRACT[kind][1]
 
 
 def numeric_jacobians(g, f, h=1e-6):
@@ -125,8 +167,8 @@ def test_pcg_without_chords_takes_one_iteration():
 
 
 def test_pcg_against_the_direct_solve_on_the_test_graphs():
-    worst = 0.0
-    for n, kind in tw.CASES:
+    worst, by_size = 0.0, {}
+    for n, kind in tw.CASES + tw.CASES_LARGE:
         g = tw.build(tw.case_spec(n, kind))
         lin = g.linearize()
         for lam in (0.0, 1e-5):
@@ -134,8 +176,10 @@ def test_pcg_against_the_direct_solve_on_the_test_graphs():
             dd = tw.Graph.solve_direct(lin, lam)
             assert its <= tw.Graph.pcg_cap(len(g.chords()))
             worst = max(worst, np.abs(d - dd).max() / np.abs(dd).max())
-    print("twin PCG against twin direct solve, largest relative difference of the step:", worst)
+            by_size[n] = max(by_size.get(n, 0.0), np.abs(d - dd).max() / np.abs(dd).max())
+    print("twin PCG against twin direct solve, largest relative difference of the step:", worst, "by size:", {n: f"{v:.2e}" for n, v in by_size.items()})
     assert worst <= RECORDED_STEP
+    assert max(by_size[n] for n in tw.SIZES_LARGE) <= max(by_size[n] for n in tw.SIZES)      # the sizes past 1 024 poses did not widen the figure
 
 
 # ---- the twin's two entry points against each other on the graphs of tests/test_gpu_posegraph.py: the figures its bars are 10 x of ----
@@ -189,3 +233,25 @@ def test_the_twin_halves_the_drift():
     after = tw.max_position_error(g.poses, spec["truth"])
     print("largest position error against truth:", before, "->", after)
     assert r["state"] == tw.CONVERGED and after <= 0.5 * before
+
+
+def test_the_grown_graph_reaches_the_optimum_of_the_whole():
+    """the graph of tests/test_gpu_posegraph_life.py, grown on the statement as that test grows it on the device (one key pose and one default optimize per step,
+    PCG, then STRICT), against the statement's direct solve on the whole graph from the composed odometry: the figure that test's last bar is 10 x of"""
+    steps, spec = rt.life_script()
+    g = rt.Graph()
+    moved = []
+    rt.grow_life(steps, tw.T_of(spec["initial"][0]), g.add_pose, g.add_prior, g.add_between, lambda: tw.T_of(g.poses[-1]),
+                 lambda n, ops: moved.append((n, g.optimize("pcg")["iterations"])))
+    ends = [(f[1], -1) if f[0] == "prior" else (f[1], f[2]) for f in spec["factors"]]
+    assert ends == [(i, j) for i, j, _, _ in g.factors] and g.k == [f[5] if f[0] == "between" else None for f in spec["factors"]]      # the same graph
+    assert all(its >= 1 for n, its in moved if n in spec["events"])      # every event moves the graph
+    a = g.optimize("pcg", **tw.STRICT)
+    whole = {}
+    for solver in ("direct", "pcg"):
+        t = rt.build_life(spec)
+        whole[solver] = (t.optimize(solver, **tw.STRICT), t.poses)
+    b = whole["direct"][0]
+    dt, dr = tw.pose_distance(g.poses, whole["direct"][1])
+    print(f"grown against whole: {dt:.3e} m {dr:.3e} rad, costs {a['final_cost']!r} {b['final_cost']!r}; whole, direct against PCG:", tw.pose_distance(whole["direct"][1], whole["pcg"][1]))
+    assert abs(a["final_cost"] - b["final_cost"]) <= 1e-9 * b["final_cost"] and dt <= RECORDED_LIFE[0] and dr <= RECORDED_LIFE[1]
