@@ -698,6 +698,8 @@ hipError_t launch_knn_walk(const KnnPair& A, int k, hipStream_t s, int* lanes_ou
   const int n0 = A.c[0].q_end - A.c[0].q_begin, n1 = A.n_clouds > 1 ? A.c[1].q_end - A.c[1].q_begin : 0;
   const int g0 = (n0 + QPB - 1) / QPB, g1 = (n1 + QPB - 1) / QPB;
   if (g0 + g1 == 0) return hipSuccess;
+  // a packet's first query is a multiple of 64, so its four own leaves are one whole subtree: what the walk's climb starts from (packet_climb)
+  for (int i = 0; i < A.n_clouds; i++) if (A.c[i].q_end > A.c[i].q_begin && A.c[i].q_begin % 64 != 0) return hipErrorInvalidValue;
   if (k > 64) {   // any k: rounds of 64 — round r searches the 64 (the last: k - 64 r) nearest ABOVE the previous round's last key (KnnCloud::lower).
                   // ceil(k / 64) full walks: correct, as slow as it sounds; the reference accepts any k, its default is 20 and ROLO never changes it
     KnnPair R = A;

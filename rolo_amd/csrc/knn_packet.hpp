@@ -1,10 +1,11 @@
 // The packet walk of the exact k-nearest-neighbour search, as device functions: packed (d2, index) keys and their min / max sorted insert, wave-uniform
 // fetches, leaf scoring and the walk itself. Included by knn_walk.hpp (K5: the queries are the cloud's own points) and by scan2map.hip (8f.4: its own walk for foreign
-// queries takes the keys, insert_slot, sub_*, sload_node, box_d2, xcd_contiguous_block and WALK_STACK from here, not packet_walk). Design notes: knn_walk.hpp.
+// queries takes the keys, insert_slot, sub_*, sload_node, xcd_contiguous_block and WALK_STACK from here, not packet_walk; the box tests are knn_box_pair.hpp's). Design notes: knn_walk.hpp.
 #pragma once
 #include "rolo_internal.hpp"
 #include "dev_math.hpp"
 #include "knn_seed_net.hpp"
+#include "knn_box_pair.hpp"   // box_d2, box_d2_pair, the one-compare reach test
 #include <cfloat>
 #include <climits>
 
@@ -20,14 +21,6 @@ namespace rolo {
 namespace {
 
 constexpr int WALK_STACK = KNN_WALK_STACK;
-
-// squared distance from q to the box [lo, hi] in the operation order of the point distances (a true lower bound of every point distance inside)
-ROLO_DEV float box_d2(const float4& lo, const float4& hi, const float4& q) {
-  float dx = fmaxf(fmaxf(__fsub_rn(lo.x, q.x), __fsub_rn(q.x, hi.x)), 0.f);
-  float dy = fmaxf(fmaxf(__fsub_rn(lo.y, q.y), __fsub_rn(q.y, hi.y)), 0.f);
-  float dz = fmaxf(fmaxf(__fsub_rn(lo.z, q.z), __fsub_rn(q.z, hi.z)), 0.f);
-  return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
 
 ROLO_DEV double key_pack(float d2, int idx) {
   return __longlong_as_double((long long)(((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)idx));
@@ -87,6 +80,10 @@ ROLO_DEV void sload_leaf(const float4* __restrict__ p, float4 (&pts)[KNN_LEAF]) 
 // the two child boxes of node h: boxes[4h .. 4h + 3] = left lo, left hi, right lo, right hi (64 bytes)
 ROLO_DEV void sload_node(const float4* __restrict__ p, float4& llo, float4& lhi, float4& rlo, float4& rhi) { llo = p[0]; lhi = p[1]; rlo = p[2]; rhi = p[3]; }
 
+// k = 20 without a lower bound (the headline's walk): kk = KMAX, so the lane's bound IS the list's last slot — the walk reads K[19] and keeps no copies of it
+// (bkey, bd: a v_mov_b64 and a v_mov_b32 after every insert execution). A padding lane's list is zeroed after the seeds (knn_walk.hpp): no key is below (0, 0).
+template <int KMAX, bool LOWER> constexpr bool walk_bound_in_list() { return KMAX == 20 && !LOWER; }
+
 // score the KNN_LEAF (16) points of leaf g against this lane's query and insert the ones that beat its current k-th best
 template <int KMAX, bool LOWER = false>
 ROLO_DEV void knn_score_leaf(const float4* __restrict__ sorted, int g, const float4& q, double (&K)[KMAX], int kk, double& bkey, float& bd,
@@ -95,7 +92,8 @@ ROLO_DEV void knn_score_leaf(const float4* __restrict__ sorted, int g, const flo
   // (loading inside the loop serialised the scalar-cache round trips of a leaf behind the insert branch)
   float4 pts[KNN_LEAF];
   sload_leaf(sorted + KNN_LEAF * (size_t)g, pts);
-  KNN_STAT(const double bkey0 = bkey; unsigned my_acc = 0;)   // accepted against the bound at leaf entry: what a per-lane queue would hold
+  constexpr bool IN_LIST = walk_bound_in_list<KMAX, LOWER>();
+  KNN_STAT(const double bkey0 = IN_LIST ? K[KMAX - 1] : bkey; unsigned my_acc = 0;)   // accepted against the bound at leaf entry: what a per-lane queue would hold
 #ifdef ROLO_KNN_STATS2
   unsigned my_cur = 0;
 #endif
@@ -106,20 +104,23 @@ ROLO_DEV void knn_score_leaf(const float4* __restrict__ sorted, int g, const flo
     const float cd = ((dx * dx) + (dy * dy)) + (dz * dz);  // file is compiled with -ffp-contract=off (the compiler already pairs x and y into v_pk_add_f32 / v_pk_mul_f32)
     const double ck0 = key_pack(cd, __float_as_int(c.w));
     const double ck = (LOWER && !(ck0 > lo)) ? key_pack(INFINITY, INT_MAX) : ck0;   // LOWER: a point of an earlier round's 64 is no candidate
-    KNN_STAT(if (__any(ck < bkey)) { n_ins++; lane_acc += (unsigned)__popcll(__ballot(ck < bkey)); })
+    const bool better = IN_LIST ? ck < K[KMAX - 1] : ck < bkey;
+    KNN_STAT(if (__any(better)) { n_ins++; lane_acc += (unsigned)__popcll(__ballot(better)); })
     KNN_STAT(if (ck < bkey0) my_acc++;)
 #ifdef ROLO_KNN_STATS2
-    if (ck < bkey) my_cur++;   // accepted against the CURRENT bound: this lane's own inserts
+    if (better) my_cur++;   // accepted against the CURRENT bound: this lane's own inserts
 #endif
-    if (ck < bkey) {
+    if (better) {
       // sorted insert, descending slot order so every step reads not-yet-overwritten neighbours — in four tiers: a slot whose lower
       // neighbour is already <= the candidate in EVERY lane keeps its value (min(ck, K[s]) = K[s] and K[s-1] <= K[s]), so the lower tiers
       // run only if some lane's candidate sorts below them. Late in the walk candidates barely beat the k-th best: most executions stop
       // after the first tier (the insert is two thirds of the walk's VALU instructions; v_min_f64 / v_max_f64 issue at the fp32 rate, profiles/tools/valu_rate.hip).
       insert_tiered<KMAX>(K, ck);
+      if constexpr (!IN_LIST) {
 #pragma unroll
-      for (int s = 0; s < KMAX; s++) if (s == kk - 1) bkey = K[s];
-      bd = key_d2(bkey);
+        for (int s = 0; s < KMAX; s++) if (s == kk - 1) bkey = K[s];
+        bd = key_d2(bkey);
+      }
     }
   }
 #ifdef ROLO_KNN_STATS
@@ -230,8 +231,9 @@ ROLO_DEV void packet_walk(const float4* __restrict__ sorted, const float4* __res
       st_nodes++;
       float4 llo, lhi, rlo, rhi;
       sload_node(boxes + 4 * (size_t)h, llo, lhi, rlo, rhi);
-      const float bl = box_d2(llo, lhi, q), br = box_d2(rlo, rhi, q);
-      const bool okl = (bl <= bd) && (bl < INFINITY), okr = (br <= bd) && (br < INFINITY);
+      const box_f2 d = box_d2_pair(llo, lhi, rlo, rhi, q);
+      const float bl = d[0], br = d[1], bdc = box_bound_clamp(walk_bound_in_list<KMAX, LOWER>() ? key_d2(K[KMAX - 1]) : bd);
+      const bool okl = box_reached(bl, bdc), okr = box_reached(br, bdc);
       const unsigned long long ml = __ballot(okl), mr = __ballot(okr);
       if (ml != 0ull && mr != 0ull) {
         // nearer child first, by majority vote of the lanes that reach either child (a "lane with the largest
@@ -254,6 +256,30 @@ ROLO_DEV void packet_walk(const float4* __restrict__ sorted, const float4* __res
     if (sp == 0) return;
     sp--;
     h = stk[sp];
+  }
+}
+
+// The walk of a packet whose own leaves were scored as seeds: CLIMB from their common ancestor a = (P + g_mine0) >> 2 (g_mine0 is a multiple of 4: the four own
+// leaves are a's whole subtree) instead of descending from the root. On every level the SIBLING of a — its box is one half of the parent's record — is tested
+// against the lanes' current bounds, and walked (packet_walk: it is an internal node, two levels above the leaves at least) if some lane reaches it. A descent from
+// the root visits the same path: a full node visit per level whose near child is always live, the sibling pushed and popped later in this very order (nearest
+// first), and two more visits that lead to leaves it then skips. A sibling is tested when its turn comes, against bounds that only shrank meanwhile, which can only
+// prune more; the search is exact either way, so the list is the twenty smallest distinct keys in both forms. P < 4: a <= 1, nothing to climb — all leaves are seeds.
+template <int KMAX, bool LOWER>
+ROLO_DEV void packet_climb(const float4* __restrict__ sorted, const float4* __restrict__ boxes, int P, int g_mine0, int g_own0, int g_own1, const float4& q, double (&K)[KMAX], int kk,
+                           double& bkey, float& bd, double lo, lds_int* stk,
+                           unsigned& st_nodes, unsigned& st_leaves, unsigned& st_ins, unsigned& st_lane, unsigned& st_rounds, unsigned& st_push) {
+  for (int a = (P + g_mine0) >> 2; a > 1; a >>= 1) {
+    const int s = a ^ 1;
+    const float4* __restrict__ rec = boxes + 4 * (size_t)(a >> 1) + 2 * (s & 1);   // the sibling's half of the parent's record: lo, hi
+    const float4 slo = rec[0], shi = rec[1];
+    const float d = box_d2(slo, shi, q);
+    const float bdc = box_bound_clamp(walk_bound_in_list<KMAX, LOWER>() ? key_d2(K[KMAX - 1]) : bd);
+    KNN_STAT(st_nodes++;)
+    if (__ballot(box_reached(d, bdc)) != 0ull) {
+      int sp = 0;
+      packet_walk<KMAX, LOWER>(sorted, boxes, P, g_own0, g_own1, q, K, kk, bkey, bd, lo, stk, sp, s, st_nodes, st_leaves, st_ins, st_lane, st_rounds, st_push);
+    }
   }
 }
 

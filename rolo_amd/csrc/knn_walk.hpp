@@ -6,8 +6,12 @@
 // measured 2.45 ms per 131k-point cloud, vs 0.59 ms for the packet. Here every control decision is wave-uniform:
 //   * seed: the wavefront's own 64 points (64 / KNN_LEAF = 4 consecutive leaves of 16) and a leaf on either side are scored first, so every lane starts the walk
 //     with a finite search radius (k = 20: by sorting / merging networks, knn_seed_net.hpp — nearly every seed candidate is accepted by some lane);
-//   * a node is expanded if ANY lane's search sphere reaches its box (ballot); of two live children the one
+//   * the walk CLIMBS from the common ancestor of the packet's four own leaves (all seeds) instead of descending from the root: on every level the ancestor's
+//     sibling is tested — one box, one compare — and walked downwards only if some lane reaches it (packet_climb, knn_packet.hpp);
+//   * a node is expanded if ANY lane's search sphere reaches its box (ballot); both child boxes are tested as one pair in packed math with one compare per
+//     child against the bound clamped to FLT_MAX (knn_box_pair.hpp); of two live children the one
 //     nearer to the majority of interested lanes goes first, the other is pushed on ONE small per-wave stack in LDS;
+//   * k = 20: a lane's bound is its list's last slot, K[19] — no copies to keep after an insert;
 //   * node boxes and leaf points are fetched through wave-uniform addresses, so a leaf's 16 points are loaded
 //     once per wave, not once per lane;
 //   * each lane keeps its k best as packed 64-bit keys  (float_bits(d2) << 32) | index : for non-negative floats
@@ -129,7 +133,12 @@ ROLO_DEV void walk_seeds(const float4* __restrict__ sorted, int g_mine0, int g_o
     st_leaves++;
   }
   if constexpr (KMAX == 20 && !LOWER) {
-    if (active) { bkey = K[KMAX - 1]; bd = key_d2(bkey); }   // (padding lanes keep bd = -1 and the key nothing is below)
+    // the bound is K[19] from here on (walk_bound_in_list). A padding lane's query is at +infinity, so every box is at distance +inf from it and out of reach of
+    // any clamped bound; its list — whatever the networks left there — becomes twenty keys (0, 0), which no candidate's key is below: it accepts nothing
+    if (!active) {
+#pragma unroll
+      for (int u = 0; u < KMAX; u++) K[u] = key_pack(0.f, 0);
+    }
   }
 }
 
@@ -147,7 +156,7 @@ __global__ __launch_bounds__(256, KMAX > 32 ? 2 : (MOMENTS ? 6 : ROLO_KNN_WALK_O
   const int n_sorted = A.c[which].n_sorted, P = A.c[which].P;
   const int lane_ = tid & 63;
   const int j = A.c[which].q_begin + (blk - (which ? split : 0)) * 256 + wv * 64 + lane_;
-  float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 q = make_float4(INFINITY, INFINITY, INFINITY, 0.f);   // a padding lane: at distance +inf from every box (and bd = -1, and a bound key nothing is below)
   int qi = INT_MAX;
   if (j < A.c[which].q_end) { q = sorted[j]; qi = __float_as_int(q.w); }
   const bool active = qi != INT_MAX;  // not padding
@@ -177,13 +186,15 @@ __global__ __launch_bounds__(256, KMAX > 32 ? 2 : (MOMENTS ? 6 : ROLO_KNN_WALK_O
   // ---- packet walk ----
   // (a stack in one vector register — slot i in lane i, v_writelane / v_readlane — measured the same as this LDS stack: 0.202 vs 0.200 ms;
   // gfx950's v_writelane takes its lane select from M0 when the value is an SGPR, which inline asm may not clobber safely)
-  int sp = 0;
-  int h = 1;
+  // The walk climbs from the packet's own subtree (packet_climb): its four leaves were seeds, nothing below their ancestor is left to visit.
+  // (a wavefront past the cloud's last leaf is all padding and walks nothing)
+  int g_climb = g_mine0;
 #ifdef ROLO_KNN_STATS
   unsigned long long wt0;
-  asm("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)\n\ts_mov_b32 %1, 1" : "=s"(wt0), "=s"(h));
+  { int zero; asm("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)\n\ts_mov_b32 %1, 0" : "=s"(wt0), "=s"(zero)); g_climb += zero; }   // (the walk's start depends on this asm: it cannot move)
 #endif
-  packet_walk<KMAX, LOWER>(sorted, boxes, P, g_own0, g_own1, q, K, kk, bkey, bd, lo, (lds_int*)&stk[wv][0], sp, h, st_nodes, st_leaves, st_ins, st_lane, st_rounds, st_push);
+  if (g_mine0 < n_leaves)
+    packet_climb<KMAX, LOWER>(sorted, boxes, P, g_climb, g_own0, g_own1, q, K, kk, bkey, bd, lo, (lds_int*)&stk[wv][0], st_nodes, st_leaves, st_ins, st_lane, st_rounds, st_push);
 #ifdef ROLO_KNN_STATS
   { unsigned long long wt1; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(wt1));
     unsigned st_rounds_rec = st_rounds;

@@ -516,7 +516,8 @@ __global__ __launch_bounds__(256) void s2m_assoc_kernel(S2mArgs A, int split /* 
         n_nodes++;
         float4 llo, lhi, rlo, rhi;
         sload_node(boxes + 4 * (size_t)h, llo, lhi, rlo, rhi);
-        const float bl = box_d2(llo, lhi, q), br = box_d2(rlo, rhi, q);
+        const box_f2 bd2 = box_d2_pair(llo, lhi, rlo, rhi, q);
+        const float bl = bd2[0], br = bd2[1];
         const bool okl = (bl <= bd) && (bl < INFINITY), okr = (br <= bd) && (br < INFINITY);
         const unsigned long long ml = __ballot(okl), mr = __ballot(okr);
         if (ml != 0ull && mr != 0ull) {
