@@ -659,9 +659,22 @@ int rolo_pgo_get_trace(rolo_pgo* g, rolo_pgo_trace_rec* out, int cap);
 /* test hooks. linearise at the current poses: cost, grad[6N], diag[N x 36], chain[(N - 1) x 36] (the blocks H[k, k+1]), chord[chords x 36] (H[i, j] of the
  * factor as given) and chord_ij[chords x 2], each optional; solve_linear: the step a trial would take on the last linearisation */
 int rolo_pgo_linearize(rolo_pgo* g, double* cost, double* grad, double* diag, double* chain, double* chord, int32_t* chord_ij);
+/* The solve (of solve_linear and of every trial of optimise) has two forms that return the same bits: delta, the iteration count, the residual and the
+ * not-positive-definite flag. ONE_WG runs the factorisation and the whole PCG loop in one workgroup of one launch. GRID cuts the same arithmetic into launches
+ * that cover the device, one per level of the reduction and per stage of an iteration; PCG's scalars and its exit live in device memory and the host looks at
+ * them once per batch of iterations. Every element is the same expression in both; the dot products keep the one-workgroup form's summation order. */
 int rolo_pgo_solve_linear(rolo_pgo* g, double lambda, double pcg_tol, int pcg_max, double* delta, int* pcg_iterations, double* residual);
+/* which form a graph's solves take. AUTO (the default): ONE_WG below a measured pose count, GRID from it on (512 poses: DESIGN.md 7). Any other value is ROLO_EINVAL and
+ * the form stays as it was. get: the form asked for and the one the latest solve ran (0 before any solve); each output is optional. Per graph, at any time
+ * between calls */
+#define ROLO_PGO_SOLVE_AUTO 0
+#define ROLO_PGO_SOLVE_ONE_WG 1
+#define ROLO_PGO_SOLVE_GRID 2
+int rolo_pgo_set_solve_form(rolo_pgo* g, int form);
+int rolo_pgo_get_solve_form(rolo_pgo* g, int* requested, int* last_used);
 /* device milliseconds of the last optimise, summed over its trials: ms4[0] linearise + assemble and [3] retract + cost between HIP events; [1] the cyclic
- * reduction's factorisation and [2] the PCG loop, which share one launch, by the device's wall clock inside it */
+ * reduction's factorisation and [2] the PCG loop: in the one-workgroup form they share one launch and are read from the device's wall clock inside it, in the
+ * grid form they lie between HIP events */
 int rolo_pgo_last_ms(rolo_pgo* g, float* ms4);
 /* correctPoses (:1301-1314) in one call: poses 0 .. n - 1 of the key map (n x 6 floats); n above the key map's size is ROLO_EINVAL */
 int rolo_keymap_set_poses(rolo_keymap* km, const float* pose6, int n);

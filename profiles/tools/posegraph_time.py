@@ -7,7 +7,9 @@ HIP events; the cyclic reduction's factorisation and the PCG loop, which share o
 the exit, iterations, trials and PCG iterations. `keyframe_call`: the zero-loop per-key-frame use, the median of --reps addOdomFactor + optimise calls on a graph of
 N - reps poses without loops. `host_direct_solve_s`: scipy's sparse direct solve (spsolve, SuperLU on the host cores) of the SAME first linear system, taken from
 the device's linearisation, wall clock: for scale, NOT a baseline (the reference's iSAM2 is incremental and cannot be built here). --cauchy K adds every loop
-under a Cauchy(K) loss, as performSCLoopClosure does with K = 1 (profiles/r11/posegraph_robust.json); without it every factor is plain."""
+under a Cauchy(K) loss, as performSCLoopClosure does with K = 1 (profiles/r11/posegraph_robust.json); without it every factor is plain. --solve-form one | grid
+takes the one-workgroup or the grid form of the linear solve (in the grid form the factorisation and PCG lie between HIP events); --repeats R runs every optimise on
+R fresh graphs after an untimed one and records the medians, every repeat and the spread (profiles/r14/posegraph_grid.json: the parent's build, one, grid)."""
 import argparse
 import json
 import os
@@ -43,12 +45,17 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--host-solve-max", type=int, default=60000, help="largest N whose first system is also solved on the host")
     ap.add_argument("--cauchy", type=float, default=None, help="every loop under a Cauchy loss with this constant")
+    ap.add_argument("--repeats", type=int, default=1, help="above 1: each optimise is run on this many fresh graphs after one untimed one; the row holds the medians, "
+                    "every repeat, and the spread (max - min) of the device total")
+    ap.add_argument("--solve-form", default=None, choices=PoseGraph.SOLVE_FORMS if hasattr(PoseGraph, "SOLVE_FORMS") else None,
+                    help="the form of the linear solve (PoseGraph.setSolveForm); without it the library's AUTO decides")
     a = ap.parse_args()
     rows = []
     for N in [int(x) for x in a.sizes.split(",")]:
         base = tw.circuit(N, 0, seed=N)
         # the zero-loop per-key-frame call
         g = PoseGraph()
+        if a.solve_form: g.setSolveForm(a.solve_form)
         n0 = N - a.reps
         for X in base["initial"][:n0]:
             g.addPose(tw.T_of(X))
@@ -68,21 +75,30 @@ def main():
         print(N, "per key frame", key, flush=True)
         for loops in [int(x) for x in a.loops.split(",")]:
             spec = tw.circuit(N, loops, seed=N)
-            g = PoseGraph()
-            fill(g, spec, cauchy=a.cauchy)
-            n, f, c = g.size()
-            host = None
-            if N <= a.host_solve_max:
-                lin = g.linearize()
+            rep_ms, rep_wall = [], []
+            for rep in range(a.repeats + (1 if a.repeats > 1 else 0)):
+                if rep: g.close()
+                g = PoseGraph()
+                if a.solve_form: g.setSolveForm(a.solve_form)
+                fill(g, spec, cauchy=a.cauchy)
+                n, f, c = g.size()
+                host = None
+                if N <= a.host_solve_max and rep == 0:
+                    lin = g.linearize()
+                    t0 = time.perf_counter()
+                    tw.Graph.solve_direct(lin, 1e-5)
+                    host = time.perf_counter() - t0
                 t0 = time.perf_counter()
-                tw.Graph.solve_direct(lin, 1e-5)
-                host = time.perf_counter() - t0
-            t0 = time.perf_counter()
-            r = g.optimize()
-            wall_ms = 1e3 * (time.perf_counter() - t0)
+                r = g.optimize()
+                rep_wall.append(1e3 * (time.perf_counter() - t0)); rep_ms.append([float(x) for x in g.lastMs()])
+            if a.repeats > 1: rep_ms, rep_wall = rep_ms[1:], rep_wall[1:]     # the first graph of a size and loop count is the warm-up
+            totals = [sum(m) for m in rep_ms]
             row = dict(poses=n, factors=f, chords=c, state=PoseGraph.STATES[r["state"]], iterations=r["iterations"], trials=r["trials"], pcg_iterations=r["pcg_iterations"],
-                       initial_cost=r["initial_cost"], final_cost=r["final_cost"], ms_linearise_factor_pcg_retract=[float(x) for x in g.lastMs()], wall_ms=wall_ms,
-                       pcg_per_trial=[t["pcg_iterations"] for t in g.trace()], host_direct_solve_s=host, keyframe_call=key, cauchy=a.cauchy)
+                       initial_cost=r["initial_cost"], final_cost=r["final_cost"], ms_linearise_factor_pcg_retract=[float(x) for x in np.median(np.array(rep_ms), axis=0)],
+                       wall_ms=float(np.median(rep_wall)), device_total_ms=float(np.median(totals)), device_total_spread_ms=float(max(totals) - min(totals)),
+                       repeats_ms=rep_ms if a.repeats > 1 else None,
+                       pcg_per_trial=[t["pcg_iterations"] for t in g.trace()], host_direct_solve_s=host, keyframe_call=key, cauchy=a.cauchy,
+                       solve_form=a.solve_form, solve_form_used=g.solveForm()[1] if a.solve_form else None)
             g.close()
             rows.append(row)
             print(row, flush=True)

@@ -209,6 +209,8 @@ SYMBOLS = {
     "rolo_pgo_get_trace": (C.c_int, [vp, C.POINTER(PgoTraceRec), C.c_int]),
     "rolo_pgo_linearize": (C.c_int, [vp, dp, dp, dp, dp, dp, ip]),
     "rolo_pgo_solve_linear": (C.c_int, [vp, C.c_double, C.c_double, C.c_int, dp, C.POINTER(C.c_int), dp]),
+    "rolo_pgo_set_solve_form": (C.c_int, [vp, C.c_int]),
+    "rolo_pgo_get_solve_form": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rolo_pgo_last_ms": (C.c_int, [vp, fp]),
     "rolo_keymap_set_poses": (C.c_int, [vp, fp, C.c_int]),
     "rolo_keymap_loop_last_ms": (C.c_int, [vp, fp]),

@@ -550,6 +550,19 @@ class PoseGraph:
         check(lib().rolo_pgo_get_factor_errors(self._h, r2.ctypes.data_as(dp), w.ctypes.data_as(dp), f), "rolo_pgo_get_factor_errors")
         return r2[:f], w[:f]
 
+    SOLVE_FORMS = ("auto", "one", "grid")   # ROLO_PGO_SOLVE_AUTO, _ONE_WG, _GRID
+
+    def setSolveForm(self, form: str):
+        """which form the solves of this graph take: "one" (one workgroup), "grid" (launches that cover the device) or "auto" (the default: by pose count).
+        Both forms return the same bits; anything else is an error and the form stays as it was"""
+        check(lib().rolo_pgo_set_solve_form(self._h, self.SOLVE_FORMS.index(form) if form in self.SOLVE_FORMS else -1), "rolo_pgo_set_solve_form")
+
+    def solveForm(self):
+        """(requested, last_used) as the names of setSolveForm; last_used is None before any solve"""
+        a, b = C.c_int(0), C.c_int(0)
+        check(lib().rolo_pgo_get_solve_form(self._h, C.byref(a), C.byref(b)), "rolo_pgo_get_solve_form")
+        return self.SOLVE_FORMS[a.value], (self.SOLVE_FORMS[b.value] if b.value else None)
+
     def lastMs(self):
         """device milliseconds of the last optimise: linearise + assemble, factorisation, PCG, retract + cost"""
         ms = np.zeros(4, np.float32)

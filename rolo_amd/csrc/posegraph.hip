@@ -332,6 +332,8 @@ struct SolveArgs {
   double *x, *r, *z, *p, *q, *cscr;
   double* delta;
   double* info;           // pinned: PCG iterations, sqrt(r z) / sqrt(r0 z0), 1 = a block was not positive definite, wall-clock ticks of the factorisation and of PCG
+  // the grid form only: PCG's scalars (PGO_ST_*) and the lane sums of a dot product in device memory; a pinned word that is 1 once the loop has left
+  double *st, *lanes, *done;
 };
 
 // W = A^-1 of a symmetric positive definite 6 x 6 block through its Cholesky factor (the lower triangle of A is read); false: a pivot was not positive
@@ -373,10 +375,20 @@ PGO_DEV bool inv6(const double* __restrict__ A, double* __restrict__ W) {
   return ok;
 }
 
-PGO_DEV double pgo_dot(const double* a, const double* b, int n, double* red) {
+// The solve has two forms that compute the same bits: pgo_solve_kernel, one workgroup that runs everything, and the pgo_grid_* kernels, the same arithmetic cut
+// into launches at every seam where one level, sweep or product needs all of the one before. Every element of every level, sweep, matrix-vector row and vector
+// update is ONE of the bodies below, evaluated by one thread; both forms call the same text. Only the dot product depends on the thread layout, and both forms
+// keep that layout: PGO_SOLVE_THREADS lane sums, lane t adding elements t, t + 1024, ... in order, then one halving tree over the lanes.
+
+// lane `lane` of the PGO_SOLVE_THREADS lane sums of a . b
+PGO_DEV double pgo_dot_lane(const double* a, const double* b, int n, int lane) {
   double s = 0;
-  for (int i = threadIdx.x; i < n; i += PGO_SOLVE_THREADS) s += a[i] * b[i];
-  red[threadIdx.x] = s;
+  for (int i = lane; i < n; i += PGO_SOLVE_THREADS) s += a[i] * b[i];
+  return s;
+}
+
+// the halving tree over red[0 .. PGO_SOLVE_THREADS), which the caller's PGO_SOLVE_THREADS threads have filled (one lane each, not yet synchronised)
+PGO_DEV double pgo_dot_tree(double* red) {
   __syncthreads();
   for (int h = PGO_SOLVE_THREADS / 2; h > 0; h >>= 1) {
     if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
@@ -387,134 +399,203 @@ PGO_DEV double pgo_dot(const double* a, const double* b, int n, double* red) {
   return v;
 }
 
+PGO_DEV double pgo_dot(const double* a, const double* b, int n, double* red) {
+  red[threadIdx.x] = pgo_dot_lane(a, b, n, threadIdx.x);
+  return pgo_dot_tree(red);
+}
+
+// level 0, element q of M x 36: the damped diagonal and the chain; identity blocks beyond N
+PGO_DEV void pgo_fill_elem(const SolveArgs& S, int q) {
+  const int k = q / 36, e = q % 36;
+  const double I = (e % 7 == 0) ? 1.0 : 0.0;
+  S.LD[q] = k < S.N ? S.diag[q] + S.lambda * I : I;
+  S.LU[q] = k + 1 < S.N ? S.chain[q] : 0.0;
+}
+
+// the right-hand side of level 0, element q of M x 6: src, zero beyond N
+PGO_DEV void pgo_rhs_elem(const SolveArgs& S, const double* src, int q) { S.B[q] = q < 6 * S.N ? src[q] : 0.0; }
+
+// the down sweep, element q of the nn x 6 of the level above `off`: the odd unknowns of this level leave
+PGO_DEV void pgo_down_elem(const SolveArgs& S, int off, int noff, int q) {
+  const int m = q / 6, r = q % 6;
+  double acc = S.B[6 * (size_t)(off + 2 * m) + r];
+  {
+    const double* U = S.LU + 36 * (size_t)(off + 2 * m);
+    const double* W = S.LW + 36 * (size_t)(off + 2 * m + 1);
+    const double* b = S.B + 6 * (size_t)(off + 2 * m + 1);
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+      double y = 0;
+#pragma unroll
+      for (int d = 0; d < 6; d++) y += W[6 * c + d] * b[d];
+      acc -= U[6 * r + c] * y;
+    }
+  }
+  if (m > 0) {
+    const double* U = S.LU + 36 * (size_t)(off + 2 * m - 1);
+    const double* W = S.LW + 36 * (size_t)(off + 2 * m - 1);
+    const double* b = S.B + 6 * (size_t)(off + 2 * m - 1);
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+      double y = 0;
+#pragma unroll
+      for (int d = 0; d < 6; d++) y += W[6 * c + d] * b[d];
+      acc -= U[6 * c + r] * y;
+    }
+  }
+  S.B[6 * (size_t)(noff + m) + r] = acc;
+}
+
+// the top level's one block at `off`, row r
+PGO_DEV void pgo_top_elem(const SolveArgs& S, int off, int r) {
+  const double* W = S.LW + 36 * (size_t)off;
+  double s = 0;
+#pragma unroll
+  for (int c = 0; c < 6; c++) s += W[6 * r + c] * S.B[6 * (size_t)off + c];
+  S.X[6 * (size_t)off + r] = s;
+}
+
+// the up sweep, element q of the level's n x 6: the even unknowns come from the level above, the odd ones from their two neighbours
+PGO_DEV void pgo_up_elem(const SolveArgs& S, int off, int noff, int nn, int q) {
+  const int k = q / 6, r = q % 6;
+  double out;
+  if ((k & 1) == 0) out = S.X[6 * (size_t)(noff + (k >> 1)) + r];
+  else {
+    const int m = k >> 1;
+    const double* Um = S.LU + 36 * (size_t)(off + k - 1);
+    const double* Uk = S.LU + 36 * (size_t)(off + k);
+    const double* W = S.LW + 36 * (size_t)(off + k);
+    const double* xl = S.X + 6 * (size_t)(noff + m);
+    const double* xr = S.X + 6 * (size_t)(noff + m + 1);
+    const bool have_r = m + 1 < nn;
+    out = 0;
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+      double t = S.B[6 * (size_t)(off + k) + c];
+#pragma unroll
+      for (int a = 0; a < 6; a++) t -= Um[6 * a + c] * xl[a];
+      if (have_r) {
+#pragma unroll
+        for (int a = 0; a < 6; a++) t -= Uk[6 * c + a] * xr[a];
+      }
+      out += W[6 * r + c] * t;
+    }
+  }
+  S.X[6 * (size_t)(off + k) + r] = out;
+}
+
+// where level l starts among the (2M) stored blocks; it has M >> l blocks, and level l + 1 starts right behind it
+PGO_DEV int pgo_level_off(const SolveArgs& S, int l) { return 2 * S.M - ((2 * S.M) >> l); }
+
 // dst = T^-1 src through the stored levels; every thread of the workgroup calls it
 PGO_DEV void pgo_apply(const SolveArgs& S, const double* src, double* dst) {
   const int tid = threadIdx.x, n6 = 6 * S.N;
-  for (int q = tid; q < 6 * S.M; q += PGO_SOLVE_THREADS) S.B[q] = q < n6 ? src[q] : 0.0;
+  for (int q = tid; q < 6 * S.M; q += PGO_SOLVE_THREADS) pgo_rhs_elem(S, src, q);
   __syncthreads();
-  for (int l = 0; l < S.L; l++) {   // down: the odd unknowns of level l leave
-    const int off = 2 * S.M - ((2 * S.M) >> l), n = S.M >> l, noff = off + n, nn = n >> 1;
-    for (int q = tid; q < 6 * nn; q += PGO_SOLVE_THREADS) {
-      const int m = q / 6, r = q % 6;
-      double acc = S.B[6 * (size_t)(off + 2 * m) + r];
-      {
-        const double* U = S.LU + 36 * (size_t)(off + 2 * m);
-        const double* W = S.LW + 36 * (size_t)(off + 2 * m + 1);
-        const double* b = S.B + 6 * (size_t)(off + 2 * m + 1);
-#pragma unroll
-        for (int c = 0; c < 6; c++) {
-          double y = 0;
-#pragma unroll
-          for (int d = 0; d < 6; d++) y += W[6 * c + d] * b[d];
-          acc -= U[6 * r + c] * y;
-        }
-      }
-      if (m > 0) {
-        const double* U = S.LU + 36 * (size_t)(off + 2 * m - 1);
-        const double* W = S.LW + 36 * (size_t)(off + 2 * m - 1);
-        const double* b = S.B + 6 * (size_t)(off + 2 * m - 1);
-#pragma unroll
-        for (int c = 0; c < 6; c++) {
-          double y = 0;
-#pragma unroll
-          for (int d = 0; d < 6; d++) y += W[6 * c + d] * b[d];
-          acc -= U[6 * c + r] * y;
-        }
-      }
-      S.B[6 * (size_t)(noff + m) + r] = acc;
-    }
+  for (int l = 0; l < S.L; l++) {
+    const int off = pgo_level_off(S, l), n = S.M >> l, noff = off + n, nn = n >> 1;
+    for (int q = tid; q < 6 * nn; q += PGO_SOLVE_THREADS) pgo_down_elem(S, off, noff, q);
     __syncthreads();
   }
-  {
-    const int off = 2 * S.M - ((2 * S.M) >> S.L);   // the top level: one block
-    for (int r = tid; r < 6; r += PGO_SOLVE_THREADS) {
-      const double* W = S.LW + 36 * (size_t)off;
-      double s = 0;
-#pragma unroll
-      for (int c = 0; c < 6; c++) s += W[6 * r + c] * S.B[6 * (size_t)off + c];
-      S.X[6 * (size_t)off + r] = s;
-    }
-    __syncthreads();
-  }
-  for (int l = S.L - 1; l >= 0; l--) {   // up: the even unknowns come from the level above, the odd ones from their two neighbours
-    const int off = 2 * S.M - ((2 * S.M) >> l), n = S.M >> l, noff = off + n, nn = n >> 1;
-    for (int q = tid; q < 6 * n; q += PGO_SOLVE_THREADS) {
-      const int k = q / 6, r = q % 6;
-      double out;
-      if ((k & 1) == 0) out = S.X[6 * (size_t)(noff + (k >> 1)) + r];
-      else {
-        const int m = k >> 1;
-        const double* Um = S.LU + 36 * (size_t)(off + k - 1);
-        const double* Uk = S.LU + 36 * (size_t)(off + k);
-        const double* W = S.LW + 36 * (size_t)(off + k);
-        const double* xl = S.X + 6 * (size_t)(noff + m);
-        const double* xr = S.X + 6 * (size_t)(noff + m + 1);
-        const bool have_r = m + 1 < nn;
-        out = 0;
-#pragma unroll
-        for (int c = 0; c < 6; c++) {
-          double t = S.B[6 * (size_t)(off + k) + c];
-#pragma unroll
-          for (int a = 0; a < 6; a++) t -= Um[6 * a + c] * xl[a];
-          if (have_r) {
-#pragma unroll
-            for (int a = 0; a < 6; a++) t -= Uk[6 * c + a] * xr[a];
-          }
-          out += W[6 * r + c] * t;
-        }
-      }
-      S.X[6 * (size_t)(off + k) + r] = out;
-    }
+  for (int r = tid; r < 6; r += PGO_SOLVE_THREADS) pgo_top_elem(S, pgo_level_off(S, S.L), r);
+  __syncthreads();
+  for (int l = S.L - 1; l >= 0; l--) {
+    const int off = pgo_level_off(S, l), n = S.M >> l, noff = off + n, nn = n >> 1;
+    for (int q = tid; q < 6 * n; q += PGO_SOLVE_THREADS) pgo_up_elem(S, off, noff, nn, q);
     __syncthreads();
   }
   for (int q = tid; q < n6; q += PGO_SOLVE_THREADS) dst[q] = S.X[q];
   __syncthreads();
 }
 
-// q = (H + lambda I) p: the block-tridiagonal part from level 0, the chords through their scratch rows, gathered per pose in chord order
+// q = (H + lambda I) p in three bodies: a row of the block-tridiagonal part from level 0, a chord's row into its scratch, the gather per pose in chord order
+PGO_DEV void pgo_mv_tri_elem(const SolveArgs& S, const double* p, double* q, int u) {
+  const int k = u / 6, r = u % 6;
+  const double* D = S.LD + 36 * (size_t)k;
+  double s = 0;
+#pragma unroll
+  for (int c = 0; c < 6; c++) s += D[6 * r + c] * p[6 * (size_t)k + c];
+  if (k + 1 < S.N) {
+    const double* U = S.LU + 36 * (size_t)k;
+#pragma unroll
+    for (int c = 0; c < 6; c++) s += U[6 * r + c] * p[6 * (size_t)(k + 1) + c];
+  }
+  if (k > 0) {
+    const double* U = S.LU + 36 * (size_t)(k - 1);
+#pragma unroll
+    for (int c = 0; c < 6; c++) s += U[6 * c + r] * p[6 * (size_t)(k - 1) + c];
+  }
+  q[u] = s;
+}
+
+PGO_DEV void pgo_mv_chord_elem(const SolveArgs& S, const double* p, int u) {
+  const int ch = u / 12, side = (u % 12) / 6, r = u % 6;
+  const double* H = S.chordH + 36 * (size_t)ch;
+  const int i = S.chord_ij[2 * ch], j = S.chord_ij[2 * ch + 1];
+  double s = 0;
+  if (side == 0) {   // row i: H p_j
+#pragma unroll
+    for (int a = 0; a < 6; a++) s += H[6 * r + a] * p[6 * (size_t)j + a];
+  } else {           // row j: H^T p_i
+#pragma unroll
+    for (int a = 0; a < 6; a++) s += H[6 * a + r] * p[6 * (size_t)i + a];
+  }
+  S.cscr[u] = s;
+}
+
+PGO_DEV void pgo_mv_gather_elem(const SolveArgs& S, double* q, int u) {
+  const int t = u / 6, r = u % 6;
+  double s = q[6 * (size_t)S.touched[t] + r];
+  for (int e = S.touched_ptr[t]; e < S.touched_ptr[t + 1]; e++) { const int ent = S.touched_ent[e]; s += S.cscr[12 * (size_t)(ent >> 1) + 6 * (ent & 1) + r]; }
+  q[6 * (size_t)S.touched[t] + r] = s;
+}
+
 PGO_DEV void pgo_matvec(const SolveArgs& S, const double* p, double* q) {
   const int tid = threadIdx.x;
-  for (int u = tid; u < 6 * S.N; u += PGO_SOLVE_THREADS) {
-    const int k = u / 6, r = u % 6;
-    const double* D = S.LD + 36 * (size_t)k;
-    double s = 0;
-#pragma unroll
-    for (int c = 0; c < 6; c++) s += D[6 * r + c] * p[6 * (size_t)k + c];
-    if (k + 1 < S.N) {
-      const double* U = S.LU + 36 * (size_t)k;
-#pragma unroll
-      for (int c = 0; c < 6; c++) s += U[6 * r + c] * p[6 * (size_t)(k + 1) + c];
-    }
-    if (k > 0) {
-      const double* U = S.LU + 36 * (size_t)(k - 1);
-#pragma unroll
-      for (int c = 0; c < 6; c++) s += U[6 * c + r] * p[6 * (size_t)(k - 1) + c];
-    }
-    q[u] = s;
-  }
-  for (int u = tid; u < 12 * S.n_chords; u += PGO_SOLVE_THREADS) {
-    const int ch = u / 12, side = (u % 12) / 6, r = u % 6;
-    const double* H = S.chordH + 36 * (size_t)ch;
-    const int i = S.chord_ij[2 * ch], j = S.chord_ij[2 * ch + 1];
-    double s = 0;
-    if (side == 0) {   // row i: H p_j
-#pragma unroll
-      for (int a = 0; a < 6; a++) s += H[6 * r + a] * p[6 * (size_t)j + a];
-    } else {           // row j: H^T p_i
-#pragma unroll
-      for (int a = 0; a < 6; a++) s += H[6 * a + r] * p[6 * (size_t)i + a];
-    }
-    S.cscr[u] = s;
-  }
+  for (int u = tid; u < 6 * S.N; u += PGO_SOLVE_THREADS) pgo_mv_tri_elem(S, p, q, u);
+  for (int u = tid; u < 12 * S.n_chords; u += PGO_SOLVE_THREADS) pgo_mv_chord_elem(S, p, u);
   __syncthreads();
-  for (int u = tid; u < 6 * S.n_touched; u += PGO_SOLVE_THREADS) {
-    const int t = u / 6, r = u % 6;
-    double s = q[6 * (size_t)S.touched[t] + r];
-    for (int e = S.touched_ptr[t]; e < S.touched_ptr[t + 1]; e++) { const int ent = S.touched_ent[e]; s += S.cscr[12 * (size_t)(ent >> 1) + 6 * (ent & 1) + r]; }
-    q[6 * (size_t)S.touched[t] + r] = s;
-  }
+  for (int u = tid; u < 6 * S.n_touched; u += PGO_SOLVE_THREADS) pgo_mv_gather_elem(S, q, u);
   __syncthreads();
 }
+
+// the factorisation's step from level `off` to the next, element q of nn x 36: LD and LU of the level above through W = inv6 of this level's odd blocks
+PGO_DEV void pgo_reduce_elem(const SolveArgs& S, int off, int noff, int q) {
+  const int m = q / 36, e = q % 36, r = e / 6, c = e % 6;
+  const double* U = S.LU + 36 * (size_t)(off + 2 * m);
+  const double* W = S.LW + 36 * (size_t)(off + 2 * m + 1);
+  const double* U2 = S.LU + 36 * (size_t)(off + 2 * m + 1);
+  double d = S.LD[36 * (size_t)(off + 2 * m) + e], u = 0;
+#pragma unroll
+  for (int a = 0; a < 6; a++) {
+    double wd = 0, wu = 0;
+#pragma unroll
+    for (int b = 0; b < 6; b++) { wd += W[6 * a + b] * U[6 * c + b]; wu += W[6 * a + b] * U2[6 * b + c]; }
+    d -= U[6 * r + a] * wd;   // - U W U^T
+    u -= U[6 * r + a] * wu;   // - U W U'
+  }
+  if (m > 0) {
+    const double* Um = S.LU + 36 * (size_t)(off + 2 * m - 1);
+    const double* Wm = S.LW + 36 * (size_t)(off + 2 * m - 1);
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+      double wd = 0;
+#pragma unroll
+      for (int b = 0; b < 6; b++) wd += Wm[6 * a + b] * Um[6 * b + c];
+      d -= Um[6 * a + r] * wd;   // - U^T W U of the block before
+    }
+  }
+  S.LD[36 * (size_t)(noff + m) + e] = d;
+  S.LU[36 * (size_t)(noff + m) + e] = u;
+}
+
+// W of odd block m of the level at `off`; false: not positive definite
+PGO_DEV bool pgo_inv_elem(const SolveArgs& S, int off, int m) { return inv6(S.LD + 36 * (size_t)(off + 2 * m + 1), S.LW + 36 * (size_t)(off + 2 * m + 1)); }
+
+// the vector updates of PCG, element q of 6N
+PGO_DEV void pgo_start_elem(const SolveArgs& S, int q) { S.x[q] = 0.0; S.r[q] = -S.grad[q]; }
+PGO_DEV void pgo_step_elem(const SolveArgs& S, double a, int q) { S.x[q] += a * S.p[q]; S.r[q] -= a * S.q[q]; }
+PGO_DEV void pgo_dir_elem(const SolveArgs& S, double beta, int q) { S.p[q] = S.z[q] + beta * S.p[q]; }
 
 __global__ __launch_bounds__(PGO_SOLVE_THREADS) void pgo_solve_kernel(SolveArgs S) {
   __shared__ double red[PGO_SOLVE_THREADS];
@@ -522,54 +603,22 @@ __global__ __launch_bounds__(PGO_SOLVE_THREADS) void pgo_solve_kernel(SolveArgs 
   const int tid = threadIdx.x, n6 = 6 * S.N;
   const long long t0 = wall_clock64();
   if (tid == 0) bad = 0;
-  for (int q = tid; q < 36 * S.M; q += PGO_SOLVE_THREADS) {   // level 0: the damped diagonal and the chain; identity blocks beyond N
-    const int k = q / 36, e = q % 36;
-    const double I = (e % 7 == 0) ? 1.0 : 0.0;
-    S.LD[q] = k < S.N ? S.diag[q] + S.lambda * I : I;
-    S.LU[q] = k + 1 < S.N ? S.chain[q] : 0.0;
-  }
+  for (int q = tid; q < 36 * S.M; q += PGO_SOLVE_THREADS) pgo_fill_elem(S, q);
   __syncthreads();
   for (int l = 0; l < S.L; l++) {
-    const int off = 2 * S.M - ((2 * S.M) >> l), n = S.M >> l, noff = off + n, nn = n >> 1;
+    const int off = pgo_level_off(S, l), n = S.M >> l, noff = off + n, nn = n >> 1;
     for (int m = tid; m < nn; m += PGO_SOLVE_THREADS)
-      if (!inv6(S.LD + 36 * (size_t)(off + 2 * m + 1), S.LW + 36 * (size_t)(off + 2 * m + 1))) bad = 1;
+      if (!pgo_inv_elem(S, off, m)) bad = 1;
     __syncthreads();
-    for (int q = tid; q < 36 * nn; q += PGO_SOLVE_THREADS) {
-      const int m = q / 36, e = q % 36, r = e / 6, c = e % 6;
-      const double* U = S.LU + 36 * (size_t)(off + 2 * m);
-      const double* W = S.LW + 36 * (size_t)(off + 2 * m + 1);
-      const double* U2 = S.LU + 36 * (size_t)(off + 2 * m + 1);
-      double d = S.LD[36 * (size_t)(off + 2 * m) + e], u = 0;
-#pragma unroll
-      for (int a = 0; a < 6; a++) {
-        double wd = 0, wu = 0;
-#pragma unroll
-        for (int b = 0; b < 6; b++) { wd += W[6 * a + b] * U[6 * c + b]; wu += W[6 * a + b] * U2[6 * b + c]; }
-        d -= U[6 * r + a] * wd;   // - U W U^T
-        u -= U[6 * r + a] * wu;   // - U W U'
-      }
-      if (m > 0) {
-        const double* Um = S.LU + 36 * (size_t)(off + 2 * m - 1);
-        const double* Wm = S.LW + 36 * (size_t)(off + 2 * m - 1);
-#pragma unroll
-        for (int a = 0; a < 6; a++) {
-          double wd = 0;
-#pragma unroll
-          for (int b = 0; b < 6; b++) wd += Wm[6 * a + b] * Um[6 * b + c];
-          d -= Um[6 * a + r] * wd;   // - U^T W U of the block before
-        }
-      }
-      S.LD[36 * (size_t)(noff + m) + e] = d;
-      S.LU[36 * (size_t)(noff + m) + e] = u;
-    }
+    for (int q = tid; q < 36 * nn; q += PGO_SOLVE_THREADS) pgo_reduce_elem(S, off, noff, q);
     __syncthreads();
   }
-  if (tid == 0) { const int off = 2 * S.M - ((2 * S.M) >> S.L); if (!inv6(S.LD + 36 * (size_t)off, S.LW + 36 * (size_t)off)) bad = 1; }
+  if (tid == 0) { const int off = pgo_level_off(S, S.L); if (!inv6(S.LD + 36 * (size_t)off, S.LW + 36 * (size_t)off)) bad = 1; }
   __syncthreads();
   const long long t1 = wall_clock64();
   int iters = 0;
   double residual = 0.0;
-  for (int q = tid; q < n6; q += PGO_SOLVE_THREADS) { S.x[q] = 0.0; S.r[q] = -S.grad[q]; }
+  for (int q = tid; q < n6; q += PGO_SOLVE_THREADS) pgo_start_elem(S, q);
   __syncthreads();
   if (!bad) {
     pgo_apply(S, S.r, S.z);
@@ -584,14 +633,14 @@ __global__ __launch_bounds__(PGO_SOLVE_THREADS) void pgo_solve_kernel(SolveArgs 
         if (!(pq > 0.0)) break;
         iters = it;
         const double a = rz / pq;
-        for (int q = tid; q < n6; q += PGO_SOLVE_THREADS) { S.x[q] += a * S.p[q]; S.r[q] -= a * S.q[q]; }
+        for (int q = tid; q < n6; q += PGO_SOLVE_THREADS) pgo_step_elem(S, a, q);
         __syncthreads();
         pgo_apply(S, S.r, S.z);
         const double rzn = pgo_dot(S.r, S.z, n6, red);
         if (!(rzn > 0.0)) { rz = 0.0; break; }
         const bool done = sqrt(rzn) <= S.tol * sqrt(rz0);
         const double beta = rzn / rz;
-        for (int q = tid; q < n6; q += PGO_SOLVE_THREADS) S.p[q] = S.z[q] + beta * S.p[q];
+        for (int q = tid; q < n6; q += PGO_SOLVE_THREADS) pgo_dir_elem(S, beta, q);
         __syncthreads();
         rz = rzn;
         if (done) break;
@@ -603,6 +652,178 @@ __global__ __launch_bounds__(PGO_SOLVE_THREADS) void pgo_solve_kernel(SolveArgs 
   if (tid == 0) {
     S.info[0] = (double)iters; S.info[1] = residual; S.info[2] = bad ? 1.0 : 0.0;
     S.info[3] = (double)(t1 - t0); S.info[4] = (double)(wall_clock64() - t1);
+  }
+}
+
+// ---- the grid form: the same bodies, one launch per seam ---------------------------------------------------------------------------------------
+// A seam is where every element of a stage may read what any thread of the stage before wrote: between two levels of the reduction, between a sweep and a dot
+// product, between a dot product and the update that uses it. Each seam is the end of a launch: no workgroup ever waits for another, so nothing here can hang.
+// A level of at most PGO_GRID_TOP blocks is finished, together with every level above it, by ONE workgroup (the loop of pgo_solve_kernel on the top of the
+// tree). PCG's scalars live in S.st; every launch of the loop returns at once when PGO_ST_DONE is set, so iterations enqueued past the exit change nothing.
+constexpr int PGO_GRID_THREADS = 256;
+constexpr int PGO_GRID_TOP = 256;      // blocks: at 1 024 threads the fused top has at most one element of the down sweep and two of the up sweep per thread and level
+constexpr int PGO_GRID_TILE = 32;      // blocks of the NEXT level that one workgroup of a level's launch makes, from 64 blocks of its own
+constexpr int PGO_GRID_LANE_WG = 64;   // the 1 024 lane sums of a dot product go over 16 workgroups
+constexpr int PGO_GRID_BATCH = 4;      // PCG iterations enqueued between two looks at the pinned done word
+// rolo_pgo's AUTO: the grid form from this many poses on. The smallest size of profiles/r14/posegraph_grid.json from which the grid form beat the one-workgroup
+// form at 1, 10 and 100 loops and in the per-key-frame call by more than the spread of the repeats (slower up to 256 poses, faster from 512 on)
+constexpr int PGO_GRID_FROM = 512;
+enum { PGO_ST_RZ, PGO_ST_RZ0, PGO_ST_PQ, PGO_ST_ALPHA, PGO_ST_BETA, PGO_ST_ITERS, PGO_ST_BAD, PGO_ST_DONE, PGO_ST_WORDS };
+enum { PGO_DOT_RZ0, PGO_DOT_PQ, PGO_DOT_RZ };
+
+PGO_DEV bool pgo_grid_stop(const SolveArgs& S) { return S.st[PGO_ST_DONE] != 0.0; }
+
+__global__ __launch_bounds__(PGO_GRID_THREADS) void pgo_grid_fill_kernel(SolveArgs S) {
+  const int q = blockIdx.x * PGO_GRID_THREADS + threadIdx.x;
+  if (q < PGO_ST_WORDS) S.st[q] = 0.0;
+  if (q == 0) S.done[0] = 0.0;
+  if (q < 36 * S.M) pgo_fill_elem(S, q);
+}
+
+__global__ __launch_bounds__(64) void pgo_grid_inv_kernel(SolveArgs S, int l) {
+  const int off = pgo_level_off(S, l), nn = S.M >> (l + 1), m = blockIdx.x * 64 + threadIdx.x;
+  if (m < nn && !pgo_inv_elem(S, off, m)) S.st[PGO_ST_BAD] = 1.0;
+}
+
+__global__ __launch_bounds__(PGO_GRID_THREADS) void pgo_grid_reduce_kernel(SolveArgs S, int l) {
+  const int off = pgo_level_off(S, l), n = S.M >> l, noff = off + n, nn = n >> 1;
+  for (int e = threadIdx.x; e < 36 * PGO_GRID_TILE; e += PGO_GRID_THREADS) {
+    const int q = blockIdx.x * 36 * PGO_GRID_TILE + e;
+    if (q < 36 * nn) pgo_reduce_elem(S, off, noff, q);
+  }
+}
+
+// levels l0 .. L of the factorisation: pgo_solve_kernel's loop from l0 on
+__global__ __launch_bounds__(PGO_SOLVE_THREADS) void pgo_grid_top_factor_kernel(SolveArgs S, int l0) {
+  const int tid = threadIdx.x;
+  for (int l = l0; l < S.L; l++) {
+    const int off = pgo_level_off(S, l), n = S.M >> l, noff = off + n, nn = n >> 1;
+    for (int m = tid; m < nn; m += PGO_SOLVE_THREADS)
+      if (!pgo_inv_elem(S, off, m)) S.st[PGO_ST_BAD] = 1.0;
+    __syncthreads();
+    for (int q = tid; q < 36 * nn; q += PGO_SOLVE_THREADS) pgo_reduce_elem(S, off, noff, q);
+    __syncthreads();
+  }
+  if (tid == 0) { const int off = pgo_level_off(S, S.L); if (!inv6(S.LD + 36 * (size_t)off, S.LW + 36 * (size_t)off)) S.st[PGO_ST_BAD] = 1.0; }
+}
+
+// x = 0, r = -g and the first right-hand side; a factorisation that was not positive definite ends the loop before it starts
+__global__ __launch_bounds__(PGO_GRID_THREADS) void pgo_grid_start_kernel(SolveArgs S) {
+  const int q = blockIdx.x * PGO_GRID_THREADS + threadIdx.x;
+  if (q == 0 && S.st[PGO_ST_BAD] != 0.0) { S.st[PGO_ST_DONE] = 1.0; S.done[0] = 1.0; }
+  if (q < 6 * S.N) pgo_start_elem(S, q);
+  if (q < 6 * S.M) pgo_rhs_elem(S, S.r, q);
+}
+
+__global__ __launch_bounds__(PGO_GRID_THREADS) void pgo_grid_down_kernel(SolveArgs S, int l) {
+  if (pgo_grid_stop(S)) return;
+  const int off = pgo_level_off(S, l), n = S.M >> l, noff = off + n, nn = n >> 1;
+  for (int e = threadIdx.x; e < 6 * PGO_GRID_TILE; e += PGO_GRID_THREADS) {
+    const int q = blockIdx.x * 6 * PGO_GRID_TILE + e;
+    if (q < 6 * nn) pgo_down_elem(S, off, noff, q);
+  }
+}
+
+// levels l0 .. L down, the top block, levels L - 1 .. l0 up: pgo_apply's loops from l0 on. dst is written where level 0 is among them
+__global__ __launch_bounds__(PGO_SOLVE_THREADS) void pgo_grid_top_apply_kernel(SolveArgs S, int l0, double* dst) {
+  if (pgo_grid_stop(S)) return;
+  const int tid = threadIdx.x;
+  for (int l = l0; l < S.L; l++) {
+    const int off = pgo_level_off(S, l), n = S.M >> l, noff = off + n, nn = n >> 1;
+    for (int q = tid; q < 6 * nn; q += PGO_SOLVE_THREADS) pgo_down_elem(S, off, noff, q);
+    __syncthreads();
+  }
+  for (int r = tid; r < 6; r += PGO_SOLVE_THREADS) pgo_top_elem(S, pgo_level_off(S, S.L), r);
+  __syncthreads();
+  for (int l = S.L - 1; l >= l0; l--) {
+    const int off = pgo_level_off(S, l), n = S.M >> l, noff = off + n, nn = n >> 1;
+    for (int q = tid; q < 6 * n; q += PGO_SOLVE_THREADS) pgo_up_elem(S, off, noff, nn, q);
+    __syncthreads();
+  }
+  if (l0 == 0)
+    for (int q = tid; q < 6 * S.N; q += PGO_SOLVE_THREADS) dst[q] = S.X[q];
+}
+
+// one level of the up sweep; level 0 also hands the solution to dst (level 0 starts at block 0: X's index there is q)
+__global__ __launch_bounds__(PGO_GRID_THREADS) void pgo_grid_up_kernel(SolveArgs S, int l, double* dst) {
+  if (pgo_grid_stop(S)) return;
+  const int off = pgo_level_off(S, l), n = S.M >> l, noff = off + n, nn = n >> 1;
+  for (int e = threadIdx.x; e < 12 * PGO_GRID_TILE; e += PGO_GRID_THREADS) {
+    const int q = blockIdx.x * 12 * PGO_GRID_TILE + e;
+    if (q < 6 * n) {
+      pgo_up_elem(S, off, noff, nn, q);
+      if (l == 0 && q < 6 * S.N) dst[q] = S.X[q];
+    }
+  }
+}
+
+__global__ __launch_bounds__(PGO_GRID_THREADS) void pgo_grid_mv_kernel(SolveArgs S) {
+  if (pgo_grid_stop(S)) return;
+  const int u = blockIdx.x * PGO_GRID_THREADS + threadIdx.x;
+  if (u < 6 * S.N) pgo_mv_tri_elem(S, S.p, S.q, u);
+  if (u < 12 * S.n_chords) pgo_mv_chord_elem(S, S.p, u);
+}
+
+__global__ __launch_bounds__(PGO_GRID_THREADS) void pgo_grid_gather_kernel(SolveArgs S) {
+  if (pgo_grid_stop(S)) return;
+  const int u = blockIdx.x * PGO_GRID_THREADS + threadIdx.x;
+  if (u < 6 * S.n_touched) pgo_mv_gather_elem(S, S.q, u);
+}
+
+// the PGO_SOLVE_THREADS lane sums of a . b, PGO_GRID_LANE_WG lanes per workgroup: each lane adds what its thread of pgo_solve_kernel adds, in that order
+__global__ __launch_bounds__(PGO_GRID_LANE_WG) void pgo_grid_lanes_kernel(SolveArgs S, const double* a, const double* b) {
+  if (pgo_grid_stop(S)) return;
+  const int lane = blockIdx.x * PGO_GRID_LANE_WG + threadIdx.x;
+  S.lanes[lane] = pgo_dot_lane(a, b, 6 * S.N, lane);
+}
+
+// the tree over the lane sums, and what pgo_solve_kernel does with the value: which = PGO_DOT_RZ0 (r0 z0), PGO_DOT_PQ (p q), PGO_DOT_RZ (r z of an iteration)
+__global__ __launch_bounds__(PGO_SOLVE_THREADS) void pgo_grid_scalar_kernel(SolveArgs S, int which) {
+  __shared__ double red[PGO_SOLVE_THREADS];
+  if (pgo_grid_stop(S)) return;
+  red[threadIdx.x] = S.lanes[threadIdx.x];
+  const double v = pgo_dot_tree(red);
+  if (threadIdx.x != 0) return;
+  bool done = false;
+  if (which == PGO_DOT_RZ0) {
+    S.st[PGO_ST_RZ] = v; S.st[PGO_ST_RZ0] = v;
+    done = !(v > 0.0);
+  } else if (which == PGO_DOT_PQ) {
+    S.st[PGO_ST_PQ] = v;
+    if (!(v > 0.0)) done = true;
+    else { S.st[PGO_ST_ITERS] += 1.0; S.st[PGO_ST_ALPHA] = S.st[PGO_ST_RZ] / v; }
+  } else {
+    if (!(v > 0.0)) { S.st[PGO_ST_RZ] = 0.0; done = true; }
+    else {
+      done = sqrt(v) <= S.tol * sqrt(S.st[PGO_ST_RZ0]);
+      S.st[PGO_ST_BETA] = v / S.st[PGO_ST_RZ];
+      S.st[PGO_ST_RZ] = v;
+    }
+  }
+  if (done) { S.st[PGO_ST_DONE] = 1.0; S.done[0] = 1.0; }
+}
+
+__global__ __launch_bounds__(PGO_GRID_THREADS) void pgo_grid_step_kernel(SolveArgs S) {
+  if (pgo_grid_stop(S)) return;
+  const int q = blockIdx.x * PGO_GRID_THREADS + threadIdx.x;
+  if (q < 6 * S.N) { pgo_step_elem(S, S.st[PGO_ST_ALPHA], q); pgo_rhs_elem(S, S.r, q); }
+}
+
+// first: p = z; later: p = z + beta p (after the exit of the loop p is read by nobody, so the launch may return with the others)
+__global__ __launch_bounds__(PGO_GRID_THREADS) void pgo_grid_dir_kernel(SolveArgs S, int first) {
+  if (pgo_grid_stop(S)) return;
+  const int q = blockIdx.x * PGO_GRID_THREADS + threadIdx.x;
+  if (q >= 6 * S.N) return;
+  if (first) S.p[q] = S.z[q];
+  else pgo_dir_elem(S, S.st[PGO_ST_BETA], q);
+}
+
+__global__ __launch_bounds__(PGO_GRID_THREADS) void pgo_grid_finish_kernel(SolveArgs S) {
+  const int q = blockIdx.x * PGO_GRID_THREADS + threadIdx.x;
+  if (q < 6 * S.N) S.delta[q] = S.x[q];
+  if (q == 0) {
+    const double rz0 = S.st[PGO_ST_RZ0];
+    S.info[0] = S.st[PGO_ST_ITERS]; S.info[1] = rz0 > 0.0 ? sqrt(S.st[PGO_ST_RZ]) / sqrt(rz0) : 0.0; S.info[2] = S.st[PGO_ST_BAD] != 0.0 ? 1.0 : 0.0;
   }
 }
 
@@ -641,7 +862,10 @@ struct rolo_pgo {
   double* vec[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; size_t vec_cap[5] = {0, 0, 0, 0, 0};
   double *cscr = nullptr, *delta = nullptr, *partials = nullptr; size_t cscr_cap = 0, delta_cap = 0, partials_cap = 0;
   double* ferr = nullptr; size_t ferr_cap = 0;   // rolo_pgo_get_factor_errors: F x r^2, then F x w
-  double* h_info = nullptr;                // pinned: [0] cost, [1..5] the solve's info
+  double* gst = nullptr; size_t gst_cap = 0;   // the grid form's PGO_ST_WORDS scalars, then its PGO_SOLVE_THREADS lane sums
+  int solve_form = ROLO_PGO_SOLVE_AUTO, last_form = 0;
+  hipEvent_t gev[3] = {nullptr, nullptr, nullptr};   // the grid form: before the factorisation, between it and PCG, after PCG
+  double* h_info = nullptr;                // pinned: [0] cost, [1..5] the solve's info, [6] the grid form's done word
   std::vector<void*> retired;
   float ms[4] = {0.f, 0.f, 0.f, 0.f};
   std::vector<rolo_pgo_trace_rec> trace;
@@ -733,6 +957,7 @@ int pgo_sync_graph(rolo_pgo* g) {
   if ((rc = pgo_grow(g, g->LW, g->LW_cap, 72 * (size_t)M))) return rc;
   if ((rc = pgo_grow(g, g->B, g->B_cap, 12 * (size_t)M))) return rc;
   if ((rc = pgo_grow(g, g->X, g->X_cap, 12 * (size_t)M))) return rc;
+  if ((rc = pgo_grow(g, g->gst, g->gst_cap, (size_t)PGO_ST_WORDS + PGO_SOLVE_THREADS))) return rc;
   if ((rc = pgo_grow(g, g->partials, g->partials_cap, (size_t)(std::max(N, F) + PGO_FACTOR_THREADS - 1) / PGO_FACTOR_THREADS + 1))) return rc;
   PCHK(hipStreamSynchronize(s));   // the host vectors are free again
   g->pending.clear();
@@ -759,6 +984,74 @@ int pgo_cap(int n_chords, int pcg_max) {
   return n_chords ? std::min(12 * n_chords + 2, 1000) : 1;   // without chords the preconditioner is the matrix: one application is the solve
 }
 
+// the grid form of the solve on the graph's stream. The host enqueues PCG iterations PGO_GRID_BATCH at a time and reads the pinned done word once after each
+// batch; the iterations of a batch that follow the exit are empty launches. Never more than pcg_cap iterations are enqueued: the cap is the host's count
+int pgo_enqueue_solve_grid(rolo_pgo* g, const SolveArgs& S) {
+  hipStream_t s = g->stream;
+  const int T = PGO_GRID_THREADS;
+  const auto blocks = [](int n, int per) { return (n + per - 1) / per; };
+  int l0 = 0;   // the first level that the fused top takes
+  while ((S.M >> l0) > PGO_GRID_TOP) l0++;
+  const auto apply = [&](double* dst) -> int {   // dst = T^-1 (the right-hand side in B)
+    for (int l = 0; l < l0; l++) { pgo_grid_down_kernel<<<blocks(S.M >> (l + 1), PGO_GRID_TILE), T, 0, s>>>(S, l); PCHK(hipGetLastError()); }
+    pgo_grid_top_apply_kernel<<<1, PGO_SOLVE_THREADS, 0, s>>>(S, l0, dst);
+    PCHK(hipGetLastError());
+    for (int l = l0 - 1; l >= 0; l--) { pgo_grid_up_kernel<<<blocks(S.M >> (l + 1), PGO_GRID_TILE), T, 0, s>>>(S, l, dst); PCHK(hipGetLastError()); }
+    return ROLO_OK;
+  };
+  const auto dot = [&](const double* a, const double* b, int which) -> int {
+    pgo_grid_lanes_kernel<<<PGO_SOLVE_THREADS / PGO_GRID_LANE_WG, PGO_GRID_LANE_WG, 0, s>>>(S, a, b);
+    PCHK(hipGetLastError());
+    pgo_grid_scalar_kernel<<<1, PGO_SOLVE_THREADS, 0, s>>>(S, which);
+    PCHK(hipGetLastError());
+    return ROLO_OK;
+  };
+  int rc;
+  PCHK(hipEventRecord(g->gev[0], s));
+  pgo_grid_fill_kernel<<<blocks(36 * S.M, T), T, 0, s>>>(S);
+  PCHK(hipGetLastError());
+  for (int l = 0; l < l0; l++) {
+    const int nn = S.M >> (l + 1);
+    pgo_grid_inv_kernel<<<blocks(nn, 64), 64, 0, s>>>(S, l);
+    PCHK(hipGetLastError());
+    pgo_grid_reduce_kernel<<<blocks(nn, PGO_GRID_TILE), T, 0, s>>>(S, l);
+    PCHK(hipGetLastError());
+  }
+  pgo_grid_top_factor_kernel<<<1, PGO_SOLVE_THREADS, 0, s>>>(S, l0);
+  PCHK(hipGetLastError());
+  PCHK(hipEventRecord(g->gev[1], s));
+  pgo_grid_start_kernel<<<blocks(6 * S.M, T), T, 0, s>>>(S);
+  PCHK(hipGetLastError());
+  if ((rc = apply(S.z))) return rc;
+  if ((rc = dot(S.r, S.z, PGO_DOT_RZ0))) return rc;
+  pgo_grid_dir_kernel<<<blocks(6 * S.N, T), T, 0, s>>>(S, 1);
+  PCHK(hipGetLastError());
+  for (int it = 0; it < S.pcg_cap;) {
+    const int batch = std::min(PGO_GRID_BATCH, S.pcg_cap - it);
+    for (int k = 0; k < batch; k++) {
+      pgo_grid_mv_kernel<<<blocks(std::max(6 * S.N, 12 * S.n_chords), T), T, 0, s>>>(S);
+      PCHK(hipGetLastError());
+      if (S.n_touched) { pgo_grid_gather_kernel<<<blocks(6 * S.n_touched, T), T, 0, s>>>(S); PCHK(hipGetLastError()); }
+      if ((rc = dot(S.p, S.q, PGO_DOT_PQ))) return rc;
+      pgo_grid_step_kernel<<<blocks(6 * S.N, T), T, 0, s>>>(S);
+      PCHK(hipGetLastError());
+      if ((rc = apply(S.z))) return rc;
+      if ((rc = dot(S.r, S.z, PGO_DOT_RZ))) return rc;
+      pgo_grid_dir_kernel<<<blocks(6 * S.N, T), T, 0, s>>>(S, 0);
+      PCHK(hipGetLastError());
+    }
+    it += batch;
+    if (it < S.pcg_cap) {
+      PCHK(hipStreamSynchronize(s));
+      if (*(volatile double*)S.done != 0.0) break;
+    }
+  }
+  pgo_grid_finish_kernel<<<blocks(6 * S.N, T), T, 0, s>>>(S);
+  PCHK(hipGetLastError());
+  PCHK(hipEventRecord(g->gev[2], s));
+  return ROLO_OK;
+}
+
 int pgo_enqueue_solve(rolo_pgo* g, double lambda, double tol, int pcg_max) {
   SolveArgs S{};
   S.N = g->N; S.M = 1; S.L = 0;
@@ -770,9 +1063,22 @@ int pgo_enqueue_solve(rolo_pgo* g, double lambda, double tol, int pcg_max) {
   S.LD = g->LD; S.LU = g->LU; S.LW = g->LW; S.B = g->B; S.X = g->X;
   S.x = g->vec[0]; S.r = g->vec[1]; S.z = g->vec[2]; S.p = g->vec[3]; S.q = g->vec[4]; S.cscr = g->cscr;
   S.delta = g->delta; S.info = g->h_info + 1;
+  S.st = g->gst; S.lanes = g->gst + PGO_ST_WORDS; S.done = g->h_info + 6;
+  const int form = g->solve_form != ROLO_PGO_SOLVE_AUTO ? g->solve_form : S.N >= PGO_GRID_FROM ? ROLO_PGO_SOLVE_GRID : ROLO_PGO_SOLVE_ONE_WG;
+  g->last_form = form;
+  if (form == ROLO_PGO_SOLVE_GRID) return pgo_enqueue_solve_grid(g, S);
   pgo_solve_kernel<<<1, PGO_SOLVE_THREADS, 0, g->stream>>>(S);
   PCHK(hipGetLastError());
   return ROLO_OK;
+}
+
+// device milliseconds of the last solve once the stream has been waited for: k = 0 the factorisation, 1 PCG. Between HIP events in the grid form; by the
+// device's wall clock inside the one launch of the one-workgroup form
+double pgo_solve_ms(rolo_pgo* g, int k) {
+  if (g->last_form != ROLO_PGO_SOLVE_GRID) return g->h_info[4 + k] / g->wall_khz;
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, g->gev[k], g->gev[k + 1]);
+  return (double)ms;
 }
 
 void pose6_of(const double* P, float* o) {   // pcl::getTranslationAndEulerAngles, transformTobeMapped order
@@ -813,6 +1119,7 @@ int rolo_pgo_create(int device, rolo_pgo** out) {
   int khz = 0;
   if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) g->wall_khz = (double)khz;
   if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&g->ev[0]) != hipSuccess || hipEventCreate(&g->ev[1]) != hipSuccess ||
+      hipEventCreate(&g->gev[0]) != hipSuccess || hipEventCreate(&g->gev[1]) != hipSuccess || hipEventCreate(&g->gev[2]) != hipSuccess ||
       hipHostMalloc((void**)&g->h_info, sizeof(double) * 8) != hipSuccess) {
     ctx_set_error("rolo_pgo_create: stream, events or pinned memory");
     rolo_pgo_destroy(g);
@@ -829,11 +1136,12 @@ void rolo_pgo_destroy(rolo_pgo* g) {
   for (void* p : {(void*)g->poses, (void*)g->trial, (void*)g->d_factors, (void*)g->slots, (void*)g->rowptr, (void*)g->entries, (void*)g->diag, (void*)g->chain, (void*)g->grad,
                   (void*)g->chordH, (void*)g->d_chord_factor, (void*)g->d_chord_ij, (void*)g->touched, (void*)g->touched_ptr, (void*)g->touched_ent, (void*)g->LD, (void*)g->LU,
                   (void*)g->LW, (void*)g->B, (void*)g->X, (void*)g->vec[0], (void*)g->vec[1], (void*)g->vec[2], (void*)g->vec[3], (void*)g->vec[4], (void*)g->cscr, (void*)g->delta,
-                  (void*)g->partials, (void*)g->ferr})
+                  (void*)g->partials, (void*)g->ferr, (void*)g->gst})
     if (p) (void)hipFree(p);
   for (void* p : g->retired) (void)hipFree(p);
   if (g->h_info) (void)hipHostFree(g->h_info);
   for (hipEvent_t e : g->ev) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : g->gev) if (e) (void)hipEventDestroy(e);
   if (g->stream) (void)hipStreamDestroy(g->stream);
   delete g;
 }
@@ -984,7 +1292,7 @@ int rolo_pgo_optimize(rolo_pgo* g, const rolo_pgo_params* P, rolo_pgo_result* ou
     PCHK(hipEventRecord(g->ev[1], s));
     PCHK(hipEventSynchronize(g->ev[1]));
     (void)hipEventElapsedTime(&ms, g->ev[0], g->ev[1]);
-    acc_ms[3] += ms; acc_ms[1] += g->h_info[4] / g->wall_khz; acc_ms[2] += g->h_info[5] / g->wall_khz;
+    acc_ms[3] += ms; acc_ms[1] += pgo_solve_ms(g, 0); acc_ms[2] += pgo_solve_ms(g, 1);
     const bool bad = g->h_info[3] != 0.0;
     const double trial_cost = bad ? INFINITY : g->h_info[0];
     const int its = (int)g->h_info[1];
@@ -1056,6 +1364,23 @@ int rolo_pgo_get_trace(rolo_pgo* g, rolo_pgo_trace_rec* out, int cap) {
   const int m = (int)g->trace.size();
   for (int i = 0; i < std::min(m, cap); i++) out[i] = g->trace[i];
   return m;
+}
+
+int rolo_pgo_set_solve_form(rolo_pgo* g, int form) {
+  if (!g) return ROLO_EINVAL;
+  if (form != ROLO_PGO_SOLVE_AUTO && form != ROLO_PGO_SOLVE_ONE_WG && form != ROLO_PGO_SOLVE_GRID) {
+    ctx_set_error("rolo_pgo_set_solve_form: the form is ROLO_PGO_SOLVE_AUTO, ROLO_PGO_SOLVE_ONE_WG or ROLO_PGO_SOLVE_GRID");
+    return ROLO_EINVAL;
+  }
+  g->solve_form = form;
+  return ROLO_OK;
+}
+
+int rolo_pgo_get_solve_form(rolo_pgo* g, int* requested, int* last_used) {
+  if (!g) return ROLO_EINVAL;
+  if (requested) *requested = g->solve_form;
+  if (last_used) *last_used = g->last_form;
+  return ROLO_OK;
 }
 
 int rolo_pgo_last_ms(rolo_pgo* g, float* ms4) {
