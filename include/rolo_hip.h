@@ -280,7 +280,10 @@ int rolo_peer_info(rolo_ctx* ctx, int* rank, int* world, char* mem_kind16);
  * [10] nanoseconds the host was blocked in rolo_register_wait's hipEventSynchronize, [11] nanoseconds of the rest of rolo_register_wait (std::chrono::steady_clock;
  * bench.py's host_enqueue_us_per_frame — round 5's verdict, item 2a), [12] frames whose resident LM kernel (fused_lm = 2) could not get all its workgroups onto the chip within its
  * admission time and gave the stage back to the host, which finished it with pass + controller launches, [13] what the context has LEARNED about load it cannot count (another
- * process on the GPU): 0 = its frames last what they last alone (idle-device kernels), 1 = trying the busy-device kernels, 2 = keeping them (rolo_set_load_hint -1 only). */
+ * process on the GPU): 0 = its frames last what they last alone (idle-device kernels), 1 = trying the busy-device kernels, 2 = keeping them (rolo_set_load_hint -1 only),
+ * [14] "kept_trials": rotation-stage trials, summed over the frames, that cost no pass — with fixed_iterations > 0 a converged-but-rejected trial repeats unchanged until the
+ * iterations are used up, and the step answers the repeats from the cost it holds (ROLO_LM_KEEP_COST=0: every repeat is a pass again). rolo_stats::n_passes / n_cost_only and
+ * the LM trace keep counting the solve's trials, these included. */
 int rolo_ctx_counters(rolo_ctx* ctx, long long* out, int n);
 /* the form of the context's last resident LM launch (fused_lm = 2, one launch per frame): out[0] workgroups, [1] threads per workgroup, [2] points per thread,
  * [3] points per thread of the interleaved body (1, 2, 4; 0: the generic body, one point after the other), [4] points of a thread that go through a body together,

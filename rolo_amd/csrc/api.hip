@@ -459,7 +459,7 @@ void reset_to_fresh(rolo_ctx* c) {
   c->want_knn_lists = false; c->prof_on = false; c->shard_knn = false;
   c->rank = 0; c->world = 1; c->load_hint = -1; c->busy_credit = 0;
   front_reset_object_state(c);   // no projection, armed de-skew or pre-cleared arrays of the previous owner
-  c->n_frames = c->n_replays = c->n_captures = c->n_eager = c->n_topup_frames = c->n_topup_chunks = 0;   // rolo_ctx_counters counts per object
+  c->n_frames = c->n_replays = c->n_captures = c->n_eager = c->n_topup_frames = c->n_topup_chunks = c->n_kept_trials = 0;   // rolo_ctx_counters counts per object
   c->ns_enqueue = c->ns_wait_blocked = c->ns_wait_other = 0; c->n_persist_bails = 0;
   // (schedule hints, their windows and the captured graph stay on purpose: they are keyed on sizes, buffers and parameters, not on the object's
   // identity — a frame loop that constructs its operator per frame, src/lidarOdometry.cpp:460, keeps replaying its graph. Drivers created on the

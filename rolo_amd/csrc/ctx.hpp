@@ -155,6 +155,7 @@ struct rolo_ctx {
   // async registration bookkeeping
   bool async_pending = false;
   long long n_frames = 0, n_replays = 0, n_captures = 0, n_eager = 0, n_topup_frames = 0, n_topup_chunks = 0;   // rolo_ctx_counters
+  long long n_kept_trials = 0;   // rotation trials answered from the kept cost (LmState::rot_kept), summed over the frames
   long long n_persist_bails = 0;   // frames whose resident LM kernel gave the stage back to the host (rolo_ctx_counters [12])
   long long ns_enqueue = 0, ns_wait_blocked = 0, ns_wait_other = 0;   // host time inside rolo_register_async / the event wait / the rest of rolo_register_wait (steady_clock)
   hipGraphExec_t dbg_chain_exec = nullptr; int dbg_chain_key[3] = {-1, -1, -1};   // rolo_debug_chain: the captured chain and its (kind, n_pairs, grid)

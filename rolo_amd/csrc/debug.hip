@@ -39,7 +39,9 @@ extern "C" int rolo_debug_lm_script_align(rolo_ctx* c, const rolo_lm_script* S, 
   if (c->async_pending) { g_err = "a registration is in flight on this context"; return ROLO_ESTATE; }
   int rc = set_device(c); if (rc) return rc;
   double R[9], t[3]; guess_to_Rt(guess16, R, t);
-  HIPCHK(launch_rot_begin(c->state, make_rot_begin(c, R, t, 0), c->stream));
+  RotBegin rb = make_rot_begin(c, R, t, 0);
+  rb.keep_cost = 0;   // a script names a cost per (outer, trial): the repeat of a converged-but-rejected trial is not bound to return the same one, so each is asked for
+  HIPCHK(launch_rot_begin(c->state, rb, c->stream));
   if ((rc = script_stage(c, S, 1, c->P.optimizer == ROLO_OPT_SO3_LM ? 3 : 6, generic_ctrl))) return rc;
   c->have_corr = c->h_state->tr_n_corr > 0;   // what computeTranslation asks for: a linearisation that left correspondences
   fill_rot_outputs(c->h_state, Tf, Td, stats);
@@ -121,9 +123,9 @@ int rolo_get_trace(rolo_ctx* c, rolo_trace_rec* out, int cap) {
 
 int rolo_ctx_counters(rolo_ctx* c, long long* out, int n) {
   if (!c || !out || n < 0) return ROLO_EINVAL;
-  const long long v[14] = {c->n_frames, c->n_replays, c->n_captures, c->n_eager, c->n_topup_frames, c->n_topup_chunks, c->hint_rot, c->hint_trans, c->walk_lanes,
-                           c->ns_enqueue, c->ns_wait_blocked, c->ns_wait_other, c->n_persist_bails, c->learn.mode};
-  for (int i = 0; i < n && i < 14; i++) out[i] = v[i];
+  const long long v[15] = {c->n_frames, c->n_replays, c->n_captures, c->n_eager, c->n_topup_frames, c->n_topup_chunks, c->hint_rot, c->hint_trans, c->walk_lanes,
+                           c->ns_enqueue, c->ns_wait_blocked, c->ns_wait_other, c->n_persist_bails, c->learn.mode, c->n_kept_trials};
+  for (int i = 0; i < n && i < 15; i++) out[i] = v[i];
   return ROLO_OK;
 }
 

@@ -636,6 +636,13 @@ ROLO_DEV void trace_push(LmState* __restrict__ st, rolo_trace_rec* __restrict__ 
   for (int i = 0; i < DOF; i++) dn += st->d[i] * st->d[i];
   r.dnorm = sqrt(dn);
 }
+// the record of a converged-but-rejected rotation trial once more, for the repeat of that trial the step answers from its kept cost (rot_step_t): the state's outer / trial
+// apart, the record pushed last. ONE: the slot keeps that first record and only the count advances — lmp_trace_flush writes the repeats from it.
+template <int DOF, bool ONE>
+ROLO_DEV void trace_push_repeat(LmState* __restrict__ st, rolo_trace_rec* __restrict__ trace, double yi, double rho) {
+  if (ONE) { st->trace_count++; return; }
+  trace_push<DOF, false>(st, trace, 0, 2, yi, rho);
+}
 
 // The damping update lambda * max(1/3, 1 - pow(2 rho - 1, 3)) (lsq_registration_impl.hpp:129, 262, 318): std::pow(double, int) is glibc's pow, whose result is the
 // correctly rounded cube but for arguments within ~0.02 ulp of a rounding tie; q * q * q rounds twice and lands one ulp off for about a quarter of all q. The cube here
@@ -764,12 +771,29 @@ ROLO_DEV void rot_step_t(LmState* __restrict__ st, const double* __restrict__ S,
     if (delta_converged(st, dof == 3)) {  // returns true without moving x0
       trace_push<DOF, ONE>(st, trace, 0, 2, yi, rho);
       st->outer++;
-      const bool done = st->fixed_iterations > 0 ? (st->outer >= st->fixed_iterations) : true;
+      bool done = st->fixed_iterations > 0 ? (st->outer >= st->fixed_iterations) : true;
       if (done) { rot_finish(st, true, false); return; }
       // the reference re-linearises at the same x0: identical H, b, y0, correspondences — and, lambda staying what this trial's step was solved with, the identical
       // step: d, delta and xt are already what rot_begin_outer's LDLT + exponential would write again, bit for bit (the scalar step is a third of this launch)
       st->nu = 2.0; st->trial = 0;
       st->lin_skip = st->spec_lin;   // a rejected trial: the next pass evaluates its trial's cost alone (LmState::lin_skip)
+      if (!st->keep_cost) return;    // ROLO_LM_KEEP_COST=0 (the A/B): the repeats below are passes of their own
+      // ... one step further: the pass that would follow evaluates the cost of THIS xt against the correspondences of THIS buffer `cur` with the Mahalanobis matrices of
+      // THIS x0 (the cache is M(x0) again whenever a pass reads it; the passes without one invert at x0 themselves), every point's term formed and the rows summed in the
+      // same fixed order by the same launch form: the yi it returns is the one above, bit for bit. y0, lambda, d and b are untouched, so rho is the one above, negative
+      // again, and delta has not moved, so delta_converged holds again: the step would stand exactly here with outer one higher and trial = 0 — until the forced
+      // iterations are used up (only fixed_iterations > 0 comes here). DOF 3 and 6 alike: nothing above depends on it. With spec_lin = 0 that pass would also run its (B)
+      // half at xt; it writes corr[cur ^ 1], which is not current and is written again before anything reads it (it becomes current only through an accepted trial's own
+      // (B) half or a phase-0 pass), and the resident kernel's cache, which is refilled on demand: neither is observable. So every remaining iteration is taken here: its
+      // trace record, its counts (rot_passes / rot_cost_only stay the solve's trials; rot_kept says how many of them cost no pass) and the bookkeeping of the exit above.
+      while (!done) {
+        st->rot_passes++; st->rot_kept++;
+        if (st->lin_skip) st->rot_cost_only++;
+        trace_push_repeat<DOF, ONE>(st, trace, yi, rho);
+        st->outer++;
+        done = st->outer >= st->fixed_iterations;
+      }
+      rot_finish(st, true, false);
       return;
     }
     trace_push<DOF, ONE>(st, trace, 0, 0, yi, rho);
@@ -1186,9 +1210,12 @@ ROLO_DEV void lmp_trace_flush(rolo_trace_rec* __restrict__ trace, int count_befo
   constexpr int NWORD = sizeof(rolo_trace_rec) / sizeof(int);
   const int t = (int)threadIdx.x - (THREADS - 64);
   if (t < 0 || t >= NWORD) return;
-  const int count = lmp_sst.trace_count;
-  if (count == count_before || count_before >= TRACE_CAP) return;
-  reinterpret_cast<int*>(trace + count_before)[t] = reinterpret_cast<const int*>(&lmp_trace_slot)[t];
+  // a step leaves one record, or none — or, where it answered the repeats of a converged-but-rejected trial from the kept cost (rot_step_t), that trial's record and a
+  // count that advanced once per repeat: repeat j is the slot's record with outer + j and trial = 0 (trace_push_repeat). Beyond TRACE_CAP only the count advances.
+  static_assert(offsetof(rolo_trace_rec, outer) == 4 && offsetof(rolo_trace_rec, trial) == 8, "the counter fields of a repeated record");
+  const int n = min(lmp_sst.trace_count, TRACE_CAP) - count_before;
+  const int w = reinterpret_cast<const int*>(&lmp_trace_slot)[t];
+  for (int j = 0; j < n; j++) reinterpret_cast<int*>(trace + count_before + j)[t] = (j == 0 || t > 2 || t == 0) ? w : (t == 1 ? w + j : 0);
 }
 
 // publish row[0 .. nv) as words of epoch e, collect all G rows, add them in a fixed order into sums[] (V_* slots). Returns false if a row did not arrive in time.
@@ -1530,6 +1557,7 @@ __global__ __launch_bounds__(THREADS, OCC) void lm_persist_kernel(PassArgs a, Lm
   rolo_trace_rec* tr = wg == 0 ? trace : nullptr;   // without a buffer trace_count still advances
   int trial = 0;
   bool ok = true;
+  bool cost_end = false;   // the last rotation trial was a cost-only one: the cache it read was written by lmp_fill_cache, as the translation stage's is
   // ---- rotation / 6-dof stage ----
   while (ok && uni(sst.stage) == 1) {
     const bool only_first = uni(sst.phase) == 1 && uni(sst.lin_skip) != 0;
@@ -1566,9 +1594,20 @@ __global__ __launch_bounds__(THREADS, OCC) void lm_persist_kernel(PassArgs a, Lm
     // what the cache holds now (rot_step_t): a linearisation pass (phase 0) left M(x0); a trial WITH a (B) half overwrote it with M(xt) — M(x0) of the next trial exactly if
     // the step accepted and took the speculated linearisation (cur flipped); a cost-only trial only read it (if it was accepted, a phase-0 pass follows and writes)
     m_valid = phase_in == 0 || only_first || uni(sst.cur) != cur_in;
+    cost_end = only_first;
     LMP_ACC();
   }
-  m_valid = false;   // (tr_R is the LAST linearisation point, not always x0: the first translation pass fills the cache)
+  // tr_R is the LAST linearisation point, not always x0: the first translation pass fills the cache — unless it holds those very matrices already. It holds M(x0) of buffer
+  // `cur` when the last rotation trial left it so (above); that is M(tr_R) of buffer `tr_cur` exactly if tr_cur is cur and tr_R is x0, bit for bit (tr_S is then x0_S: both are
+  // lm_set_rrt of the same matrix) — the stage ended on cost-only trials or on a kept cost, not on an accepted step that moved x0 past its linearisation. Only a cache
+  // that lmp_fill_cache wrote is kept (cost_end), so that the matrices are those of the same code as the refill's, not a (B) half's.
+  // (keep_cost = 0, the A/B: refilled always, as before the kept cost)
+  if (m_valid) {
+    bool same = cost_end && uni(sst.keep_cost) != 0 && uni(sst.tr_cur) == uni(sst.cur);
+#pragma unroll
+    for (int k = 0; k < 9; k++) same = same && __double_as_longlong(sst.tr_R[k]) == __double_as_longlong(sst.x0_R[k]);
+    m_valid = same;
+  }
   // ---- translation stage ----
   while (ok && uni(sst.stage) == 2) {
     const bool only_first = uni(sst.phase) == 1 && uni(sst.lin_skip) != 0;

@@ -121,6 +121,9 @@ struct LmState {
   // six rejections — so the controller marks the next pass lin_skip = 1: (A) only. If that trial is accepted after all, the controller sets phase = 0 and the next pass
   // linearises at the accepted pose: the state after it is the one the full pass would have left, one launch later. spec_lin = 0 (ROLO_LM_SPEC_LIN=0) never skips.
   int lin_skip, spec_lin;
+  // keep_cost (ROLO_LM_KEEP_COST, default 1): with forced iterations a converged-but-rejected trial is followed by the SAME trial until the iterations are used up; the step
+  // answers those repeats from the cost it holds instead of asking for another pass (passes.hip rot_step_t). rot_kept counts the trials of rot_passes answered that way.
+  int keep_cost, rot_kept;
   int rot_cost_only, trans_cost_only;   // passes of rot_passes / trans_passes that ran with lin_skip set (counted by the step that consumes them): rolo_stats::n_cost_only
   int lmp_bailed;   // the resident LM kernel (fused_lm = 2) did not get all its workgroups resident within the admission time and left WITHOUT touching the stage: the host
                     // finishes the frame with pass + controller launches (passes.hip lm_persist_kernel, schedule.hip run_stage)
@@ -260,7 +263,7 @@ hipError_t launch_peer_cov_exchange(const PeerArgs& peer, size_t area_bytes, siz
 hipError_t launch_peer_selftest_fill(const PeerArgs& peer, size_t area_bytes, size_t seg_doubles, hipStream_t s);
 hipError_t launch_peer_selftest_check(const PeerArgs& peer, size_t area_bytes, size_t seg_doubles, unsigned* bad, hipStream_t s);
 
-struct RotBegin { double R[9], t[3]; int optimizer, max_iterations, fixed_iterations, lm_max, q2_intended; double rot_eps, trans_eps, lm_init; int run_trans; int spec_lin; };
+struct RotBegin { double R[9], t[3]; int optimizer, max_iterations, fixed_iterations, lm_max, q2_intended; double rot_eps, trans_eps, lm_init; int run_trans; int spec_lin; int keep_cost; };
 struct TransBegin { double t0[3], g[3], l[3], dtn, dtn1; float ct_lambda; int direct; /* 1: start now (rotation already done) */
                     // the knobs computeTranslation reads when IT runs (lsq_registration_impl.hpp:63, :98, :142-148 read the members live): a setter called between align and
                     // computeTranslation counts — until round 6 the stage ran on what the last align had copied into the state

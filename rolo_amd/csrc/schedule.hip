@@ -125,6 +125,7 @@ RotBegin make_rot_begin(const rolo_ctx* c, const double* R9, const double* t3, i
   b.lm_max = c->P.lm_max_iterations; b.q2_intended = c->P.q2_intended; b.rot_eps = c->P.rotation_epsilon;
   b.trans_eps = c->P.transformation_epsilon; b.lm_init = c->P.lm_init_lambda_factor; b.run_trans = run_trans;
   b.spec_lin = switches().lm_spec_lin;   // 0: every pass carries both halves (the A/B, rounds 1-4)
+  b.keep_cost = switches().lm_keep_cost; // 0: the repeats of a converged-but-rejected trial under forced iterations are passes of their own (the A/B)
   return b;
 }
 
@@ -167,6 +168,10 @@ static void frame_chunks(const rolo_ctx* c, int& nrot, int& ntrans) {
 // Round 5: with pass + controller launches the schedule holds EXACTLY the window's maximum — through round 4 it held one pair more, rounded up to an even count (what
 // the fused launches' double-buffered state needs): 22 + 12 pairs for frames that use 21 + 9..10, i.e. six to eight no-op launches of ~2.5 us on every frame's
 // critical path. A frame that needs more than any of the last 64 did tops up through one host round trip and raises the hint.
+// `used` counts launches that RAN: a rotation trial answered from the kept cost (LmState::rot_kept) is a trial of the solve and no launch — sized from rot_passes, every
+// forced-iteration frame would carry a dozen predicated no-op pairs. (The resident kernel has no schedule: its hint only keys the frame's hipGraph, and keeps following the
+// solve's trials, which differ less from pair to pair than the launches do — a hint that moves means an eager frame and a new capture.)
+static int rot_launches(const rolo_ctx* c, const LmState* s) { return lm_persist(c) ? s->rot_passes : s->rot_passes - s->rot_kept; }
 static void update_hint(int& hint, rolo_ctx::NeedWindow& w, int used, bool fused) {
   constexpr int WN = 64;
   w.need[w.pos] = used; w.pos = (w.pos + 1) % WN; if (w.n < WN) w.n++;
@@ -306,7 +311,7 @@ int rolo_align(rolo_ctx* c, const float* guess16, float* Tf, double* Td, rolo_st
     if ((rc = run_stage(c, a, grid, 1, 8, bailed))) return rc;
   }
   c->have_corr = true;
-  if (!c->h_state->error) update_hint(c->hint_rot, c->win_rot, c->h_state->rot_passes, lm_fused(c));
+  if (!c->h_state->error) { update_hint(c->hint_rot, c->win_rot, rot_launches(c, c->h_state), lm_fused(c)); c->n_kept_trials += c->h_state->rot_kept; }
   fill_rot_outputs(c->h_state, Tf, Td, stats);
   if (c->h_state->error) { g_err = c->h_state->error == ROLO_ENOCORR ? "no correspondences" : "device-side error during align"; return c->h_state->error; }
   return ROLO_OK;
@@ -476,7 +481,8 @@ int rolo_register_wait(rolo_ctx* c, float* Tf, double* Td, double* trans_out, ro
   if (!c->h_state->trans_done && !c->h_state->error) { if ((rc = run_stage(c, a, grid, 2, 8, bailed))) return rc; }
   c->have_corr = true;
   const LmState* s = c->h_state;
-  if (!s->error) { update_hint(c->hint_rot, c->win_rot, s->rot_passes, lm_fused(c)); update_hint(c->hint_trans, c->win_trans, s->trans_passes, lm_fused(c)); }
+  if (!s->error) { update_hint(c->hint_rot, c->win_rot, rot_launches(c, s), lm_fused(c)); update_hint(c->hint_trans, c->win_trans, s->trans_passes, lm_fused(c)); }
+  c->n_kept_trials += s->rot_kept;
   fill_rot_outputs(s, Tf, Td, rs);
   fill_trans_outputs(s, trans_out, ts);
   if (s->error) { g_err = "device-side error during registration"; return s->error; }
@@ -628,6 +634,7 @@ int rolo_batch_register_wait(rolo_batch* b, float* Tf, double* Td, double* trans
     }
     c->have_corr = true;
     const LmState* s = c->h_state;
+    c->n_kept_trials += s->rot_kept;
     fill_rot_outputs(s, Tf ? Tf + 16 * (size_t)i : nullptr, Td ? Td + 16 * (size_t)i : nullptr, rs ? rs + i : nullptr);
     fill_trans_outputs(s, trans_out ? trans_out + 3 * (size_t)i : nullptr, ts ? ts + i : nullptr);
     if (s->error && !first_err) { g_err = "device-side error in a batch member"; first_err = s->error; }
