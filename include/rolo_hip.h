@@ -289,6 +289,18 @@ int rolo_ctx_counters(rolo_ctx* ctx, long long* out, int n);
  * [3] points per thread of the interleaved body (1, 2, 4; 0: the generic body, one point after the other), [4] points of a thread that go through a body together,
  * [5] 1 if the Mahalanobis cache sits in LDS, [6] dynamic LDS in bytes. All zero if the last LM chain of the context did not use the resident kernel. */
 int rolo_ctx_lm_form(rolo_ctx* ctx, int* out, int n);
+/* test hook: how the context's current voxel map was built — host-side facts, kept where the build is enqueued (a frame replayed from its hipGraph reports what its capture
+ * baked in). out[0] the form: the map's own launches behind rolo_build_voxelmap and the stage-level evaluations, over the target in input order (STAGED_INPUT) or in the
+ * order of the search's curve (STAGED_CURVE: chosen from the points per voxel of the context's previous map, before there is one for the POLAR grid); inside the
+ * launches of the target's neighbour search (SEARCH: rolo_align / rolo_register_async on a target without covariances); the staged launches as a frame or a batch member
+ * enqueues them behind a search that had finished before, or was not needed (FRAME). out[1] 1: the covariance sums are fixed point too, 0: fp64 atomics (handed-in
+ * covariances, unbounded regularisations). out[2] where max |coordinate|, which sets the fixed-point scale, came from: 0 the search's bounding box, 1 the points
+ * themselves (no search ran on this target). out[3] slots of the hash table. ROLO_ESTATE without a map. */
+#define ROLO_VOXBUILD_STAGED_INPUT 0
+#define ROLO_VOXBUILD_STAGED_CURVE 1
+#define ROLO_VOXBUILD_SEARCH 2
+#define ROLO_VOXBUILD_FRAME 3
+int rolo_debug_voxel_build(rolo_ctx* ctx, int32_t out[4]);
 /* device buffer (re)allocations made so far by the registration contexts of this process (every hipMalloc behind a rolo_ctx's buffers; a captured hipGraph is keyed on it):
  * a steady-state frame loop must stop moving it */
 long long rolo_alloc_count(void);

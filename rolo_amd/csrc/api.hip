@@ -186,6 +186,15 @@ bool voxel_fixed_cov(const rolo_ctx* c) {
   return !c->tgt.cov_user && (r == ROLO_REG_PLANE || r == ROLO_REG_NORMALIZED_MIN_EIG || r == ROLO_REG_PLANE_S);
 }
 
+// form: ROLO_VOXBUILD_* (rolo_hip.h). The search's own launches only ever carry fixed-point covariances and take the scale from the box they computed.
+void note_voxel_build(rolo_ctx* c, int form) {
+  const bool fused = form == ROLO_VOXBUILD_SEARCH;
+  c->vox_build[0] = form;
+  c->vox_build[1] = fused || voxel_fixed_cov(c) ? 1 : 0;
+  c->vox_build[2] = fused || c->tgt.bbox6 ? 0 : 1;
+  c->vox_build[3] = (int)(c->tab.mask + 1u);
+}
+
 static void fill_table_params(rolo_ctx* c) {
   c->tab.polar_exact = switches().polar_exact;
   c->tab.voxel_type = c->P.voxel_type;
@@ -222,6 +231,7 @@ int ensure_map(rolo_ctx* c) {
   if (rc) return rc;
   if (c->have_map) return ROLO_OK;
   if ((rc = size_voxel_table(c))) return rc;
+  note_voxel_build(c, voxel_morton_order(c) && c->tgt.have_sorted ? ROLO_VOXBUILD_STAGED_CURVE : ROLO_VOXBUILD_STAGED_INPUT);
   { ProfScope ps(c, ROLO_PROF_VOXEL_BUILD); HIPCHK(launch_voxel_build(c->tgt, c->tab, c->tgt_keys, c->tgt_slot, c->counters, voxel_morton_order(c), voxel_fixed_cov(c), c->tgt.bbox6, false, c->stream)); }
   HIPCHK(hipMemcpyAsync(c->h_counters, c->counters, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));

@@ -126,6 +126,7 @@ struct rolo_ctx {
   unsigned long long* stamps = nullptr; size_t stamps_cap = 0; unsigned long long* h_stamps = nullptr;   // ROLO_STAMP=1 debug timeline (pinned)
   rolo::VoxelFuse vf{};     // enqueue_frame arms it before the search when the map can be built inside the search's launches
   bool vf_done = false;     // the search just enqueued did carry the map build
+  int vox_build[4] = {-1, 0, 0, 0};   // the last map build as enqueued (rolo_debug_voxel_build): form, fixed-point covariances, scale from the points, slots
   int n_edge = 0;   // target points of the last map build within 1e-12 of a POLAR bin edge
   // passes
   int* corr[2] = {nullptr, nullptr}; size_t corr_cap[2] = {0, 0};
@@ -175,9 +176,10 @@ struct rolo_ctx {
   int walk_lanes = 1;   // lanes per query of the last K5 walk enqueued (rolo_ctx_counters [8])
   struct NeedWindow { int need[64] = {0}; int n = 0, pos = 0; } win_rot, win_trans;   // passes the last 64 frames needed per stage
   bool graph_nrm_written = false;   // the captured build_clouds left the PLANE covariances as I - m m^T too (CloudDev::have_nrm after a replay)
+  int graph_vox_build[4] = {-1, 0, 0, 0};   // vox_build of the captured frame: what a replay builds the map with
   // the captured frame of the OTHER load regime (GraphKey::busy): a context whose load estimate flips — the learner's periodic second look, a second context that comes and
   // goes — swaps its two graphs instead of capturing again (42 captures in 11 000 frames of the two-process run before this slot existed)
-  struct GraphSlot { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key{}; bool nrm = false; } galt;
+  struct GraphSlot { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key{}; bool nrm = false; int vox_build[4] = {-1, 0, 0, 0}; } galt;
   // per-kernel event timing (rolo_prof_*)
   bool prof_on = false;
   struct ProfEv { int slot; hipEvent_t a, b; };
@@ -246,6 +248,7 @@ int ensure_covs(rolo_ctx* c);
 int ensure_map(rolo_ctx* c);
 bool voxel_morton_order(const rolo_ctx* c);
 bool voxel_fixed_cov(const rolo_ctx* c);
+void note_voxel_build(rolo_ctx* c, int form);   // a map build is being enqueued with the context's current choices: keep what rolo_debug_voxel_build reports
 int size_voxel_table(rolo_ctx* c);     // the table and the per-point arrays of a map of the current target, VoxelTable's parameters from the context's
 int take_map_counters(rolo_ctx* c);    // after the host has synchronised with a map build: its error (code returned, text set) or n_voxels / n_edge / have_map
 int fetch_state(rolo_ctx* c);

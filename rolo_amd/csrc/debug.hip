@@ -137,6 +137,13 @@ int rolo_ctx_lm_form(rolo_ctx* c, int* out, int n) {
   return ROLO_OK;
 }
 
+int rolo_debug_voxel_build(rolo_ctx* c, int32_t out[4]) {
+  if (!c || !out) return ROLO_EINVAL;
+  if (!c->have_map || c->vox_build[0] < 0) { g_err = "rolo_debug_voxel_build needs a built voxel map"; return ROLO_ESTATE; }
+  for (int i = 0; i < 4; i++) out[i] = c->vox_build[i];
+  return ROLO_OK;
+}
+
 int rolo_prof_enable(rolo_ctx* c, int on) {
   if (!c) return ROLO_EINVAL;
   c->prof_on = on != 0;

@@ -131,6 +131,24 @@ ROLO_DEV void wave_reduce_scatter(const double (&acc)[NV], double* __restrict__ 
 }
 
 // only_first (wave-uniform): a pass that evaluated the trial cost alone (LmState::lin_skip) has ONE value to sum — acc[0] — and writes zeros to the other slots
+// The wavefronts' sums are added in groups of PASS_THREADS / 64, the groups after one another: the row of a fat workgroup (the one-launch-per-trial form, the resident
+// kernel) is the sum, in order, of the rows that the pass kernel's workgroups write for the same points, so a cloud that is ONE row there (up to 512 points at one point
+// per thread) ends at the same bits in all three launch forms. (Until then the 8 wavefronts of a 512-thread workgroup were added in one run: the forms differed in
+// the last bit of H and b, tests/test_gpu_voxel_cases.py.) With THREADS == PASS_THREADS this is the one run it always was.
+template <int ROWS>
+ROLO_DEV double sum_wave_rows(const double (*red)[NV_MAX], int col) {
+  constexpr int G = PASS_THREADS / 64;
+  static_assert(ROWS % G == 0, "a workgroup is whole groups of the pass kernel's wavefronts");
+  double s = 0;
+#pragma unroll
+  for (int g0 = 0; g0 < ROWS; g0 += G) {
+    double sg = 0;
+#pragma unroll
+    for (int w = 0; w < G; w++) sg += red[g0 + w][col];
+    s += sg;
+  }
+  return s;
+}
 template <int NV, int THREADS = PASS_THREADS>
 ROLO_DEV void block_reduce_store(double (&acc)[NV], const int (&slot)[NV], double* __restrict__ out_row, bool only_first = false) {
   __shared__ double red[THREADS / 64][NV_MAX];
@@ -144,10 +162,7 @@ ROLO_DEV void block_reduce_store(double (&acc)[NV], const int (&slot)[NV], doubl
     __syncthreads();
     if (threadIdx.x < NV) {
       double s0 = 0;
-      if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 0; w < THREADS / 64; w++) s0 += red[w][0];
-      }
+      if (threadIdx.x == 0) s0 = sum_wave_rows<THREADS / 64>(red, 0);
       int sl = 0;
 #pragma unroll
       for (int v = 0; v < NV; v++) if (threadIdx.x == v) sl = slot[v];
@@ -158,9 +173,7 @@ ROLO_DEV void block_reduce_store(double (&acc)[NV], const int (&slot)[NV], doubl
   wave_reduce_scatter<NV>(acc, red[wv]);
   __syncthreads();
   if (threadIdx.x < NV) {
-    double s = 0;
-#pragma unroll
-    for (int w = 0; w < THREADS / 64; w++) s += red[w][threadIdx.x];
+    const double s = sum_wave_rows<THREADS / 64>(red, threadIdx.x);
     // slot[] is a compile-time table; pick by thread index
     int sl = 0;
 #pragma unroll

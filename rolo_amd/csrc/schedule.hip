@@ -360,6 +360,7 @@ static int enqueue_frame(rolo_ctx* c, bool with_trans) {   // with_trans = false
     c->vf.enabled = 0;
     if (rc) return rc;
     STAMP(1);
+    note_voxel_build(c, c->vf_done ? ROLO_VOXBUILD_SEARCH : ROLO_VOXBUILD_FRAME);
     { ProfScope ps(c, ROLO_PROF_VOXEL_BUILD); HIPCHK(launch_voxel_build(c->tgt, c->tab, c->tgt_keys, c->tgt_slot, c->counters, voxel_morton_order(c), voxel_fixed_cov(c), c->tgt.bbox6, c->vf_done, c->stream, c->h_counters, c->state, c->h_args)); }   // the finalize kernel leaves the counters in pinned memory and starts the frame's LM state from c->h_args (pinned)
     c->vf_done = false;
   }
@@ -409,19 +410,23 @@ static int register_async_impl(rolo_ctx* c, const float* guess16, const double* 
     CapturedSchedule<GraphKey>& g = c->sched;
     if (c->galt.exec && same_key(key, c->galt.key) && !replay_due(g, key)) {   // the other regime's frame is cached: swap
       std::swap(g.graph, c->galt.graph); std::swap(g.exec, c->galt.exec); std::swap(g.key, c->galt.key); std::swap(c->graph_nrm_written, c->galt.nrm);
+      std::swap(c->graph_vox_build, c->galt.vox_build);
     } else if (g.exec && g.key.busy != key.busy && capture_due(g, key)) {   // keep the other regime's frame in the second slot (whatever was there goes)
       if (c->galt.exec) (void)hipGraphExecDestroy(c->galt.exec);
       if (c->galt.graph) (void)hipGraphDestroy(c->galt.graph);
       c->galt.graph = g.graph; c->galt.exec = g.exec; c->galt.key = g.key; c->galt.nrm = c->graph_nrm_written;
+      std::copy(c->graph_vox_build, c->graph_vox_build + 4, c->galt.vox_build);
       g.graph = nullptr; g.exec = nullptr;
     }
   }
   Ran ran;
   rc = run_captured(c->sched, c->stream, graphable ? &key : nullptr, [&](bool) { return enqueue_frame(c, true); },
-                    [&] { c->graph_nrm_written = c->src.have_nrm && c->tgt.have_nrm; }, [&] { c->src.have_cov = false; c->tgt.have_cov = false; }, &ran);
+                    [&] { c->graph_nrm_written = c->src.have_nrm && c->tgt.have_nrm; std::copy(c->vox_build, c->vox_build + 4, c->graph_vox_build); },
+                    [&] { c->src.have_cov = false; c->tgt.have_cov = false; }, &ran);
   if (rc) return rc;
   if (ran == Ran::Replayed) {
     c->n_replays++;
+    std::copy(c->graph_vox_build, c->graph_vox_build + 4, c->vox_build);
     c->src.have_cov = true; c->tgt.have_cov = true; c->src.have_sorted = true; c->tgt.have_sorted = true;
     c->src.have_nrm = c->tgt.have_nrm = c->graph_nrm_written;   // what build_clouds decided when this graph was captured (recorded then, not re-derived: advisor, round 5)
   } else if (ran == Ran::Captured) c->n_captures++;
@@ -558,6 +563,7 @@ static int enqueue_batch(rolo_batch* b, bool fork) {
     if (!c->src.have_cov && (rc = build_src(c, s1))) return rc;
     if (!c->tgt.have_cov && (rc = build_tgt(c, s2))) return rc;
     if ((rc = size_voxel_table(c))) return rc;
+    note_voxel_build(c, ROLO_VOXBUILD_FRAME);
     HIPCHK(launch_voxel_build(c->tgt, c->tab, c->tgt_keys, c->tgt_slot, c->counters, voxel_morton_order(c), voxel_fixed_cov(c), c->tgt.bbox6, false, s2));
     HIPCHK(hipMemcpyAsync(c->h_counters, c->counters, 4 * sizeof(int), hipMemcpyDeviceToHost, s2));
     if (fork) { HIPCHK(hipEventRecord(b->ev_join[2 * i], s1)); HIPCHK(hipEventRecord(b->ev_join[2 * i + 1], s2)); }

@@ -9,7 +9,9 @@
 // kernel accumulates points into the records: consecutive lanes that hit the same voxel (targets arrive in scan
 // order, so runs are long) are combined inside the wavefront first, so HBM sees one atomic add per run
 // instead of one per point. The sums are 64-bit FIXED-POINT integers (scale = the power of two that keeps n * max|value| below
-// 2^62: float coordinates are then represented exactly, covariances to ~6e-14): integer addition is associative, so every
+// 2^62: a position counts in units of 2^(bits_n + e + 1 - 62), bits_n = bit_length(n), e = the exponent of max |coordinate| or -1 below 0.5. A float
+// coordinate whose lowest set bit is at least that unit goes in exactly - all of them when the magnitudes span less than 2^(38 - bits_n) - a smaller one is
+// rounded to the unit; covariances to ~6e-14): integer addition is associative, so every
 // voxel's mean and covariance come out bit-identical run after run and in either point order (fp64 atomics summed in arrival
 // order). A third kernel finalises (mean /= n, cov /= n, w = sqrt(n)). Lookups in the pass
 // kernels are then: pack key -> hash -> probe 8-byte slots -> 96-byte record gather.

@@ -240,6 +240,13 @@ class RotVGICP:
         check(lib().rolo_get_voxels(self._h, _i(keys), _i(counts), _d(means), _d(covs)), "rolo_get_voxels")
         return keys, counts, means, covs
 
+    def voxelBuildForm(self):
+        """Test hook (rolo_debug_voxel_build): (form, fixed-point covariances, scale from the points, table slots) of the current map's build;
+        form 0 = staged launches in input order, 1 = in curve order, 2 = inside the search's launches, 3 = a frame's staged launches (ROLO_VOXBUILD_*)"""
+        out = np.zeros(4, np.int32)
+        check(lib().rolo_debug_voxel_build(self._h, _i(out)), "rolo_debug_voxel_build")
+        return tuple(int(v) for v in out)
+
     def targetVoxelKeys(self):
         keys = np.zeros((self._nt, 3), np.int32)
         check(lib().rolo_get_target_voxel_keys(self._h, _i(keys)), "rolo_get_target_voxel_keys")

@@ -177,7 +177,9 @@ def test_voxel_map_built_inside_the_search_is_the_same_map(pair):
 @pytest.mark.parametrize("n", [21, 65, 257, 1025, 4097, 16385, 30011])
 def test_odd_sizes_through_the_sort_tree_and_fused_map(n):
     """sizes around the sort's tile / workgroup / leaf boundaries: neighbour lists bit-exact against the oracle (small n), covariances and
-    voxel map of the fused frame path (twice: eager, then a replayed graph) the same bits as the separate launches"""
+    voxel map of the fused frame path (three frames on clouds set anew: eager, then captured, then replayed while the schedule holds) and of a fourth frame on the
+    clouds as they are — their covariances kept, so the map comes from the frame's own staged launches — the same bits as the separate launches. (Until the build form
+    could be read back, the later frames handed the SAME arrays to the setters, which take that for a no-op as the reference does: they never went through the search again.)"""
     rng = np.random.default_rng(n)
     src0, tgt0, _ = synth.dense_pair("os1-64", col_stride=2)
     si = np.sort(rng.choice(src0.shape[0], n, replace=False)); ti = np.sort(rng.choice(tgt0.shape[0], max(21, n - int(rng.integers(0, 7))), replace=False))
@@ -190,17 +192,19 @@ def test_odd_sizes_through_the_sort_tree_and_fused_map(n):
         g = ctx(); idx_g, d2_g = g.knn(0); g.close()
         assert np.array_equal(idx_o, idx_g) and np.array_equal(d2_o, d2_g)
     g = ctx(); g.buildVoxelMap()
+    assert g.voxelBuildForm()[0] == 0   # the separate launches, input order
     k, c, m, v = g.voxels(); o = np.lexsort(k.T[::-1]); ref = (k[o], c[o], m[o], v[o]); cov_ref = g.getTargetCovariances().copy()
     g.close()
     g = ctx(); z = np.zeros(3)
-    for it in range(3):
-        if it:
-            g.setInputTarget(tgt); g.setInputSource(src)
+    for it in range(4):
+        if it in (1, 2):
+            g.setInputTarget(tgt.copy()); g.setInputSource(src.copy())
         g.register_async(None, z, z, z, 0.1, 0.1, 0.3)
         try:
             g.register_wait()
         except Exception as ex:   # a handful of scattered points: an empty correspondence set is the reference's behaviour too (ROLO_ENOCORR)
             assert "-4" in str(ex) and n < 1000
+        assert g.voxelBuildForm()[0] == (2 if it < 3 else 3)   # inside the search's launches (a captured or replayed frame too); the last frame: staged, behind the kept search
         k, c, m, v = g.voxels(); o = np.lexsort(k.T[::-1])
         for a, b in zip(ref, (k[o], c[o], m[o], v[o])):
             assert np.array_equal(a, b)
@@ -1233,10 +1237,12 @@ def test_voxel_map_through_the_workgroup_table(kind):
         sg = np.lexsort(kg.T[::-1])
         assert kg.shape == ko.shape and np.array_equal(kg[sg], ko[so]) and np.array_equal(cg[sg], co[so])
         assert np.abs(mg[sg] - mo[so]).max() < 1e-12 and np.abs(vg[sg] - vo[so]).max() < 1e-9
-    g.buildVoxelMap(); check()                       # the staged build: voxel_accum_sorted_kernel
+    g.buildVoxelMap(); check()                       # the staged build; a fresh UNIFORM context takes the target in input order: voxel_accum_kernel
+    assert g.voxelBuildForm()[0] == 0
     g2 = RotVGICP(); g2.setResolution(0.5); g2.setInputTarget(tgt); g2.setInputSource(src)
     G = np.zeros(3)
     g2.register_async(None, np.zeros(3), G, G); g2.register_wait()
     g_keep, g = g, g2
     check()                                          # the frame's own build: the tail's accumulation
+    assert g.voxelBuildForm()[0] == 2
     g_keep.close(); g2.close()
