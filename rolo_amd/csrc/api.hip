@@ -407,14 +407,6 @@ static int ctx_create_impl(int device, bool high_priority, rolo_ctx** out) {
   return ROLO_OK;
 }
 
-void rolo_front_destroy(rolo_ctx* c);  // front.hip
-void rolo_s2m_destroy(rolo_ctx* c);    // scan2map.hip
-void rolo_loopicp_destroy(rolo_ctx* c);   // loopicp.hip
-void rolo_s2m_forget(rolo_ctx* c);     // scan2map.hip: a context going back to the pool forgets its resident sub-map and gives its helper context back
-}
-namespace rolo { void front_reset_object_state(rolo_ctx* c); }   // front.hip
-extern "C" {
-
 void rolo_ctx_destroy(rolo_ctx* c) {
   if (!c) return;
   count_in_flight(c, false);

@@ -1,8 +1,8 @@
 // The context as the HOST units of librolo_hip.so see it (api.hip: context, clouds, voxel map; schedule.hip: LM launch planning, the per-frame schedule, batches;
 // peer.hip: shards, RCCL, the peer exchange; debug.hip: test hooks, profiling, counters). Not installed, and not for front.hip / odometry.hip / scan2map.hip / submap.hip:
-// they reach the context through the rolo::ctx_* accessors of rolo_internal.hpp's users, the layout stays private to the four units above.
+// they reach the context through the rolo::ctx_* accessors of ctx_access.hpp, the layout stays private to the four units above.
 #pragma once
-#include "rolo_internal.hpp"
+#include "ctx_access.hpp"   // fail_hip / HIPCHK
 #include "load_learner.hpp"
 #include "switches.hpp"
 #include <cstring>
@@ -16,11 +16,6 @@
 namespace rolo {
 
 extern thread_local std::string g_err;   // rolo_last_error (api.hip)
-inline int fail_hip(hipError_t e, const char* what) {
-  g_err = std::string(what) + ": " + hipGetErrorString(e);
-  return ROLO_EHIP;
-}
-#define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) return rolo::fail_hip(_e, #x); } while (0)
 
 extern std::atomic<unsigned long long> g_alloc_epoch;  // bumped on every (re)allocation: captured graphs hold raw device pointers (api.hip)
 

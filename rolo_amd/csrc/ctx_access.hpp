@@ -1,0 +1,91 @@
+// What the units of librolo_hip.so share without sharing the context's layout (ctx.hpp): every function that crosses a unit boundary and is no part of the C ABI,
+// the one HIP check, and the one store for device buffers that only grow. Included by the units that define these functions (api.hip through ctx.hpp, front.hip,
+// scan2map.hip, submap.hip, scancontext.hip, loopicp.hip) as well as by their users: the compiler checks every definition against the declaration here.
+#pragma once
+#include "rolo_internal.hpp"
+#include <string>
+#include <vector>
+
+namespace rolo {
+// ---- api.hip ----
+void ctx_set_error(const char* msg);   // what rolo_last_error returns on this thread
+hipStream_t ctx_stream(rolo_ctx* c);
+int ctx_device(rolo_ctx* c);
+void** ctx_front_slot(rolo_ctx* c);    // the units' own state hanging off a context: front.hip, scan2map.hip, loopicp.hip
+void** ctx_s2m_slot(rolo_ctx* c);
+void** ctx_loop_slot(rolo_ctx* c);
+unsigned long long ctx_cloud_epoch(rolo_ctx* c);   // changes whenever the context's source / target clouds change hands
+void ctx_set_fused_lm(rolo_ctx* c, int mode);
+int ctx_create_high_priority(int device, rolo_ctx** out);
+int ctx_set_pair_device(rolo_ctx* c, const float* d_src, int n_src, int stride_src, const float* T16_host_or_null, const float* d_tgt, int n_tgt, int stride_tgt);
+int ctx_build_map_trees(rolo_ctx* c, const float* corner, int nc, const float* surf, int ns, int stride, KnnPair* out, bool on_device = false);
+// ---- front.hip ----
+void front_reset_object_state(rolo_ctx* c);
+// ---- submap.hip: the resident sub-map as device clouds (n x 4 floats), the event a reader's stream waits for and the one it records when it has read them ----
+int keymap_device_submap(rolo_keymap* km, const float** d_corner, int* m_corner, const float** d_surf, int* m_surf, hipEvent_t* ready, hipEvent_t* consumed, int* device);
+void keymap_mark_consumed(rolo_keymap* km);
+}  // namespace rolo
+
+extern "C" {   // called by rolo_ctx_destroy / rolo_ctx_release (api.hip); no part of include/rolo_hip.h
+void rolo_front_destroy(rolo_ctx* c);     // front.hip
+void rolo_s2m_destroy(rolo_ctx* c);       // scan2map.hip
+void rolo_s2m_forget(rolo_ctx* c);        // scan2map.hip: a context going back to the pool forgets its resident sub-map and gives its helper context back
+void rolo_loopicp_destroy(rolo_ctx* c);   // loopicp.hip
+}
+
+#pragma GCC visibility push(hidden)
+namespace rolo {
+
+inline int fail_hip(hipError_t e, const char* what) {
+  ctx_set_error((std::string(what) + ": " + hipGetErrorString(e)).c_str());
+  return ROLO_EHIP;
+}
+#define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) return rolo::fail_hip(_e, #x); } while (0)
+
+// Device (and pinned host) buffers that only grow, counted in elements. An outgrown buffer is retired, not freed, until release(): a hipFree is a device-wide
+// synchronisation that would stall the frames other contexts have in flight, and work queued on the owner's stream may still read the old buffer. Sizes grow by
+// half, so the retired buffers together stay below twice the live one. The owner frees its live buffers itself, after it has drained its stream.
+struct DevStore {
+  hipStream_t stream = nullptr;   // carries the copy of the `keep` elements
+  const char* who = "";           // names the unit in the allocation's error message
+  size_t slack = 256;             // elements a buffer gets beyond one and a half times the need
+  std::vector<void*> retired, retired_host;
+
+  // exactly n elements, the first `keep` of the old buffer copied over on the stream
+  template <typename T>
+  int replace(T*& p, size_t n, size_t keep = 0) {
+    T* q = nullptr;
+    if (hipMalloc((void**)&q, n * sizeof(T)) != hipSuccess) { ctx_set_error((std::string("hipMalloc failed (") + who + ")").c_str()); return ROLO_EHIP; }
+    if (p && keep) HIPCHK(hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, stream));
+    retire(p);
+    p = q;
+    return ROLO_OK;
+  }
+  template <typename T>
+  int grow(T*& p, size_t& cap, size_t need, size_t keep = 0) {
+    if (need <= cap && p) return ROLO_OK;
+    const size_t want = need + need / 2 + slack;
+    const int rc = replace(p, want, keep);
+    if (rc == ROLO_OK) cap = want;
+    return rc;
+  }
+  template <typename T>
+  int grow_pinned(T*& p, size_t& cap, size_t need, size_t pinned_slack) {
+    if (need <= cap && p) return ROLO_OK;
+    const size_t want = need + need / 2 + pinned_slack;
+    T* q = nullptr;
+    if (hipHostMalloc((void**)&q, want * sizeof(T)) != hipSuccess) { ctx_set_error((std::string("hipHostMalloc failed (") + who + ")").c_str()); return ROLO_EHIP; }
+    if (p) retired_host.push_back(p);
+    p = q; cap = want;
+    return ROLO_OK;
+  }
+  void retire(void* p) { if (p) retired.push_back(p); }
+  void release() {
+    for (void* p : retired) (void)hipFree(p);
+    for (void* p : retired_host) (void)hipHostFree(p);
+    retired.clear(); retired_host.clear();
+  }
+};
+
+}  // namespace rolo
+#pragma GCC visibility pop

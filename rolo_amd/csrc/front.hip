@@ -18,7 +18,7 @@
 //       sector (only the two sectors touching the cloud ends keep the serial walk); the label<=0 collection is a ballot
 //       compaction, and pcl::VoxelGrid is a second bitonic sort of (cell << 32 | order) keys followed by per-run centroids.
 // fp32 arithmetic follows the reference expression by expression; this file is compiled with -ffp-contract=off.
-#include "rolo_internal.hpp"
+#include "ctx_access.hpp"
 #include <atomic>
 #include "dev_math.hpp"
 #include <cfloat>
@@ -991,21 +991,13 @@ void front_free(Front* f) {
 
 }  // namespace
 
-// accessors implemented in api.hip
-void** ctx_front_slot(rolo_ctx* c);
-hipStream_t ctx_stream(rolo_ctx* c);
-int ctx_device(rolo_ctx* c);
-void ctx_set_error(const char* msg);
-
-#define FCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { ctx_set_error((std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); return ROLO_EHIP; } } while (0)
-
 namespace {
 
 // device buffers for frames of up to n_raw points / n_scan x horizon_scan pixels
 int front_prepare(rolo_ctx* c, const rolo_front_params* P, int n_raw, int stride, bool stage_raw, Front** out) {
   if (P->n_scan <= 0 || P->horizon_scan <= 0 || P->downsample_rate <= 0) { ctx_set_error("bad front params"); return ROLO_EINVAL; }
   if (P->horizon_scan > FRONT_MAX_H_BIG) { ctx_set_error("Horizon_SCAN above the limit of this build (4096)"); return ROLO_EUNSUPPORTED; }
-  FCHK(hipSetDevice(ctx_device(c)));
+  HIPCHK(hipSetDevice(ctx_device(c)));
   void** slot = ctx_front_slot(c);
   if (!*slot) *slot = new Front();
   Front* f = static_cast<Front*>(*slot);
@@ -1080,7 +1072,7 @@ int front_project_enqueue(Front* f, const rolo_front_params* P, const float* d_p
                                         f->col + FRONT_GUARD, f->range + FRONT_GUARD, f->start_ring, f->end_ring, want_range_mat ? f->range_mat : nullptr,
                                         f->counters, f->deskew_armed ? f->deskew : DeskewArgs{});
   f->deskew_armed = false;
-  FCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return ROLO_OK;
 }
 
@@ -1091,9 +1083,9 @@ int front_extract_enqueue(Front* f, const rolo_front_params* P, hipStream_t s, f
   // guards of curvature / picked / label are zero; live entries are written by the smoothness kernel
   const size_t np = npix + 2 * FRONT_GUARD;
   if (!f->extract_cleared) {   // a projection loaded from the host (rolo_front_load_projection): nobody cleared them yet
-    FCHK(hipMemsetAsync(f->curv, 0, sizeof(float) * np, s));
-    FCHK(hipMemsetAsync(f->picked, 0, sizeof(int) * np, s));
-    FCHK(hipMemsetAsync(f->label, 0, sizeof(int) * np, s));
+    HIPCHK(hipMemsetAsync(f->curv, 0, sizeof(float) * np, s));
+    HIPCHK(hipMemsetAsync(f->picked, 0, sizeof(int) * np, s));
+    HIPCHK(hipMemsetAsync(f->label, 0, sizeof(int) * np, s));
   }
   f->extract_cleared = false;
   // (K3 — calculateSmoothness + markOccludedPoints — runs inside extract_kernel; curv / picked / label are zero at this point)
@@ -1109,7 +1101,7 @@ int front_extract_enqueue(Front* f, const rolo_front_params* P, hipStream_t s, f
     constexpr size_t lds = front_ring_bytes(FRONT_MAX_H);
     static std::atomic<unsigned long long> attr_set{0};   // per device ordinal (bit d): the attribute belongs to the device's code object
     const unsigned long long dev_bit = 1ull << (f->device & 63);
-    if (!(attr_set.load() & dev_bit)) { FCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(extract_kernel<FRONT_MAX_H, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr_set.fetch_or(dev_bit); }
+    if (!(attr_set.load() & dev_bit)) { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(extract_kernel<FRONT_MAX_H, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr_set.fetch_or(dev_bit); }
     extract_kernel<FRONT_MAX_H, false><<<NS, XT, lds, s>>>(A);
   }
   if (fused_out) {
@@ -1118,7 +1110,7 @@ int front_extract_enqueue(Front* f, const rolo_front_params* P, hipStream_t s, f
     concat_kernel<<<NS * 6, 256, 0, s>>>(f->corner_stage, f->corner_cnt, NS * 6, 20, f->corner_out, f->counters + 1);
     concat_kernel<<<NS, 256, 0, s>>>(f->surf_stage, f->surf_cnt, NS, f->maxh, f->surf_out, f->counters + 2);
   }
-  FCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   f->paths_valid = true;
   return ROLO_OK;
 }
@@ -1139,20 +1131,20 @@ int front_frame_features_enqueue(rolo_ctx* c, const rolo_front_params* P, const 
   hipStream_t s = ctx_stream(c);
   const float* d_pts = pts; const unsigned short* d_ring = ring;
   if (!on_device) {
-    FCHK(hipMemcpyAsync(f->raw, pts, sizeof(float) * (size_t)n_raw * stride, hipMemcpyHostToDevice, s));
-    FCHK(hipMemcpyAsync(f->ring, ring, sizeof(uint16_t) * (size_t)n_raw, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(f->raw, pts, sizeof(float) * (size_t)n_raw * stride, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(f->ring, ring, sizeof(uint16_t) * (size_t)n_raw, hipMemcpyHostToDevice, s));
     d_pts = f->raw; d_ring = f->ring;
   }
   if ((rc = front_project_enqueue(f, P, d_pts, stride, d_ring, n_raw, false, s))) return rc;
   if ((rc = front_extract_enqueue(f, P, s, d_feat, h_counts3))) return rc;   // h_counts3 is pinned: the gather kernel writes the counts there itself
-  FCHK(hipGetLastError());
-  if (done) FCHK(hipEventRecord(done, s));
+  HIPCHK(hipGetLastError());
+  if (done) HIPCHK(hipEventRecord(done, s));
   // the next frame's clear, behind this frame's features: nobody reads the per-point arrays of a fused frame any more (its outputs are d_feat
   // and the three counts), and the front-end stream is idle until the next frame arrives — 3.6 us and a kernel boundary off its critical path
   {
     const size_t npix = f->cap_pix;
     front_clear_kernel<<<512, 256, 0, s>>>(f->owner, npix, f->col, f->range, f->curv, f->picked, f->label, npix + 2 * FRONT_GUARD);
-    FCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     f->precleared_np = npix + 2 * FRONT_GUARD;
   }
   f->projected = false;  // the staged rolo_extract_features must not run on top of a fused frame
@@ -1179,11 +1171,11 @@ int front_frame_features_from_msg(rolo_ctx* c, const rolo_front_params* P, const
   const unsigned char* d_data = data;
   if (!on_device) {
     if (bytes > f->cap_msg || !f->msg_raw) { if (!dev_alloc(f->msg_raw, bytes)) { ctx_set_error("hipMalloc failed (message payload)"); return ROLO_EHIP; } f->cap_msg = bytes; }
-    FCHK(hipMemcpyAsync(f->msg_raw, data, bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(f->msg_raw, data, bytes, hipMemcpyHostToDevice, s));
     d_data = f->msg_raw;
   }
   if (n_raw > 0) unpack_cloud_kernel<<<(n_raw + 255) / 256, 256, 0, s>>>(d_data, *L, n_raw, f->msg_xyz, f->msg_ring, f->msg_time);
-  FCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   if (f->deskew_from_msg && L->time_kind != 0) {   // without a time field the projection interpolates the times from the azimuth
     f->deskew_from_msg = false;
     f->deskew.rel_time = f->msg_time;
@@ -1218,7 +1210,7 @@ void rolo_front_destroy(rolo_ctx* c) {
 
 int rolo_front_set_deskew(rolo_ctx* c, const rolo_deskew* d, const float* rel_time, int n_raw, int on_device) {
   if (!c || !d) return ROLO_EINVAL;
-  FCHK(hipSetDevice(ctx_device(c)));
+  HIPCHK(hipSetDevice(ctx_device(c)));
   void** slot = ctx_front_slot(c);
   if (!*slot) *slot = new Front();
   Front* f = static_cast<Front*>(*slot);
@@ -1237,7 +1229,7 @@ int rolo_front_set_deskew(rolo_ctx* c, const rolo_deskew* d, const float* rel_ti
       if (!dev_alloc(f->rel_time, (size_t)n_raw)) { ctx_set_error("hipMalloc failed (de-skew times)"); return ROLO_EHIP; }
       f->cap_time = (size_t)n_raw;
     }
-    FCHK(hipMemcpyAsync(f->rel_time, rel_time, sizeof(float) * (size_t)n_raw, hipMemcpyHostToDevice, ctx_stream(c)));
+    HIPCHK(hipMemcpyAsync(f->rel_time, rel_time, sizeof(float) * (size_t)n_raw, hipMemcpyHostToDevice, ctx_stream(c)));
     dt = f->rel_time;
   }
   f->deskew = DeskewArgs{dt, d->odom_incre_rpy[0], d->odom_incre_rpy[1], d->odom_incre_rpy[2], d->scan_period, d->odom_time_diff};
@@ -1261,21 +1253,21 @@ int rolo_project_frame(rolo_ctx* c, const rolo_front_params* P, const float* pts
   hipStream_t s = ctx_stream(c);
   const int NS = P->n_scan;
   const size_t npix = (size_t)NS * P->horizon_scan;
-  FCHK(hipMemcpyAsync(f->raw, pts, sizeof(float) * (size_t)n_raw * stride, hipMemcpyHostToDevice, s));
-  FCHK(hipMemcpyAsync(f->ring, ring, sizeof(uint16_t) * (size_t)n_raw, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(f->raw, pts, sizeof(float) * (size_t)n_raw * stride, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(f->ring, ring, sizeof(uint16_t) * (size_t)n_raw, hipMemcpyHostToDevice, s));
   if ((rc = front_project_enqueue(f, P, f->raw, stride, f->ring, n_raw, true, s))) return rc;
   int nv = 0;
-  FCHK(hipMemcpyAsync(&nv, f->counters, sizeof(int), hipMemcpyDeviceToHost, s));
-  FCHK(hipStreamSynchronize(s));
+  HIPCHK(hipMemcpyAsync(&nv, f->counters, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   f->n_valid = nv;
   *n_valid = nv;
-  if (extracted && nv) FCHK(hipMemcpyAsync(extracted, f->extracted + FRONT_GUARD, sizeof(float4) * (size_t)nv, hipMemcpyDeviceToHost, s));
-  if (point_col_ind && nv) FCHK(hipMemcpyAsync(point_col_ind, f->col + FRONT_GUARD, sizeof(int) * (size_t)nv, hipMemcpyDeviceToHost, s));
-  if (point_range && nv) FCHK(hipMemcpyAsync(point_range, f->range + FRONT_GUARD, sizeof(float) * (size_t)nv, hipMemcpyDeviceToHost, s));
-  if (start_ring) FCHK(hipMemcpyAsync(start_ring, f->start_ring, sizeof(int) * (size_t)NS, hipMemcpyDeviceToHost, s));
-  if (end_ring) FCHK(hipMemcpyAsync(end_ring, f->end_ring, sizeof(int) * (size_t)NS, hipMemcpyDeviceToHost, s));
-  if (range_mat) FCHK(hipMemcpyAsync(range_mat, f->range_mat, sizeof(float) * npix, hipMemcpyDeviceToHost, s));
-  FCHK(hipStreamSynchronize(s));
+  if (extracted && nv) HIPCHK(hipMemcpyAsync(extracted, f->extracted + FRONT_GUARD, sizeof(float4) * (size_t)nv, hipMemcpyDeviceToHost, s));
+  if (point_col_ind && nv) HIPCHK(hipMemcpyAsync(point_col_ind, f->col + FRONT_GUARD, sizeof(int) * (size_t)nv, hipMemcpyDeviceToHost, s));
+  if (point_range && nv) HIPCHK(hipMemcpyAsync(point_range, f->range + FRONT_GUARD, sizeof(float) * (size_t)nv, hipMemcpyDeviceToHost, s));
+  if (start_ring) HIPCHK(hipMemcpyAsync(start_ring, f->start_ring, sizeof(int) * (size_t)NS, hipMemcpyDeviceToHost, s));
+  if (end_ring) HIPCHK(hipMemcpyAsync(end_ring, f->end_ring, sizeof(int) * (size_t)NS, hipMemcpyDeviceToHost, s));
+  if (range_mat) HIPCHK(hipMemcpyAsync(range_mat, f->range_mat, sizeof(float) * npix, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   f->projected = true;
   return ROLO_OK;
 }
@@ -1310,17 +1302,17 @@ int rolo_front_load_projection(rolo_ctx* c, const rolo_front_params* P, const fl
   const int NS = P->n_scan;
   const size_t np = (size_t)NS * P->horizon_scan + 2 * FRONT_GUARD;
   // guard cells and everything behind N are zero, as after a projection
-  FCHK(hipMemsetAsync(f->col, 0, sizeof(int) * np, s));
-  FCHK(hipMemsetAsync(f->range, 0, sizeof(float) * np, s));
+  HIPCHK(hipMemsetAsync(f->col, 0, sizeof(int) * np, s));
+  HIPCHK(hipMemsetAsync(f->range, 0, sizeof(float) * np, s));
   if (n_valid) {
-    FCHK(hipMemcpyAsync(f->extracted + FRONT_GUARD, extracted, sizeof(float4) * (size_t)n_valid, hipMemcpyHostToDevice, s));
-    FCHK(hipMemcpyAsync(f->col + FRONT_GUARD, point_col_ind, sizeof(int) * (size_t)n_valid, hipMemcpyHostToDevice, s));
-    FCHK(hipMemcpyAsync(f->range + FRONT_GUARD, point_range, sizeof(float) * (size_t)n_valid, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(f->extracted + FRONT_GUARD, extracted, sizeof(float4) * (size_t)n_valid, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(f->col + FRONT_GUARD, point_col_ind, sizeof(int) * (size_t)n_valid, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(f->range + FRONT_GUARD, point_range, sizeof(float) * (size_t)n_valid, hipMemcpyHostToDevice, s));
   }
-  FCHK(hipMemcpyAsync(f->start_ring, start_ring, sizeof(int) * (size_t)NS, hipMemcpyHostToDevice, s));
-  FCHK(hipMemcpyAsync(f->end_ring, end_ring, sizeof(int) * (size_t)NS, hipMemcpyHostToDevice, s));
-  FCHK(hipMemcpyAsync(f->counters, &n_valid, sizeof(int), hipMemcpyHostToDevice, s));
-  FCHK(hipStreamSynchronize(s));   // n_valid is a stack variable; pageable copies are staged anyway
+  HIPCHK(hipMemcpyAsync(f->start_ring, start_ring, sizeof(int) * (size_t)NS, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(f->end_ring, end_ring, sizeof(int) * (size_t)NS, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(f->counters, &n_valid, sizeof(int), hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));   // n_valid is a stack variable; pageable copies are staged anyway
   f->n_valid = n_valid;
   f->projected = true;
   f->extract_cleared = false; f->precleared_np = 0;   // the arrays hold this projection now
@@ -1333,21 +1325,21 @@ int rolo_extract_features(rolo_ctx* c, const rolo_front_params* P, float* corner
   void** slot = ctx_front_slot(c);
   Front* f = static_cast<Front*>(*slot);
   if (!f || !f->projected) { ctx_set_error("rolo_extract_features needs a preceding rolo_project_frame"); return ROLO_ESTATE; }
-  FCHK(hipSetDevice(ctx_device(c)));
+  HIPCHK(hipSetDevice(ctx_device(c)));
   hipStream_t s = ctx_stream(c);
   const int n = f->n_valid;
   int rc = front_extract_enqueue(f, P, s);
   if (rc) return rc;
   int cnts[3] = {0, 0, 0};
-  FCHK(hipMemcpyAsync(cnts, f->counters, sizeof(int) * 3, hipMemcpyDeviceToHost, s));
-  FCHK(hipStreamSynchronize(s));
+  HIPCHK(hipMemcpyAsync(cnts, f->counters, sizeof(int) * 3, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   *n_corner = cnts[1]; *n_surface = cnts[2];
-  if (corner && cnts[1]) FCHK(hipMemcpyAsync(corner, f->corner_out, sizeof(float4) * (size_t)cnts[1], hipMemcpyDeviceToHost, s));
-  if (surface && cnts[2]) FCHK(hipMemcpyAsync(surface, f->surf_out, sizeof(float4) * (size_t)cnts[2], hipMemcpyDeviceToHost, s));
-  if (curvature && n) FCHK(hipMemcpyAsync(curvature, f->curv + FRONT_GUARD, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, s));
-  if (neighbor_picked && n) FCHK(hipMemcpyAsync(neighbor_picked, f->picked + FRONT_GUARD, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s));
-  if (label && n) FCHK(hipMemcpyAsync(label, f->label + FRONT_GUARD, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s));
-  FCHK(hipStreamSynchronize(s));
+  if (corner && cnts[1]) HIPCHK(hipMemcpyAsync(corner, f->corner_out, sizeof(float4) * (size_t)cnts[1], hipMemcpyDeviceToHost, s));
+  if (surface && cnts[2]) HIPCHK(hipMemcpyAsync(surface, f->surf_out, sizeof(float4) * (size_t)cnts[2], hipMemcpyDeviceToHost, s));
+  if (curvature && n) HIPCHK(hipMemcpyAsync(curvature, f->curv + FRONT_GUARD, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, s));
+  if (neighbor_picked && n) HIPCHK(hipMemcpyAsync(neighbor_picked, f->picked + FRONT_GUARD, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s));
+  if (label && n) HIPCHK(hipMemcpyAsync(label, f->label + FRONT_GUARD, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   return ROLO_OK;
 }
 
@@ -1358,10 +1350,10 @@ int rolo_debug_extract_paths(rolo_ctx* c, int32_t* out, int n_scan) {
   Front* f = static_cast<Front*>(*slot);
   if (!f || !f->paths_valid) { ctx_set_error("rolo_debug_extract_paths needs a preceding extraction"); return ROLO_ESTATE; }
   if (n_scan != f->n_scan) { ctx_set_error("rolo_debug_extract_paths: n_scan is not the last projection's"); return ROLO_EINVAL; }
-  FCHK(hipSetDevice(ctx_device(c)));
+  HIPCHK(hipSetDevice(ctx_device(c)));
   hipStream_t s = ctx_stream(c);
-  FCHK(hipMemcpyAsync(out, f->paths, sizeof(int) * (size_t)n_scan, hipMemcpyDeviceToHost, s));
-  FCHK(hipStreamSynchronize(s));
+  HIPCHK(hipMemcpyAsync(out, f->paths, sizeof(int) * (size_t)n_scan, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   return ROLO_OK;
 }
 

@@ -1,19 +1,13 @@
 // The key map's state, shared by the units that work on it: submap.hip (key-frame store, sub-map assembly, voxel filter) and scancontext.hip (Scan Context
-// descriptors of the same key frames). One rule for both: the key map's own stream, buffers that only grow, nothing freed before rolo_keymap_destroy.
+// descriptors of the same key frames). One rule for both: the key map's own stream, buffers that only grow (km->store), nothing freed before rolo_keymap_destroy.
 #pragma once
-#include "rolo_internal.hpp"
-#include <string>
-#include <vector>
+#include "ctx_access.hpp"
 
 namespace rolo {
-void ctx_set_error(const char* msg);
-
 struct Seg { const float4* src; int n; int dst; float T[12]; };   // one key frame's cloud in the concatenation
 struct ScStore;                                                    // scancontext.hip
 void sc_store_destroy(ScStore* sc);                                // frees what the descriptor store holds (rolo_keymap_destroy, after the stream has drained)
 }  // namespace rolo
-
-#define KCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { rolo::ctx_set_error((std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); return ROLO_EHIP; } } while (0)
 
 struct rolo_keymap {
   int device = 0;
@@ -42,7 +36,7 @@ struct rolo_keymap {
   float* h_box = nullptr;            // pinned [2][8]
   int* h_m = nullptr;                // pinned [2]
   rolo::Seg* h_segs = nullptr; size_t h_segs_cap = 0;   // pinned staging of the segment table
-  std::vector<void*> retired, retired_host;   // outgrown scratch buffers (device, pinned host), freed by rolo_keymap_destroy
+  rolo::DevStore store;              // grows the scratch on the key map's stream; its retired buffers are freed by rolo_keymap_destroy
   int m_sub[2] = {0, 0};
   bool have_submap = false;
   rolo::ScStore* sc = nullptr;       // the Scan Context descriptors (scancontext.hip), created by the first rolo_keymap_sc_* call
@@ -57,19 +51,6 @@ struct rolo_keymap {
 };
 
 namespace rolo {
-
-// elements; scratch only grows, and an outgrown buffer is kept until rolo_keymap_destroy: a hipFree is a device-wide synchronisation that would stall the frames
-// other contexts have in flight (scan2map.hip), and work queued on the key map's stream may still read the old buffer. Sizes grow by half: the retired ones
-// together stay below twice the live one.
-template <typename T>
-int km_grow(rolo_keymap* km, T*& p, size_t& cap, size_t need) {
-  if (need <= cap && p) return ROLO_OK;
-  if (p) { km->retired.push_back(p); p = nullptr; cap = 0; }
-  const size_t want = need + need / 2 + 256;
-  if (hipMalloc((void**)&p, want * sizeof(T)) != hipSuccess) { ctx_set_error("hipMalloc failed (keymap)"); return ROLO_EHIP; }
-  cap = want;
-  return ROLO_OK;
-}
 
 // submap.hip: a host cloud (n x 4 floats, 0 < n <= ROLO_KEYMAP_MAX_POINTS) onto the device through the key map's scratch and, with leaf > 0, through the voxel
 // filter (vg_enqueue_box / vg_enqueue_filter) without leaving the device. *d_out (n_out points) is valid on the key map's stream until the next call that

@@ -8,11 +8,12 @@
 // iterations: one wavefront walks the target's tree once for its 64 queries (ballot-driven descent, node boxes and leaves through wave-uniform fetches, as
 // knn_packet.hpp's walk) with ONE best key per lane, (d2, index) packed so that an integer minimum is the nearest point with the smallest index. The search starts
 // at the correspondence cap, so a source point beyond it leaves the tree at the root. The same kernel forms the 17 fp64 sums of the kept pairs and reduces them per
-// workgroup; icp_sum_kernel adds the workgroups' rows in a fixed order into pinned host memory (one 136-byte read-back per iteration, the precedent of scan2map.hip).
-// The 3 x 3 SVD and the convergence tests run on the host in double; icp_transform_kernel multiplies the resident source by the float increment.
+// workgroup; sum_rows (dev_rows.hpp) adds the workgroups' rows in a fixed order into pinned host memory (one 136-byte read-back per iteration, the precedent of scan2map.hip).
+// The 3 x 3 SVD and the convergence tests run on the host in double; icp_transform_kernel (transform12) multiplies the resident source by the float increment.
 // The tree and the walk live in a registration context (its stream, its builder); the scratch hangs off that context, only grows and is freed with it.
 #include "keymap.hpp"
 #include "knn_packet.hpp"
+#include "dev_rows.hpp"
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -20,11 +21,6 @@
 #include <vector>
 
 namespace rolo {
-int ctx_build_map_trees(rolo_ctx* c, const float* corner, int nc, const float* surf, int ns, int stride, KnnPair* out, bool on_device = false);   // api.hip
-void** ctx_loop_slot(rolo_ctx* c);
-hipStream_t ctx_stream(rolo_ctx* c);
-int ctx_device(rolo_ctx* c);
-
 namespace {
 
 constexpr int ICP_THREADS = 256;
@@ -135,37 +131,15 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_assoc_kernel(IcpArgs A) {
   }
 }
 
-// the workgroups' rows summed in a fixed order (the scheme of s2m_sum_kernel: 8 strided groups of 32 lanes, then the groups in order); the 17 sums go straight
-// to pinned host memory
-__global__ __launch_bounds__(256) void icp_sum_kernel(const double* __restrict__ partials, int nblocks, double* __restrict__ out) {
-  __shared__ double part[8][32];
-  const int v = threadIdx.x & 31, q = threadIdx.x >> 5;
-  double s = 0;
-  if (v < ICP_NV) for (int b = q; b < nblocks; b += 8) s += partials[(size_t)b * ICP_NV + v];
-  part[q][v] = s;
-  __syncthreads();
-  if (threadIdx.x < ICP_NV) {
-    double t = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) t += part[k][threadIdx.x];
-    out[threadIdx.x] = t;
-  }
-}
-
 struct Rows12 { float T[12]; };
-// out = T * in, each row T0 x + (T1 y + (T2 z + T3)) in float (km_transform_kernel's statement); w is carried; a padding slot (KEEP_PAD, index INT_MAX) stays as it is
+// out = T * in (transform12); a padding slot (KEEP_PAD, index INT_MAX) stays as it is
 template <bool KEEP_PAD>
 __global__ __launch_bounds__(256) void icp_transform_kernel(const float4* in, float4* out /* may be in */, int n, Rows12 R) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const float4 p = in[i];
   if (KEEP_PAD && __float_as_int(p.w) == INT_MAX) { out[i] = p; return; }
-  float4 o;
-  o.x = R.T[0] * p.x + (R.T[1] * p.y + (R.T[2] * p.z + R.T[3]));
-  o.y = R.T[4] * p.x + (R.T[5] * p.y + (R.T[6] * p.z + R.T[7]));
-  o.z = R.T[8] * p.x + (R.T[9] * p.y + (R.T[10] * p.z + R.T[11]));
-  o.w = p.w;
-  out[i] = o;
+  out[i] = transform12(R.T, p);
 }
 
 // ---- host: Umeyama without scaling, in double ------------------------------------------------------------------------------------------------
@@ -251,33 +225,21 @@ struct LoopIcp {
   double* part = nullptr; size_t part_cap = 0;
   int32_t* idx = nullptr; size_t idx_cap = 0;
   float* d2 = nullptr; size_t d2_cap = 0;
-  double* h_sum = nullptr;          // pinned: the 17 sums of an association, written by icp_sum_kernel
+  double* h_sum = nullptr;          // pinned: the 17 sums of an association, written by sum_rows
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   float ms[4] = {0.f, 0.f, 0.f, 0.f};
-  std::vector<void*> retired;       // outgrown buffers: freed with the context (a hipFree would stall every context's frames in flight)
+  DevStore store{nullptr, "loop ICP"};   // grows the buffers above (nothing is kept across a growth: no stream); what they outgrew is freed with the context
   std::vector<rolo_loopicp_trace_rec> trace;
 };
-
-#define LCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { rolo::ctx_set_error((std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); return ROLO_EHIP; } } while (0)
-
-template <typename T>
-int loop_grow(LoopIcp* W, T*& p, size_t& cap, size_t need) {
-  if (need <= cap && p) return ROLO_OK;
-  if (p) { W->retired.push_back(p); p = nullptr; cap = 0; }
-  const size_t want = need + need / 2 + 256;
-  if (hipMalloc((void**)&p, want * sizeof(T)) != hipSuccess) { ctx_set_error("hipMalloc failed (loop ICP)"); return ROLO_EHIP; }
-  cap = want;
-  return ROLO_OK;
-}
 
 int loop_state(rolo_ctx* c, LoopIcp** out) {
   LoopIcp* W = static_cast<LoopIcp*>(*ctx_loop_slot(c));
   if (!W) {
     W = new LoopIcp();
     *ctx_loop_slot(c) = W;
-    LCHK(hipSetDevice(ctx_device(c)));
-    LCHK(hipHostMalloc((void**)&W->h_sum, sizeof(double) * ICP_NV));
-    for (int i = 0; i < 4; i++) LCHK(hipEventCreate(&W->ev[i]));
+    HIPCHK(hipSetDevice(ctx_device(c)));
+    HIPCHK(hipHostMalloc((void**)&W->h_sum, sizeof(double) * ICP_NV));
+    for (int i = 0; i < 4; i++) HIPCHK(hipEventCreate(&W->ev[i]));
   }
   *out = W;
   return ROLO_OK;
@@ -294,19 +256,19 @@ int loop_setup(rolo_ctx* c, LoopIcp* W, const float4* d_src, int ns, const float
   int rc;
   const float4* moved = d_src;
   if (T16 && !is_identity16(T16)) {
-    if ((rc = loop_grow(W, W->srcg, W->srcg_cap, (size_t)ns))) return rc;
+    if ((rc = W->store.grow(W->srcg, W->srcg_cap, (size_t)ns))) return rc;
     Rows12 R; std::memcpy(R.T, T16, sizeof(R.T));
     icp_transform_kernel<false><<<(ns + 255) / 256, 256, 0, s>>>(d_src, W->srcg, ns, R);
-    LCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     moved = W->srcg;
   }
   KnnPair pair{};
   if ((rc = ctx_build_map_trees(c, reinterpret_cast<const float*>(d_tgt), nt, reinterpret_cast<const float*>(moved), ns, 4, &pair, true))) return rc;
   const int n_sorted = pair.c[1].n_sorted;
   *grid = (n_sorted + ICP_THREADS - 1) / ICP_THREADS;
-  if ((rc = loop_grow(W, W->cur, W->cur_cap, (size_t)n_sorted))) return rc;
-  if ((rc = loop_grow(W, W->part, W->part_cap, (size_t)*grid * ICP_NV))) return rc;
-  LCHK(hipMemcpyAsync(W->cur, pair.c[1].sorted, sizeof(float4) * (size_t)n_sorted, hipMemcpyDeviceToDevice, s));
+  if ((rc = W->store.grow(W->cur, W->cur_cap, (size_t)n_sorted))) return rc;
+  if ((rc = W->store.grow(W->part, W->part_cap, (size_t)*grid * ICP_NV))) return rc;
+  HIPCHK(hipMemcpyAsync(W->cur, pair.c[1].sorted, sizeof(float4) * (size_t)n_sorted, hipMemcpyDeviceToDevice, s));
   *A = IcpArgs{};
   A->cur = W->cur; A->n_sorted = n_sorted; A->tsorted = pair.c[0].sorted; A->tboxes = pair.c[0].boxes; A->txyz = pair.c[0].xyz; A->P = pair.c[0].P;
   A->n_leaves = pair.c[0].n_leaves; A->partials = W->part;
@@ -317,10 +279,10 @@ int loop_setup(rolo_ctx* c, LoopIcp* W, const float4* d_src, int ns, const float
 int loop_associate(rolo_ctx* c, LoopIcp* W, const IcpArgs& A, int grid) {
   hipStream_t s = ctx_stream(c);
   icp_assoc_kernel<<<grid, ICP_THREADS, 0, s>>>(A);
-  LCHK(hipGetLastError());
-  icp_sum_kernel<<<1, 256, 0, s>>>(A.partials, grid, W->h_sum);
-  LCHK(hipGetLastError());
-  LCHK(hipStreamSynchronize(s));
+  HIPCHK(hipGetLastError());
+  sum_rows<ICP_NV, 1><<<1, 256, 0, s>>>(A.partials, grid, W->h_sum);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(s));
   return ROLO_OK;
 }
 
@@ -340,7 +302,7 @@ int loop_align(rolo_ctx* c, const float4* d_src, int ns, const float4* d_tgt, in
   int rc = loop_state(c, &W);
   if (rc) return rc;
   if (!(P->max_correspondence_distance >= 0.0) || P->max_iterations < 0) { ctx_set_error("loop ICP: bad parameters"); return ROLO_EINVAL; }
-  LCHK(hipSetDevice(ctx_device(c)));
+  HIPCHK(hipSetDevice(ctx_device(c)));
   hipStream_t s = ctx_stream(c);
   rolo_loopicp_result res{};
   for (int i = 0; i < 16; i++) res.T[i] = guess16 ? guess16[i] : ((i % 5 == 0) ? 1.f : 0.f);
@@ -348,11 +310,11 @@ int loop_align(rolo_ctx* c, const float4* d_src, int ns, const float4* d_tgt, in
   W->trace.clear();
   for (float& m : W->ms) m = 0.f;
   if (ns <= 0 || nt <= 0) { res.state = ROLO_ICP_NO_CORRESPONDENCES; *out = res; return ROLO_OK; }
-  LCHK(hipEventRecord(W->ev[0], s));
+  HIPCHK(hipEventRecord(W->ev[0], s));
   IcpArgs A{};
   int grid = 0;
   if ((rc = loop_setup(c, W, d_src, ns, d_tgt, nt, guess16, &A, &grid))) return rc;
-  LCHK(hipEventRecord(W->ev[1], s));
+  HIPCHK(hipEventRecord(W->ev[1], s));
   A.cap2 = cap2_float(P->max_correspondence_distance);
   const double rot_thr = P->rotation_epsilon > 0 ? P->rotation_epsilon : 1.0 - P->transformation_epsilon;
   double prev = DBL_MAX;
@@ -373,7 +335,7 @@ int loop_align(rolo_ctx* c, const float4* d_src, int ns, const float4* d_tgt, in
     W->trace.push_back(tr);
     Rows12 Rw; std::memcpy(Rw.T, inc, sizeof(Rw.T));
     icp_transform_kernel<true><<<(A.n_sorted + 255) / 256, 256, 0, s>>>(W->cur, W->cur, A.n_sorted, Rw);
-    LCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     matmul4f(inc, res.T, res.T);
     res.iterations++;
     const double cosa = 0.5 * ((double)inc[0] + (double)inc[5] + (double)inc[10] - 1.0);
@@ -385,7 +347,7 @@ int loop_align(rolo_ctx* c, const float4* d_src, int ns, const float4* d_tgt, in
     if (std::fabs(mse - prev) / prev < P->euclidean_fitness_epsilon) { res.state = ROLO_ICP_REL_MSE; res.converged = 1; break; }
     prev = mse;
   }
-  LCHK(hipEventRecord(W->ev[2], s));
+  HIPCHK(hipEventRecord(W->ev[2], s));
   {   // getFitnessScore(): the moved source as it stands, no cap
     A.cap2 = INFINITY;
     if ((rc = loop_associate(c, W, A, grid))) return rc;
@@ -395,8 +357,8 @@ int loop_align(rolo_ctx* c, const float4* d_src, int ns, const float4* d_tgt, in
     W->trace.push_back(tr);
     res.fitness = tr.n > 0 ? tr.mse : DBL_MAX;
   }
-  LCHK(hipEventRecord(W->ev[3], s));
-  LCHK(hipEventSynchronize(W->ev[3]));
+  HIPCHK(hipEventRecord(W->ev[3], s));
+  HIPCHK(hipEventSynchronize(W->ev[3]));
   (void)hipEventElapsedTime(&W->ms[0], W->ev[0], W->ev[1]);
   (void)hipEventElapsedTime(&W->ms[1], W->ev[1], W->ev[2]);
   (void)hipEventElapsedTime(&W->ms[2], W->ev[2], W->ev[3]);
@@ -407,11 +369,11 @@ int loop_align(rolo_ctx* c, const float4* d_src, int ns, const float4* d_tgt, in
 
 int loop_upload(rolo_ctx* c, LoopIcp* W, const float* src, int ns, const float* tgt, int nt) {
   int rc;
-  if ((rc = loop_grow(W, W->src, W->src_cap, (size_t)std::max(ns, 1)))) return rc;
-  if ((rc = loop_grow(W, W->tgt, W->tgt_cap, (size_t)std::max(nt, 1)))) return rc;
+  if ((rc = W->store.grow(W->src, W->src_cap, (size_t)std::max(ns, 1)))) return rc;
+  if ((rc = W->store.grow(W->tgt, W->tgt_cap, (size_t)std::max(nt, 1)))) return rc;
   hipStream_t s = ctx_stream(c);
-  if (ns > 0) LCHK(hipMemcpyAsync(W->src, src, sizeof(float4) * (size_t)ns, hipMemcpyHostToDevice, s));
-  if (nt > 0) LCHK(hipMemcpyAsync(W->tgt, tgt, sizeof(float4) * (size_t)nt, hipMemcpyHostToDevice, s));
+  if (ns > 0) HIPCHK(hipMemcpyAsync(W->src, src, sizeof(float4) * (size_t)ns, hipMemcpyHostToDevice, s));
+  if (nt > 0) HIPCHK(hipMemcpyAsync(W->tgt, tgt, sizeof(float4) * (size_t)nt, hipMemcpyHostToDevice, s));
   return ROLO_OK;
 }
 
@@ -434,7 +396,7 @@ void rolo_loopicp_destroy(rolo_ctx* c) {   // called by rolo_ctx_destroy
   LoopIcp* W = static_cast<LoopIcp*>(*ctx_loop_slot(c));
   if (!W) return;
   for (void* p : {(void*)W->src, (void*)W->tgt, (void*)W->srcg, (void*)W->cur, (void*)W->part, (void*)W->idx, (void*)W->d2}) if (p) (void)hipFree(p);
-  for (void* p : W->retired) (void)hipFree(p);
+  W->store.release();
   if (W->h_sum) (void)hipHostFree(W->h_sum);
   for (hipEvent_t e : W->ev) if (e) (void)hipEventDestroy(e);
   delete W;
@@ -459,7 +421,7 @@ int rolo_loopicp_align(rolo_ctx* c, const float* source, int n_source, const flo
   LoopIcp* W = nullptr;
   int rc = loop_state(c, &W);
   if (rc) return rc;
-  LCHK(hipSetDevice(ctx_device(c)));
+  HIPCHK(hipSetDevice(ctx_device(c)));
   if ((rc = loop_upload(c, W, source, n_source, target, n_target))) return rc;
   rc = loop_align(c, W->src, n_source, W->tgt, n_target, params, guess16, out);
   if (rc) (void)hipStreamSynchronize(ctx_stream(c));   // the caller's arrays are free again, whatever happened
@@ -492,11 +454,11 @@ int rolo_loopicp_associate(rolo_ctx* c, const float* source, int n_source, const
   LoopIcp* W = nullptr;
   int rc = loop_state(c, &W);
   if (rc) return rc;
-  LCHK(hipSetDevice(ctx_device(c)));
+  HIPCHK(hipSetDevice(ctx_device(c)));
   hipStream_t s = ctx_stream(c);
   if ((rc = loop_upload(c, W, source, n_source, target, n_target))) return rc;
-  if ((rc = loop_grow(W, W->idx, W->idx_cap, (size_t)n_source))) return rc;
-  if ((rc = loop_grow(W, W->d2, W->d2_cap, (size_t)n_source))) return rc;
+  if ((rc = W->store.grow(W->idx, W->idx_cap, (size_t)n_source))) return rc;
+  if ((rc = W->store.grow(W->d2, W->d2_cap, (size_t)n_source))) return rc;
   IcpArgs A{};
   int grid = 0;
   W->trace.clear();
@@ -509,9 +471,9 @@ int rolo_loopicp_associate(rolo_ctx* c, const float* source, int n_source, const
   tr.n = (int)(W->h_sum[0] + 0.5); tr.mse = tr.n > 0 ? W->h_sum[1] / tr.n : 0.0;
   std::memcpy(tr.sums, W->h_sum, sizeof(tr.sums));
   W->trace.push_back(tr);
-  LCHK(hipMemcpyAsync(index_out, W->idx, sizeof(int32_t) * (size_t)n_source, hipMemcpyDeviceToHost, s));
-  LCHK(hipMemcpyAsync(d2_out, W->d2, sizeof(float) * (size_t)n_source, hipMemcpyDeviceToHost, s));
-  LCHK(hipStreamSynchronize(s));
+  HIPCHK(hipMemcpyAsync(index_out, W->idx, sizeof(int32_t) * (size_t)n_source, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(d2_out, W->d2, sizeof(float) * (size_t)n_source, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   return ROLO_OK;
 }
 

@@ -5,21 +5,13 @@
 // (rolo_register_async / rolo_register_wait: both LM stages enqueued back to back, one host wait per frame).
 // The fp32 pose algebra restates pcl::getTransformation / getTranslationAndEulerAngles / Eigen::Affine3f products
 // (PCL, Eigen: not vendored by the reference).
-#include "rolo_internal.hpp"
+#include "ctx_access.hpp"
 #include "switches.hpp"
 #include "polar_f32.hpp"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-
-namespace rolo {
-void ctx_set_error(const char* msg);
-int ctx_device(rolo_ctx* c);
-void ctx_set_fused_lm(rolo_ctx* c, int on);
-int ctx_create_high_priority(int device, rolo_ctx** out);
-int ctx_set_pair_device(rolo_ctx* c, const float* d_src, int n_src, int stride_src, const float* T16_host_or_null, const float* d_tgt, int n_tgt, int stride_tgt);
-}
 
 namespace {
 

@@ -14,7 +14,7 @@
 //   pgo_factor_error_kernel  one factor per thread: r^2 = |e / sigma|^2 and the loss's weight at the current poses, for rolo_pgo_get_factor_errors
 // The Levenberg-Marquardt controller runs on the host in double with one small read-back per trial (cost, PCG iterations, residual) through pinned memory.
 // Every loop is bounded: PCG by its cap, the trials by PGO_MAX_TRIALS and the lambda bound. A graph works on a stream of its own; its device store only grows.
-#include "rolo_internal.hpp"
+#include "ctx_access.hpp"
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -22,7 +22,6 @@
 #include <algorithm>
 
 namespace rolo {
-void ctx_set_error(const char* msg);
 namespace {
 
 constexpr int PGO_SLOT = 121;        // gi 6, gj 6, Hii 36, Hjj 36, Hij 36, cost 1
@@ -832,8 +831,6 @@ __global__ __launch_bounds__(PGO_GRID_THREADS) void pgo_grid_finish_kernel(Solve
 
 using namespace rolo;
 
-#define PCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { rolo::ctx_set_error((std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); return ROLO_EHIP; } } while (0)
-
 struct rolo_pgo {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -866,49 +863,37 @@ struct rolo_pgo {
   int solve_form = ROLO_PGO_SOLVE_AUTO, last_form = 0;
   hipEvent_t gev[3] = {nullptr, nullptr, nullptr};   // the grid form: before the factorisation, between it and PCG, after PCG
   double* h_info = nullptr;                // pinned: [0] cost, [1..5] the solve's info, [6] the grid form's done word
-  std::vector<void*> retired;
+  DevStore store;                          // grows the device store on the graph's stream
   float ms[4] = {0.f, 0.f, 0.f, 0.f};
   std::vector<rolo_pgo_trace_rec> trace;
 };
 
 namespace {
 
-template <typename T>
-int pgo_grow(rolo_pgo* g, T*& p, size_t& cap, size_t need, size_t keep = 0) {   // keep: elements of the old buffer copied over on the graph's stream
-  if (need <= cap && p) return ROLO_OK;
-  const size_t want = need + need / 2 + 64;
-  T* q = nullptr;
-  if (hipMalloc((void**)&q, want * sizeof(T)) != hipSuccess) { ctx_set_error("hipMalloc failed (pose graph)"); return ROLO_EHIP; }
-  if (p && keep) PCHK(hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, g->stream));
-  if (p) g->retired.push_back(p);
-  p = q; cap = want;
-  return ROLO_OK;
-}
-
 bool finite_n(const double* v, int n) { for (int i = 0; i < n; i++) if (!std::isfinite(v[i])) return false; return true; }
 
 // what the host has added since the last call goes to the device: new poses, new factors, the changed tail of the incidence list, the chord tables
 int pgo_sync_graph(rolo_pgo* g) {
-  PCHK(hipSetDevice(g->device));
+  HIPCHK(hipSetDevice(g->device));
   hipStream_t s = g->stream;
   int rc;
   const int N = g->N, F = (int)g->factors.size();
   if (g->up_poses < N) {
-    if ((rc = pgo_grow(g, g->poses, g->poses_cap, 12 * (size_t)N, 12 * (size_t)g->up_poses))) return rc;
-    PCHK(hipMemcpyAsync(g->poses + 12 * (size_t)g->up_poses, g->pending.data(), sizeof(double) * g->pending.size(), hipMemcpyHostToDevice, s));
+    if ((rc = g->store.grow(g->poses, g->poses_cap, 12 * (size_t)N, 12 * (size_t)g->up_poses))) return rc;
+    HIPCHK(hipMemcpyAsync(g->poses + 12 * (size_t)g->up_poses, g->pending.data(), sizeof(double) * g->pending.size(), hipMemcpyHostToDevice, s));
   }
-  if ((rc = pgo_grow(g, g->trial, g->trial_cap, 12 * (size_t)N))) return rc;
+  if ((rc = g->store.grow(g->trial, g->trial_cap, 12 * (size_t)N))) return rc;
   if (g->up_factors < F) {
     const size_t cap0 = g->factors_cap;
-    if ((rc = pgo_grow(g, g->d_factors, g->factors_cap, (size_t)F))) return rc;
+    if ((rc = g->store.grow(g->d_factors, g->factors_cap, (size_t)F))) return rc;
     const int from = g->factors_cap != cap0 ? 0 : g->up_factors;
-    PCHK(hipMemcpyAsync(g->d_factors + from, g->factors.data() + from, sizeof(PgoFactor) * (size_t)(F - from), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(g->d_factors + from, g->factors.data() + from, sizeof(PgoFactor) * (size_t)(F - from), hipMemcpyHostToDevice, s));
   }
-  if ((rc = pgo_grow(g, g->slots, g->slots_cap, (size_t)PGO_SLOT * std::max(F, 1)))) return rc;
+  if ((rc = g->store.grow(g->slots, g->slots_cap, (size_t)PGO_SLOT * std::max(F, 1)))) return rc;
   if (g->dirty_from < N || (int)g->h_rowptr.size() != N + 1) {
     const size_t c0 = g->rowptr_cap, c1 = g->entries_cap;
-    if ((rc = pgo_grow(g, g->rowptr, g->rowptr_cap, (size_t)N + 1))) return rc;
-    if ((rc = pgo_grow(g, g->entries, g->entries_cap, 2 * (size_t)std::max(F, 1)))) return rc;
+    if ((rc = g->store.grow(g->rowptr, g->rowptr_cap, (size_t)N + 1))) return rc;
+    if ((rc = g->store.grow(g->entries, g->entries_cap, 2 * (size_t)std::max(F, 1)))) return rc;
     int from = std::min(g->dirty_from, std::max((int)g->h_rowptr.size() - 1, 0));
     if (g->rowptr_cap != c0 || g->entries_cap != c1) from = 0;
     g->h_rowptr.resize((size_t)N + 1);
@@ -916,9 +901,9 @@ int pgo_sync_graph(rolo_pgo* g) {
     g->h_entries.resize((size_t)e0);
     for (int k = from; k < N; k++) { g->h_rowptr[k] = (int)g->h_entries.size(); g->h_entries.insert(g->h_entries.end(), g->inc[k].begin(), g->inc[k].end()); }
     g->h_rowptr[N] = (int)g->h_entries.size();
-    PCHK(hipMemcpyAsync(g->rowptr + from, g->h_rowptr.data() + from, sizeof(int) * (size_t)(N + 1 - from), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(g->rowptr + from, g->h_rowptr.data() + from, sizeof(int) * (size_t)(N + 1 - from), hipMemcpyHostToDevice, s));
     if ((int)g->h_entries.size() > e0)
-      PCHK(hipMemcpyAsync(g->entries + e0, g->h_entries.data() + e0, sizeof(int) * (g->h_entries.size() - (size_t)e0), hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(g->entries + e0, g->h_entries.data() + e0, sizeof(int) * (g->h_entries.size() - (size_t)e0), hipMemcpyHostToDevice, s));
   }
   const int nc = (int)g->chord_factor.size();
   std::vector<int> touched, tptr, tent;
@@ -932,34 +917,34 @@ int pgo_sync_graph(rolo_pgo* g) {
     }
     tptr.push_back((int)ends.size());
     g->n_touched = (int)touched.size();
-    if ((rc = pgo_grow(g, g->d_chord_factor, g->d_chord_factor_cap, (size_t)nc))) return rc;
-    if ((rc = pgo_grow(g, g->d_chord_ij, g->d_chord_ij_cap, 2 * (size_t)nc))) return rc;
-    if ((rc = pgo_grow(g, g->touched, g->touched_cap, touched.size()))) return rc;
-    if ((rc = pgo_grow(g, g->touched_ptr, g->touched_ptr_cap, tptr.size()))) return rc;
-    if ((rc = pgo_grow(g, g->touched_ent, g->touched_ent_cap, tent.size()))) return rc;
-    PCHK(hipMemcpyAsync(g->d_chord_factor, g->chord_factor.data(), sizeof(int) * (size_t)nc, hipMemcpyHostToDevice, s));
-    PCHK(hipMemcpyAsync(g->d_chord_ij, g->chord_ij.data(), sizeof(int) * 2 * (size_t)nc, hipMemcpyHostToDevice, s));
-    PCHK(hipMemcpyAsync(g->touched, touched.data(), sizeof(int) * touched.size(), hipMemcpyHostToDevice, s));
-    PCHK(hipMemcpyAsync(g->touched_ptr, tptr.data(), sizeof(int) * tptr.size(), hipMemcpyHostToDevice, s));
-    PCHK(hipMemcpyAsync(g->touched_ent, tent.data(), sizeof(int) * tent.size(), hipMemcpyHostToDevice, s));
+    if ((rc = g->store.grow(g->d_chord_factor, g->d_chord_factor_cap, (size_t)nc))) return rc;
+    if ((rc = g->store.grow(g->d_chord_ij, g->d_chord_ij_cap, 2 * (size_t)nc))) return rc;
+    if ((rc = g->store.grow(g->touched, g->touched_cap, touched.size()))) return rc;
+    if ((rc = g->store.grow(g->touched_ptr, g->touched_ptr_cap, tptr.size()))) return rc;
+    if ((rc = g->store.grow(g->touched_ent, g->touched_ent_cap, tent.size()))) return rc;
+    HIPCHK(hipMemcpyAsync(g->d_chord_factor, g->chord_factor.data(), sizeof(int) * (size_t)nc, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(g->d_chord_ij, g->chord_ij.data(), sizeof(int) * 2 * (size_t)nc, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(g->touched, touched.data(), sizeof(int) * touched.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(g->touched_ptr, tptr.data(), sizeof(int) * tptr.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(g->touched_ent, tent.data(), sizeof(int) * tent.size(), hipMemcpyHostToDevice, s));
   }
-  if ((rc = pgo_grow(g, g->chordH, g->chordH_cap, 36 * (size_t)std::max(nc, 1)))) return rc;
-  if ((rc = pgo_grow(g, g->cscr, g->cscr_cap, 12 * (size_t)std::max(nc, 1)))) return rc;
-  if ((rc = pgo_grow(g, g->diag, g->diag_cap, 36 * (size_t)N))) return rc;
-  if ((rc = pgo_grow(g, g->chain, g->chain_cap, 36 * (size_t)N))) return rc;
-  if ((rc = pgo_grow(g, g->grad, g->grad_cap, 6 * (size_t)N))) return rc;
-  if ((rc = pgo_grow(g, g->delta, g->delta_cap, 6 * (size_t)N))) return rc;
-  for (int v = 0; v < 5; v++) if ((rc = pgo_grow(g, g->vec[v], g->vec_cap[v], 6 * (size_t)N))) return rc;
+  if ((rc = g->store.grow(g->chordH, g->chordH_cap, 36 * (size_t)std::max(nc, 1)))) return rc;
+  if ((rc = g->store.grow(g->cscr, g->cscr_cap, 12 * (size_t)std::max(nc, 1)))) return rc;
+  if ((rc = g->store.grow(g->diag, g->diag_cap, 36 * (size_t)N))) return rc;
+  if ((rc = g->store.grow(g->chain, g->chain_cap, 36 * (size_t)N))) return rc;
+  if ((rc = g->store.grow(g->grad, g->grad_cap, 6 * (size_t)N))) return rc;
+  if ((rc = g->store.grow(g->delta, g->delta_cap, 6 * (size_t)N))) return rc;
+  for (int v = 0; v < 5; v++) if ((rc = g->store.grow(g->vec[v], g->vec_cap[v], 6 * (size_t)N))) return rc;
   int M = 1;
   while (M < N) M <<= 1;
-  if ((rc = pgo_grow(g, g->LD, g->LD_cap, 72 * (size_t)M))) return rc;
-  if ((rc = pgo_grow(g, g->LU, g->LU_cap, 72 * (size_t)M))) return rc;
-  if ((rc = pgo_grow(g, g->LW, g->LW_cap, 72 * (size_t)M))) return rc;
-  if ((rc = pgo_grow(g, g->B, g->B_cap, 12 * (size_t)M))) return rc;
-  if ((rc = pgo_grow(g, g->X, g->X_cap, 12 * (size_t)M))) return rc;
-  if ((rc = pgo_grow(g, g->gst, g->gst_cap, (size_t)PGO_ST_WORDS + PGO_SOLVE_THREADS))) return rc;
-  if ((rc = pgo_grow(g, g->partials, g->partials_cap, (size_t)(std::max(N, F) + PGO_FACTOR_THREADS - 1) / PGO_FACTOR_THREADS + 1))) return rc;
-  PCHK(hipStreamSynchronize(s));   // the host vectors are free again
+  if ((rc = g->store.grow(g->LD, g->LD_cap, 72 * (size_t)M))) return rc;
+  if ((rc = g->store.grow(g->LU, g->LU_cap, 72 * (size_t)M))) return rc;
+  if ((rc = g->store.grow(g->LW, g->LW_cap, 72 * (size_t)M))) return rc;
+  if ((rc = g->store.grow(g->B, g->B_cap, 12 * (size_t)M))) return rc;
+  if ((rc = g->store.grow(g->X, g->X_cap, 12 * (size_t)M))) return rc;
+  if ((rc = g->store.grow(g->gst, g->gst_cap, (size_t)PGO_ST_WORDS + PGO_SOLVE_THREADS))) return rc;
+  if ((rc = g->store.grow(g->partials, g->partials_cap, (size_t)(std::max(N, F) + PGO_FACTOR_THREADS - 1) / PGO_FACTOR_THREADS + 1))) return rc;
+  HIPCHK(hipStreamSynchronize(s));   // the host vectors are free again
   g->pending.clear();
   g->up_poses = N; g->up_factors = F; g->dirty_from = N; g->chords_dirty = false;
   return ROLO_OK;
@@ -970,12 +955,12 @@ int pgo_enqueue_linearize(rolo_pgo* g) {
   hipStream_t s = g->stream;
   const int N = g->N, F = (int)g->factors.size(), nc = (int)g->chord_factor.size();
   pgo_linearize_kernel<<<(F + PGO_FACTOR_THREADS - 1) / PGO_FACTOR_THREADS, PGO_FACTOR_THREADS, 0, s>>>(g->d_factors, F, g->poses, g->slots);
-  PCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   pgo_assemble_kernel<<<(N + PGO_ASM_POSES - 1) / PGO_ASM_POSES, 256, 0, s>>>(g->slots, g->rowptr, g->entries, N, g->diag, g->chain, g->grad);
-  PCHK(hipGetLastError());
-  if (nc) { pgo_chord_kernel<<<(36 * nc + 255) / 256, 256, 0, s>>>(g->slots, g->d_chord_factor, nc, g->chordH); PCHK(hipGetLastError()); }
+  HIPCHK(hipGetLastError());
+  if (nc) { pgo_chord_kernel<<<(36 * nc + 255) / 256, 256, 0, s>>>(g->slots, g->d_chord_factor, nc, g->chordH); HIPCHK(hipGetLastError()); }
   pgo_sum_kernel<<<1, PGO_SUM_THREADS, 0, s>>>(g->slots, PGO_SLOT, 120, F, g->h_info);
-  PCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return ROLO_OK;
 }
 
@@ -993,62 +978,62 @@ int pgo_enqueue_solve_grid(rolo_pgo* g, const SolveArgs& S) {
   int l0 = 0;   // the first level that the fused top takes
   while ((S.M >> l0) > PGO_GRID_TOP) l0++;
   const auto apply = [&](double* dst) -> int {   // dst = T^-1 (the right-hand side in B)
-    for (int l = 0; l < l0; l++) { pgo_grid_down_kernel<<<blocks(S.M >> (l + 1), PGO_GRID_TILE), T, 0, s>>>(S, l); PCHK(hipGetLastError()); }
+    for (int l = 0; l < l0; l++) { pgo_grid_down_kernel<<<blocks(S.M >> (l + 1), PGO_GRID_TILE), T, 0, s>>>(S, l); HIPCHK(hipGetLastError()); }
     pgo_grid_top_apply_kernel<<<1, PGO_SOLVE_THREADS, 0, s>>>(S, l0, dst);
-    PCHK(hipGetLastError());
-    for (int l = l0 - 1; l >= 0; l--) { pgo_grid_up_kernel<<<blocks(S.M >> (l + 1), PGO_GRID_TILE), T, 0, s>>>(S, l, dst); PCHK(hipGetLastError()); }
+    HIPCHK(hipGetLastError());
+    for (int l = l0 - 1; l >= 0; l--) { pgo_grid_up_kernel<<<blocks(S.M >> (l + 1), PGO_GRID_TILE), T, 0, s>>>(S, l, dst); HIPCHK(hipGetLastError()); }
     return ROLO_OK;
   };
   const auto dot = [&](const double* a, const double* b, int which) -> int {
     pgo_grid_lanes_kernel<<<PGO_SOLVE_THREADS / PGO_GRID_LANE_WG, PGO_GRID_LANE_WG, 0, s>>>(S, a, b);
-    PCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     pgo_grid_scalar_kernel<<<1, PGO_SOLVE_THREADS, 0, s>>>(S, which);
-    PCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return ROLO_OK;
   };
   int rc;
-  PCHK(hipEventRecord(g->gev[0], s));
+  HIPCHK(hipEventRecord(g->gev[0], s));
   pgo_grid_fill_kernel<<<blocks(36 * S.M, T), T, 0, s>>>(S);
-  PCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   for (int l = 0; l < l0; l++) {
     const int nn = S.M >> (l + 1);
     pgo_grid_inv_kernel<<<blocks(nn, 64), 64, 0, s>>>(S, l);
-    PCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     pgo_grid_reduce_kernel<<<blocks(nn, PGO_GRID_TILE), T, 0, s>>>(S, l);
-    PCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
   pgo_grid_top_factor_kernel<<<1, PGO_SOLVE_THREADS, 0, s>>>(S, l0);
-  PCHK(hipGetLastError());
-  PCHK(hipEventRecord(g->gev[1], s));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(g->gev[1], s));
   pgo_grid_start_kernel<<<blocks(6 * S.M, T), T, 0, s>>>(S);
-  PCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   if ((rc = apply(S.z))) return rc;
   if ((rc = dot(S.r, S.z, PGO_DOT_RZ0))) return rc;
   pgo_grid_dir_kernel<<<blocks(6 * S.N, T), T, 0, s>>>(S, 1);
-  PCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   for (int it = 0; it < S.pcg_cap;) {
     const int batch = std::min(PGO_GRID_BATCH, S.pcg_cap - it);
     for (int k = 0; k < batch; k++) {
       pgo_grid_mv_kernel<<<blocks(std::max(6 * S.N, 12 * S.n_chords), T), T, 0, s>>>(S);
-      PCHK(hipGetLastError());
-      if (S.n_touched) { pgo_grid_gather_kernel<<<blocks(6 * S.n_touched, T), T, 0, s>>>(S); PCHK(hipGetLastError()); }
+      HIPCHK(hipGetLastError());
+      if (S.n_touched) { pgo_grid_gather_kernel<<<blocks(6 * S.n_touched, T), T, 0, s>>>(S); HIPCHK(hipGetLastError()); }
       if ((rc = dot(S.p, S.q, PGO_DOT_PQ))) return rc;
       pgo_grid_step_kernel<<<blocks(6 * S.N, T), T, 0, s>>>(S);
-      PCHK(hipGetLastError());
+      HIPCHK(hipGetLastError());
       if ((rc = apply(S.z))) return rc;
       if ((rc = dot(S.r, S.z, PGO_DOT_RZ))) return rc;
       pgo_grid_dir_kernel<<<blocks(6 * S.N, T), T, 0, s>>>(S, 0);
-      PCHK(hipGetLastError());
+      HIPCHK(hipGetLastError());
     }
     it += batch;
     if (it < S.pcg_cap) {
-      PCHK(hipStreamSynchronize(s));
+      HIPCHK(hipStreamSynchronize(s));
       if (*(volatile double*)S.done != 0.0) break;
     }
   }
   pgo_grid_finish_kernel<<<blocks(6 * S.N, T), T, 0, s>>>(S);
-  PCHK(hipGetLastError());
-  PCHK(hipEventRecord(g->gev[2], s));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(g->gev[2], s));
   return ROLO_OK;
 }
 
@@ -1068,7 +1053,7 @@ int pgo_enqueue_solve(rolo_pgo* g, double lambda, double tol, int pcg_max) {
   g->last_form = form;
   if (form == ROLO_PGO_SOLVE_GRID) return pgo_enqueue_solve_grid(g, S);
   pgo_solve_kernel<<<1, PGO_SOLVE_THREADS, 0, g->stream>>>(S);
-  PCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return ROLO_OK;
 }
 
@@ -1113,7 +1098,7 @@ int rolo_pgo_create(int device, rolo_pgo** out) {
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) { ctx_set_error("no HIP device"); return ROLO_EHIP; }
   if (device < 0 || device >= count) return ROLO_EINVAL;
-  PCHK(hipSetDevice(device));
+  HIPCHK(hipSetDevice(device));
   rolo_pgo* g = new rolo_pgo();
   g->device = device;
   int khz = 0;
@@ -1125,6 +1110,7 @@ int rolo_pgo_create(int device, rolo_pgo** out) {
     rolo_pgo_destroy(g);
     return ROLO_EHIP;
   }
+  g->store.stream = g->stream; g->store.who = "pose graph"; g->store.slack = 64;
   *out = g;
   return ROLO_OK;
 }
@@ -1138,7 +1124,7 @@ void rolo_pgo_destroy(rolo_pgo* g) {
                   (void*)g->LW, (void*)g->B, (void*)g->X, (void*)g->vec[0], (void*)g->vec[1], (void*)g->vec[2], (void*)g->vec[3], (void*)g->vec[4], (void*)g->cscr, (void*)g->delta,
                   (void*)g->partials, (void*)g->ferr, (void*)g->gst})
     if (p) (void)hipFree(p);
-  for (void* p : g->retired) (void)hipFree(p);
+  g->store.release();
   if (g->h_info) (void)hipHostFree(g->h_info);
   for (hipEvent_t e : g->ev) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : g->gev) if (e) (void)hipEventDestroy(e);
@@ -1228,11 +1214,11 @@ int rolo_pgo_linearize(rolo_pgo* g, double* cost, double* grad, double* diag, do
   if ((rc = pgo_enqueue_linearize(g))) return rc;
   hipStream_t s = g->stream;
   const size_t N = (size_t)g->N, nc = g->chord_factor.size();
-  if (grad) PCHK(hipMemcpyAsync(grad, g->grad, sizeof(double) * 6 * N, hipMemcpyDeviceToHost, s));
-  if (diag) PCHK(hipMemcpyAsync(diag, g->diag, sizeof(double) * 36 * N, hipMemcpyDeviceToHost, s));
-  if (chain && N > 1) PCHK(hipMemcpyAsync(chain, g->chain, sizeof(double) * 36 * (N - 1), hipMemcpyDeviceToHost, s));
-  if (chord && nc) PCHK(hipMemcpyAsync(chord, g->chordH, sizeof(double) * 36 * nc, hipMemcpyDeviceToHost, s));
-  PCHK(hipStreamSynchronize(s));
+  if (grad) HIPCHK(hipMemcpyAsync(grad, g->grad, sizeof(double) * 6 * N, hipMemcpyDeviceToHost, s));
+  if (diag) HIPCHK(hipMemcpyAsync(diag, g->diag, sizeof(double) * 36 * N, hipMemcpyDeviceToHost, s));
+  if (chain && N > 1) HIPCHK(hipMemcpyAsync(chain, g->chain, sizeof(double) * 36 * (N - 1), hipMemcpyDeviceToHost, s));
+  if (chord && nc) HIPCHK(hipMemcpyAsync(chord, g->chordH, sizeof(double) * 36 * nc, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   if (chord_ij) for (size_t k = 0; k < 2 * nc; k++) chord_ij[k] = g->chord_ij[k];
   if (cost) *cost = g->h_info[0];
   g->linearized = true;
@@ -1242,11 +1228,11 @@ int rolo_pgo_linearize(rolo_pgo* g, double* cost, double* grad, double* diag, do
 int rolo_pgo_solve_linear(rolo_pgo* g, double lambda, double pcg_tol, int pcg_max, double* delta, int* pcg_iterations, double* residual) {
   if (!g || !(lambda >= 0.0) || !(pcg_tol >= 0.0) || pcg_max < 0) return ROLO_EINVAL;
   if (!g->linearized) { ctx_set_error("rolo_pgo_solve_linear: call rolo_pgo_linearize first (the graph has changed since, or was never linearised)"); return ROLO_ESTATE; }
-  PCHK(hipSetDevice(g->device));
+  HIPCHK(hipSetDevice(g->device));
   int rc;
   if ((rc = pgo_enqueue_solve(g, lambda, pcg_tol, pcg_max))) return rc;
-  if (delta) PCHK(hipMemcpyAsync(delta, g->delta, sizeof(double) * 6 * (size_t)g->N, hipMemcpyDeviceToHost, g->stream));
-  PCHK(hipStreamSynchronize(g->stream));
+  if (delta) HIPCHK(hipMemcpyAsync(delta, g->delta, sizeof(double) * 6 * (size_t)g->N, hipMemcpyDeviceToHost, g->stream));
+  HIPCHK(hipStreamSynchronize(g->stream));
   if (g->h_info[3] != 0.0) { ctx_set_error("rolo_pgo_solve_linear: H + lambda I is not positive definite (lambda = 0 on a graph without a prior?)"); return ROLO_EINVAL; }
   if (pcg_iterations) *pcg_iterations = (int)g->h_info[1];
   if (residual) *residual = g->h_info[2];
@@ -1267,11 +1253,11 @@ int rolo_pgo_optimize(rolo_pgo* g, const rolo_pgo_params* P, rolo_pgo_result* ou
   double acc_ms[4] = {0, 0, 0, 0};
   float ms = 0.f;
   auto linearize = [&]() -> int {
-    PCHK(hipEventRecord(g->ev[0], s));
+    HIPCHK(hipEventRecord(g->ev[0], s));
     int r = pgo_enqueue_linearize(g);
     if (r) return r;
-    PCHK(hipEventRecord(g->ev[1], s));
-    PCHK(hipEventSynchronize(g->ev[1]));
+    HIPCHK(hipEventRecord(g->ev[1], s));
+    HIPCHK(hipEventSynchronize(g->ev[1]));
     (void)hipEventElapsedTime(&ms, g->ev[0], g->ev[1]);
     acc_ms[0] += ms;
     return ROLO_OK;
@@ -1284,13 +1270,13 @@ int rolo_pgo_optimize(rolo_pgo* g, const rolo_pgo_params* P, rolo_pgo_result* ou
     if (res.iterations >= P->max_iterations || res.trials >= PGO_MAX_TRIALS) { res.state = ROLO_PGO_ITERATIONS; break; }
     if (lambda > P->lambda_upper) { res.state = ROLO_PGO_LAMBDA; break; }
     if ((rc = pgo_enqueue_solve(g, lambda, P->pcg_tol, P->pcg_max_iterations))) return rc;
-    PCHK(hipEventRecord(g->ev[0], s));
+    HIPCHK(hipEventRecord(g->ev[0], s));
     pgo_retract_cost_kernel<<<grid, PGO_FACTOR_THREADS, 0, s>>>(g->d_factors, F, g->poses, N, g->delta, g->trial, g->partials);
-    PCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     pgo_sum_kernel<<<1, PGO_SUM_THREADS, 0, s>>>(g->partials, 1, 0, grid, g->h_info);
-    PCHK(hipGetLastError());
-    PCHK(hipEventRecord(g->ev[1], s));
-    PCHK(hipEventSynchronize(g->ev[1]));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(g->ev[1], s));
+    HIPCHK(hipEventSynchronize(g->ev[1]));
     (void)hipEventElapsedTime(&ms, g->ev[0], g->ev[1]);
     acc_ms[3] += ms; acc_ms[1] += pgo_solve_ms(g, 0); acc_ms[2] += pgo_solve_ms(g, 1);
     const bool bad = g->h_info[3] != 0.0;
@@ -1315,7 +1301,7 @@ int rolo_pgo_optimize(rolo_pgo* g, const rolo_pgo_params* P, rolo_pgo_result* ou
       lambda *= P->lambda_factor;
     }
   }
-  PCHK(hipStreamSynchronize(s));
+  HIPCHK(hipStreamSynchronize(s));
   res.final_cost = cost; res.lambda = lambda;
   for (int k = 0; k < 4; k++) g->ms[k] = (float)acc_ms[k];
   *out = res;
@@ -1329,8 +1315,8 @@ int rolo_pgo_get_poses(rolo_pgo* g, double* T16_out, float* pose6_out, int cap) 
   int rc;
   if ((rc = pgo_sync_graph(g))) return rc;
   std::vector<double> P(12 * (size_t)n);
-  PCHK(hipMemcpyAsync(P.data(), g->poses, sizeof(double) * P.size(), hipMemcpyDeviceToHost, g->stream));
-  PCHK(hipStreamSynchronize(g->stream));
+  HIPCHK(hipMemcpyAsync(P.data(), g->poses, sizeof(double) * P.size(), hipMemcpyDeviceToHost, g->stream));
+  HIPCHK(hipStreamSynchronize(g->stream));
   for (int k = 0; k < n; k++) {
     const double* p = P.data() + 12 * (size_t)k;
     if (T16_out) {
@@ -1350,12 +1336,12 @@ int rolo_pgo_get_factor_errors(rolo_pgo* g, double* r2, double* weight, int cap)
   if (n == 0 || (!r2 && !weight)) return F;
   int rc;
   if ((rc = pgo_sync_graph(g))) return rc;
-  if ((rc = pgo_grow(g, g->ferr, g->ferr_cap, 2 * (size_t)F))) return rc;
+  if ((rc = g->store.grow(g->ferr, g->ferr_cap, 2 * (size_t)F))) return rc;
   pgo_factor_error_kernel<<<(F + PGO_FACTOR_THREADS - 1) / PGO_FACTOR_THREADS, PGO_FACTOR_THREADS, 0, g->stream>>>(g->d_factors, F, g->poses, g->ferr, g->ferr + F);
-  PCHK(hipGetLastError());
-  if (r2) PCHK(hipMemcpyAsync(r2, g->ferr, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
-  if (weight) PCHK(hipMemcpyAsync(weight, g->ferr + F, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
-  PCHK(hipStreamSynchronize(g->stream));
+  HIPCHK(hipGetLastError());
+  if (r2) HIPCHK(hipMemcpyAsync(r2, g->ferr, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
+  if (weight) HIPCHK(hipMemcpyAsync(weight, g->ferr + F, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
+  HIPCHK(hipStreamSynchronize(g->stream));
   return F;
 }
 

@@ -14,9 +14,9 @@
 // algorithms: cv::eigen of a symmetric float matrix = OpenCV's largest-pivot Jacobi scheme, eigenvalues descending, eigenvectors as rows;
 // colPivHouseholderQr().solve of the 5 x 3 plane system = Eigen's column-pivoted Householder QR. The C++ oracle (oracle/rolo_oracle_backend.cpp)
 // restates the same algorithms independently: selection flags bit-identical, coefficients to float rounding (tests/test_gpu_backend.py).
-#include "rolo_internal.hpp"
+#include "ctx_access.hpp"
 #include "switches.hpp"
-#include "dev_math.hpp"
+#include "dev_rows.hpp"
 #include "knn_packet.hpp"
 #include <cfloat>
 #include <climits>
@@ -26,15 +26,6 @@
 #include <vector>
 
 namespace rolo {
-int ctx_build_map_trees(rolo_ctx* c, const float* corner, int nc, const float* surf, int ns, int stride, KnnPair* out, bool on_device = false);
-int keymap_device_submap(rolo_keymap* km, const float** d_corner, int* m_corner, const float** d_surf, int* m_surf, hipEvent_t* ready, hipEvent_t* consumed, int* device);   // submap.hip
-void keymap_mark_consumed(rolo_keymap* km);
-extern "C" int rolo_ctx_acquire(int device, rolo_ctx** out);
-extern "C" void rolo_ctx_release(rolo_ctx* c);
-hipStream_t ctx_stream(rolo_ctx* c);
-int ctx_device(rolo_ctx* c);
-void ctx_set_error(const char* msg);
-
 namespace {
 
 constexpr int S2M_THREADS = 128;
@@ -554,31 +545,6 @@ __global__ __launch_bounds__(256) void s2m_assoc_kernel(S2mArgs A, int split /* 
   s2m_block_sum<4>(acc, red, A.partials, blk);
 }
 
-// the rows of the workgroups summed in a fixed order (deterministic for a given grid): 8 strided groups of 32 lanes with eight loads in flight each, then
-// the groups in order; the 28 sums go straight to pinned host memory (one wait per iteration, no copy launch)
-__global__ __launch_bounds__(256) void s2m_sum_kernel(const double* __restrict__ partials, int nblocks, double* __restrict__ out) {
-  __shared__ double part[8][32];
-  const int v = threadIdx.x & 31, q = threadIdx.x >> 5;
-  double s = 0;
-  if (v < S2M_NV) {
-    for (int b0 = q; b0 < nblocks; b0 += 64) {
-      double r[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) { const int b = b0 + 8 * u; const double x = partials[(size_t)min(b, nblocks - 1) * S2M_NV + v]; r[u] = b < nblocks ? x : 0.0; }
-#pragma unroll
-      for (int u = 0; u < 8; u++) s += r[u];
-    }
-  }
-  part[q][v] = s;
-  __syncthreads();
-  if (threadIdx.x < S2M_NV) {
-    double t = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) t += part[k][threadIdx.x];
-    out[threadIdx.x] = t;
-  }
-}
-
 // ---- host side: float linear algebra of LMOptimization ------------------------------------------------------------------------
 // cv::solve(AtA, AtB, X, DECOMP_QR) on a 6 x 6 float system: Householder QR in float
 bool solve_qr6f(const float* Ain, const float* bin, float* x) {
@@ -625,23 +591,21 @@ bool invert6f(const float* Ain, float* inv) {   // matV.inv() (LU with partial p
 
 using namespace rolo;
 
-#define SCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { ctx_set_error((std::string(#x) + ": " + hipGetErrorString(_e)).c_str()); return ROLO_EHIP; } } while (0)
-
 namespace rolo {
-void** ctx_s2m_slot(rolo_ctx* c);   // api.hip
-unsigned long long ctx_cloud_epoch(rolo_ctx* c);   // api.hip: changes whenever the context's source / target clouds change hands
-struct S2mScratch { float4* feat = nullptr; double *part = nullptr, *sum = nullptr; unsigned char* sel = nullptr; float4* coeff = nullptr;
-                    size_t feat_cap = 0, part_cap = 0, sum_cap = 0, sel_cap = 0, coeff_cap = 0;
+struct S2mScratch { float4* feat = nullptr; double* part = nullptr; unsigned char* sel = nullptr; float4* coeff = nullptr;
+                    size_t feat_cap = 0, part_cap = 0, sel_cap = 0, coeff_cap = 0;
+                    DevStore store{nullptr, "scan2map"};   // grows the four above (nothing is kept across a growth: no stream); what they outgrew is freed with the context
                     KnnPair maps{}; int m_corner = 0, m_surf = 0; bool have_maps = false;   // the resident sub-map (rolo_scan2map_set_submap): trees of the context's two clouds
                     bool map_set = false; unsigned long long maps_epoch = 0;   // a sub-map was handed in (possibly too small to search); the context's cloud epoch when its trees were built —
                                                                                // any later upload into the context (rolo_set_input_*, a registration, the pool) makes the raw pointers in `maps` stale
                     rolo_ctx* qctx = nullptr; hipEvent_t qev = nullptr;
-                    double* h_sum = nullptr; };   // pinned: the 28 sums of an iteration, written by s2m_sum_kernel itself   // helper context (from the pool): the scan's features sorted along the curve, its two clouds
+                    double* h_sum = nullptr; };   // pinned: the 28 sums of an iteration, written by sum_rows itself   // helper context (from the pool): the scan's features sorted along the curve, its two clouds
 }  // namespace rolo
 extern "C" void rolo_s2m_destroy(rolo_ctx* c) {   // called by rolo_ctx_destroy
   S2mScratch* W = static_cast<S2mScratch*>(*ctx_s2m_slot(c));
   if (!W) return;
-  for (void* p : {(void*)W->feat, (void*)W->part, (void*)W->sum, (void*)W->sel, (void*)W->coeff}) if (p) (void)hipFree(p);
+  for (void* p : {(void*)W->feat, (void*)W->part, (void*)W->sel, (void*)W->coeff}) if (p) (void)hipFree(p);
+  W->store.release();
   if (W->qev) (void)hipEventDestroy(W->qev);
   if (W->h_sum) (void)hipHostFree(W->h_sum);
   rolo_ctx* q = W->qctx;
@@ -688,11 +652,11 @@ extern "C" int rolo_scan2map_set_submap_keymap(rolo_ctx* c, rolo_keymap* km) {
   if (!W) { W = new S2mScratch(); *ctx_s2m_slot(c) = W; }
   W->have_maps = false; W->map_set = false; W->m_corner = 0; W->m_surf = 0;
   if (m_corner < 5 || m_surf < 5) { W->map_set = true; W->m_corner = m_corner; W->m_surf = m_surf; return ROLO_OK; }
-  SCHK(hipStreamWaitEvent(ctx_stream(c), ready, 0));
+  HIPCHK(hipStreamWaitEvent(ctx_stream(c), ready, 0));
   KnnPair built{};
   rc = ctx_build_map_trees(c, d_corner, m_corner, d_surf, m_surf, 4, &built, true);
   // the key map may overwrite its sub-map only after this context has read it (also after a failed build: the pack may be in flight)
-  SCHK(hipEventRecord(consumed, ctx_stream(c)));
+  HIPCHK(hipEventRecord(consumed, ctx_stream(c)));
   keymap_mark_consumed(km);
   if (rc) return rc;
   W->maps = built; W->m_corner = m_corner; W->m_surf = m_surf; W->maps_epoch = ctx_cloud_epoch(c);
@@ -738,27 +702,20 @@ extern "C" int rolo_scan2map_optimize(rolo_ctx* c, const float* corner, int n_co
   int grid = (n + S2M_THREADS - 1) / S2M_THREADS, split = 0;
   if (use_packets) {
     S2mScratch* Wq = static_cast<S2mScratch*>(*ctx_s2m_slot(c));
-    if (!Wq->qctx) { if (rolo_ctx_acquire(ctx_device(c), &Wq->qctx) != ROLO_OK) return ROLO_EHIP; SCHK(hipEventCreateWithFlags(&Wq->qev, hipEventDisableTiming)); }
+    if (!Wq->qctx) { if (rolo_ctx_acquire(ctx_device(c), &Wq->qctx) != ROLO_OK) return ROLO_EHIP; HIPCHK(hipEventCreateWithFlags(&Wq->qev, hipEventDisableTiming)); }
     const int rq = ctx_build_map_trees(Wq->qctx, corner, n_corner, surf, n_surf, 4, &qp);   // upload + Hilbert sort (+ a tree nobody walks) on the helper's stream
     if (rq) return rq;
-    SCHK(hipEventRecord(Wq->qev, ctx_stream(Wq->qctx)));
-    SCHK(hipStreamWaitEvent(s, Wq->qev, 0));
+    HIPCHK(hipEventRecord(Wq->qev, ctx_stream(Wq->qctx)));
+    HIPCHK(hipStreamWaitEvent(s, Wq->qev, 0));
     split = (qp.c[0].n_sorted + 4 * S2M_FPW - 1) / (4 * S2M_FPW);
     grid = split + (qp.c[1].n_sorted + 4 * S2M_FPW - 1) / (4 * S2M_FPW);
   }
-  // scratch lives with the context and only grows: hipFree is a device-wide synchronisation that would stall the frames other contexts have in flight
+  // scratch lives with the context and only grows (W->store)
   S2mScratch* W = static_cast<S2mScratch*>(*ctx_s2m_slot(c));
   if (!W) { W = new S2mScratch(); *ctx_s2m_slot(c) = W; }
-  auto grow = [&](void** p, size_t& cap, size_t bytes) -> bool {
-    if (bytes <= cap && *p) return true;
-    if (*p) { (void)hipFree(*p); *p = nullptr; cap = 0; }
-    const size_t want = bytes + bytes / 4 + 256;
-    if (hipMalloc(p, want) != hipSuccess) return false;
-    cap = want; return true;
-  };
-  if (!grow((void**)&W->feat, W->feat_cap, sizeof(float4) * (size_t)n) || !grow((void**)&W->part, W->part_cap, sizeof(double) * S2M_NV * (size_t)grid) ||
-      !grow((void**)&W->sum, W->sum_cap, sizeof(double) * S2M_NV) || (selected_out && !grow((void**)&W->sel, W->sel_cap, (size_t)n)) ||
-      (coeff_out && !grow((void**)&W->coeff, W->coeff_cap, sizeof(float4) * (size_t)n))) { ctx_set_error("hipMalloc failed (scan2map)"); return ROLO_EHIP; }
+  int rg;
+  if ((rg = W->store.grow(W->feat, W->feat_cap, (size_t)n)) || (rg = W->store.grow(W->part, W->part_cap, S2M_NV * (size_t)grid)) ||
+      (selected_out && (rg = W->store.grow(W->sel, W->sel_cap, (size_t)n))) || (coeff_out && (rg = W->store.grow(W->coeff, W->coeff_cap, (size_t)n)))) return rg;
   float4* d_feat = W->feat; double* d_part = W->part; unsigned char* d_sel = selected_out ? W->sel : nullptr; float4* d_coeff = coeff_out ? W->coeff : nullptr;
   if (!use_packets &&   // (s2m_assoc_kernel reads the features from the helper context's sorted clouds)
       (hipMemcpyAsync(d_feat, corner, sizeof(float4) * (size_t)n_corner, hipMemcpyHostToDevice, s) != hipSuccess ||
@@ -768,11 +725,11 @@ extern "C" int rolo_scan2map_optimize(rolo_ctx* c, const float* corner, int n_co
   A.qry[0] = qp.c[0]; A.qry[1] = qp.c[1];
   const char* stats_path = switches().s2m_stats;
   int4* d_wstats = nullptr;
-  if (stats_path && use_packets) { SCHK(hipMalloc((void**)&d_wstats, sizeof(int4) * 4 * (size_t)grid)); SCHK(hipMemsetAsync(d_wstats, 0, sizeof(int4) * 4 * (size_t)grid, s)); A.wstats = d_wstats; }
+  if (stats_path && use_packets) { HIPCHK(hipMalloc((void**)&d_wstats, sizeof(int4) * 4 * (size_t)grid)); HIPCHK(hipMemsetAsync(d_wstats, 0, sizeof(int4) * 4 * (size_t)grid, s)); A.wstats = d_wstats; }
   float* tf = transformTobeMapped;
   bool isDegenerate = false;
   float matP[36]; for (int i = 0; i < 36; i++) matP[i] = (i % 7 == 0) ? 1.f : 0.f;
-  if (!W->h_sum) SCHK(hipHostMalloc((void**)&W->h_sum, sizeof(double) * S2M_NV));
+  if (!W->h_sum) HIPCHK(hipHostMalloc((void**)&W->h_sum, sizeof(double) * S2M_NV));
   double* h_sum = W->h_sum;
   for (int iterCount = 0; iterCount < 30; iterCount++) {
     // trans2Affine3f :339-342 = pcl::getTransformation(x, y, z, roll, pitch, yaw), float
@@ -786,9 +743,9 @@ extern "C" int rolo_scan2map_optimize(rolo_ctx* c, const float* corner, int n_co
     A.srx = std::sin(tf[1]); A.crx = std::cos(tf[1]); A.sry = std::sin(tf[2]); A.cry = std::cos(tf[2]); A.srz = std::sin(tf[0]); A.crz = std::cos(tf[0]);
     if (use_packets) s2m_assoc_kernel<<<grid, 256, 0, s>>>(A, split);
     else s2m_kernel<<<grid, S2M_THREADS, 0, s>>>(A);
-    SCHK(hipGetLastError());
-    s2m_sum_kernel<<<1, 256, 0, s>>>(d_part, grid, h_sum);
-    SCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
+    sum_rows<S2M_NV, 8><<<1, 256, 0, s>>>(d_part, grid, h_sum);
+    HIPCHK(hipGetLastError());
     if (hipStreamSynchronize(s) != hipSuccess) { ctx_set_error("scan2map iteration failed"); return ROLO_EHIP; }
     st.iterations = iterCount + 1;
     st.n_selected = (int)(h_sum[27] + 0.5);
@@ -818,13 +775,13 @@ extern "C" int rolo_scan2map_optimize(rolo_ctx* c, const float* corner, int n_co
   }
   if (d_wstats) {   // one line per wavefront: nodes, leaves, walk ticks (100 MHz), block
     std::vector<int4> hw(4 * (size_t)grid);
-    SCHK(hipMemcpy(hw.data(), d_wstats, sizeof(int4) * hw.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hw.data(), d_wstats, sizeof(int4) * hw.size(), hipMemcpyDeviceToHost));
     if (FILE* f = fopen(stats_path, "w")) { for (const int4& r : hw) fprintf(f, "%d %d %d %d\n", r.x, r.y, r.z, r.w); fclose(f); }
     (void)hipFree(d_wstats);
   }
   st.degenerate = isDegenerate ? 1 : 0;
-  if (selected_out) SCHK(hipMemcpy(selected_out, d_sel, (size_t)n, hipMemcpyDeviceToHost));
-  if (coeff_out) SCHK(hipMemcpy(coeff_out, d_coeff, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost));
+  if (selected_out) HIPCHK(hipMemcpy(selected_out, d_sel, (size_t)n, hipMemcpyDeviceToHost));
+  if (coeff_out) HIPCHK(hipMemcpy(coeff_out, d_coeff, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost));
   if (stats) *stats = st;
   return ROLO_OK;
 }

@@ -300,7 +300,7 @@ void sc_defaults(rolo_sc_params* p) {   // Scancontext.h:80-95
 
 int sc_store(rolo_keymap* km, ScStore** out) {
   if (!km->sc) {
-    KCHK(hipSetDevice(km->device));
+    HIPCHK(hipSetDevice(km->device));
     ScStore* sc = new ScStore();
     sc_defaults(&sc->P);
     hipError_t e = hipHostMalloc((void**)&sc->h_flag, sizeof(int));
@@ -314,26 +314,17 @@ int sc_store(rolo_keymap* km, ScStore** out) {
   return ROLO_OK;
 }
 
-// room for one more descriptor: a larger array, the stored ones copied on the key map's stream, the outgrown array retired (never freed before rolo_keymap_destroy)
-template <typename T>
-int sc_grow_one(rolo_keymap* km, T*& p, size_t new_cap, size_t per, int n) {
-  T* q = nullptr;
-  if (hipMalloc((void**)&q, new_cap * per * sizeof(T)) != hipSuccess) { ctx_set_error("hipMalloc failed (descriptor store)"); return ROLO_EHIP; }
-  if (p && n) KCHK(hipMemcpyAsync(q, p, (size_t)n * per * sizeof(T), hipMemcpyDeviceToDevice, km->stream));
-  if (p) km->retired.push_back(p);
-  p = q;
-  return ROLO_OK;
-}
-
+// room for one more descriptor: four larger arrays (sc->cap counts descriptors, so the sizes are given outright), the stored descriptors copied on the key map's
+// stream, the outgrown arrays retired
 int sc_reserve(rolo_keymap* km, ScStore* sc) {
   if ((size_t)sc->n < sc->cap) return ROLO_OK;
   const size_t want = sc->cap + sc->cap / 2 + 64;
-  const size_t R = (size_t)sc->P.num_ring, S = (size_t)sc->P.num_sector;
+  const size_t R = (size_t)sc->P.num_ring, S = (size_t)sc->P.num_sector, n = (size_t)sc->n;
   int rc;
-  if ((rc = sc_grow_one(km, sc->desc, want, R * S, sc->n))) return rc;
-  if ((rc = sc_grow_one(km, sc->colnorm, want, S, sc->n))) return rc;
-  if ((rc = sc_grow_one(km, sc->seckey, want, S, sc->n))) return rc;
-  if ((rc = sc_grow_one(km, sc->ringkey, want, R, sc->n))) return rc;
+  if ((rc = km->store.replace(sc->desc, want * R * S, n * R * S))) return rc;
+  if ((rc = km->store.replace(sc->colnorm, want * S, n * S))) return rc;
+  if ((rc = km->store.replace(sc->seckey, want * S, n * S))) return rc;
+  if ((rc = km->store.replace(sc->ringkey, want * R, n * R))) return rc;
   sc->cap = want;
   return ROLO_OK;
 }
@@ -345,9 +336,9 @@ int sc_add_device(rolo_keymap* km, ScStore* sc, const float4* d_pts, int n) {
   const size_t R = (size_t)sc->P.num_ring, S = (size_t)sc->P.num_sector, i = (size_t)sc->n;
   const ScGeom G{sc->P.num_ring, sc->P.num_sector, sc->P.max_radius, sc->P.lidar_height};
   sc_make_kernel<<<1, SC_MAKE_THREADS, 0, km->stream>>>(d_pts, n, G, sc->desc + i * R * S, sc->colnorm + i * S, sc->seckey + i * S, sc->ringkey + i * R, sc->h_flag);
-  KCHK(hipGetLastError());
-  KCHK(hipEventRecord(sc->t1, km->stream));
-  KCHK(hipStreamSynchronize(km->stream));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(sc->t1, km->stream));
+  HIPCHK(hipStreamSynchronize(km->stream));
   (void)hipEventElapsedTime(&sc->last_ms, sc->t0, sc->t1);
   if (*sc->h_flag != 0) { ctx_set_error("a non-finite coordinate reached the Scan Context descriptor"); return ROLO_ENONFINITE; }
   return sc->n++;
@@ -381,7 +372,7 @@ int rolo_keymap_sc_set_params(rolo_keymap* km, const rolo_sc_params* p) {
   }
   if (sc->cap > 0 && (p->num_ring != sc->P.num_ring || p->num_sector != sc->P.num_sector)) {
     // no descriptor is stored, but an add that failed (a non-finite coordinate) has already sized the arrays for the old geometry: retire them, the next add allocates anew
-    for (void* q : {(void*)sc->desc, (void*)sc->colnorm, (void*)sc->seckey, (void*)sc->ringkey}) if (q) km->retired.push_back(q);
+    for (void* q : {(void*)sc->desc, (void*)sc->colnorm, (void*)sc->seckey, (void*)sc->ringkey}) km->store.retire(q);
     sc->desc = nullptr; sc->colnorm = nullptr; sc->seckey = nullptr; sc->ringkey = nullptr;
     sc->cap = 0;
   }
@@ -402,8 +393,8 @@ int rolo_keymap_sc_add_surface(rolo_keymap* km, int keyframe) {
   ScStore* sc;
   int rc;
   if ((rc = sc_store(km, &sc))) return rc;
-  KCHK(hipSetDevice(km->device));
-  KCHK(hipEventRecord(sc->t0, km->stream));
+  HIPCHK(hipSetDevice(km->device));
+  HIPCHK(hipEventRecord(sc->t0, km->stream));
   return sc_add_device(km, sc, f.pts[1], f.n[1]);
 }
 
@@ -413,8 +404,8 @@ int rolo_keymap_sc_add_cloud(rolo_keymap* km, const float* pts, int n, float lea
   ScStore* sc;
   int rc;
   if ((rc = sc_store(km, &sc))) return rc;
-  KCHK(hipSetDevice(km->device));
-  KCHK(hipEventRecord(sc->t0, km->stream));
+  HIPCHK(hipSetDevice(km->device));
+  HIPCHK(hipEventRecord(sc->t0, km->stream));
   const float4* d = nullptr; int m = 0;
   if ((rc = keymap_stage_cloud(km, pts, n, leaf, &d, &m))) return rc;
   if (m <= 0) { ctx_set_error("rolo_keymap_sc_add_cloud: empty cloud"); return ROLO_EINVAL; }
@@ -427,13 +418,13 @@ int rolo_keymap_sc_get(rolo_keymap* km, int index, double* desc, float* ringkey,
   if (!km || !km->sc || index < 0 || index >= km->sc->n) return ROLO_EINVAL;
   ScStore* sc = km->sc;
   const size_t R = (size_t)sc->P.num_ring, S = (size_t)sc->P.num_sector, i = (size_t)index;
-  KCHK(hipSetDevice(km->device));
+  HIPCHK(hipSetDevice(km->device));
   std::vector<float> m(desc ? R * S : 0);
-  if (desc) KCHK(hipMemcpyAsync(m.data(), sc->desc + i * R * S, sizeof(float) * R * S, hipMemcpyDeviceToHost, km->stream));
-  if (ringkey) KCHK(hipMemcpyAsync(ringkey, sc->ringkey + i * R, sizeof(float) * R, hipMemcpyDeviceToHost, km->stream));
-  if (sectorkey) KCHK(hipMemcpyAsync(sectorkey, sc->seckey + i * S, sizeof(double) * S, hipMemcpyDeviceToHost, km->stream));
-  if (colnorm) KCHK(hipMemcpyAsync(colnorm, sc->colnorm + i * S, sizeof(double) * S, hipMemcpyDeviceToHost, km->stream));
-  KCHK(hipStreamSynchronize(km->stream));
+  if (desc) HIPCHK(hipMemcpyAsync(m.data(), sc->desc + i * R * S, sizeof(float) * R * S, hipMemcpyDeviceToHost, km->stream));
+  if (ringkey) HIPCHK(hipMemcpyAsync(ringkey, sc->ringkey + i * R, sizeof(float) * R, hipMemcpyDeviceToHost, km->stream));
+  if (sectorkey) HIPCHK(hipMemcpyAsync(sectorkey, sc->seckey + i * S, sizeof(double) * S, hipMemcpyDeviceToHost, km->stream));
+  if (colnorm) HIPCHK(hipMemcpyAsync(colnorm, sc->colnorm + i * S, sizeof(double) * S, hipMemcpyDeviceToHost, km->stream));
+  HIPCHK(hipStreamSynchronize(km->stream));
   if (desc) for (size_t r = 0; r < R; r++) for (size_t s = 0; s < S; s++) desc[r * S + s] = (double)m[s * R + r];
   return ROLO_OK;
 }
@@ -445,33 +436,33 @@ int rolo_keymap_sc_detect(rolo_keymap* km, int query, int n_search, rolo_sc_resu
   ScStore* sc = km->sc;
   out->loop_id = -1; out->yaw_diff_rad = 0.f; out->nn_idx = 0; out->nn_align = 0; out->min_dist = SC_FAR; out->n_candidates = 0;
   if (n_search <= 0) return ROLO_OK;   // :263-267
-  KCHK(hipSetDevice(km->device));
+  HIPCHK(hipSetDevice(km->device));
   hipStream_t s = km->stream;
   const int R = sc->P.num_ring, S = sc->P.num_sector, K = sc->P.num_candidates;
   const int ncand = K > 0 ? std::min(K, n_search) : n_search;
   const int radius = (int)std::min<double>(std::round(0.5 * sc->P.search_ratio * (double)S), (double)S);   // :123
   int rc;
-  if ((rc = km_grow(km, sc->cdist, sc->cdist_cap, (size_t)ncand))) return rc;
-  if ((rc = km_grow(km, sc->calign, sc->calign_cap, (size_t)ncand))) return rc;
-  KCHK(hipEventRecord(sc->t0, s));
+  if ((rc = km->store.grow(sc->cdist, sc->cdist_cap, (size_t)ncand))) return rc;
+  if ((rc = km->store.grow(sc->calign, sc->calign_cap, (size_t)ncand))) return rc;
+  HIPCHK(hipEventRecord(sc->t0, s));
   const u64* sel = nullptr;
   if (K > 0) {
     const int blocks = std::min((n_search + SC_THREADS - 1) / SC_THREADS, SC_RK_BLOCKS);
-    if ((rc = km_grow(km, sc->keys, sc->keys_cap, (size_t)n_search))) return rc;
-    if ((rc = km_grow(km, sc->part, sc->part_cap, (size_t)(SC_RK_BLOCKS + 1) * SC_MAX_CAND))) return rc;
+    if ((rc = km->store.grow(sc->keys, sc->keys_cap, (size_t)n_search))) return rc;
+    if ((rc = km->store.grow(sc->part, sc->part_cap, (size_t)(SC_RK_BLOCKS + 1) * SC_MAX_CAND))) return rc;
     u64* merged = sc->part + (size_t)SC_RK_BLOCKS * SC_MAX_CAND;
     sc_ringkey_kernel<<<blocks, SC_THREADS, 0, s>>>(sc->ringkey, R, query, n_search, ncand, sc->keys, sc->part);
-    KCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     sc_select_kernel<<<1, SC_THREADS, 0, s>>>(sc->part, blocks * ncand, ncand, merged);
-    KCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     sel = merged;
   }
   sc_distance_kernel<<<ncand, SC_THREADS, 0, s>>>(sc->desc, sc->colnorm, sc->seckey, R, S, query, sel, radius, sc->cdist, sc->calign);
-  KCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   sc_best_kernel<<<1, SC_THREADS, 0, s>>>(sc->cdist, sc->calign, sel, ncand, sc->h_best);
-  KCHK(hipGetLastError());
-  KCHK(hipEventRecord(sc->t1, s));
-  KCHK(hipStreamSynchronize(s));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(sc->t1, s));
+  HIPCHK(hipStreamSynchronize(s));
   (void)hipEventElapsedTime(&sc->last_ms, sc->t0, sc->t1);
   const ScBest b = *sc->h_best;
   out->nn_idx = b.nn_idx; out->nn_align = b.nn_align; out->min_dist = b.min_dist; out->n_candidates = ncand;
@@ -484,14 +475,14 @@ int rolo_keymap_sc_detect(rolo_keymap* km, int query, int n_search, rolo_sc_resu
     if (cand_idx) {
       if (sel) {
         std::vector<u64> h((size_t)m);
-        KCHK(hipMemcpy(h.data(), sel, sizeof(u64) * (size_t)m, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h.data(), sel, sizeof(u64) * (size_t)m, hipMemcpyDeviceToHost));
         for (int i = 0; i < m; i++) cand_idx[i] = (int32_t)(h[(size_t)i] & 0xffffffffull);
       } else {
         for (int i = 0; i < m; i++) cand_idx[i] = i;
       }
     }
-    if (cand_dist) KCHK(hipMemcpy(cand_dist, sc->cdist, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost));
-    if (cand_align) KCHK(hipMemcpy(cand_align, sc->calign, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost));
+    if (cand_dist) HIPCHK(hipMemcpy(cand_dist, sc->cdist, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost));
+    if (cand_align) HIPCHK(hipMemcpy(cand_align, sc->calign, sizeof(int) * (size_t)m, hipMemcpyDeviceToHost));
   }
   return ROLO_OK;
 }

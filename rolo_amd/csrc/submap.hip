@@ -16,6 +16,7 @@
 //
 // transformPointCloud: the oracle's float statement p0 + (p1 + (p2 + c3)) per row (orc_transform_cloud_f, the parity target of the tests), no contraction.
 #include "keymap.hpp"
+#include "dev_rows.hpp"
 #include <algorithm>
 #include <array>
 #include <cfloat>
@@ -41,13 +42,7 @@ constexpr size_t CHUNK_POINTS = 1u << 20;              // the store grows in chu
 __global__ __launch_bounds__(SM_THREADS) void km_transform_kernel(const Seg* __restrict__ segs, float4* __restrict__ out) {
   const Seg s = segs[blockIdx.y];
   for (int i = blockIdx.x * SM_THREADS + threadIdx.x; i < s.n; i += gridDim.x * SM_THREADS) {
-    const float4 p = s.src[i];
-    float4 o;
-    o.x = s.T[0] * p.x + (s.T[1] * p.y + (s.T[2] * p.z + s.T[3]));
-    o.y = s.T[4] * p.x + (s.T[5] * p.y + (s.T[6] * p.z + s.T[7]));
-    o.z = s.T[8] * p.x + (s.T[9] * p.y + (s.T[10] * p.z + s.T[11]));
-    o.w = p.w;
-    out[(size_t)s.dst + i] = o;
+    out[(size_t)s.dst + i] = transform12(s.T, s.src[i]);
   }
 }
 
@@ -327,14 +322,14 @@ int km_sort_scratch(rolo_keymap* km, int n) {
   const int nblocks = (n + SORT_TILE - 1) / SORT_TILE, nrun = (n + RUN_TILE - 1) / RUN_TILE;
   int rc;
   for (int b = 0; b < 2; b++) {
-    if ((rc = km_grow(km, km->keys[b], km->keys_cap[b], (size_t)n))) return rc;
-    if ((rc = km_grow(km, km->vals[b], km->vals_cap[b], (size_t)n))) return rc;
+    if ((rc = km->store.grow(km->keys[b], km->keys_cap[b], (size_t)n))) return rc;
+    if ((rc = km->store.grow(km->vals[b], km->vals_cap[b], (size_t)n))) return rc;
   }
-  if ((rc = km_grow(km, km->hist, km->hist_cap, 256 * (size_t)nblocks))) return rc;
-  if ((rc = km_grow(km, km->dtot, km->dtot_cap, (size_t)4 * 256))) return rc;
-  if ((rc = km_grow(km, km->bcnt, km->bcnt_cap, (size_t)nrun))) return rc;
-  if ((rc = km_grow(km, km->starts, km->starts_cap, (size_t)n))) return rc;
-  if ((rc = km_grow(km, km->box_part, km->box_part_cap, 2 * 8 * (size_t)BOX_BLOCKS_MAX))) return rc;
+  if ((rc = km->store.grow(km->hist, km->hist_cap, 256 * (size_t)nblocks))) return rc;
+  if ((rc = km->store.grow(km->dtot, km->dtot_cap, (size_t)4 * 256))) return rc;
+  if ((rc = km->store.grow(km->bcnt, km->bcnt_cap, (size_t)nrun))) return rc;
+  if ((rc = km->store.grow(km->starts, km->starts_cap, (size_t)n))) return rc;
+  if ((rc = km->store.grow(km->box_part, km->box_part_cap, 2 * 8 * (size_t)BOX_BLOCKS_MAX))) return rc;
   return ROLO_OK;
 }
 
@@ -343,9 +338,9 @@ int vg_enqueue_box(rolo_keymap* km, const float4* pts, int n, int slot) {
   if (n <= 0) return ROLO_OK;
   const int blocks = std::min((n + SM_THREADS - 1) / SM_THREADS, BOX_BLOCKS_MAX);
   vg_box_kernel<<<blocks, SM_THREADS, 0, km->stream>>>(pts, n, km->box_part + 8 * (size_t)BOX_BLOCKS_MAX * slot);
-  KCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   vg_box_final_kernel<<<1, SM_THREADS, 0, km->stream>>>(km->box_part + 8 * (size_t)BOX_BLOCKS_MAX * slot, blocks, km->h_box + 8 * slot);
-  KCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return ROLO_OK;
 }
 
@@ -360,7 +355,7 @@ int vg_enqueue_filter(rolo_keymap* km, const float4* pts, int n, float leaf, int
   long long ext[3];
   for (int d = 0; d < 3; d++) { const float e = (hb[3 + d] - hb[d]) * inv; ext[d] = e < 4e18f ? (long long)e + 1 : (long long)INT32_MAX + 1; }
   if (ext[0] > INT32_MAX || ext[1] > INT32_MAX || ext[0] * ext[1] > INT32_MAX || ext[0] * ext[1] * ext[2] > INT32_MAX) {
-    KCHK(hipMemcpyAsync(out, pts, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, km->stream));
+    HIPCHK(hipMemcpyAsync(out, pts, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, km->stream));
     *direct = true; *m_direct = n;
     return ROLO_OK;
   }
@@ -376,27 +371,27 @@ int vg_enqueue_filter(rolo_keymap* km, const float4* pts, int n, float leaf, int
   hipStream_t s = km->stream;
   const int nblocks = (n + SORT_TILE - 1) / SORT_TILE, nrun = (n + RUN_TILE - 1) / RUN_TILE;
   vg_key_kernel<<<(n + SM_THREADS - 1) / SM_THREADS, SM_THREADS, 0, s>>>(pts, n, G, km->keys[0], km->vals[0]);
-  KCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   int cur = 0;
-  KCHK(hipMemsetAsync(km->dtot, 0, sizeof(unsigned) * 4 * 256, s));
+  HIPCHK(hipMemsetAsync(km->dtot, 0, sizeof(unsigned) * 4 * 256, s));
   for (int shift = 0; shift < bits; shift += 8) {
     unsigned* dtot = km->dtot + 256 * (shift / 8);
     sort_hist_kernel<<<nblocks, SM_THREADS, 0, s>>>(km->keys[cur], n, shift, km->hist, nblocks, dtot);
-    KCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     sort_scan_kernel<<<256, SM_THREADS, 0, s>>>(km->hist, nblocks, dtot);
-    KCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     sort_scatter_kernel<<<nblocks, SM_THREADS, 0, s>>>(km->keys[cur], km->vals[cur], km->keys[cur ^ 1], km->vals[cur ^ 1], n, shift, km->hist, nblocks);
-    KCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     cur ^= 1;
   }
   run_heads_kernel<0><<<nrun, SM_THREADS, 0, s>>>(km->keys[cur], n, km->bcnt, km->starts);
-  KCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   scan_excl_kernel<<<1, 1024, 0, s>>>(km->bcnt, nrun, km->d_m + slot, km->h_m + slot);
-  KCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   run_heads_kernel<1><<<nrun, SM_THREADS, 0, s>>>(km->keys[cur], n, km->bcnt, km->starts);
-  KCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   vg_runsum_kernel<<<(n + SM_THREADS - 1) / SM_THREADS, SM_THREADS, 0, s>>>(pts, km->vals[cur], km->starts, km->d_m + slot, n, out);
-  KCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return ROLO_OK;
 }
 
@@ -434,7 +429,6 @@ int km_alloc_points(rolo_keymap* km, size_t n, float4** out) {
 }  // namespace
 
 namespace rolo {
-// scan2map.hip: the resident sub-map as device clouds (n x 4 floats), the event a reader's stream waits for and the one it records when it has read them
 int keymap_device_submap(rolo_keymap* km, const float** d_corner, int* m_corner, const float** d_surf, int* m_surf, hipEvent_t* ready, hipEvent_t* consumed, int* device) {
   if (!km->have_submap) { ctx_set_error("the key map holds no sub-map: call rolo_keymap_extract first"); return ROLO_ESTATE; }
   *d_corner = reinterpret_cast<const float*>(km->sub[0]); *m_corner = km->m_sub[0];
@@ -445,24 +439,24 @@ int keymap_device_submap(rolo_keymap* km, const float** d_corner, int* m_corner,
 void keymap_mark_consumed(rolo_keymap* km) { km->consumer_pending = true; }
 
 int keymap_stage_cloud(rolo_keymap* km, const float* pts, int n, float leaf, const float4** d_out, int* n_out) {
-  KCHK(hipSetDevice(km->device));
+  HIPCHK(hipSetDevice(km->device));
   hipStream_t s = km->stream;
   int rc;
-  if ((rc = km_grow(km, km->cat[0], km->cat_cap[0], (size_t)n))) return rc;
+  if ((rc = km->store.grow(km->cat[0], km->cat_cap[0], (size_t)n))) return rc;
   if (!(leaf > 0.f)) {
-    KCHK(hipMemcpyAsync(km->cat[0], pts, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, s));
-    KCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpyAsync(km->cat[0], pts, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
     *d_out = km->cat[0]; *n_out = n;
     return ROLO_OK;
   }
   if ((rc = km_sort_scratch(km, n))) return rc;
-  if ((rc = km_grow(km, km->ds_out, km->ds_cap, (size_t)n))) return rc;
-  KCHK(hipMemcpyAsync(km->cat[0], pts, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, s));
+  if ((rc = km->store.grow(km->ds_out, km->ds_cap, (size_t)n))) return rc;
+  HIPCHK(hipMemcpyAsync(km->cat[0], pts, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, s));
   if ((rc = vg_enqueue_box(km, km->cat[0], n, 0))) return rc;
-  KCHK(hipStreamSynchronize(s));
+  HIPCHK(hipStreamSynchronize(s));
   bool direct; int m_direct = 0;
   if ((rc = vg_enqueue_filter(km, km->cat[0], n, leaf, 0, km->ds_out, &direct, &m_direct))) return rc;
-  KCHK(hipStreamSynchronize(s));
+  HIPCHK(hipStreamSynchronize(s));
   const int mm = direct ? m_direct : km->h_m[0];
   if (mm < 0 || mm > n) { ctx_set_error("the key map's voxel filter returned an inconsistent cell count"); return ROLO_ESTATE; }
   *d_out = km->ds_out; *n_out = mm;
@@ -478,7 +472,7 @@ int rolo_keymap_create(int device, rolo_keymap** out) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { ctx_set_error("no HIP device"); return ROLO_EHIP; }
   if (device < 0 || device >= ndev) return ROLO_EINVAL;
-  KCHK(hipSetDevice(device));
+  HIPCHK(hipSetDevice(device));
   rolo_keymap* km = new rolo_keymap();
   km->device = device;
   hipError_t e = hipStreamCreateWithFlags(&km->stream, hipStreamNonBlocking);
@@ -488,6 +482,7 @@ int rolo_keymap_create(int device, rolo_keymap** out) {
   if (e == hipSuccess) e = hipHostMalloc((void**)&km->h_m, sizeof(int) * 2);
   if (e == hipSuccess) e = hipMalloc((void**)&km->d_m, sizeof(int) * 2);
   if (e != hipSuccess) { ctx_set_error((std::string("rolo_keymap_create: ") + hipGetErrorString(e)).c_str()); rolo_keymap_destroy(km); return ROLO_EHIP; }
+  km->store.stream = km->stream; km->store.who = "keymap";
   *out = km;
   return ROLO_OK;
 }
@@ -500,8 +495,7 @@ void rolo_keymap_destroy(rolo_keymap* km) {
   if (km->sc) { sc_store_destroy(km->sc); km->sc = nullptr; }
   if (km->loop_ctx) { rolo_ctx_release(km->loop_ctx); km->loop_ctx = nullptr; }
   for (auto& c : km->chunks) (void)hipFree(c.p);
-  for (void* p : km->retired) (void)hipFree(p);
-  for (void* p : km->retired_host) (void)hipHostFree(p);
+  km->store.release();
   for (void* p : {(void*)km->cat[0], (void*)km->cat[1], (void*)km->sub[0], (void*)km->sub[1], (void*)km->ds_out, (void*)km->keys[0], (void*)km->keys[1], (void*)km->vals[0],
                   (void*)km->vals[1], (void*)km->hist, (void*)km->dtot, (void*)km->bcnt, (void*)km->starts, (void*)km->box_part, (void*)km->segs, (void*)km->d_m, (void*)km->loop[0], (void*)km->loop[1]})
     if (p) (void)hipFree(p);
@@ -519,7 +513,7 @@ int rolo_keymap_size(rolo_keymap* km) { return km ? (int)km->frames.size() : ROL
 int rolo_keymap_add_keyframe(rolo_keymap* km, const float* corner, int n_corner, const float* surf, int n_surf, const float* pose6, double time) {
   if (!km || !pose6 || n_corner < 0 || n_surf < 0 || (n_corner && !corner) || (n_surf && !surf) || n_corner > KM_MAX_POINTS || n_surf > KM_MAX_POINTS) return ROLO_EINVAL;
   if (km->frames.size() >= (size_t)INT_MAX) return ROLO_EINVAL;
-  KCHK(hipSetDevice(km->device));
+  HIPCHK(hipSetDevice(km->device));
   rolo_keymap::Frame f{};
   const float* src[2] = {corner, surf};
   const int n[2] = {n_corner, n_surf};
@@ -527,10 +521,10 @@ int rolo_keymap_add_keyframe(rolo_keymap* km, const float* corner, int n_corner,
     float4* d = nullptr;
     const int rc = km_alloc_points(km, (size_t)n[t], &d);
     if (rc) return rc;
-    if (n[t]) KCHK(hipMemcpyAsync(d, src[t], sizeof(float4) * (size_t)n[t], hipMemcpyHostToDevice, km->stream));
+    if (n[t]) HIPCHK(hipMemcpyAsync(d, src[t], sizeof(float4) * (size_t)n[t], hipMemcpyHostToDevice, km->stream));
     f.pts[t] = d; f.n[t] = n[t];
   }
-  KCHK(hipStreamSynchronize(km->stream));   // the caller's arrays are free again
+  HIPCHK(hipStreamSynchronize(km->stream));   // the caller's arrays are free again
   std::memcpy(f.pose, pose6, sizeof(f.pose));
   f.time = time;
   km->frames.push_back(f);
@@ -558,26 +552,21 @@ int rolo_keymap_extract(rolo_keymap* km, const int32_t* indices, int n, float co
     for (int t = 0; t < 2; t++) { const int c = km->frames[indices[i]].n[t]; total[t] += c; if (c) nseg[t]++; max_n = std::max(max_n, c); }
   }
   if (total[0] > KM_MAX_POINTS || total[1] > KM_MAX_POINTS) { ctx_set_error("rolo_keymap_extract: more than ROLO_KEYMAP_MAX_POINTS points in one fused cloud"); return ROLO_EINVAL; }
-  KCHK(hipSetDevice(km->device));
+  HIPCHK(hipSetDevice(km->device));
   hipStream_t s = km->stream;
-  if (km->consumer_pending) { KCHK(hipStreamWaitEvent(s, km->consumed, 0)); km->consumer_pending = false; }   // the last reader of the sub-map this call overwrites
+  if (km->consumer_pending) { HIPCHK(hipStreamWaitEvent(s, km->consumed, 0)); km->consumer_pending = false; }   // the last reader of the sub-map this call overwrites
   km->have_submap = false;
   int rc;
   const int nmax = (int)std::max(total[0], total[1]);
   if (nmax > 0 && (rc = km_sort_scratch(km, nmax))) return rc;
   const size_t nsegs = (size_t)nseg[0] + nseg[1];
   if (nsegs) {
-    if (nsegs > km->h_segs_cap) {
-      if (km->h_segs) { km->retired_host.push_back(km->h_segs); km->h_segs = nullptr; km->h_segs_cap = 0; }
-      const size_t want = nsegs + nsegs / 2 + 64;
-      KCHK(hipHostMalloc((void**)&km->h_segs, want * sizeof(Seg)));
-      km->h_segs_cap = want;
-    }
-    if ((rc = km_grow(km, km->segs, km->segs_cap, nsegs))) return rc;
+    if ((rc = km->store.grow_pinned(km->h_segs, km->h_segs_cap, nsegs, 64))) return rc;
+    if ((rc = km->store.grow(km->segs, km->segs_cap, nsegs))) return rc;
   }
   for (int t = 0; t < 2; t++) {
-    if ((rc = km_grow(km, km->cat[t], km->cat_cap[t], (size_t)std::max<long long>(total[t], 1)))) return rc;
-    if ((rc = km_grow(km, km->sub[t], km->sub_cap[t], (size_t)std::max<long long>(total[t], 1)))) return rc;
+    if ((rc = km->store.grow(km->cat[t], km->cat_cap[t], (size_t)std::max<long long>(total[t], 1)))) return rc;
+    if ((rc = km->store.grow(km->sub[t], km->sub_cap[t], (size_t)std::max<long long>(total[t], 1)))) return rc;
   }
   // the segment table: corner segments, then surface segments, each in list order
   size_t k = 0;
@@ -592,23 +581,23 @@ int rolo_keymap_extract(rolo_keymap* km, const int32_t* indices, int n, float co
       dst += f.n[t];
     }
   }
-  if (nsegs) KCHK(hipMemcpyAsync(km->segs, km->h_segs, nsegs * sizeof(Seg), hipMemcpyHostToDevice, s));
+  if (nsegs) HIPCHK(hipMemcpyAsync(km->segs, km->h_segs, nsegs * sizeof(Seg), hipMemcpyHostToDevice, s));
   const int gx = std::min((max_n + SM_THREADS - 1) / SM_THREADS, 128);
   for (int t = 0; t < 2; t++) {
     const Seg* base = km->segs + (t ? nseg[0] : 0);
     for (int y0 = 0; y0 < nseg[t]; y0 += 32768) {
       km_transform_kernel<<<dim3(gx, std::min(nseg[t] - y0, 32768)), SM_THREADS, 0, s>>>(base + y0, km->cat[t]);
-      KCHK(hipGetLastError());
+      HIPCHK(hipGetLastError());
     }
     if ((rc = vg_enqueue_box(km, km->cat[t], (int)total[t], t))) return rc;
   }
-  KCHK(hipStreamSynchronize(s));
+  HIPCHK(hipStreamSynchronize(s));
   bool direct[2]; int m_direct[2] = {0, 0};
   const float leaf[2] = {corner_leaf, surf_leaf};
   for (int t = 0; t < 2; t++)
     if ((rc = vg_enqueue_filter(km, km->cat[t], (int)total[t], leaf[t], t, km->sub[t], &direct[t], &m_direct[t]))) return rc;
-  KCHK(hipEventRecord(km->ready, s));
-  KCHK(hipStreamSynchronize(s));
+  HIPCHK(hipEventRecord(km->ready, s));
+  HIPCHK(hipStreamSynchronize(s));
   for (int t = 0; t < 2; t++) km->m_sub[t] = direct[t] ? m_direct[t] : km->h_m[t];
   km->have_submap = true;
   if (m_corner) *m_corner = km->m_sub[0];
@@ -620,10 +609,10 @@ int rolo_keymap_get_submap(rolo_keymap* km, float* corner_out, int cap_corner, f
   if (!km || cap_corner < 0 || cap_surf < 0) return ROLO_EINVAL;
   if (!km->have_submap) { ctx_set_error("the key map holds no sub-map: call rolo_keymap_extract first"); return ROLO_ESTATE; }
   if (km->m_sub[0] > cap_corner || km->m_sub[1] > cap_surf || (km->m_sub[0] && !corner_out) || (km->m_sub[1] && !surf_out)) return ROLO_EINVAL;
-  KCHK(hipSetDevice(km->device));
-  if (km->m_sub[0]) KCHK(hipMemcpyAsync(corner_out, km->sub[0], sizeof(float4) * (size_t)km->m_sub[0], hipMemcpyDeviceToHost, km->stream));
-  if (km->m_sub[1]) KCHK(hipMemcpyAsync(surf_out, km->sub[1], sizeof(float4) * (size_t)km->m_sub[1], hipMemcpyDeviceToHost, km->stream));
-  KCHK(hipStreamSynchronize(km->stream));
+  HIPCHK(hipSetDevice(km->device));
+  if (km->m_sub[0]) HIPCHK(hipMemcpyAsync(corner_out, km->sub[0], sizeof(float4) * (size_t)km->m_sub[0], hipMemcpyDeviceToHost, km->stream));
+  if (km->m_sub[1]) HIPCHK(hipMemcpyAsync(surf_out, km->sub[1], sizeof(float4) * (size_t)km->m_sub[1], hipMemcpyDeviceToHost, km->stream));
+  HIPCHK(hipStreamSynchronize(km->stream));
   return ROLO_OK;
 }
 
@@ -634,7 +623,7 @@ int rolo_keymap_downsample(rolo_keymap* km, const float* pts, int n, float leaf,
   const float4* d = nullptr; int mm = 0;
   const int rc = keymap_stage_cloud(km, pts, n, leaf, &d, &mm);
   if (rc) return rc;
-  if (mm) KCHK(hipMemcpy(out, d, sizeof(float4) * (size_t)mm, hipMemcpyDeviceToHost));
+  if (mm) HIPCHK(hipMemcpy(out, d, sizeof(float4) * (size_t)mm, hipMemcpyDeviceToHost));
   *m = mm;
   return ROLO_OK;
 }
@@ -694,23 +683,18 @@ int rolo_keymap_loop_cloud(rolo_keymap* km, int slot, int key, int search_num, i
   int max_n = 1;
   for (int k = lo; k <= hi; k++) for (int t = 0; t < 2; t++) { const int c = km->frames[k].n[t]; total += c; if (c) nsegs++; max_n = std::max(max_n, c); }
   if (total > KM_MAX_POINTS) { ctx_set_error("rolo_keymap_loop_cloud: more than ROLO_KEYMAP_MAX_POINTS points in one loop cloud"); return ROLO_EINVAL; }
-  KCHK(hipSetDevice(km->device));
+  HIPCHK(hipSetDevice(km->device));
   hipStream_t s = km->stream;
-  if (!km->loop_t0) { KCHK(hipEventCreate(&km->loop_t0)); KCHK(hipEventCreate(&km->loop_t1)); }
+  if (!km->loop_t0) { HIPCHK(hipEventCreate(&km->loop_t0)); HIPCHK(hipEventCreate(&km->loop_t1)); }
   km->loop_ms[slot] = 0.f;
   if (total == 0) { km->have_loop[slot] = true; if (m) *m = 0; return ROLO_OK; }   // :2587 — "if (nearKeyframes->empty()) return"
   int rc;
   const int n = (int)total;
   if ((rc = km_sort_scratch(km, n))) return rc;
-  if (nsegs > km->h_segs_cap) {
-    if (km->h_segs) { km->retired_host.push_back(km->h_segs); km->h_segs = nullptr; km->h_segs_cap = 0; }
-    const size_t want = nsegs + nsegs / 2 + 64;
-    KCHK(hipHostMalloc((void**)&km->h_segs, want * sizeof(Seg)));
-    km->h_segs_cap = want;
-  }
-  if ((rc = km_grow(km, km->segs, km->segs_cap, nsegs))) return rc;
-  if ((rc = km_grow(km, km->cat[0], km->cat_cap[0], (size_t)n))) return rc;
-  if ((rc = km_grow(km, km->loop[slot], km->loop_cap[slot], (size_t)n))) return rc;
+  if ((rc = km->store.grow_pinned(km->h_segs, km->h_segs_cap, nsegs, 64))) return rc;
+  if ((rc = km->store.grow(km->segs, km->segs_cap, nsegs))) return rc;
+  if ((rc = km->store.grow(km->cat[0], km->cat_cap[0], (size_t)n))) return rc;
+  if ((rc = km->store.grow(km->loop[slot], km->loop_cap[slot], (size_t)n))) return rc;
   size_t q = 0;
   int dst = 0;
   for (int k = lo; k <= hi; k++) {
@@ -723,20 +707,20 @@ int rolo_keymap_loop_cloud(rolo_keymap* km, int slot, int key, int search_num, i
       dst += f.n[t];
     }
   }
-  KCHK(hipEventRecord(km->loop_t0, s));
-  KCHK(hipMemcpyAsync(km->segs, km->h_segs, nsegs * sizeof(Seg), hipMemcpyHostToDevice, s));
+  HIPCHK(hipEventRecord(km->loop_t0, s));
+  HIPCHK(hipMemcpyAsync(km->segs, km->h_segs, nsegs * sizeof(Seg), hipMemcpyHostToDevice, s));
   const int gx = std::min((max_n + SM_THREADS - 1) / SM_THREADS, 128);
   for (size_t y0 = 0; y0 < nsegs; y0 += 32768) {
     km_transform_kernel<<<dim3(gx, (unsigned)std::min<size_t>(nsegs - y0, 32768)), SM_THREADS, 0, s>>>(km->segs + y0, km->cat[0]);
-    KCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
   if ((rc = vg_enqueue_box(km, km->cat[0], n, 0))) return rc;
-  KCHK(hipStreamSynchronize(s));
+  HIPCHK(hipStreamSynchronize(s));
   // :2593-2595 — ONE downSizeFilterICP over corner and surface together
   bool direct; int m_direct = 0;
   if ((rc = vg_enqueue_filter(km, km->cat[0], n, leaf, 0, km->loop[slot], &direct, &m_direct))) return rc;
-  KCHK(hipEventRecord(km->loop_t1, s));
-  KCHK(hipStreamSynchronize(s));
+  HIPCHK(hipEventRecord(km->loop_t1, s));
+  HIPCHK(hipStreamSynchronize(s));
   const int mm = direct ? m_direct : km->h_m[0];
   if (mm < 0 || mm > n) { ctx_set_error("the key map's voxel filter returned an inconsistent cell count"); return ROLO_ESTATE; }
   (void)hipEventElapsedTime(&km->loop_ms[slot], km->loop_t0, km->loop_t1);
@@ -750,9 +734,9 @@ int rolo_keymap_get_loop_cloud(rolo_keymap* km, int slot, float* out, int cap) {
   if (!km->have_loop[slot]) { ctx_set_error("the key map holds no loop cloud in this slot: call rolo_keymap_loop_cloud first"); return ROLO_ESTATE; }
   const int mm = km->m_loop[slot];
   if (mm > cap || (mm && !out)) return ROLO_EINVAL;
-  KCHK(hipSetDevice(km->device));
-  if (mm) KCHK(hipMemcpyAsync(out, km->loop[slot], sizeof(float4) * (size_t)mm, hipMemcpyDeviceToHost, km->stream));
-  KCHK(hipStreamSynchronize(km->stream));
+  HIPCHK(hipSetDevice(km->device));
+  if (mm) HIPCHK(hipMemcpyAsync(out, km->loop[slot], sizeof(float4) * (size_t)mm, hipMemcpyDeviceToHost, km->stream));
+  HIPCHK(hipStreamSynchronize(km->stream));
   return mm;
 }
 

@@ -138,6 +138,40 @@ def test_resident_submap_goes_stale_with_the_contexts_clouds():
     g.close()
 
 
+def test_scratch_regrown_inside_one_context_keeps_the_bits():
+    """the scratch of rolo_scan2map_optimize only grows, and what it outgrows is retired, not freed: a context that has optimised a scan of 64 corner + 256 surface
+    features and then one more than four times as large in both kinds — features, workgroup rows, flags and coefficients all past one and a half times the first
+    size + 256 — gives the large scan the bits a fresh context gives it, and the small scan its first bits again on the grown scratch"""
+    corner, surf = features("vlp16", dict(n_scan=16, horizon_scan=1800), np.eye(3), np.zeros(3), synth.SEED)
+    small = (np.ascontiguousarray(corner[::4][:64]), np.ascontiguousarray(surf[::36][:256]))
+    large = (corner, np.ascontiguousarray(surf[::3]))
+    n_small, n_large = 64 + 256, len(large[0]) + len(large[1])
+    assert (len(small[0]), len(small[1])) == (64, 256) and len(large[0]) >= 4 * 64 and len(large[1]) >= 4 * 256
+    cap = lambda need: need + need // 2 + 256                          # what a buffer that needed `need` elements holds
+    assert n_large > cap(n_small)                                      # features, flags, coefficients: one element per feature
+    # the rows: 28 doubles per workgroup; a workgroup takes 64 features of one kind (the default kernel form) or 128 of either (the cross-check form)
+    assert 28 * (n_large // 128) > cap(28 * (n_small // 64 + 2))
+    guess = np.array([0.004, -0.003, 0.01, 0.06, -0.04, 0.02], np.float32)
+
+    def run(g, scan):
+        tf, sel, co = g.scan2MapOptimization(scan[0], scan[1], None, None, guess, want_debug=True)
+        st = g.last_stats
+        return tf.tobytes(), (st.skipped, st.iterations, st.converged, st.degenerate, st.n_selected), sel.tobytes(), co.tobytes()
+
+    g, fresh = Scan2Map(), Scan2Map()
+    try:
+        g.setSubmap(corner, surf); fresh.setSubmap(corner, surf)
+        first = run(g, small)
+        grown = run(g, large)
+        want = run(fresh, large)
+        print("small", first[1], "large", grown[1], "fresh", want[1])
+        assert first[1][0] == 0 and grown[1][0] == 0 and grown[1][4] >= 50
+        assert grown == want
+        assert run(g, small) == first
+    finally:
+        g.close(); fresh.close()
+
+
 @pytest.mark.parametrize("switch", ["ROLO_S2M_PACKETS=0"])
 def test_association_kernel_variants_keep_the_oracles_flags(switch):
     """the association kernel's cross-check form (s2m_kernel, one walk per lane; the default is s2m_assoc_kernel, four lanes per feature) is an exact search

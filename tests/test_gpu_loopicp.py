@@ -113,6 +113,56 @@ def test_sums_against_numpy_and_run_to_run(icp):
     assert icp.trace()[-1]["sums"].tobytes() == got.tobytes()
 
 
+@pytest.mark.parametrize("g", [1, 7, 8, 9, 63, 64, 65])
+def test_sums_at_the_row_groups_edges(icp, g):
+    """256 g source points are g workgroups, so g rows for the row sum (8 groups of lanes, group q adds rows q, q + 8, ...): fewer rows than groups, one full
+    round of the groups with and without a remainder, and 64 rows, where a form of the sum with 8 loads in flight takes its second step. The bound is the one of
+    test_sums_against_numpy_and_run_to_run."""
+    rng = np.random.default_rng(600 + g)
+    src = rng.uniform(-30, 30, (256 * g, 3)).astype(f32); tgt = rng.uniform(-30, 30, (2000, 3)).astype(f32)
+    i, d, moved = check_association(icp, src, tgt, motion(), cap=4.0)
+    terms = T.pair_terms(moved, tgt, i, d)
+    got = icp.trace()[-1]["sums"]
+    assert 0 < len(terms) < len(src) and got[0] == len(terms)
+    bound = 1e-12 * np.abs(terms).sum(axis=0)
+    err = np.abs(got - terms.sum(axis=0))
+    print("g", g, "pairs", len(terms), "sums: worst error / bound", (err / np.maximum(bound, 1e-300)).max())
+    assert np.all(err <= bound)
+    icp.associate(xyzi(src), xyzi(tgt), motion(), 4.0)
+    assert icp.trace()[-1]["sums"].tobytes() == got.tobytes()
+
+
+def test_buffers_regrown_inside_one_context_keep_the_bits():
+    """the context's loop ICP buffers only grow, and what they outgrow is retired, not freed: after a 300-point pair, a 5 000-point pair on the same context
+    (every buffer past one and a half times its first size + 256) gives the result, the trace and the 17 association sums of a fresh context; then the small
+    pair gives its first bits again"""
+    P = loop_icp_params(2.0)
+    small, large = moved_pair(n_tgt=300, n_src=300, seed=11)[:2], moved_pair(n_tgt=5000, n_src=5000, seed=12)[:2]
+    cap = lambda need: need + need // 2 + 256                          # what a buffer that needed `need` elements holds
+    rows = lambda n: ((n + 15) // 16 * 16 + 255) // 256                # workgroups: 256 points each of the source padded to whole leaves of 16
+    assert 5000 > cap(300) and 17 * rows(5000) > cap(17 * rows(300))   # the clouds and per-point arrays; the workgroups' rows of 17 sums
+
+    def run(h, pair):
+        src, tgt = xyzi(pair[0]), xyzi(pair[1])
+        r = h.align(src, tgt, P)
+        tr = h.trace()
+        idx, d2 = h.associate(src, tgt, motion(), 2.0)
+        return (r["T"].tobytes(), np.float64(r["fitness"]).tobytes(), r["converged"], r["iterations"], r["state"], r["n_source"], r["n_target"], r["n_last"],
+                [(x["n"], np.float64(x["mse"]).tobytes(), x["sums"].tobytes(), x["increment"].tobytes()) for x in tr],
+                idx.tobytes(), d2.tobytes(), h.trace()[-1]["sums"].tobytes())
+
+    g, fresh = LoopIcp(), LoopIcp()
+    try:
+        first = run(g, small)
+        grown = run(g, large)
+        want = run(fresh, large)
+        assert grown[3] >= 1 and grown[2] and len(grown[8]) == grown[3] + 1
+        assert grown == want
+        assert run(g, small) == first
+    finally:
+        g.close(); fresh.close()
+
+
 def test_alignment_is_bit_reproducible(icp):
     src, tgt, _ = moved_pair()
     P = loop_icp_params(2.0)
