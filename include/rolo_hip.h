@@ -608,6 +608,30 @@ int rolo_loopicp_associate(rolo_ctx* ctx, const float* source, int n_source, con
 int rolo_loopicp_last_ms(rolo_ctx* ctx, float* ms4);
 int rolo_keymap_loop_last_ms(rolo_keymap* km, float* ms6);
 
+/* ---- back end: the global map (publishGlobalMap, src/backMapping.cpp:1611-1665; saveGlobalPCDs' cloudGlobal.pcd, :1546-1557) --------------------------
+ * rolo_keymap_global_map: for every listed key frame, in list order and with repeats, its corner and then its surface cloud moved by the frame's current pose
+ * (rolo_keymap_loop_cloud's statement), all concatenated, then ONE pcl::VoxelGrid of `leaf` (:1660-1663). The concatenation may hold up to 2^31 - 1 points: past
+ * ROLO_KEYMAP_MAX_POINTS it never exists as a whole. A list of at most `batch` points (rolo_keymap_global_set_batch) goes through the filter of
+ * rolo_keymap_extract in one piece (the one-shot form); a longer one is worked through in batches of exactly `batch` points, cut wherever that falls, each sorted
+ * by cell and merged into a table of (cell, running sums, count) kept in cell order (the streamed form). A cell's sums are continued from batch to batch in
+ * concatenation order, never split into partial sums: both forms return the bits of the filter over the whole cloud. Differences between the forms: PCL's "leaf
+ * size is too small" (copy-through in the one-shot form) is ROLO_EINVAL in the streamed form, whose answer would be the whole input; a table that cannot be
+ * grown is ROLO_EHIP ("hipMalloc failed"). The map stays on the device in a slot of its own; working memory follows the batch and the number of cells. */
+int rolo_keymap_global_map(rolo_keymap* km, const int32_t* indices, int n, float leaf, int* m);
+/* the last global map (n x 4 floats) into out; returns its size. ROLO_ESTATE before the first rolo_keymap_global_map, ROLO_EINVAL if cap is too small */
+int rolo_keymap_get_global_map(rolo_keymap* km, float* out, int cap);
+/* points per batch, 1 .. ROLO_KEYMAP_MAX_POINTS; 0: the default (ROLO_KEYMAP_GLOBAL_BATCH). For callers short of device memory, and for the tests */
+#define ROLO_KEYMAP_GLOBAL_BATCH (1 << 24)
+int rolo_keymap_global_set_batch(rolo_keymap* km, int points);
+/* of the last rolo_keymap_global_map, the first min(n, 5) of: input points, batches, cells, the form (0 one-shot, 1 streamed), the largest table size (cells) */
+int rolo_keymap_global_info(rolo_keymap* km, long long* out, int n);
+/* device time of the last rolo_keymap_global_map in milliseconds between HIP events: ms3[0] the box pass (one-shot: transform + box), [1] the sort + merge
+ * pass (one-shot: the filter), [2] the finish (one-shot: 0) */
+int rolo_keymap_global_last_ms(rolo_keymap* km, float* ms3);
+/* cloudGlobal.pcd's cloud (:1546-1557): the same concatenation unfiltered, batch by batch through the device into out (cap points of 4 floats on the host); nothing
+ * of the list's size lives on the device. Returns the number of points, or an error code; ROLO_EINVAL if cap is smaller */
+long long rolo_keymap_global_cloud(rolo_keymap* km, const int32_t* indices, int n, float* out, long long cap);
+
 /* ---- back end: pose-graph optimisation for the loop closures ----------------------------------------------------------------------------
  * saveKeyFramesAndFactor / addOdomFactor / addLoopFactor / addPriorFactor / correctPoses (src/backMapping.cpp:1094-1320) as a BATCH minimiser of the objective
  * the reference hands to iSAM2, built from the same factors and the same noise models. GTSAM is not in the reference tree and iSAM2 is incremental: this is not a

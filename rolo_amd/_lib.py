@@ -214,6 +214,12 @@ SYMBOLS = {
     "rolo_pgo_last_ms": (C.c_int, [vp, fp]),
     "rolo_keymap_set_poses": (C.c_int, [vp, fp, C.c_int]),
     "rolo_keymap_loop_last_ms": (C.c_int, [vp, fp]),
+    "rolo_keymap_global_map": (C.c_int, [vp, ip, C.c_int, C.c_float, C.POINTER(C.c_int)]),
+    "rolo_keymap_get_global_map": (C.c_int, [vp, fp, C.c_int]),
+    "rolo_keymap_global_set_batch": (C.c_int, [vp, C.c_int]),
+    "rolo_keymap_global_info": (C.c_int, [vp, C.POINTER(C.c_longlong), C.c_int]),
+    "rolo_keymap_global_last_ms": (C.c_int, [vp, fp]),
+    "rolo_keymap_global_cloud": (C.c_longlong, [vp, ip, C.c_int, fp, C.c_longlong]),
     "rolo_num_voxels": (C.c_int, [vp]),
     "rolo_num_edge_points": (C.c_int, [vp]),
     "rolo_get_voxels": (C.c_int, [vp, ip, ip, dp, dp]),

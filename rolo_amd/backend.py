@@ -1,7 +1,8 @@
 """Host mirrors of the back end: the scan-to-submap optimisation (reference src/backMapping.cpp:681-1058) over rolo_scan2map_optimize, the
 device-resident key frames with sub-map assembly (:558-678) over rolo_keymap_*, Scan Context loop detection (src/scancontext/Scancontext.cpp) over
-rolo_keymap_sc_*, the loop closure's clouds, radius-search detector and ICP (:2307-2624) over rolo_keymap_loop_* / rolo_loopicp_*, and the factor graph
-(:1222-1320) as a batch pose-graph optimisation over rolo_pgo_*."""
+rolo_keymap_sc_*, the loop closure's clouds, radius-search detector and ICP (:2307-2624) over rolo_keymap_loop_* / rolo_loopicp_*, the factor graph
+(:1222-1320) as a batch pose-graph optimisation over rolo_pgo_*, and the clouds of the exports (publishGlobalMap :1611-1665, cloudGlobal.pcd :1546-1557) over
+rolo_keymap_global_*."""
 from __future__ import annotations
 
 import ctypes as C
@@ -65,6 +66,13 @@ def select_nearby(xyz, times, time_cur, search_radius=50.0, density=2.0, recent_
                                                 out.ctypes.data_as(ip), out.shape[0]), "rolo_keyposes_select_nearby")
     assert m <= out.shape[0]
     return out[:m].copy()
+
+
+def select_global(xyz, search_radius=1000.0, pose_density=10.0):
+    """publishGlobalMap's selection (:1619-1654): select_nearby's radius search, pose filter and range test with no key pose admitted by its time (the reference
+    has no "recent" clause here); host only"""
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    return select_nearby(xyz, np.zeros(xyz.shape[0]), 0.0, search_radius, pose_density, -np.inf)
 
 
 def detect_loop_distance(xyz, times, time_cur, search_radius=30.0, time_diff=30.0) -> int:
@@ -157,7 +165,8 @@ class KeyFrameMap:
         check(lib().rolo_keymap_create(device, C.byref(self._h)), "rolo_keymap_create")
         self.corner_leaf, self.surf_leaf = mappingCornerLeafSize, mappingSurfLeafSize
         self.poses, self.times = [], []   # transformTobeMapped order: roll, pitch, yaw, x, y, z
-        self.m_corner = self.m_surf = 0
+        self._sizes = []                  # corner + surface points per key frame (sizes globalCloud's array)
+        self.m_corner = self.m_surf = self.m_global = 0
 
     def close(self):
         if self._h:
@@ -174,7 +183,7 @@ class KeyFrameMap:
         p = np.ascontiguousarray(pose6, np.float32).reshape(6)
         k = check(lib().rolo_keymap_add_keyframe(self._h, a[0].ctypes.data_as(fp), a[0].shape[0], a[1].ctypes.data_as(fp), a[1].shape[0], p.ctypes.data_as(fp), float(time)),
                   "rolo_keymap_add_keyframe")
-        self.poses.append(p.copy()); self.times.append(float(time))
+        self.poses.append(p.copy()); self.times.append(float(time)); self._sizes.append(a[0].shape[0] + a[1].shape[0])
         return k
 
     def setPose(self, index: int, pose6):
@@ -307,6 +316,55 @@ class KeyFrameMap:
         """detectLoopClosureDistance (:2481-2515) on the stored key poses"""
         xyz = np.array([p[3:6] for p in self.poses], np.float32).reshape(-1, 3)
         return detect_loop_distance(xyz, self.times, time_cur, search_radius, time_diff)
+
+    # ---- the global map (publishGlobalMap :1611-1665, saveGlobalPCDs' cloudGlobal.pcd :1546-1557) ----
+    def selectGlobal(self, search_radius: float = 1000.0, pose_density: float = 10.0):
+        """the key frames publishGlobalMap fuses (:1619-1654), in its order: selectNearby's radius rule and pose filter, nothing admitted by time"""
+        return select_global(np.array([p[3:6] for p in self.poses], np.float32).reshape(-1, 3), search_radius, pose_density)
+
+    def globalMap(self, indices, leaf: float = 1.0, download: bool = True):
+        """:1656-1663 — the listed key frames' clouds at their current poses through one VoxelGrid; the map stays on the device. Returns it (m x 4), or with
+        download = False its size (globalMapPoints fetches it later)"""
+        idx = np.ascontiguousarray(indices, np.int32).reshape(-1)
+        m = C.c_int(0)
+        check(lib().rolo_keymap_global_map(self._h, idx.ctypes.data_as(C.POINTER(C.c_int32)), idx.shape[0], leaf, C.byref(m)), "rolo_keymap_global_map")
+        self.m_global = m.value
+        return self.globalMapPoints() if download else m.value
+
+    def globalMapPoints(self):
+        """download of the last globalMap"""
+        out = np.zeros((self.m_global, 4), np.float32)
+        got = check(lib().rolo_keymap_get_global_map(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.shape[0]), "rolo_keymap_get_global_map")
+        return out[:got]
+
+    def globalCloud(self, indices):
+        """:1546-1557 — the same clouds concatenated, unfiltered (cloudGlobal.pcd's points)"""
+        idx = np.ascontiguousarray(indices, np.int32).reshape(-1)
+        ip = idx.ctypes.data_as(C.POINTER(C.c_int32))
+        total = sum(self._sizes[k] for k in idx.tolist()) if all(0 <= k < len(self._sizes) for k in idx.tolist()) else 0
+        out = np.zeros((total, 4), np.float32)
+        got = check(lib().rolo_keymap_global_cloud(self._h, ip, idx.shape[0], out.ctypes.data_as(C.POINTER(C.c_float)), total), "rolo_keymap_global_cloud")
+        return out[:got]
+
+    def setGlobalBatch(self, points: int):
+        """points per batch of globalMap / globalCloud; 0: the library's default"""
+        check(lib().rolo_keymap_global_set_batch(self._h, int(points)), "rolo_keymap_global_set_batch")
+
+    def globalInfo(self) -> dict:
+        """of the last globalMap: input points, batches, cells, the form that ran, the largest table size"""
+        v = (C.c_longlong * 5)()
+        check(lib().rolo_keymap_global_info(self._h, v, 5), "rolo_keymap_global_info")
+        return dict(points=v[0], batches=v[1], cells=v[2], form=("one-shot", "streamed")[v[3]], table=v[4])
+
+    def globalLastMs(self):
+        """device milliseconds of the last globalMap: box pass, sort + merge pass, finish"""
+        ms = np.zeros(3, np.float32)
+        check(lib().rolo_keymap_global_last_ms(self._h, ms.ctypes.data_as(C.POINTER(C.c_float))), "rolo_keymap_global_last_ms")
+        return ms
+
+    def publishGlobalMap(self, search_radius: float = 1000.0, pose_density: float = 10.0, leaf: float = 1.0):
+        """publishGlobalMap (:1611-1665) with config/params.yaml:67-69's defaults: selectGlobal, then globalMap"""
+        return self.globalMap(self.selectGlobal(search_radius, pose_density), leaf)
 
 
 class ScanContextManager:

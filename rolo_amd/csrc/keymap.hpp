@@ -48,6 +48,21 @@ struct rolo_keymap {
   float loop_ms[2] = {0.f, 0.f};     // device time of the last assembly per slot
   hipEvent_t loop_t0 = nullptr, loop_t1 = nullptr;   // with timing, created by the first assembly
   rolo_ctx* loop_ctx = nullptr;      // the pooled registration context whose tree builder and stream the ICP uses; given back by rolo_keymap_destroy
+  // the global map (rolo_keymap_global_* in submap.hip): the result, and the streamed form's two ping-pong tables of (cell, running sums, count) in cell order
+  int gm_batch = 0;                  // points per batch; 0: ROLO_KEYMAP_GLOBAL_BATCH
+  float4* gmap = nullptr; size_t gmap_cap = 0;
+  int m_gmap = 0;
+  bool have_gmap = false;
+  unsigned* gt_key[2] = {nullptr, nullptr}; size_t gt_key_cap[2] = {0, 0};
+  float4* gt_sum[2] = {nullptr, nullptr}; size_t gt_sum_cap[2] = {0, 0};
+  int* gt_cnt[2] = {nullptr, nullptr}; size_t gt_cnt_cap[2] = {0, 0};
+  unsigned* gm_ncnt = nullptr; size_t gm_ncnt_cap = 0;   // new cells per workgroup of the batch's runs, then their exclusive scan
+  int* gm_npre = nullptr; size_t gm_npre_cap = 0;        // per run: the new cells among the runs before it; [runs]: all of them
+  int* gm_d = nullptr;               // [2] on the device: the batch's new cells
+  int* gm_h = nullptr;               // pinned [2]
+  long long gm_info[5] = {0, 0, 0, 0, 0};
+  float gm_ms[3] = {0.f, 0.f, 0.f};
+  hipEvent_t gm_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // with timing, created by the first global map
 };
 
 namespace rolo {

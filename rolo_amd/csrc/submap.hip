@@ -1,7 +1,8 @@
 // The back end's sub-map assembly on gfx950: a device-resident key-frame store (rolo_keymap_*), extractCloud and pcl::VoxelGrid for clouds of any size.
 // Replaces (reference src/backMapping.cpp) extractNearby :575-614 (rolo_keyposes_select_nearby, host), extractCloud :617-658 with transformPointCloud :301-320
 // (rolo_keymap_extract), downsampleCurrentScan :666-678 (rolo_keymap_downsample) and the key-frame bookkeeping of saveKeyFramesAndFactor :1140-1181 /
-// correctPoses :1287-1320 (rolo_keymap_add_keyframe / rolo_keymap_set_pose).
+// correctPoses :1287-1320 (rolo_keymap_add_keyframe / rolo_keymap_set_pose), and the clouds of the exports: publishGlobalMap :1611-1665 (rolo_keymap_global_map)
+// and saveGlobalPCDs' cloudGlobal.pcd :1546-1557 (rolo_keymap_global_cloud), past ROLO_KEYMAP_MAX_POINTS through the streamed form of the filter (gm_* below).
 //
 // pcl::VoxelGrid<PointXYZI>::filter, bit-identical to the oracle's orc_voxelgrid (oracle/rolo_oracle_front.cpp): float min / max of the cloud, the integer
 // cell index as written there, cells in ascending index order, and per cell the four float sums taken SERIALLY IN ORIGINAL POINT ORDER, divided by the float
@@ -271,6 +272,90 @@ __global__ __launch_bounds__(SM_THREADS) void vg_runsum_kernel(const float4* __r
   out[r] = make_float4(sx / cnt, sy / cnt, sz / cnt, si / cnt);
 }
 
+// ---- the streamed filter (rolo_keymap_global_map): a batch's runs merged into a table of (cell, running sums, count) kept in cell order -------------------
+// The table carries every cell's serial chain from batch to batch: a run of a cell the table holds starts from the kept sums and adds its points in order, so the
+// sums are those of one pass over the whole concatenation. Two tables in turn: every old entry and every run writes its own place in the other one, no
+// atomics, no workgroup waits for another; each seam is a launch.
+//   gm_find_kernel        one lane per run: the lower bound of its cell in the table, found or new; new cells per workgroup -> ncnt (scanned by scan_excl_kernel)
+//   gm_merge_runs_kernel  one lane per run: its place = lower bound + the new runs before it; sums continued from the table's, or from 0, through the run's points
+//   gm_move_old_kernel    one lane per old entry no run continues: its place = its index + the new runs below its cell
+//   gm_finish_kernel      sums / float(count)
+__device__ __forceinline__ int lower_bound_u32(const unsigned* __restrict__ a, int n, unsigned key) {
+  int lo = 0, hi = n;
+  while (lo < hi) { const int mid = lo + ((hi - lo) >> 1); if (a[mid] < key) lo = mid + 1; else hi = mid; }
+  return lo;
+}
+
+// rkey[r]: the run's cell; lbv[r]: its lower bound in the table, as ~bound when the table does not hold the cell
+__global__ __launch_bounds__(SM_THREADS) void gm_find_kernel(const unsigned* __restrict__ keys, const int* __restrict__ starts, const int* __restrict__ nruns_ptr,
+                                                             const unsigned* __restrict__ tkey, int m_old, unsigned* __restrict__ rkey, int* __restrict__ lbv,
+                                                             unsigned* __restrict__ ncnt) {
+  __shared__ unsigned wsum[SM_THREADS / 64];
+  const int r = blockIdx.x * SM_THREADS + threadIdx.x;
+  bool isnew = false;
+  if (r < *nruns_ptr) {
+    const unsigned key = keys[starts[r]];
+    const int lb = lower_bound_u32(tkey, m_old, key);
+    isnew = !(lb < m_old && tkey[lb] == key);
+    rkey[r] = key;
+    lbv[r] = isnew ? ~lb : lb;
+  }
+  const unsigned long long b = __ballot(isnew);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = (unsigned)__popcll(b);
+  __syncthreads();
+  if (threadIdx.x == 0) { unsigned t = 0; for (int w = 0; w < SM_THREADS / 64; w++) t += wsum[w]; ncnt[blockIdx.x] = t; }
+}
+
+struct GmTable { unsigned* key; float4* sum; int* cnt; };
+
+__global__ __launch_bounds__(SM_THREADS) void gm_merge_runs_kernel(const float4* __restrict__ pts, const int* __restrict__ idx, const int* __restrict__ starts,
+                                                                   const int* __restrict__ nruns_ptr, int n, const unsigned* __restrict__ rkey,
+                                                                   const int* __restrict__ lbv, const unsigned* __restrict__ ncnt /* scanned */, GmTable told,
+                                                                   GmTable tnew, int* __restrict__ npre) {
+  __shared__ unsigned wsum[SM_THREADS / 64];
+  const int r = blockIdx.x * SM_THREADS + threadIdx.x, nruns = *nruns_ptr;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int code = r < nruns ? lbv[r] : 0;
+  const bool isnew = code < 0;
+  const unsigned long long b = __ballot(isnew);
+  if (lane == 0) wsum[wv] = (unsigned)__popcll(b);
+  __syncthreads();
+  unsigned before = 0;
+  for (int w = 0; w < wv; w++) before += wsum[w];
+  if (r >= nruns) return;
+  const int pre = (int)(ncnt[blockIdx.x] + before + (unsigned)__popcll(b & ((1ull << lane) - 1ull)));
+  npre[r] = pre;
+  if (r == nruns - 1) npre[nruns] = pre + (isnew ? 1 : 0);
+  const int lb = isnew ? ~code : code;
+  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  int c = 0;
+  if (!isnew) { s = told.sum[lb]; c = told.cnt[lb]; }
+  const int j0 = starts[r], j1 = r + 1 < nruns ? starts[r + 1] : n;
+  for (int j = j0; j < j1; j++) { const float4 p = pts[idx[j]]; s.x += p.x; s.y += p.y; s.z += p.z; s.w += p.w; }
+  const size_t dst = (size_t)lb + (size_t)pre;   // < old entries + new cells: the lower bound counts the old cells below, pre the new ones
+  tnew.key[dst] = rkey[r]; tnew.sum[dst] = s; tnew.cnt[dst] = c + (j1 - j0);
+}
+
+__global__ __launch_bounds__(SM_THREADS) void gm_move_old_kernel(GmTable told, int m_old, const unsigned* __restrict__ rkey, const int* __restrict__ nruns_ptr,
+                                                                 const int* __restrict__ npre, GmTable tnew) {
+  const int i = blockIdx.x * SM_THREADS + threadIdx.x;
+  if (i >= m_old) return;
+  const int nruns = *nruns_ptr;
+  const unsigned key = told.key[i];
+  const int j = lower_bound_u32(rkey, nruns, key);
+  if (j < nruns && rkey[j] == key) return;   // continued by a run: gm_merge_runs_kernel writes it
+  const size_t dst = (size_t)i + (size_t)npre[j];
+  tnew.key[dst] = key; tnew.sum[dst] = told.sum[i]; tnew.cnt[dst] = told.cnt[i];
+}
+
+__global__ __launch_bounds__(SM_THREADS) void gm_finish_kernel(const float4* __restrict__ sum, const int* __restrict__ cnt, int m, float4* __restrict__ out) {
+  const int i = blockIdx.x * SM_THREADS + threadIdx.x;
+  if (i >= m) return;
+  const float4 s = sum[i];
+  const float c = (float)cnt[i];
+  out[i] = make_float4(s.x / c, s.y / c, s.z / c, s.w / c);
+}
+
 // ---- host restatement of the same filter (the key poses of extractNearby: a few hundred points) ------------------------------------------------------------
 int host_voxelgrid(const std::vector<std::array<float, 4>>& in, float leaf, std::vector<std::array<float, 4>>& out) {
   out.clear();
@@ -344,30 +429,27 @@ int vg_enqueue_box(rolo_keymap* km, const float4* pts, int n, int slot) {
   return ROLO_OK;
 }
 
-// second half: keys, sort, cells, centroids into out; the number of cells lands in h_m[slot] (valid after the stream has been waited for).
-// *direct: the result is known without the device (n = 0, or PCL's "leaf size is too small": the input copied through)
-int vg_enqueue_filter(rolo_keymap* km, const float4* pts, int n, float leaf, int slot, float4* out, bool* direct, int* m_direct) {
-  *direct = false;
-  if (n <= 0) { *direct = true; *m_direct = 0; return ROLO_OK; }
-  const float* hb = km->h_box + 8 * slot;
-  if (hb[6] != 0.f) { ctx_set_error("a non-finite coordinate reached the voxel grid filter"); return ROLO_ENONFINITE; }
+// the grid of a box (h_box's 7 floats) at a leaf: false for PCL's "leaf size is too small" (more than INT32_MAX cells by the extents). *bits: what the sort needs
+bool vg_grid_of_box(const float* hb, float leaf, VgGrid* G, int* bits) {
   const float inv = 1.0f / leaf;
   long long ext[3];
   for (int d = 0; d < 3; d++) { const float e = (hb[3 + d] - hb[d]) * inv; ext[d] = e < 4e18f ? (long long)e + 1 : (long long)INT32_MAX + 1; }
-  if (ext[0] > INT32_MAX || ext[1] > INT32_MAX || ext[0] * ext[1] > INT32_MAX || ext[0] * ext[1] * ext[2] > INT32_MAX) {
-    HIPCHK(hipMemcpyAsync(out, pts, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, km->stream));
-    *direct = true; *m_direct = n;
-    return ROLO_OK;
-  }
-  VgGrid G{};
-  G.inv = inv;
+  if (ext[0] > INT32_MAX || ext[1] > INT32_MAX || ext[0] * ext[1] > INT32_MAX || ext[0] * ext[1] * ext[2] > INT32_MAX) return false;
+  *G = VgGrid{};
+  G->inv = inv;
   int div[3];
-  for (int d = 0; d < 3; d++) { G.min_b[d] = (int)std::floor(hb[d] * inv); div[d] = (int)std::floor(hb[3 + d] * inv) - G.min_b[d] + 1; }
-  G.mul[0] = 1u; G.mul[1] = (unsigned)div[0]; G.mul[2] = (unsigned)div[0] * (unsigned)div[1];
+  for (int d = 0; d < 3; d++) { G->min_b[d] = (int)std::floor(hb[d] * inv); div[d] = (int)std::floor(hb[3 + d] * inv) - G->min_b[d] + 1; }
+  G->mul[0] = 1u; G->mul[1] = (unsigned)div[0]; G->mul[2] = (unsigned)div[0] * (unsigned)div[1];
   const long long cells = (long long)div[0] * div[1] * div[2];
-  int bits = 32;
-  if (cells <= (long long)INT32_MAX) { bits = 1; while (bits < 31 && (1ll << bits) < cells) bits++; G.flip = 0u; }
-  else G.flip = 0x80000000u;   // div_b's product wraps the int (the extents' product did not): signed order through the flipped sign bit
+  *bits = 32;
+  if (cells <= (long long)INT32_MAX) { *bits = 1; while (*bits < 31 && (1ll << *bits) < cells) (*bits)++; G->flip = 0u; }
+  else G->flip = 0x80000000u;   // div_b's product wraps the int (the extents' product did not): signed order through the flipped sign bit
+  return true;
+}
+
+// keys of pts[0 .. n), the stable sort by cell, the run heads: sorted keys / point indices in km->keys[*cur] / km->vals[*cur], km->starts, the number of runs in
+// d_m[slot] and h_m[slot] (valid after the stream has been waited for)
+int vg_enqueue_sort_runs(rolo_keymap* km, const float4* pts, int n, const VgGrid& G, int bits, int slot, int* cur_out) {
   hipStream_t s = km->stream;
   const int nblocks = (n + SORT_TILE - 1) / SORT_TILE, nrun = (n + RUN_TILE - 1) / RUN_TILE;
   vg_key_kernel<<<(n + SM_THREADS - 1) / SM_THREADS, SM_THREADS, 0, s>>>(pts, n, G, km->keys[0], km->vals[0]);
@@ -390,7 +472,27 @@ int vg_enqueue_filter(rolo_keymap* km, const float4* pts, int n, float leaf, int
   HIPCHK(hipGetLastError());
   run_heads_kernel<1><<<nrun, SM_THREADS, 0, s>>>(km->keys[cur], n, km->bcnt, km->starts);
   HIPCHK(hipGetLastError());
-  vg_runsum_kernel<<<(n + SM_THREADS - 1) / SM_THREADS, SM_THREADS, 0, s>>>(pts, km->vals[cur], km->starts, km->d_m + slot, n, out);
+  *cur_out = cur;
+  return ROLO_OK;
+}
+
+// second half: keys, sort, cells, centroids into out; the number of cells lands in h_m[slot] (valid after the stream has been waited for).
+// *direct: the result is known without the device (n = 0, or PCL's "leaf size is too small": the input copied through)
+int vg_enqueue_filter(rolo_keymap* km, const float4* pts, int n, float leaf, int slot, float4* out, bool* direct, int* m_direct) {
+  *direct = false;
+  if (n <= 0) { *direct = true; *m_direct = 0; return ROLO_OK; }
+  const float* hb = km->h_box + 8 * slot;
+  if (hb[6] != 0.f) { ctx_set_error("a non-finite coordinate reached the voxel grid filter"); return ROLO_ENONFINITE; }
+  VgGrid G; int bits = 0;
+  if (!vg_grid_of_box(hb, leaf, &G, &bits)) {
+    HIPCHK(hipMemcpyAsync(out, pts, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, km->stream));
+    *direct = true; *m_direct = n;
+    return ROLO_OK;
+  }
+  int cur = 0;
+  const int rc = vg_enqueue_sort_runs(km, pts, n, G, bits, slot, &cur);
+  if (rc) return rc;
+  vg_runsum_kernel<<<(n + SM_THREADS - 1) / SM_THREADS, SM_THREADS, 0, km->stream>>>(pts, km->vals[cur], km->starts, km->d_m + slot, n, out);
   HIPCHK(hipGetLastError());
   return ROLO_OK;
 }
@@ -423,6 +525,139 @@ int km_alloc_points(rolo_keymap* km, size_t n, float4** out) {
   rolo_keymap::Chunk& c = km->chunks.back();
   *out = c.p + c.used;
   c.used += n;
+  return ROLO_OK;
+}
+
+// ---- the global map's concatenation: per listed key frame its corner, then its surface cloud; never held as a whole -----------------------------------------
+struct GmPiece { const float4* src; int n; int frame; long long off; };   // one non-empty cloud and where it starts in the concatenation
+
+int gm_list(rolo_keymap* km, const int32_t* indices, int n, const char* who, std::vector<GmPiece>& pieces, long long* total) {
+  pieces.clear();
+  long long off = 0;
+  for (int i = 0; i < n; i++) {
+    if (indices[i] < 0 || indices[i] >= (int)km->frames.size()) { ctx_set_error((std::string(who) + ": key-frame index out of range").c_str()); return ROLO_EINVAL; }
+    const rolo_keymap::Frame& f = km->frames[indices[i]];
+    for (int t = 0; t < 2; t++) {
+      if (!f.n[t]) continue;
+      pieces.push_back({f.pts[t], f.n[t], indices[i], off});
+      off += f.n[t];
+    }
+    if (off > (long long)INT32_MAX) { ctx_set_error((std::string(who) + ": more than 2^31 - 1 points listed").c_str()); return ROLO_EINVAL; }
+  }
+  *total = off;
+  return ROLO_OK;
+}
+
+int gm_batch_of(const rolo_keymap* km) { return km->gm_batch > 0 ? km->gm_batch : ROLO_KEYMAP_GLOBAL_BATCH; }
+
+// scratch of one batch: the transformed points, the segment table (a batch of nb points holds at most nb non-empty clouds)
+int gm_batch_scratch(rolo_keymap* km, int nb, size_t npieces) {
+  const size_t nsegs = std::max<size_t>(std::min<size_t>(npieces, (size_t)nb), 1);
+  int rc;
+  if ((rc = km->store.grow_pinned(km->h_segs, km->h_segs_cap, nsegs, 64))) return rc;
+  if ((rc = km->store.grow(km->segs, km->segs_cap, nsegs))) return rc;
+  return km->store.grow(km->cat[0], km->cat_cap[0], (size_t)nb);
+}
+
+// points [b0, b0 + nb) of the concatenation, moved by their frames' poses, into cat[0]: a Seg with an offset source is a slice, so a batch may begin and end inside
+// a cloud. *cursor: the first piece that reaches b0 or beyond (batches are taken in order). The pinned segment table is reused: the stream has been waited for
+// since the last batch's copy
+int gm_enqueue_batch(rolo_keymap* km, const std::vector<GmPiece>& pieces, size_t* cursor, long long b0, int nb) {
+  while (*cursor < pieces.size() && pieces[*cursor].off + pieces[*cursor].n <= b0) ++*cursor;
+  size_t nsegs = 0;
+  int max_n = 1;
+  for (size_t q = *cursor; q < pieces.size() && pieces[q].off < b0 + nb; q++) {
+    const GmPiece& pc = pieces[q];
+    const long long lo = std::max(pc.off, b0), hi = std::min(pc.off + pc.n, b0 + nb);
+    Seg& g = km->h_segs[nsegs++];
+    g.src = pc.src + (lo - pc.off); g.n = (int)(hi - lo); g.dst = (int)(lo - b0);
+    pose_to_T(km->frames[pc.frame].pose, g.T);
+    max_n = std::max(max_n, g.n);
+  }
+  hipStream_t s = km->stream;
+  HIPCHK(hipMemcpyAsync(km->segs, km->h_segs, nsegs * sizeof(Seg), hipMemcpyHostToDevice, s));
+  const int gx = std::min((max_n + SM_THREADS - 1) / SM_THREADS, 128);
+  for (size_t y0 = 0; y0 < nsegs; y0 += 32768) {
+    km_transform_kernel<<<dim3(gx, (unsigned)std::min<size_t>(nsegs - y0, 32768)), SM_THREADS, 0, s>>>(km->segs + y0, km->cat[0]);
+    HIPCHK(hipGetLastError());
+  }
+  return ROLO_OK;
+}
+
+// the streamed form: total > batch points. The events 1 .. 3 are recorded here
+int gm_streamed(rolo_keymap* km, const std::vector<GmPiece>& pieces, long long total, int batch, float leaf, int* m_out) {
+  hipStream_t s = km->stream;
+  const long long nbatches = (total + batch - 1) / batch;
+  int rc;
+  if ((rc = km_sort_scratch(km, batch))) return rc;
+  if ((rc = gm_batch_scratch(km, batch, pieces.size()))) return rc;
+  const int nblk = (batch + SM_THREADS - 1) / SM_THREADS;
+  if ((rc = km->store.grow(km->gm_ncnt, km->gm_ncnt_cap, (size_t)nblk))) return rc;
+  if ((rc = km->store.grow(km->gm_npre, km->gm_npre_cap, (size_t)batch + 1))) return rc;
+  // pass 1: the box of the whole concatenation; min, max and the flag are exact in any order
+  float box[7] = {FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX, 0.f};
+  size_t cursor = 0;
+  for (long long b = 0; b < nbatches; b++) {
+    const long long b0 = b * batch;
+    const int nb = (int)std::min<long long>(batch, total - b0);
+    if ((rc = gm_enqueue_batch(km, pieces, &cursor, b0, nb))) return rc;
+    if ((rc = vg_enqueue_box(km, km->cat[0], nb, 0))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    for (int k = 0; k < 3; k++) { box[k] = std::min(box[k], km->h_box[k]); box[3 + k] = std::max(box[3 + k], km->h_box[3 + k]); }
+    if (km->h_box[6] != 0.f) box[6] = 1.f;
+  }
+  HIPCHK(hipEventRecord(km->gm_ev[1], s));
+  if (box[6] != 0.f) { ctx_set_error("a non-finite coordinate reached the voxel grid filter"); return ROLO_ENONFINITE; }
+  VgGrid G; int bits = 0;
+  if (!vg_grid_of_box(box, leaf, &G, &bits)) {
+    ctx_set_error("rolo_keymap_global_map: leaf size is too small for the listed clouds (more than INT32_MAX cells): the streamed form does not return the whole input");
+    return ROLO_EINVAL;
+  }
+  // pass 2: the same points again, batch by batch: keys with the global grid, sort, runs, merge into the other table
+  int m_tab = 0, tcur = 0;
+  long long m_peak = 0;
+  cursor = 0;
+  for (long long b = 0; b < nbatches; b++) {
+    const long long b0 = b * batch;
+    const int nb = (int)std::min<long long>(batch, total - b0);
+    if ((rc = gm_enqueue_batch(km, pieces, &cursor, b0, nb))) return rc;
+    int cur = 0;
+    if ((rc = vg_enqueue_sort_runs(km, km->cat[0], nb, G, bits, 0, &cur))) return rc;
+    const int blocks = (nb + SM_THREADS - 1) / SM_THREADS;
+    unsigned* rkey = km->keys[cur ^ 1];   // the sort's other pair is free now: the runs' cells and their lower bounds
+    int* lbv = km->vals[cur ^ 1];
+    gm_find_kernel<<<blocks, SM_THREADS, 0, s>>>(km->keys[cur], km->starts, km->d_m, km->gt_key[tcur], m_tab, rkey, lbv, km->gm_ncnt);
+    HIPCHK(hipGetLastError());
+    scan_excl_kernel<<<1, 1024, 0, s>>>(km->gm_ncnt, blocks, km->gm_d, km->gm_h);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    const int nruns = km->h_m[0], nnew = km->gm_h[0];
+    if (nruns <= 0 || nruns > nb || nnew < 0 || nnew > nruns || (long long)m_tab + nnew > (long long)INT32_MAX) {
+      ctx_set_error("the key map's streamed voxel filter returned an inconsistent cell count"); return ROLO_ESTATE;
+    }
+    const int tn = tcur ^ 1;
+    const size_t m_new = (size_t)m_tab + (size_t)nnew;
+    if ((rc = km->store.grow(km->gt_key[tn], km->gt_key_cap[tn], m_new))) return rc;
+    if ((rc = km->store.grow(km->gt_sum[tn], km->gt_sum_cap[tn], m_new))) return rc;
+    if ((rc = km->store.grow(km->gt_cnt[tn], km->gt_cnt_cap[tn], m_new))) return rc;
+    const GmTable told{km->gt_key[tcur], km->gt_sum[tcur], km->gt_cnt[tcur]}, tnew{km->gt_key[tn], km->gt_sum[tn], km->gt_cnt[tn]};
+    gm_merge_runs_kernel<<<blocks, SM_THREADS, 0, s>>>(km->cat[0], km->vals[cur], km->starts, km->d_m, nb, rkey, lbv, km->gm_ncnt, told, tnew, km->gm_npre);
+    HIPCHK(hipGetLastError());
+    if (m_tab > 0) {
+      gm_move_old_kernel<<<(m_tab + SM_THREADS - 1) / SM_THREADS, SM_THREADS, 0, s>>>(told, m_tab, rkey, km->d_m, km->gm_npre, tnew);
+      HIPCHK(hipGetLastError());
+    }
+    m_tab = (int)m_new; tcur = tn;
+    m_peak = std::max<long long>(m_peak, m_tab);
+  }
+  HIPCHK(hipEventRecord(km->gm_ev[2], s));
+  if ((rc = km->store.grow(km->gmap, km->gmap_cap, (size_t)std::max(m_tab, 1)))) return rc;
+  gm_finish_kernel<<<(m_tab + SM_THREADS - 1) / SM_THREADS, SM_THREADS, 0, s>>>(km->gt_sum[tcur], km->gt_cnt[tcur], m_tab, km->gmap);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(km->gm_ev[3], s));
+  HIPCHK(hipStreamSynchronize(s));
+  km->gm_info[1] = nbatches; km->gm_info[2] = m_tab; km->gm_info[3] = 1; km->gm_info[4] = m_peak;
+  *m_out = m_tab;
   return ROLO_OK;
 }
 
@@ -481,6 +716,8 @@ int rolo_keymap_create(int device, rolo_keymap** out) {
   if (e == hipSuccess) e = hipHostMalloc((void**)&km->h_box, sizeof(float) * 16);
   if (e == hipSuccess) e = hipHostMalloc((void**)&km->h_m, sizeof(int) * 2);
   if (e == hipSuccess) e = hipMalloc((void**)&km->d_m, sizeof(int) * 2);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&km->gm_h, sizeof(int) * 2);
+  if (e == hipSuccess) e = hipMalloc((void**)&km->gm_d, sizeof(int) * 2);
   if (e != hipSuccess) { ctx_set_error((std::string("rolo_keymap_create: ") + hipGetErrorString(e)).c_str()); rolo_keymap_destroy(km); return ROLO_EHIP; }
   km->store.stream = km->stream; km->store.who = "keymap";
   *out = km;
@@ -497,13 +734,16 @@ void rolo_keymap_destroy(rolo_keymap* km) {
   for (auto& c : km->chunks) (void)hipFree(c.p);
   km->store.release();
   for (void* p : {(void*)km->cat[0], (void*)km->cat[1], (void*)km->sub[0], (void*)km->sub[1], (void*)km->ds_out, (void*)km->keys[0], (void*)km->keys[1], (void*)km->vals[0],
-                  (void*)km->vals[1], (void*)km->hist, (void*)km->dtot, (void*)km->bcnt, (void*)km->starts, (void*)km->box_part, (void*)km->segs, (void*)km->d_m, (void*)km->loop[0], (void*)km->loop[1]})
+                  (void*)km->vals[1], (void*)km->hist, (void*)km->dtot, (void*)km->bcnt, (void*)km->starts, (void*)km->box_part, (void*)km->segs, (void*)km->d_m, (void*)km->loop[0], (void*)km->loop[1],
+                  (void*)km->gmap, (void*)km->gt_key[0], (void*)km->gt_key[1], (void*)km->gt_sum[0], (void*)km->gt_sum[1], (void*)km->gt_cnt[0], (void*)km->gt_cnt[1], (void*)km->gm_ncnt,
+                  (void*)km->gm_npre, (void*)km->gm_d})
     if (p) (void)hipFree(p);
-  for (void* p : {(void*)km->h_box, (void*)km->h_m, (void*)km->h_segs}) if (p) (void)hipHostFree(p);
+  for (void* p : {(void*)km->h_box, (void*)km->h_m, (void*)km->h_segs, (void*)km->gm_h}) if (p) (void)hipHostFree(p);
   if (km->ready) (void)hipEventDestroy(km->ready);
   if (km->consumed) (void)hipEventDestroy(km->consumed);
   if (km->loop_t0) (void)hipEventDestroy(km->loop_t0);
   if (km->loop_t1) (void)hipEventDestroy(km->loop_t1);
+  for (hipEvent_t e : km->gm_ev) if (e) (void)hipEventDestroy(e);
   if (km->stream) (void)hipStreamDestroy(km->stream);
   delete km;
 }
@@ -738,6 +978,102 @@ int rolo_keymap_get_loop_cloud(rolo_keymap* km, int slot, float* out, int cap) {
   if (mm) HIPCHK(hipMemcpyAsync(out, km->loop[slot], sizeof(float4) * (size_t)mm, hipMemcpyDeviceToHost, km->stream));
   HIPCHK(hipStreamSynchronize(km->stream));
   return mm;
+}
+
+// publishGlobalMap :1656-1663 — every listed frame's corner, then surface cloud moved by its pose, ONE downSizeFilterGlobalMapKeyFrames over all of them
+int rolo_keymap_global_map(rolo_keymap* km, const int32_t* indices, int n, float leaf, int* m) {
+  if (!km || n < 0 || (n && !indices) || !(leaf > 0.f)) return ROLO_EINVAL;
+  km->have_gmap = false; km->m_gmap = 0;
+  for (long long& v : km->gm_info) v = 0;
+  for (float& v : km->gm_ms) v = 0.f;
+  std::vector<GmPiece> pieces;
+  long long total = 0;
+  int rc;
+  if ((rc = gm_list(km, indices, n, "rolo_keymap_global_map", pieces, &total))) return rc;
+  km->gm_info[0] = total;
+  if (total == 0) { km->have_gmap = true; if (m) *m = 0; return ROLO_OK; }
+  HIPCHK(hipSetDevice(km->device));
+  hipStream_t s = km->stream;
+  for (hipEvent_t& e : km->gm_ev) if (!e) HIPCHK(hipEventCreate(&e));
+  const int batch = gm_batch_of(km);
+  int mm = 0;
+  HIPCHK(hipEventRecord(km->gm_ev[0], s));
+  if (total > batch) {
+    if ((rc = gm_streamed(km, pieces, total, batch, leaf, &mm))) return rc;
+  } else {   // the one-shot form: rolo_keymap_loop_cloud's route, no new arithmetic
+    const int np = (int)total;
+    if ((rc = km_sort_scratch(km, np))) return rc;
+    if ((rc = gm_batch_scratch(km, np, pieces.size()))) return rc;
+    if ((rc = km->store.grow(km->gmap, km->gmap_cap, (size_t)np))) return rc;
+    size_t cursor = 0;
+    if ((rc = gm_enqueue_batch(km, pieces, &cursor, 0, np))) return rc;
+    if ((rc = vg_enqueue_box(km, km->cat[0], np, 0))) return rc;
+    HIPCHK(hipEventRecord(km->gm_ev[1], s));
+    HIPCHK(hipStreamSynchronize(s));
+    bool direct; int m_direct = 0;
+    if ((rc = vg_enqueue_filter(km, km->cat[0], np, leaf, 0, km->gmap, &direct, &m_direct))) return rc;
+    HIPCHK(hipEventRecord(km->gm_ev[2], s));
+    HIPCHK(hipEventRecord(km->gm_ev[3], s));
+    HIPCHK(hipStreamSynchronize(s));
+    mm = direct ? m_direct : km->h_m[0];
+    if (mm < 0 || mm > np) { ctx_set_error("the key map's voxel filter returned an inconsistent cell count"); return ROLO_ESTATE; }
+    km->gm_info[1] = 1; km->gm_info[2] = mm; km->gm_info[3] = 0; km->gm_info[4] = 0;
+  }
+  for (int k = 0; k < 3; k++) (void)hipEventElapsedTime(&km->gm_ms[k], km->gm_ev[k], km->gm_ev[k + 1]);
+  km->m_gmap = mm; km->have_gmap = true;
+  if (m) *m = mm;
+  return ROLO_OK;
+}
+
+int rolo_keymap_get_global_map(rolo_keymap* km, float* out, int cap) {
+  if (!km || cap < 0) return ROLO_EINVAL;
+  if (!km->have_gmap) { ctx_set_error("the key map holds no global map: call rolo_keymap_global_map first"); return ROLO_ESTATE; }
+  const int mm = km->m_gmap;
+  if (mm > cap || (mm && !out)) return ROLO_EINVAL;
+  HIPCHK(hipSetDevice(km->device));
+  if (mm) HIPCHK(hipMemcpyAsync(out, km->gmap, sizeof(float4) * (size_t)mm, hipMemcpyDeviceToHost, km->stream));
+  HIPCHK(hipStreamSynchronize(km->stream));
+  return mm;
+}
+
+int rolo_keymap_global_set_batch(rolo_keymap* km, int points) {
+  if (!km || points < 0 || points > KM_MAX_POINTS) return ROLO_EINVAL;
+  km->gm_batch = points;
+  return ROLO_OK;
+}
+
+int rolo_keymap_global_info(rolo_keymap* km, long long* out, int n) {
+  if (!km || n < 0 || (n && !out)) return ROLO_EINVAL;
+  for (int k = 0; k < std::min(n, 5); k++) out[k] = km->gm_info[k];
+  return ROLO_OK;
+}
+
+int rolo_keymap_global_last_ms(rolo_keymap* km, float* ms3) {
+  if (!km || !ms3) return ROLO_EINVAL;
+  for (int k = 0; k < 3; k++) ms3[k] = km->gm_ms[k];
+  return ROLO_OK;
+}
+
+// saveGlobalPCDs :1546-1557 — cloudGlobal.pcd's cloud: a batch at a time through the scratch into the caller's array
+long long rolo_keymap_global_cloud(rolo_keymap* km, const int32_t* indices, int n, float* out, long long cap) {
+  if (!km || n < 0 || (n && !indices) || cap < 0) return ROLO_EINVAL;
+  std::vector<GmPiece> pieces;
+  long long total = 0;
+  int rc;
+  if ((rc = gm_list(km, indices, n, "rolo_keymap_global_cloud", pieces, &total))) return rc;
+  if (total > cap || (total && !out)) { ctx_set_error("rolo_keymap_global_cloud: the output array is smaller than the listed clouds"); return ROLO_EINVAL; }
+  if (total == 0) return 0;
+  HIPCHK(hipSetDevice(km->device));
+  const int batch = (int)std::min<long long>(gm_batch_of(km), total);
+  if ((rc = gm_batch_scratch(km, batch, pieces.size()))) return rc;
+  size_t cursor = 0;
+  for (long long b0 = 0; b0 < total; b0 += batch) {
+    const int nb = (int)std::min<long long>(batch, total - b0);
+    if ((rc = gm_enqueue_batch(km, pieces, &cursor, b0, nb))) return rc;
+    HIPCHK(hipMemcpyAsync(out + 4 * b0, km->cat[0], sizeof(float4) * (size_t)nb, hipMemcpyDeviceToHost, km->stream));
+    HIPCHK(hipStreamSynchronize(km->stream));
+  }
+  return total;
 }
 
 }  // extern "C"
