@@ -330,7 +330,11 @@ void rolo_front_default_params(rolo_front_params* p); /* config/params.yaml valu
 /* ImageProjection::projectPointCloud + cloudExtraction (src/imageProjection.cpp:399-505), deskew off.
  * in: n_raw points (x,y,z at float offsets 0..2 of `stride`-float records) + ring[n_raw].
  * out (host, sized n_scan*horizon_scan): extracted[N*4] (x,y,z,intensity), point_col_ind[N], point_range[N],
- * start_ring[n_scan], end_ring[n_scan]; range_mat (optional) n_scan*horizon_scan. *n_valid = N. */
+ * start_ring[n_scan], end_ring[n_scan]; range_mat (optional) n_scan*horizon_scan. *n_valid = N.
+ * The column of a point is the reference's expression (:437-444) on the CORRECTLY ROUNDED float atan2(x, y), i.e. the column a CPU run with a correctly
+ * rounded libm gives: like the POLAR voxel key (rolo_num_edge_points above), a point within a guard of a column edge — where one ulp of the device's atan2f
+ * is the neighbouring pixel — has its angle taken again in fp64. glibc 2.35's atan2f is itself not correctly rounded on about a quarter (27-28 %) of
+ * the points planted one ulp from a column edge in tests/projection_cases.py; only on such points can the column differ by one from that CPU's. */
 int rolo_project_frame(rolo_ctx* ctx, const rolo_front_params* P, const float* pts, int stride, const uint16_t* ring,
                        int n_raw, float* extracted, int32_t* point_col_ind, float* point_range, int32_t* start_ring,
                        int32_t* end_ring, float* range_mat, int* n_valid);

@@ -106,6 +106,23 @@ __global__ __launch_bounds__(256) void azimuth_time_kernel(const float* __restri
 }
 
 // ---- K1 ------------------------------------------------------------------------------------------------
+// The column of a point is the reference's expression on the CORRECTLY ROUNDED float atan2(x, y) — what a correctly rounded libm's atan2f returns by definition,
+// and the only value two machines can agree on. The device's atan2f is not that: on adjacent floats planted on either side of a column edge it is one ulp away on
+// nearly half of them, and there one ulp is the neighbouring pixel (tests/test_gpu_projection_cases.py). As voxel_dev.hpp does for the POLAR key, the fast function
+// decides except where the quotient q whose rounding gives the column lies within a guard of a half-integer; there the angle is taken again as
+// (float)atan2((double)x, (double)y): the fp64 function is good to a few fp64 ulps, so its rounding to float is the correctly rounded float unless the true value lies
+// within ~2^-50 of the midpoint of two floats.
+// The guard. Let the fast angle be E float ulps from the correctly rounded one: |da| <= E 2^-22 rad (|a| <= pi < 4). t = fl(a * 180) < 1024 moves by at most
+// 180 |da| + 2^-14 (one ulp of t for the two roundings), horizonAngle = fl(t / pi) by at most 180 / pi |da| + 2^-14 / pi + 2^-16 (one ulp of an angle < 256 deg)
+// = (0.895 E + 2.27) ulp(180 deg) with ulp(180 deg) = 2^-16 deg, and q by that over ang_res_x. HIP's math API reference lists atan2f at 1 ulp — a largest OBSERVED
+// error, so E = 2 here — and the guard is (E + 3) ulp(180 deg) / ang_res_x >= the bound: 9e-4 of a column at H = 4096, so one point in 600 takes the fp64 function.
+constexpr double COLUMN_GUARD_DEG = (2 + 3) * 0x1p-16;
+ROLO_DEV int column_of_angle(float angle, float ang_res_x, int H, double& q) {
+  const float horizonAngle = angle * 180 / M_PI;                  // imageProjection.cpp:437
+  q = (horizonAngle - 90.0) / ang_res_x;
+  return -round(q) + H / 2;                                       // :440
+}
+
 __global__ __launch_bounds__(256) void project_kernel(const float* __restrict__ pts, int stride, const unsigned short* __restrict__ ring,
                                                      int n_raw, rolo_front_params P, int* __restrict__ owner) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -120,9 +137,10 @@ __global__ __launch_bounds__(256) void project_kernel(const float* __restrict__ 
   if (rowIdn < 0 || rowIdn >= P.n_scan) return;
   if (rowIdn % P.downsample_rate != 0) return;
   const int H = P.horizon_scan;
-  const float horizonAngle = atan2f(x, y) * 180 / M_PI;           // imageProjection.cpp:437
   const float ang_res_x = 360.0 / float(H);                       // :438
-  int columnIdn = -round((horizonAngle - 90.0) / ang_res_x) + H / 2;  // :440
+  double q;
+  int columnIdn = column_of_angle(atan2f(x, y), ang_res_x, H, q);
+  if (fabs(q - floor(q) - 0.5) < COLUMN_GUARD_DEG / ang_res_x) columnIdn = column_of_angle((float)atan2((double)x, (double)y), ang_res_x, H, q);
   if (columnIdn >= H) columnIdn -= H;
   if (columnIdn < 0 || columnIdn >= H) return;
   atomicMin(&owner[rowIdn * H + columnIdn], i);  // first point wins (:451)
