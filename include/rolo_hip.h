@@ -283,7 +283,11 @@ int rolo_peer_info(rolo_ctx* ctx, int* rank, int* world, char* mem_kind16);
  * process on the GPU): 0 = its frames last what they last alone (idle-device kernels), 1 = trying the busy-device kernels, 2 = keeping them (rolo_set_load_hint -1 only),
  * [14] "kept_trials": rotation-stage trials, summed over the frames, that cost no pass — with fixed_iterations > 0 a converged-but-rejected trial repeats unchanged until the
  * iterations are used up, and the step answers the repeats from the cost it holds (ROLO_LM_KEEP_COST=0: every repeat is a pass again). rolo_stats::n_passes / n_cost_only and
- * the LM trace keep counting the solve's trials, these included. */
+ * the LM trace keep counting the solve's trials, these included,
+ * [15] "model_trials": translation-stage trials, summed over the frames and the rolo_compute_translation calls, that cost no pass — within that stage a trial's cost is a
+ * quadratic in the translation whose coefficients are in the sums of the stage's own linearisation, and the step answers the trials from it, asking for a pass only to
+ * linearise again after an accepted trial (ROLO_LM_TRANS_MODEL=0: every trial is a pass again; the costs then differ in their last bits, the decisions do not). Counted
+ * in n_passes / n_cost_only and traced like [14]. */
 int rolo_ctx_counters(rolo_ctx* ctx, long long* out, int n);
 /* the form of the context's last resident LM launch (fused_lm = 2, one launch per frame): out[0] workgroups, [1] threads per workgroup, [2] points per thread,
  * [3] points per thread of the interleaved body (1, 2, 4; 0: the generic body, one point after the other), [4] points of a thread that go through a body together,

@@ -152,6 +152,7 @@ struct rolo_ctx {
   bool async_pending = false;
   long long n_frames = 0, n_replays = 0, n_captures = 0, n_eager = 0, n_topup_frames = 0, n_topup_chunks = 0;   // rolo_ctx_counters
   long long n_kept_trials = 0;   // rotation trials answered from the kept cost (LmState::rot_kept), summed over the frames
+  long long n_model_trials = 0;  // translation trials answered from the linearisation's sums (LmState::trans_modelled), summed over the frames and rolo_compute_translation calls (rolo_ctx_counters [15])
   long long n_persist_bails = 0;   // frames whose resident LM kernel gave the stage back to the host (rolo_ctx_counters [12])
   long long ns_enqueue = 0, ns_wait_blocked = 0, ns_wait_other = 0;   // host time inside rolo_register_async / the event wait / the rest of rolo_register_wait (steady_clock)
   hipGraphExec_t dbg_chain_exec = nullptr; int dbg_chain_key[3] = {-1, -1, -1};   // rolo_debug_chain: the captured chain and its (kind, n_pairs, grid)
@@ -168,8 +169,9 @@ struct rolo_ctx {
   // passes the last frames needed per stage (update_hint): the next frame enqueues that many predicated pass/controller pairs up
   // front instead of a fixed worst-case chunk; rolo_register_wait tops up if a frame needs more
   int hint_rot = 0, hint_trans = 0;
+  int hint_ct = 0;      // the same for rolo_compute_translation's own chain
   int walk_lanes = 1;   // lanes per query of the last K5 walk enqueued (rolo_ctx_counters [8])
-  struct NeedWindow { int need[64] = {0}; int n = 0, pos = 0; } win_rot, win_trans;   // passes the last 64 frames needed per stage
+  struct NeedWindow { int need[64] = {0}; int n = 0, pos = 0; } win_rot, win_trans, win_ct;   // passes the last 64 frames needed per stage
   bool graph_nrm_written = false;   // the captured build_clouds left the PLANE covariances as I - m m^T too (CloudDev::have_nrm after a replay)
   int graph_vox_build[4] = {-1, 0, 0, 0};   // vox_build of the captured frame: what a replay builds the map with
   // the captured frame of the OTHER load regime (GraphKey::busy): a context whose load estimate flips — the learner's periodic second look, a second context that comes and

@@ -55,6 +55,7 @@ extern "C" int rolo_debug_lm_script_translation(rolo_ctx* c, const rolo_lm_scrip
   TransBegin tb{};
   for (int i = 0; i < 3; i++) { tb.t0[i] = trans[i]; tb.g[i] = g3[i]; tb.l[i] = l3[i]; }
   tb.dtn = dtn; tb.dtn1 = dtn1; tb.ct_lambda = lam; tb.direct = 1; fill_trans_knobs(c, tb);
+  tb.trans_model = 0;   // a script names a cost per (outer, trial): every trial is asked for, none answered from the linearisation's sums
   HIPCHK(launch_trans_begin(c->state, tb, c->stream));
   if ((rc = script_stage(c, S, 2, 6, generic_ctrl))) return rc;
   const LmState* s = c->h_state;
@@ -123,9 +124,9 @@ int rolo_get_trace(rolo_ctx* c, rolo_trace_rec* out, int cap) {
 
 int rolo_ctx_counters(rolo_ctx* c, long long* out, int n) {
   if (!c || !out || n < 0) return ROLO_EINVAL;
-  const long long v[15] = {c->n_frames, c->n_replays, c->n_captures, c->n_eager, c->n_topup_frames, c->n_topup_chunks, c->hint_rot, c->hint_trans, c->walk_lanes,
-                           c->ns_enqueue, c->ns_wait_blocked, c->ns_wait_other, c->n_persist_bails, c->learn.mode, c->n_kept_trials};
-  for (int i = 0; i < n && i < 15; i++) out[i] = v[i];
+  const long long v[16] = {c->n_frames, c->n_replays, c->n_captures, c->n_eager, c->n_topup_frames, c->n_topup_chunks, c->hint_rot, c->hint_trans, c->walk_lanes,
+                           c->ns_enqueue, c->ns_wait_blocked, c->ns_wait_other, c->n_persist_bails, c->learn.mode, c->n_kept_trials, c->n_model_trials};
+  for (int i = 0; i < n && i < 16; i++) out[i] = v[i];
   return ROLO_OK;
 }
 

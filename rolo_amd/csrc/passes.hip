@@ -21,6 +21,7 @@
 #include "switches.hpp"
 #include <atomic>
 #include "lm_begin.hpp"
+#include "trans_model.hpp"
 #include "dev_math.hpp"
 #include "voxel_dev.hpp"
 #include "peer_dev.hpp"
@@ -736,7 +737,7 @@ ROLO_DEV void trans_consts(LmState* st) {
 ROLO_DEV void trans_start(LmState* st) {  // lsq_registration_impl.hpp:55-61
   trans_consts(st);
   st->stage = 2; st->phase = 0; st->lin_skip = 0; st->outer = 0; st->trial = 0; st->lambda = -1.0;
-  st->trans_done = 0; st->trans_failed = 0; st->trans_outer = 0; st->trans_passes = 0; st->trans_cost_only = 0;
+  st->trans_done = 0; st->trans_failed = 0; st->trans_outer = 0; st->trans_passes = 0; st->trans_cost_only = 0; st->trans_modelled = 0; st->trans_lin_extra = 0; st->tm_free_lin = 0;
   for (int i = 0; i < 3; i++) st->tt[i] = st->t0[i];
   // lambda_/pt_size: float / size_t -> float (rot_vgicp.hpp:124, rot_vgicp_impl.hpp:557)
   st->lam_over_n = (double)(st->ct_lambda / (float)st->tr_n_corr);
@@ -857,46 +858,95 @@ ROLO_DEV void trans_finish(LmState* st, bool failed) {
   st->trans_done = 1; st->trans_failed = failed ? 1 : 0; st->trans_outer = st->outer + (failed ? 1 : 0) /* iterations started: rot_finish */; st->stage = 0;
 }
 
+// One call of the translation stage's scalar step: the sums of the pass that just ran, then — LmState::trans_model — every trial the step can answer itself.
+// Within the stage a trial's cost is a quadratic in the translation whose coefficients are in the sums of the stage's linearisation (trans_model.hpp). So once a
+// linearisation has been unpacked here (a linearise-only pass, or the (B) half of an accepted trial's full pass), the trials that follow need no pass: each turn of the
+// loop below is one trial of lsq_registration_impl.hpp:98-141 — the same rho, the same accept / reject / converged / lm_max / max_iterations exits, the same damping —
+// whose yi is the pass's (`real`: the first turn of a call that found a trial pending) or the model's. A modelled trial leaves its trace record and is counted in
+// trans_passes / trans_cost_only as if its pass had run (lin_skip says, as for a real one, whether that pass would have been a cost-only one) and in trans_modelled.
+// The call ends when the stage ends, when a trial needs a pass (no valid model: the switch is off, the scripted hook, sums that are not finite, a cost that is not), or
+// when an accepted trial needs the linearisation at the new t0: a linearise-only pass (phase = 0) — the exit for a trial accepted on a cost-only pass. Where a modelled
+// trial's pass would have been a full one, its (B) half WAS that linearisation (the same sums, bit for bit: nothing of (B) depends on the phase) and the solve counts no
+// further pass: tm_free_lin, and the step that consumes the pass counts it in trans_lin_extra.
+// ONE (the resident kernel): `trace` is the LDS slot, which takes the first record of a call (another wavefront copies it to the buffer: lmp_trace_flush); every further
+// record goes straight to the buffer `trace_g`, written by the stepping lane. Beyond TRACE_CAP only the count advances, as everywhere.
+// (One loop with the step computed in two places — opening an outer iteration, after a rejection: as a function of its own behind the parent's step, with four inlined
+// copies of the LDLT and the exponential, the resident kernel's step call needed 256 registers and 524 bytes of stack, and the kernel's scratch went from 272 to 924 bytes
+// per lane, and the headline fell although the kernel alone was shorter: profiles/DEAD_ENDS.md round 18.)
 template <bool ONE = false>
-ROLO_DEV void trans_step(LmState* __restrict__ st, const double* __restrict__ S, rolo_trace_rec* __restrict__ trace) {
-  st->trans_passes++;
+ROLO_DEV void trans_step(LmState* __restrict__ st, const double* __restrict__ S, rolo_trace_rec* __restrict__ trace, rolo_trace_rec* __restrict__ trace_g = nullptr) {
+  const int tc_in = st->trace_count;
+  if (st->phase == 0 && st->tm_free_lin) { st->tm_free_lin = 0; st->trans_lin_extra++; }
+  else st->trans_passes++;
   if (st->phase == 1 && st->lin_skip) st->trans_cost_only++;
-  if (st->phase == 0) {
-    if (st->outer == 0 && st->max_iterations <= 0) { trans_finish(st, false); return; }   // the loop of computeTranslation (:63) never runs: the start value comes back
-    const int keep = st->n_corr;
-    unpack_hb<6>(st, S);
-    st->n_corr = keep;
-    st->phase = 1; st->lin_skip = 0;
-    trans_begin_outer(st);
-    if (st->lm_max <= 0) trans_finish(st, true);   // no trial at all (:98): "lm not converged!!" right after the linearisation
-    return;
-  }
-  const double yi = S[V_YI];
-  double den = 0;
+  if (st->phase == 0 && st->outer == 0 && st->max_iterations <= 0) { trans_finish(st, false); return; }   // the loop of computeTranslation (:63) never runs: the start value comes back
+  // (the constants are read from the state where they are used, and the model lives there: nothing of it is held in registers across the next step's LDLT)
+  auto consts = [&]() {
+    TransModelConsts K;
+    K.lam_over_n = st->lam_over_n; K.inv_dtn = st->inv_dtn;
 #pragma unroll
-  for (int i = 0; i < 6; i++) den += st->d[i] * (st->lambda * st->d[i] - st->b[i]);
-  const double rho = (st->y0 - yi) / den;
-  if (rho < 0) {
-    if (t_converged(st)) { trace_push<6, ONE>(st, trace, 1, 2, yi, rho); st->outer++; trans_finish(st, false); return; }
-    trace_push<6, ONE>(st, trace, 1, 0, yi, rho);
-    st->lambda = st->nu * st->lambda; st->nu = 2 * st->nu;
-    st->trial++;
-    if (st->trial >= st->lm_max) { trans_finish(st, true); return; }
-    trans_compute_step(st);
-    st->lin_skip = st->spec_lin;   // a rejected trial: the next pass evaluates its trial's cost alone
-    return;
+    for (int i = 0; i < 3; i++) { K.g[i] = st->g[i]; K.lastA_q[i] = st->lastA_q[i]; K.lastB_q[i] = st->lastB_q[i]; }
+    return K;
+  };
+  auto push = [&](int accepted, double yi, double rho) {
+    if (ONE && st->trace_count != tc_in) trace_push<6, false>(st, trace ? trace_g : nullptr, 1, accepted, yi, rho);
+    else trace_push<6, ONE>(st, trace, 1, accepted, yi, rho);
+  };
+  bool unpack = st->phase == 0;   // the sums hold a linearisation to open an outer iteration with
+  bool real = !unpack;            // the sums hold the cost of the trial that is pending
+  bool model = false;             // st->tm is the model of the linearisation in H, b, y0
+  while (true) {
+    // (a turn of the loop starts from the state in memory: nothing that stays the same from trial to trial — H, b, the model, the stage's constants — is to be carried
+    // in registers across the turns; the resident kernel pays for every register this call clobbers with spills around it)
+    asm volatile("" ::: "memory");
+    if (unpack) {
+      const bool first = st->phase == 0;
+      const int keep = st->n_corr;
+      unpack_hb<6>(st, S);
+      st->n_corr = keep;
+      st->phase = 1; st->lin_skip = 0;
+      trans_begin_outer(st);
+      if (first && st->lm_max <= 0) { trans_finish(st, true); return; }   // no trial at all (:98): "lm not converged!!" right after the linearisation
+      unpack = false; real = false;
+      if (st->trans_model && st->tr_n_corr > 0) { trans_model_build(st->tm, st->H, st->b, st->y0, consts(), st->t0); model = st->tm.valid != 0; }
+    }
+    double yi;
+    if (real) yi = S[V_YI];
+    else {
+      if (!model) return;            // the pass the state asks for runs
+      yi = trans_model_cost(st->tm, consts(), st->tt);
+      if (!(yi == yi)) return;       // not a cost: likewise
+      st->trans_passes++; st->trans_modelled++;
+      if (st->lin_skip) st->trans_cost_only++;
+    }
+    double den = 0;
+#pragma unroll
+    for (int i = 0; i < 6; i++) den += st->d[i] * (st->lambda * st->d[i] - st->b[i]);
+    const double rho = (st->y0 - yi) / den;
+    if (rho < 0) {
+      if (t_converged(st)) { push(2, yi, rho); st->outer++; trans_finish(st, false); return; }
+      push(0, yi, rho);
+      st->lambda = st->nu * st->lambda; st->nu = 2 * st->nu;
+      st->trial++;
+      if (st->trial >= st->lm_max) { trans_finish(st, true); return; }
+      trans_compute_step(st);
+      st->lin_skip = st->spec_lin;   // a rejected trial: the next pass evaluates its trial's cost alone
+      real = false;
+      continue;
+    }
+    push(1, yi, rho);
+    for (int i = 0; i < 3; i++) st->t0[i] = st->tt[i];
+    st->lambda = lm_lambda_after_accept(st->lambda, rho);
+    st->outer++;
+    const bool conv = t_converged(st);
+    if (conv || st->outer >= st->max_iterations) { trans_finish(st, false); return; }
+    if (st->lin_skip || !real) {   // accepted on a cost-only pass, or from the model: the next pass is t3_linearize at tt (= t0 now) alone
+      if (!st->lin_skip) st->tm_free_lin = 1;
+      st->phase = 0; st->lin_skip = 0;
+      return;
+    }
+    unpack = true;   // the (B) half of this pass is that linearisation
   }
-  trace_push<6, ONE>(st, trace, 1, 1, yi, rho);
-  for (int i = 0; i < 3; i++) st->t0[i] = st->tt[i];
-  st->lambda = lm_lambda_after_accept(st->lambda, rho);
-  st->outer++;
-  const bool conv = t_converged(st);
-  if (conv || st->outer >= st->max_iterations) { trans_finish(st, false); return; }
-  if (st->lin_skip) { st->phase = 0; st->lin_skip = 0; return; }   // accepted after a cost-only pass: the next pass is t3_linearize at tt (= t0 now) alone
-  const int keep = st->n_corr;
-  unpack_hb<6>(st, S);
-  st->n_corr = keep;
-  trans_begin_outer(st);
 }
 
 // One workgroup: sums the partial rows in a fixed order (or takes the all-reduced sums on the multi-GPU path) and
@@ -1215,9 +1265,10 @@ __shared__ double lmp_sums[NV_MAX];
 // ~0.4 us of workgroup 0's step, for which all the others then wait in the next exchange)
 __shared__ rolo_trace_rec lmp_trace_slot;
 template <int DOF> __device__ __noinline__ void lmp_rot_step(bool want_trace) { rot_step_t<DOF, true>(&lmp_sst, lmp_sums, want_trace ? &lmp_trace_slot : nullptr); }
-__device__ __noinline__ void lmp_trans_step(bool want_trace) { trans_step<true>(&lmp_sst, lmp_sums, want_trace ? &lmp_trace_slot : nullptr); }
+__device__ __noinline__ void lmp_trans_step(rolo_trace_rec* trace_g) { trans_step<true>(&lmp_sst, lmp_sums, trace_g ? &lmp_trace_slot : nullptr, trace_g); }
 // after the barrier behind a step: the last wavefront of workgroup 0 copies the record the step left (if it left one) — plain stores nobody waits for before the kernel ends
-template <int THREADS>
+// RUN = false (the translation stage): the slot's record alone — a step that answered further trials from the model wrote their records itself (trans_step)
+template <int THREADS, bool RUN = true>
 ROLO_DEV void lmp_trace_flush(rolo_trace_rec* __restrict__ trace, int count_before) {
   static_assert(sizeof(rolo_trace_rec) % sizeof(int) == 0, "record copied in dwords");
   constexpr int NWORD = sizeof(rolo_trace_rec) / sizeof(int);
@@ -1226,7 +1277,7 @@ ROLO_DEV void lmp_trace_flush(rolo_trace_rec* __restrict__ trace, int count_befo
   // a step leaves one record, or none — or, where it answered the repeats of a converged-but-rejected trial from the kept cost (rot_step_t), that trial's record and a
   // count that advanced once per repeat: repeat j is the slot's record with outer + j and trial = 0 (trace_push_repeat). Beyond TRACE_CAP only the count advances.
   static_assert(offsetof(rolo_trace_rec, outer) == 4 && offsetof(rolo_trace_rec, trial) == 8, "the counter fields of a repeated record");
-  const int n = min(lmp_sst.trace_count, TRACE_CAP) - count_before;
+  const int n = RUN ? min(lmp_sst.trace_count, TRACE_CAP) - count_before : min(min(lmp_sst.trace_count, TRACE_CAP) - count_before, 1);
   const int w = reinterpret_cast<const int*>(&lmp_trace_slot)[t];
   for (int j = 0; j < n; j++) reinterpret_cast<int*>(trace + count_before + j)[t] = (j == 0 || t > 2 || t == 0) ? w : (t == 1 ? w + j : 0);
 }
@@ -1651,9 +1702,9 @@ __global__ __launch_bounds__(THREADS, OCC) void lm_persist_kernel(PassArgs a, Lm
     LMP_STAMP(1);
     ok = lmp_exchange<THREADS>(row, only_first ? 1 : 30, 21, ++e, xbuf, G, wg, xw, part, sums, &bad, timeout_ticks) && ++trial <= max_trials;
     LMP_STAMP(2);
-    if (ok && t == 0) lmp_trans_step(tr != nullptr);
+    if (ok && t == 0) lmp_trans_step(tr);
     __syncthreads();
-    if (ok && tr) lmp_trace_flush<THREADS>(tr, tc_in);
+    if (ok && tr) lmp_trace_flush<THREADS, false>(tr, tc_in);
     m_valid = true;
     LMP_ACC();
   }
@@ -1680,7 +1731,7 @@ __global__ void rot_begin_kernel(LmState* st, RotBegin a) {
 
 ROLO_DEV void trans_knobs(LmState* st, const TransBegin& a) {   // TransBegin: the stage's knobs as they are when computeTranslation is called
   st->max_iterations = a.max_iterations; st->lm_max = a.lm_max; st->q2_intended = a.q2_intended;
-  st->trans_eps = a.trans_eps; st->inv_trans_eps = 1.0 / a.trans_eps; st->lm_init = a.lm_init;
+  st->trans_eps = a.trans_eps; st->inv_trans_eps = 1.0 / a.trans_eps; st->lm_init = a.lm_init; st->trans_model = a.trans_model;
 }
 __global__ void trans_begin_kernel(LmState* st, TransBegin a) {
   if (threadIdx.x != 0) return;

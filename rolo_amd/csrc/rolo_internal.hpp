@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/rolo_hip.h"
+#include "trans_model.hpp"
 
 // Issue priority of the SHORT kernels of a frame (LM passes, controller, the search's build chain): with several contexts in flight their wavefronts share SIMDs with
 // another frame's neighbour search, whose eight older wavefronts per SIMD win the age-ordered issue arbitration; s_setprio lets the latency-bound chain go first
@@ -124,6 +125,13 @@ struct LmState {
   // keep_cost (ROLO_LM_KEEP_COST, default 1): with forced iterations a converged-but-rejected trial is followed by the SAME trial until the iterations are used up; the step
   // answers those repeats from the cost it holds instead of asking for another pass (passes.hip rot_step_t). rot_kept counts the trials of rot_passes answered that way.
   int keep_cost, rot_kept;
+  // trans_model (ROLO_LM_TRANS_MODEL, default 1): within the translation stage a trial's cost is a quadratic in the translation whose coefficients are in the sums of the
+  // stage's linearisation (trans_model.hpp); the step answers the trials that follow a linearisation itself — trace record, counts and damping of each as if its pass had
+  // run — and asks for a pass only to linearise again after an accepted trial (passes.hip trans_step). trans_modelled counts the trials of trans_passes answered
+  // that way. tm_free_lin: the linearise-only pass now pending stands in for the (B) half of an accepted trial's full pass, which the solve's count already holds — the
+  // step that consumes it counts it in trans_lin_extra instead of trans_passes. Launches of the stage that ran = trans_passes - trans_modelled + trans_lin_extra.
+  int trans_model, trans_modelled, trans_lin_extra, tm_free_lin;
+  TransModel tm;   // the model of the stage's last linearisation: written and read within one call of the step (it never crosses a launch), kept here because the state is in LDS
   int rot_cost_only, trans_cost_only;   // passes of rot_passes / trans_passes that ran with lin_skip set (counted by the step that consumes them): rolo_stats::n_cost_only
   int lmp_bailed;   // the resident LM kernel (fused_lm = 2) did not get all its workgroups resident within the admission time and left WITHOUT touching the stage: the host
                     // finishes the frame with pass + controller launches (passes.hip lm_persist_kernel, schedule.hip run_stage)
@@ -263,11 +271,12 @@ hipError_t launch_peer_cov_exchange(const PeerArgs& peer, size_t area_bytes, siz
 hipError_t launch_peer_selftest_fill(const PeerArgs& peer, size_t area_bytes, size_t seg_doubles, hipStream_t s);
 hipError_t launch_peer_selftest_check(const PeerArgs& peer, size_t area_bytes, size_t seg_doubles, unsigned* bad, hipStream_t s);
 
-struct RotBegin { double R[9], t[3]; int optimizer, max_iterations, fixed_iterations, lm_max, q2_intended; double rot_eps, trans_eps, lm_init; int run_trans; int spec_lin; int keep_cost; };
+struct RotBegin { double R[9], t[3]; int optimizer, max_iterations, fixed_iterations, lm_max, q2_intended; double rot_eps, trans_eps, lm_init; int run_trans; int spec_lin; int keep_cost; int trans_model; };
 struct TransBegin { double t0[3], g[3], l[3], dtn, dtn1; float ct_lambda; int direct; /* 1: start now (rotation already done) */
                     // the knobs computeTranslation reads when IT runs (lsq_registration_impl.hpp:63, :98, :142-148 read the members live): a setter called between align and
                     // computeTranslation counts — until round 6 the stage ran on what the last align had copied into the state
-                    int max_iterations, lm_max, q2_intended; double trans_eps, lm_init; };
+                    int max_iterations, lm_max, q2_intended; double trans_eps, lm_init;
+                    int trans_model; /* LmState::trans_model for a stage started on its own (rolo_compute_translation; the scripted hook passes 0) */ };
 struct FrameArgs { RotBegin rot; TransBegin trans; };
 hipError_t launch_rot_begin(LmState* st, const RotBegin& a, hipStream_t s);
 hipError_t launch_frame_begin(LmState* st, const FrameArgs* a, hipStream_t s);

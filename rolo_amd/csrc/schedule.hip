@@ -126,12 +126,14 @@ RotBegin make_rot_begin(const rolo_ctx* c, const double* R9, const double* t3, i
   b.trans_eps = c->P.transformation_epsilon; b.lm_init = c->P.lm_init_lambda_factor; b.run_trans = run_trans;
   b.spec_lin = switches().lm_spec_lin;   // 0: every pass carries both halves (the A/B, rounds 1-4)
   b.keep_cost = switches().lm_keep_cost; // 0: the repeats of a converged-but-rejected trial under forced iterations are passes of their own (the A/B)
+  b.trans_model = switches().lm_trans_model;   // 0: every trial of the translation stage is a pass of its own (the A/B)
   return b;
 }
 
 void fill_trans_knobs(const rolo_ctx* c, TransBegin& tb) {
   tb.max_iterations = c->P.max_iterations; tb.lm_max = c->P.lm_max_iterations; tb.q2_intended = c->P.q2_intended;
   tb.trans_eps = c->P.transformation_epsilon; tb.lm_init = c->P.lm_init_lambda_factor;
+  tb.trans_model = switches().lm_trans_model;
 }
 
 void guess_to_Rt(const float* g16, double* R, double* t) {
@@ -172,6 +174,9 @@ static void frame_chunks(const rolo_ctx* c, int& nrot, int& ntrans) {
 // forced-iteration frame would carry a dozen predicated no-op pairs. (The resident kernel has no schedule: its hint only keys the frame's hipGraph, and keeps following the
 // solve's trials, which differ less from pair to pair than the launches do — a hint that moves means an eager frame and a new capture.)
 static int rot_launches(const rolo_ctx* c, const LmState* s) { return lm_persist(c) ? s->rot_passes : s->rot_passes - s->rot_kept; }
+// ... and the same for the translation stage's trials answered from the linearisation's sums (LmState::trans_modelled; trans_lin_extra: the linearise-only launches that
+// stand in for the (B) half of a modelled trial's pass, which trans_passes does not count)
+static int trans_launches(const rolo_ctx* c, const LmState* s) { return lm_persist(c) ? s->trans_passes : s->trans_passes - s->trans_modelled + s->trans_lin_extra; }
 static void update_hint(int& hint, rolo_ctx::NeedWindow& w, int used, bool fused) {
   constexpr int WN = 64;
   w.need[w.pos] = used; w.pos = (w.pos + 1) % WN; if (w.n < WN) w.n++;
@@ -327,8 +332,11 @@ int rolo_compute_translation(rolo_ctx* c, double* trans, const double* g3, const
   for (int i = 0; i < 3; i++) { tb.t0[i] = trans[i]; tb.g[i] = g3[i]; tb.l[i] = l3[i]; }
   tb.dtn = dtn; tb.dtn1 = dtn1; tb.ct_lambda = lam; tb.direct = 1; fill_trans_knobs(c, tb);
   HIPCHK(launch_trans_begin(c->state, tb, c->stream));
-  if ((rc = run_stage(c, a, grid, 2, 12))) return rc;
+  // the first chunk: what the last 64 calls' launches were (12 before the first) — with the trials answered from the model a stage is two or three launches
+  if ((rc = run_stage(c, a, grid, 2, c->hint_ct > 0 ? c->hint_ct : 12))) return rc;
   const LmState* s = c->h_state;
+  if (!s->error) update_hint(c->hint_ct, c->win_ct, trans_launches(c, s), lm_fused(c));
+  c->n_model_trials += s->trans_modelled;
   fill_trans_outputs(s, trans, stats);
   if (s->error) { g_err = "device-side error during computeTranslation"; return s->error; }
   return ROLO_OK;
@@ -486,8 +494,8 @@ int rolo_register_wait(rolo_ctx* c, float* Tf, double* Td, double* trans_out, ro
   if (!c->h_state->trans_done && !c->h_state->error) { if ((rc = run_stage(c, a, grid, 2, 8, bailed))) return rc; }
   c->have_corr = true;
   const LmState* s = c->h_state;
-  if (!s->error) { update_hint(c->hint_rot, c->win_rot, rot_launches(c, s), lm_fused(c)); update_hint(c->hint_trans, c->win_trans, s->trans_passes, lm_fused(c)); }
-  c->n_kept_trials += s->rot_kept;
+  if (!s->error) { update_hint(c->hint_rot, c->win_rot, rot_launches(c, s), lm_fused(c)); update_hint(c->hint_trans, c->win_trans, trans_launches(c, s), lm_fused(c)); }
+  c->n_kept_trials += s->rot_kept; c->n_model_trials += s->trans_modelled;
   fill_rot_outputs(s, Tf, Td, rs);
   fill_trans_outputs(s, trans_out, ts);
   if (s->error) { g_err = "device-side error during registration"; return s->error; }
@@ -640,7 +648,7 @@ int rolo_batch_register_wait(rolo_batch* b, float* Tf, double* Td, double* trans
     }
     c->have_corr = true;
     const LmState* s = c->h_state;
-    c->n_kept_trials += s->rot_kept;
+    c->n_kept_trials += s->rot_kept; c->n_model_trials += s->trans_modelled;
     fill_rot_outputs(s, Tf ? Tf + 16 * (size_t)i : nullptr, Td ? Td + 16 * (size_t)i : nullptr, rs ? rs + i : nullptr);
     fill_trans_outputs(s, trans_out ? trans_out + 3 * (size_t)i : nullptr, ts ? ts + i : nullptr);
     if (s->error && !first_err) { g_err = "device-side error in a batch member"; first_err = s->error; }

@@ -42,7 +42,8 @@ struct Switches {
   int lm_ppt = (int)env::in_range((int)env::num("ROLO_LM_PPT", 1), 1, 16, 1);   // 1..16 (anything else 1): slabs of lm_threads points per workgroup of that form
   int lm_spec_lin = env::unless_zero("ROLO_LM_SPEC_LIN");             // =0: every pass carries both halves (no cost-only passes after a rejected trial)
   int lm_keep_cost = env::unless_zero("ROLO_LM_KEEP_COST");           // =0: with forced iterations every repeat of a converged-but-rejected trial is a pass of its own again (the A/B of rot_step_t's kept cost)
-  bool pass_nrm = env::unless_zero("ROLO_PASS_NRM");                  // =0: the passes read the six-entry covariances always, never the PLANE form I - m m^T
+  int lm_trans_model = env::unless_zero("ROLO_LM_TRANS_MODEL");       // =0: every trial of the translation stage is a pass of its own again, not answered from the linearisation's sums (the A/B of trans_model.hpp)
+  bool pass_nrm = env::unless_zero("ROLO_PASS_NRM");                 // =0: the passes read the six-entry covariances always, never the PLANE form I - m m^T
   bool pass_xcd = env::unless_zero("ROLO_PASS_XCD");                  // =0: point blocks dealt to the XCDs round-robin, not an eighth of the cloud per XCD
   bool stamp = env::if_nonzero("ROLO_STAMP");                         // =1: a device timestamp at five points of every frame (rolo_debug_stamps)
   // ---- the resident LM kernel (schedule.hip, passes.hip) ----

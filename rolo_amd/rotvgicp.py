@@ -375,10 +375,10 @@ class RotVGICP:
 
     def counters(self) -> dict:
         """rolo_ctx_counters as a dict"""
-        v = (C.c_longlong * 15)()
-        check(lib().rolo_ctx_counters(self._h, v, 15), "rolo_ctx_counters")
+        v = (C.c_longlong * 16)()
+        check(lib().rolo_ctx_counters(self._h, v, 16), "rolo_ctx_counters")
         return dict(zip(("frames", "graph_replays", "graph_captures", "eager_frames", "topup_frames", "sync_chunks", "hint_rot", "hint_trans", "walk_lanes",
-                         "host_enqueue_ns", "host_wait_blocked_ns", "host_wait_other_ns", "persist_bails", "load_mode", "kept_trials"), [int(x) for x in v]))
+                         "host_enqueue_ns", "host_wait_blocked_ns", "host_wait_other_ns", "persist_bails", "load_mode", "kept_trials", "model_trials"),[int(x) for x in v]))
 
     def lm_form(self) -> dict:
         """rolo_ctx_lm_form as a dict: the form of the last resident LM launch (all zero if the last LM chain did not use the resident kernel)"""
