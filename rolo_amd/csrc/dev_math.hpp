@@ -12,6 +12,29 @@ ROLO_DEV int f2ord(float f) { int i = __float_as_int(f); return i >= 0 ? i : i ^
 ROLO_DEV float ord2f(int k) { int i = k >= 0 ? k : k ^ 0x7fffffff; return __int_as_float(i); }
 
 
+// ---- several fp64 quotients over ONE denominator ----------------------------------------------------------------------------------------------------------
+// The compiler expands a / b into fourteen instructions: v_div_scale of b and of a, v_rcp_f64 of b, four FMAs that refine that reciprocal (y), then q = a y,
+// e = fma(-b, q, a), v_div_fmas = fma(e, y, q) and v_div_fixup. Only the last five see the numerator. div_den is the denominator's part, done once; div_shared the
+// numerator's: a multiply and two FMAs. The two scale steps change an operand (by 2^+-128) only if it is zero or subnormal, if 1 / b or a / b would be subnormal, or if the
+// exponents differ by 768 or more; the fix-up replaces the quotient only for zeros, infinities, NaNs and those same extremes. With both magnitudes inside [2^-500, 2^500]
+// (div_shared_ok; a NaN fails it) none of that happens: these are the division's own instructions on its own values, so the quotient has the same bits — the correctly
+// rounded a / b. Everything else (a zero numerator first of all: the bare sequence loses the sign of -0) takes the plain division.
+// A constant denominator folds to its correctly rounded reciprocal at compile time, which the hardware's refined one need not equal. The only such caller divides by
+// 20: y = 0x3FA999999999999A is 2^-54 above 1 / 20 in relative terms, so a y is within half an ulp of a / 20 and q = RN(a y) within one; one residual step from such a q
+// with a correctly rounded reciprocal rounds correctly (Markstein's theorem): again the bits of a / b.
+ROLO_DEV double div_den(double b) {
+  double y = __builtin_amdgcn_rcp(b);
+  double f = __builtin_fma(-b, y, 1.0);
+  y = __builtin_fma(y, f, y);
+  f = __builtin_fma(-b, y, 1.0);
+  return __builtin_fma(y, f, y);
+}
+ROLO_DEV double div_shared(double a, double b, double y) {
+  const double q = a * y;
+  return __builtin_fma(__builtin_fma(-b, q, a), y, q);
+}
+ROLO_DEV bool div_shared_ok(double v) { return fabs(v) >= 0x1p-500 && fabs(v) <= 0x1p500; }
+
 struct Sym3 { double xx, xy, xz, yy, yz, zz; };
 struct Vec3 { double x, y, z; };
 struct Mat3 { double m[9]; };  // row-major

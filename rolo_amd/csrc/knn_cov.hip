@@ -419,10 +419,14 @@ ROLO_DEV void make_jacobi(double x, double y, double z, Rot2& r) {
   if (deno < DBL_MIN) { r.c = 1; r.s = 0; return; }
   double tau = (x - z) / deno;
   double w = sqrt(tau * tau + 1.0);
-  double t = (tau > 0) ? 1.0 / (tau + w) : 1.0 / (tau - w);
-  double sign_t = t > 0 ? 1.0 : -1.0;
+  double t = 1.0 / ((tau > 0) ? tau + w : tau - w);
   double n = 1.0 / sqrt(t * t + 1.0);
-  r.s = -sign_t * (y / fabs(y)) * fabs(t) * n;
+  // Eigen's  s = -sign_t * (y / |y|) * |t| * n  with sign_t = t > 0 ? 1 : -1. y / |y| is +-1 for a finite y (zero went out above), so the first two products are exact
+  // and round-to-nearest is symmetric in the sign: the value is |t| * n, rounded once, under the sign  (t > 0) xor (y < 0)  — a sign bit, not a division and two
+  // multiplications. A NaN or infinite y made y / |y| a NaN: |y| * 0 is +0 for a finite y, which added to a magnitude changes nothing, and a NaN for those.
+  const double mag = fabs(t) * n + fabs(y) * 0.0;
+  const int flip = ((t > 0) ? (int)0x80000000 : 0) ^ (__double2hiint(y) & (int)0x80000000);
+  r.s = __hiloint2double(__double2hiint(mag) ^ flip, __double2loint(mag));
   r.c = n;
 }
 
@@ -435,7 +439,13 @@ ROLO_DEV bool jacobi_pair(double (&W)[9], double (&U)[9], double (&V)[9], double
   Rot2 rot1;
   double t = m00 + m11, d = m10 - m01;
   if (fabs(d) < DBL_MIN) { rot1.s = 0; rot1.c = 1; }
-  else { double u = t / d; double tmp = sqrt(1.0 + u * u); rot1.s = 1.0 / tmp; rot1.c = u / tmp; }
+  else {
+    double u = t / d; double tmp = sqrt(1.0 + u * u);
+    // 1 / tmp and u / tmp over one reciprocal (div_den: the same bits). tmp >= 1 and tmp >= |u| up to a rounding: one bound on tmp keeps both inside the range, u = 0
+    // (a zero trace) or a huge u take the plain divisions
+    if (fabs(u) >= 0x1p-500 && tmp <= 0x1p499) { const double rt = div_den(tmp); rot1.s = div_shared(1.0, tmp, rt); rot1.c = div_shared(u, tmp, rt); }
+    else { rot1.s = 1.0 / tmp; rot1.c = u / tmp; }
+  }
   double n00 = rot1.c * m00 + rot1.s * m10, n01 = rot1.c * m01 + rot1.s * m11, n11 = -rot1.s * m01 + rot1.c * m11;
   Rot2 jr; make_jacobi(n00, n01, n11, jr);
   Rot2 jl; { double c2 = jr.c, s2 = -jr.s; jl.c = rot1.c * c2 - rot1.s * s2; jl.s = rot1.c * s2 + rot1.s * c2; }
@@ -479,7 +489,8 @@ ROLO_DEV void jacobi_svd3(const double (&A)[9], double (&U)[9], double (&sv)[3],
   for (int i = 0; i < 3; i++) {
     double a = fabs(W[i * 4]);
     sv[i] = a * scale;
-    if (a != 0) { double sgn = W[i * 4] / a; U[0 * 3 + i] *= sgn; U[1 * 3 + i] *= sgn; U[2 * 3 + i] *= sgn; }
+    // (W / |W| is +-1 for a finite W: a sign copy; W * 0 adds a zero to it, or the NaN that the division gave for an infinite or NaN W)
+    if (a != 0) { double sgn = copysign(1.0, W[i * 4]) + W[i * 4] * 0.0; U[0 * 3 + i] *= sgn; U[1 * 3 + i] *= sgn; U[2 * 3 + i] *= sgn; }
   }
   // sort descending with matching column swaps (3 elements: selection sort as in Eigen)
   if (sv[1] > sv[0] && sv[1] >= sv[2]) { double t = sv[0]; sv[0] = sv[1]; sv[1] = t; swap_cols(U, 0, 1); swap_cols(V, 0, 1); }
@@ -700,6 +711,8 @@ hipError_t launch_knn_walk(const KnnPair& A, int k, hipStream_t s, int* lanes_ou
   if (g0 + g1 == 0) return hipSuccess;
   // a packet's first query is a multiple of 64, so its four own leaves are one whole subtree: what the walk's climb starts from (packet_climb)
   for (int i = 0; i < A.n_clouds; i++) if (A.c[i].q_end > A.c[i].q_begin && A.c[i].q_begin % 64 != 0) return hipErrorInvalidValue;
+  // the moments epilogue addresses a neighbour by a 32-bit byte offset into the float4 cloud (gather_point): indices stay below 2^28
+  for (int i = 0; i < A.n_clouds; i++) if (A.c[i].n >= KNN_MAX_POINTS) return hipErrorInvalidValue;
   if (k > 64) {   // any k: rounds of 64 — round r searches the 64 (the last: k - 64 r) nearest ABOVE the previous round's last key (KnnCloud::lower).
                   // ceil(k / 64) full walks: correct, as slow as it sounds; the reference accepts any k, its default is 20 and ROLO never changes it
     KnnPair R = A;

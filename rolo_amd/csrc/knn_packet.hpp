@@ -138,8 +138,8 @@ ROLO_DEV void knn_score_leaf(const float4* __restrict__ sorted, int g, const flo
 // ---- seed leaves: sort and merge, not one insert each ---------------------------------------------------------------------------------------
 // Before the tree walk a wavefront scores its own leaves and their curve neighbours. There "insert if some lane's candidate beats its bound" buys nothing: a
 // lane's own point is at distance 0, so nearly every candidate is accepted by some lane, and deep (curve neighbours sort to the low slots: up to 48 VALU per
-// execution, plus the bound's compare, ballot and branch). The networks of knn_seed_net.hpp take a chunk of 8 candidates into the list in 150 VALU with no
-// compare and no branch; the keys are distinct (d2, index) pairs, so the list is the one the inserts would have left, bit for bit. Padding points (INFINITY
+// execution, plus the bound's compare, ballot and branch). The networks of knn_seed_net.hpp take a chunk of 8 candidates into the list in 126 min / max (38 to sort it, 88 to
+// merge it; the first leaf's two chunks, which meet a list of sentinels, in 140 together) with no compare and no branch; the keys are distinct (d2, index) pairs, so the list is the one the inserts would have left, bit for bit. Padding points (INFINITY
 // coordinates, index INT_MAX) give exactly the sentinel key, and equal sentinels are harmless in a min / max network. (k = 20, no lower bound; the tree phase
 // keeps the tiered insert: there the hungriest lane accepts about 5 of a leaf's 16, and a network over masked keys costs more.)
 struct KeyMin { ROLO_DEV double operator()(double a, double b) const { return vmin_f64(a, b); } };
@@ -147,8 +147,7 @@ struct KeyMax { ROLO_DEV double operator()(double a, double b) const { return vm
 
 // NB candidates p[0], p[STRIDE], ... -> keys (the distance in the oracle's operation order) -> sorted -> merged into the ascending K
 template <int NB, int STRIDE, class P>
-ROLO_DEV void seed_chunk(const P& p, int first, const float4& q, double (&K)[20]) {
-  double b[NB];
+ROLO_DEV void seed_keys(const P& p, int first, const float4& q, double (&b)[NB]) {
 #pragma unroll
   for (int u = 0; u < NB; u++) {
     const float4 c = p[first + u * STRIDE];
@@ -157,16 +156,30 @@ ROLO_DEV void seed_chunk(const P& p, int first, const float4& q, double (&K)[20]
     b[u] = key_pack(cd, __float_as_int(c.w));
   }
   if constexpr (NB == 8) seednet::sort8(b, KeyMin(), KeyMax()); else seednet::sort4(b, KeyMin(), KeyMax());
+}
+template <int NB, int STRIDE, class P>
+ROLO_DEV void seed_chunk(const P& p, int first, const float4& q, double (&K)[20]) {
+  double b[NB];
+  seed_keys<NB, STRIDE>(p, first, q, b);
   seednet::merge_chunk<NB>(K, b, KeyMin(), KeyMax());
 }
 
-// the KNN_LEAF (16) points of seed leaf g against this lane's query, in two chunks of 8; the caller takes its bound from K once after the last seed
+// the KNN_LEAF (16) points of seed leaf g against this lane's query, in two chunks of 8; the caller takes its bound from K once after the last seed.
+// FIRST: K holds twenty sentinels (the first seed of a packet) — the two sorted chunks are the list, one 16-cleaner apart (seednet::first_two_chunks)
+template <bool FIRST>
 ROLO_DEV void knn_seed_leaf(const float4* __restrict__ sorted, int g, const float4& q, double (&K)[20]) {
   static_assert(KNN_LEAF == 16, "two chunks of 8");
   float4 pts[KNN_LEAF];
   sload_leaf(sorted + KNN_LEAF * (size_t)g, pts);
-  seed_chunk<8, 1>(pts, 0, q, K);
-  seed_chunk<8, 1>(pts, 8, q, K);
+  if constexpr (FIRST) {
+    double b0[8], b1[8];
+    seed_keys<8, 1>(pts, 0, q, b0);
+    seed_keys<8, 1>(pts, 8, q, b1);
+    seednet::first_two_chunks(K, b0, b1, KeyMin(), KeyMax());
+  } else {
+    seed_chunk<8, 1>(pts, 0, q, K);
+    seed_chunk<8, 1>(pts, 8, q, K);
+  }
 }
 
 // ---- SUB lanes per query (round 4): exchanges among 2 / 4 / 8 adjacent lanes by DPP -------------------------------------------------------------------

@@ -69,6 +69,13 @@ ROLO_DEV void walk_write_lists(const KnnCloud& cl, const double (&K)[KMAX], int 
   for (int u = 0; u < KMAX; u++) nbr[(size_t)(slot0 + u) * cl.n_sorted + j] = ki[u];
 }
 
+// A cloud of the neighbour search holds fewer than 2^28 points (launch_knn_walk refuses a larger one): a neighbour's index is non-negative and its byte offset into the
+// float4 array fits 32 bits. The gather's address is then the scalar base plus ONE shifted register, where a sign-extended 64-bit index costs three instructions.
+constexpr int KNN_MAX_POINTS = 1 << 28;
+ROLO_DEV float4 gather_point(const float4* __restrict__ base, int idx) {
+  return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(base) + ((unsigned)idx << 4));
+}
+
 // Round 6: a finished query gathers its kk winners ONCE, right here, and leaves the six centred second moments of its neighbourhood (the oracle's order: mean first,
 // then the products summed over the list, rot_vgicp_impl.hpp:438-455) in cov[] — 48 B/pt that the tail finishes in place — instead of 80 B/pt of indices that the tail
 // read back and gathered through again (70 MB of fabric traffic for 6 MB of algorithmic bytes, 202 VGPRs: round 5's verdict, item 4). The light wavefronts do this while
@@ -88,19 +95,29 @@ ROLO_DEV void walk_write_moments(const KnnCloud& cl, const double (&K)[KMAX], in
   const float4* __restrict__ orig = cl.xyz;
   double mx = 0, my = 0, mz = 0;
 #pragma unroll 5
-  for (int u = 0; u < kk; u++) { const float4 p = orig[s_ki[u][tid]]; mx += (double)p.x; my += (double)p.y; mz += (double)p.z; }
-  mx /= kk; my /= kk; mz /= kk;
+  for (int u = 0; u < kk; u++) { const float4 p = gather_point(orig, s_ki[u][tid]); mx += (double)p.x; my += (double)p.y; mz += (double)p.z; }
+  // the nine divisions by kk share the denominator's part (div_den: one reciprocal, a multiply and two FMAs per quotient, the bits of x / kk). A sum that is zero, or out
+  // of div_shared_ok's range — sums of float32 coordinates are not, short of an exact cancellation — sends the wavefront through the plain divisions
+  const double den = (double)kk, rden = div_den(den);
+  if (!__any(!(div_shared_ok(mx) && div_shared_ok(my) && div_shared_ok(mz)))) { mx = div_shared(mx, den, rden); my = div_shared(my, den, rden); mz = div_shared(mz, den, rden); }
+  else { mx /= kk; my /= kk; mz /= kk; }
   double cxx = 0, cxy = 0, cxz = 0, cyy = 0, cyz = 0, czz = 0;
 #pragma unroll 5
   for (int u = 0; u < kk; u++) {
-    const float4 p = orig[s_ki[u][tid]];
+    const float4 p = gather_point(orig, s_ki[u][tid]);
     const double ax = (double)p.x - mx, ay = (double)p.y - my, az = (double)p.z - mz;
     cxx += ax * ax; cxy += ax * ay; cxz += ax * az; cyy += ay * ay; cyz += ay * az; czz += az * az;
+  }
+  if (!__any(!(div_shared_ok(cxx) && div_shared_ok(cxy) && div_shared_ok(cxz) && div_shared_ok(cyy) && div_shared_ok(cyz) && div_shared_ok(czz)))) {
+    cxx = div_shared(cxx, den, rden); cxy = div_shared(cxy, den, rden); cxz = div_shared(cxz, den, rden);
+    cyy = div_shared(cyy, den, rden); cyz = div_shared(cyz, den, rden); czz = div_shared(czz, den, rden);
+  } else {
+    cxx /= kk; cxy /= kk; cxz /= kk; cyy /= kk; cyz /= kk; czz /= kk;
   }
   // by SORTED position (coalesced here and in the tail), in the scratch the index lists would have taken: 6 doubles of the 32 int slots per position
   double* __restrict__ mom = reinterpret_cast<double*>(cl.nbr);
   const size_t pitch = (size_t)cl.n_sorted;
-  mom[j] = cxx / kk; mom[pitch + j] = cxy / kk; mom[2 * pitch + j] = cxz / kk; mom[3 * pitch + j] = cyy / kk; mom[4 * pitch + j] = cyz / kk; mom[5 * pitch + j] = czz / kk;
+  mom[j] = cxx; mom[pitch + j] = cxy; mom[2 * pitch + j] = cxz; mom[3 * pitch + j] = cyy; mom[4 * pitch + j] = cyz; mom[5 * pitch + j] = czz;
 }
 
 // The walk keeps only the 20 packed keys and the query live (58 VGPRs): cut for 8 wavefronts per SIMD. Neighbour indices
@@ -126,9 +143,15 @@ template <int KMAX, bool LOWER>
 ROLO_DEV void walk_seeds(const float4* __restrict__ sorted, int g_mine0, int g_own0, int g_own1, int n_leaves, const float4& q, bool active, double (&K)[KMAX], int kk, double& bkey, float& bd, double lo,
                          unsigned& st_leaves, unsigned& st_ins, unsigned& st_lane, unsigned& st_rounds) {
   const int n_own = min(g_mine0 + 64 / KNN_LEAF, n_leaves) - g_mine0, n_before = g_mine0 - g_own0;
-  for (int i = 0; i < g_own1 - g_own0; i++) {
+  int i = 0;
+  if constexpr (KMAX == 20 && !LOWER) {
+    // the first seed meets twenty sentinels: its two sorted chunks are the list, with no merge into it (knn_seed_leaf<true>). It is the first own leaf when the packet
+    // has one, as in the loop's order below (an all-padding packet that starts right behind the cloud's last leaf has that leaf as its only seed)
+    if (g_own1 - g_own0 > 0) { knn_seed_leaf<true>(sorted, n_own > 0 ? g_mine0 : g_own0, q, K); st_leaves++; i = 1; }
+  }
+  for (; i < g_own1 - g_own0; i++) {
     const int g = i < n_own ? g_mine0 + i : (i - n_own < n_before ? g_own0 + (i - n_own) : g_mine0 + (i - n_before));
-    if constexpr (KMAX == 20 && !LOWER) knn_seed_leaf(sorted, g, q, K);
+    if constexpr (KMAX == 20 && !LOWER) knn_seed_leaf<false>(sorted, g, q, K);
     else knn_score_leaf<KMAX, LOWER>(sorted, g, q, K, kk, bkey, bd, st_ins, st_lane, st_rounds, lo);
     st_leaves++;
   }
