@@ -386,6 +386,12 @@ int rolo_extract_features(rolo_ctx* ctx, const rolo_front_params* P, float* corn
 enum { ROLO_XPATH_RING_NONE = 0, ROLO_XPATH_RING_CAPPED = 1, ROLO_XPATH_RING_APPLIED = 2 };
 enum { ROLO_XPATH_SECTOR_NOT_STAGED = 0, ROLO_XPATH_SECTOR_EMPTY = 1, ROLO_XPATH_SECTOR_PARALLEL = 2, ROLO_XPATH_SECTOR_SERIAL = 3 };
 int rolo_debug_extract_paths(rolo_ctx* ctx, int32_t* out, int n_scan);
+/* test hook: the per-point times (seconds, n = the number of raw points) that the last projection on this context de-skewed with — the caller's
+ * (rolo_front_set_deskew), fabs(time) of the message, or the ones interpolated from the azimuth (deskewCloudInfo's timeFlag == -1 branch,
+ * imageProjection.cpp:270-327) — and in *first_passed (may be NULL) the index of the point that set halfPassed in that branch: INT_MAX if no point did or
+ * the times did not come from the azimuth. Times handed over as a device pointer are read through that pointer. ROLO_ESTATE if the last projection was not
+ * de-skewed, ROLO_EINVAL if n is not its number of raw points. */
+int rolo_debug_front_times(rolo_ctx* ctx, float* out, int n, int32_t* first_passed);
 
 /* ---- per-frame odometry driver -------------------------------------------------------------------------------
  * LidarOdometry (src/lidarOdometry.cpp:325-713) between fromROSMsg and publish, on feature clouds (n x 4 floats:

@@ -286,6 +286,7 @@ SYMBOLS = {
     "rolo_extract_features": (C.c_int, [vp, C.POINTER(FrontParams), fp, C.POINTER(C.c_int), fp, C.POINTER(C.c_int), fp,
                                         ip, ip]),
     "rolo_debug_extract_paths": (C.c_int, [vp, ip, C.c_int]),
+    "rolo_debug_front_times": (C.c_int, [vp, fp, C.c_int, ip]),
 }
 
 _lib = None

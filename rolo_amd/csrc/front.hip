@@ -68,10 +68,18 @@ __global__ __launch_bounds__(256) void unpack_cloud_kernel(const unsigned char* 
 // The reference interpolates the time from the azimuth in a serial loop with one flag, halfPassed, that flips at the first
 // point whose (first-half-adjusted) azimuth is more than pi past the start: a prefix property. Kernel 1 finds that point
 // (atomicMin), kernel 2 applies the first-half rule up to and including it and the second-half rule after it.
+// Every angle is the CORRECTLY ROUNDED float atan2 — (float)atan2((double)y, (double)x), K1's remedy (below) without the guard: the rule compares the angle with
+// seven thresholds, and on adjacent floats planted on either side of them the device's atan2f, one ulp off, takes the other side on a large share
+// (tests/test_gpu_deskew_cases.py) — a time a whole scan period off, or the other rule for every later point — and where it takes the right side the bits of the time
+// still follow the angle. The fp64 function is good to a few fp64 ulps, so its rounding to float is the correctly rounded float unless the true value lies within
+// ~2^-50 of the midpoint of two floats. These kernels run only for a de-skew armed without times.
+ROLO_DEV float azimuth_of(const float* __restrict__ pts, int stride, int i) {
+  return -(float)atan2((double)pts[(size_t)i * stride + 1], (double)pts[(size_t)i * stride]);   // point.x = in.y, point.z = in.x (:303-307)
+}
 struct AzimuthRef { float start, end, diff; };
 ROLO_DEV AzimuthRef azimuth_ref(const float* __restrict__ pts, int stride, int n) {
-  float start = -atan2f(pts[1], pts[0]);                                                           // :272
-  float end = (float)((double)(-atan2f(pts[(size_t)(n - 1) * stride + 1], pts[(size_t)(n - 1) * stride])) + 2 * M_PI);   // :273
+  float start = azimuth_of(pts, stride, 0);                                                        // :272
+  float end = (float)((double)azimuth_of(pts, stride, n - 1) + 2 * M_PI);                          // :273
   if ((double)(end - start) > 3 * M_PI) end = (float)((double)end - 2 * M_PI);                     // :274-277
   else if ((double)(end - start) < M_PI) end = (float)((double)end + 2 * M_PI);
   return AzimuthRef{start, end, end - start};
@@ -85,7 +93,7 @@ __global__ __launch_bounds__(256) void azimuth_flag_kernel(const float* __restri
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const AzimuthRef r = azimuth_ref(pts, stride, n);
-  const float a = azimuth_first_half(-atan2f(pts[(size_t)i * stride + 1], pts[(size_t)i * stride]), r.start);   // point.x = in.y, point.z = in.x (:303-307)
+  const float a = azimuth_first_half(azimuth_of(pts, stride, i), r.start);
   if ((double)(a - r.start) > M_PI) atomicMin(first_passed, i);
 }
 __global__ __launch_bounds__(256) void azimuth_time_kernel(const float* __restrict__ pts, int stride, int n, float scan_period,
@@ -93,7 +101,7 @@ __global__ __launch_bounds__(256) void azimuth_time_kernel(const float* __restri
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const AzimuthRef r = azimuth_ref(pts, stride, n);
-  float ori = -atan2f(pts[(size_t)i * stride + 1], pts[(size_t)i * stride]);
+  float ori = azimuth_of(pts, stride, i);
   if (i <= *first_passed) {
     ori = azimuth_first_half(ori, r.start);
   } else {                                                                                          // :316-322
@@ -987,6 +995,7 @@ struct Front {
   int deskew_n = 0;   // length of the armed per-point time array
   DeskewArgs deskew{};
   float* rel_time = nullptr; size_t cap_time = 0;   // staging when the times come from the host
+  const float* last_times = nullptr; int last_times_n = 0; bool last_times_azimuth = false;   // what the last projection de-skewed with (rolo_debug_front_times); nullptr: it did not
   bool deskew_from_msg = false;                      // armed without times: the next message brings them
   // message-level entry: raw payload and what the unpack kernel makes of it
   unsigned char* msg_raw = nullptr; size_t cap_msg = 0;
@@ -1050,7 +1059,7 @@ int front_prepare(rolo_ctx* c, const rolo_front_params* P, int n_raw, int stride
   }
   f->maxh = maxh;
   if (!ok) { ctx_set_error("hipMalloc failed (front end)"); return ROLO_EHIP; }
-  f->n_scan = NS; f->H = H; f->projected = false; f->paths_valid = false;
+  f->n_scan = NS; f->H = H; f->projected = false; f->paths_valid = false; f->last_times = nullptr;
   *out = f;
   return ROLO_OK;
 }
@@ -1060,6 +1069,7 @@ int front_project_enqueue(Front* f, const rolo_front_params* P, const float* d_p
                           hipStream_t s) {
   const int NS = f->n_scan, H = f->H;
   const size_t npix = (size_t)NS * H;
+  bool from_azimuth = false;
   if (f->deskew_from_msg) {   // armed without times and no time field came with the points: interpolate them from the azimuth
     f->deskew_from_msg = false;
     if (n_raw > 0) {
@@ -1072,6 +1082,7 @@ int front_project_enqueue(Front* f, const rolo_front_params* P, const float* d_p
       azimuth_time_kernel<<<(n_raw + 255) / 256, 256, 0, s>>>(d_pts, stride, n_raw, f->deskew.scan_period, f->counters + 4, f->rel_time);
       f->deskew.rel_time = f->rel_time;
       f->deskew_armed = true; f->deskew_n = n_raw;
+      from_azimuth = true;
     }
   }
   if (f->deskew_armed && f->deskew_n < n_raw) {   // ring_scatter_kernel reads rel_time[o] for every raw point of this frame
@@ -1089,6 +1100,7 @@ int front_project_enqueue(Front* f, const rolo_front_params* P, const float* d_p
   ring_scatter_kernel<<<NS, 256, 0, s>>>(d_pts, stride, d_ring, f->owner, f->local_idx, f->ring_count, NS, H, f->extracted + FRONT_GUARD,
                                         f->col + FRONT_GUARD, f->range + FRONT_GUARD, f->start_ring, f->end_ring, want_range_mat ? f->range_mat : nullptr,
                                         f->counters, f->deskew_armed ? f->deskew : DeskewArgs{});
+  f->last_times = f->deskew_armed ? f->deskew.rel_time : nullptr; f->last_times_n = n_raw; f->last_times_azimuth = from_azimuth;
   f->deskew_armed = false;
   HIPCHK(hipGetLastError());
   return ROLO_OK;
@@ -1215,7 +1227,7 @@ void front_reset_object_state(rolo_ctx* c) {
   Front* f = static_cast<Front*>(*slot);
   f->projected = false; f->extract_cleared = false; f->precleared_np = 0;
   f->deskew_armed = false; f->deskew_from_msg = false; f->deskew_n = 0;
-  f->n_valid = 0; f->paths_valid = false;
+  f->n_valid = 0; f->paths_valid = false; f->last_times = nullptr;
 }
 }  // namespace rolo
 
@@ -1372,6 +1384,24 @@ int rolo_debug_extract_paths(rolo_ctx* c, int32_t* out, int n_scan) {
   hipStream_t s = ctx_stream(c);
   HIPCHK(hipMemcpyAsync(out, f->paths, sizeof(int) * (size_t)n_scan, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
+  return ROLO_OK;
+}
+
+// the per-point times the last projection on this context de-skewed with — the caller's, the message's or the azimuth-interpolated ones — and the index of
+// the point that set halfPassed in the azimuth route (INT_MAX: no point did, or the times did not come from the azimuth)
+int rolo_debug_front_times(rolo_ctx* c, float* out, int n, int32_t* first_passed) {
+  if (!c || n < 0 || (n > 0 && !out)) return ROLO_EINVAL;
+  void** slot = ctx_front_slot(c);
+  Front* f = static_cast<Front*>(*slot);
+  if (!f || !f->last_times) { ctx_set_error("rolo_debug_front_times needs a preceding de-skewed projection"); return ROLO_ESTATE; }
+  if (n != f->last_times_n) { ctx_set_error("rolo_debug_front_times: n is not the last projection's number of raw points"); return ROLO_EINVAL; }
+  HIPCHK(hipSetDevice(ctx_device(c)));
+  hipStream_t s = ctx_stream(c);
+  int fp = INT_MAX;
+  if (n) HIPCHK(hipMemcpyAsync(out, f->last_times, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, s));
+  if (f->last_times_azimuth) HIPCHK(hipMemcpyAsync(&fp, f->counters + 4, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (first_passed) *first_passed = fp;
   return ROLO_OK;
 }
 

@@ -96,6 +96,13 @@ class FrontEnd:
         check(lib().rolo_debug_extract_paths(self.ctx._h, _i(out), self.p.n_scan), "rolo_debug_extract_paths")
         return out
 
+    def deskewTimes(self, n_raw):
+        """Test hook (rolo_debug_front_times): (the per-point times the last project() de-skewed its n_raw points with, the index of the point that set
+        halfPassed in the azimuth route — INT_MAX if none did or the times were handed over)."""
+        out = np.zeros(max(n_raw, 1), np.float32); first = C.c_int32(0)
+        check(lib().rolo_debug_front_times(self.ctx._h, _f(out), n_raw, C.byref(first)), "rolo_debug_front_times")
+        return out[:n_raw], first.value
+
     def extract(self, n, debug=False):
         corner = np.zeros((max(n, 1), 4), np.float32); surf = np.zeros((max(n, 1), 4), np.float32)
         nc = C.c_int(0); ns = C.c_int(0)
