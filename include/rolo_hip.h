@@ -732,6 +732,101 @@ int rolo_pgo_last_ms(rolo_pgo* g, float* ms4);
 /* correctPoses (:1301-1314) in one call: poses 0 .. n - 1 of the key map (n x 6 floats); n above the key map's size is ROLO_EINVAL */
 int rolo_keymap_set_poses(rolo_keymap* km, const float* pose6, int n);
 
+/* ---- The ground prior: a resident ground cloud with x-y queries and patch cut (reference ground_factor::GroundModel, src/prior_pose/pose_solver.cpp) and the
+ * batched terrain pose solver (ground_factor::PoseSolver::Solve, PriorPoseNode::HandlePose prior_pose_node.cpp:164-233). tests/prior_twin.py states all of it in
+ * numpy; DESIGN.md 10 has the kernels.
+ *   cloud      n records of stride_floats floats (3 .. 8), x y z at floats 0 .. 2; the whole record is kept (a patch carries what GroundPatchType carries). A
+ *              non-finite x or y is ROLO_ENONFINITE and the model keeps what it held. n = 0 empties the model; every query on an empty model is ROLO_ESTATE
+ *              (ExtractPatch returns false on an empty cloud). The points are binned into a uniform x-y grid on the device: cells of the fit radius (0.6, or
+ *              rolo_ground_set_grid), doubled until no side has more than ROLO_GROUND_MAX_SIDE cells and the grid no more than min(max_cells, 4 n + 1024).
+ *              The grid only decides which points a query looks at, never its answer.
+ *   nearest    the smallest (d2, index) with d2 = dx dx + dy dy in float, as FLANN's L2_Simple adds its terms (the z term is 0). Among equal distances the
+ *              reference takes whatever FLANN's tree order gives; here the lowest index. Parity on that choice is unpinned.
+ *   radius     { i : d2_i < (float)(r r) }, r r in double (what pcl::KdTreeFLANN::radiusSearch passes down), strict, in ascending (d2, index): a sorted radius
+ *              search. Every sum over neighbours below is a serial fp64 sum in that order. A neighbourhood of more than ROLO_GROUND_MAX_NEIGHBOURS points does
+ *              not fit a workgroup's list: the debug query returns its true count and no list; a fit or an average height takes its nearest-point fall-back and
+ *              sets ROLO_PRIOR_STATUS_OVERFLOW.
+ *   patch      ExtractPatch: two pcl::PassThrough passes, x then y; each limit is (float)(c -+ 0.5 size) with the sum in double, both ends inclusive, a point
+ *              with a non-finite x, y or z is dropped, the caller's order is kept. With T16 (row-major 4 x 4 floats) the kept points are moved as
+ *              pcl::transformPointCloud moves them in float, each row T0 x + (T1 y + (T2 z + T3)); the other fields are copied. *m = 0 is a valid answer; a cap
+ *              below the number kept is ROLO_EINVAL and *m still receives that number.
+ * One model is single-threaded like a key map, works on a stream of its own and waits for it before returning. */
+#define ROLO_GROUND_MAX_POINTS (1 << 26)
+#define ROLO_GROUND_MAX_NEIGHBOURS 4096
+#define ROLO_GROUND_MAX_CELLS (1 << 22)
+#define ROLO_GROUND_MAX_SIDE 2048
+#define ROLO_GROUND_MAX_QUERIES 65536
+typedef struct rolo_ground rolo_ground;
+int rolo_ground_create(int device, rolo_ground** out);
+void rolo_ground_destroy(rolo_ground* g);
+/* the first cell size (> 0, finite) and the cell limit (1 .. ROLO_GROUND_MAX_CELLS) of the NEXT rolo_ground_set_cloud */
+int rolo_ground_set_grid(rolo_ground* g, float cell_size, int max_cells);
+int rolo_ground_set_cloud(rolo_ground* g, const float* pts, int n, int stride_floats);
+/* out[0] points, [1] cells along x, [2] along y, [3] how often the cell size was doubled, [4] floats per record; the first min(cap, 5) */
+int rolo_ground_info(rolo_ground* g, long long* out, int cap);
+/* debug entry points, nq <= ROLO_GROUND_MAX_QUERIES queries (x y floats: the reference casts its query to float before it searches). nearest: index and d2 per
+ * query. radius: count[q] is the number of hits whatever cap is; the first min(count, cap) (index, d2) pairs of the ordered list go to row q of idx / d2 (cap
+ * entries per row), none when count exceeds ROLO_GROUND_MAX_NEIGHBOURS */
+int rolo_ground_nearest_xy(rolo_ground* g, const float* xy, int nq, int32_t* idx, float* d2);
+int rolo_ground_radius_xy(rolo_ground* g, const float* xy, int nq, double radius, int cap, int32_t* count, int32_t* idx, float* d2);
+int rolo_ground_extract_patch(rolo_ground* g, double cx, double cy, double patch_size, const float* T16_or_null, float* out, int cap, int* m);
+/* device milliseconds between HIP events of the last grid build [0], patch [1] and solve [2] (0 before the first) */
+int rolo_ground_last_ms(rolo_ground* g, float* ms3);
+
+/* PoseSolver::Solve as written, in fp64, for a batch of (x, y, yaw): one workgroup per pose, every pose independent of the others and its result the same bits
+ * alone or in any batch.
+ *   start      R = RotZ(yaw); z = InitialZ: the least AverageHeightAt over the wheels (the nearest point, then the mean z of the radius search around THAT
+ *              point; the nearest point's z when ground_avg_radius <= 0, when the search finds nothing or fewer than ground_min_neighbors) + vehicle_com_z - 1.
+ *   residual   per wheel p = R (wx, wy, -com_z) + t and a ground point: FitLocalSurface at (float) p.xy, else the nearest point. The fit: the radius search
+ *              (fit_radius); fewer than fit_min_points hits -> no fit; the z-outlier cut with inclusive bounds mean -+ fit_outlier_factor sigma (population
+ *              sigma); fewer than fit_min_points (or than 3) inliers -> no fit; centroid and scatter matrix of the inliers, the eigenvector of the smallest
+ *              eigenvalue as the normal (a cyclic Jacobi in fp64: the height does not depend on the vector's sign or scale, and Eigen's QL iteration is not
+ *              restated); |c| < 1e-6 -> no fit; z = -(a x + b y + d) / c at the double query. d_i = (p - ground) . (R ez); f_i = k d_i if d_i < 0 else 0.
+ *              residual = sum_i f_i (1, wy_i, -wx_i) + g ((R ez) . ez, 0, 0); the Jacobian as ComputeResidualAndJacobian writes it. Sums run in wheel order.
+ *   loop       A = J^T J + lambda I, b = -J^T r; a 3 x 3 LU with full pivoting and Eigen's rank rule (a pivot counts if |p| > 3 eps |p_max|); singular ->
+ *              lambda *= 10 and the next iteration. R_new = RotX(droll) RotY(dpitch) R, then EnforceFixedYaw. Accept when the trial cost is lower: lambda =
+ *              max(lambda / 2, 1e-8), converged when |last_cost - c1| < tol_cost and |delta| < tol_step; reject: lambda *= 5. Best-so-far (z, R, cost) is
+ *              what comes back. The wheels' signed distances at the end use the NEAREST point, not the fit.
+ *   success    FailureDetection: z in [z_min, z_max], |roll| <= roll_max, |pitch| <= pitch_max, every |distance| <= wheel_distance_max, and not max_iters;
+ *              cleared too by any status bit. ROLO_PRIOR_STATUS_NONFINITE: a wheel position or a cost stopped being finite and the pose's loop ended there
+ *              (the reference would go on searching with it).
+ *   lidar pose x y z roll pitch yaw of T_world_body body_to_lidar with T_world_body = (RotZ(yaw) RotY(pitch) RotX(roll), (x, y, z)) and the angles as
+ *              tf2::Matrix3x3::getRPY takes them; HandlePose's round trips through quaternions are not restated.
+ * Unpinned: FLANN's order among equal distances, Eigen's SelfAdjointEigenSolver and FullPivLU internals, the order of Eigen's matrix-vector sums.
+ * ROLO_EINVAL: B outside 1 .. ROLO_PRIOR_MAX_BATCH, n_wheels outside 1 .. ROLO_PRIOR_MAX_WHEELS, max_iters outside 0 .. ROLO_PRIOR_MAX_ITERS, negative
+ * neighbour counts; ROLO_ENONFINITE: a non-finite parameter or pose; ROLO_ESTATE: no cloud. */
+#define ROLO_PRIOR_MAX_WHEELS 8
+#define ROLO_PRIOR_MAX_BATCH 65536
+#define ROLO_PRIOR_MAX_ITERS 10000
+#define ROLO_PRIOR_END_CONVERGED 0
+#define ROLO_PRIOR_END_MAX_ITERS 1
+#define ROLO_PRIOR_STATUS_OVERFLOW 1
+#define ROLO_PRIOR_STATUS_NONFINITE 2
+#define ROLO_PRIOR_FIT_OK 0          /* fall-backs of the fit, in the order FitLocalSurface tests them */
+#define ROLO_PRIOR_FIT_FEW_HITS 1
+#define ROLO_PRIOR_FIT_FEW_INLIERS 2
+#define ROLO_PRIOR_FIT_NO_PLANE 3    /* fewer than 3 inliers */
+#define ROLO_PRIOR_FIT_VERTICAL 4    /* |c| < 1e-6 */
+#define ROLO_PRIOR_FIT_OVERFLOW 5
+typedef struct rolo_priorpose_params {
+  int n_wheels; double wheel_xy[2 * ROLO_PRIOR_MAX_WHEELS]; double vehicle_com_z; double body_to_lidar_t[3]; double body_to_lidar_R[9];   /* R row-major */
+  double k_spring, g; int max_iters; double lm_lambda, tol_cost, tol_step, ground_avg_radius; int ground_min_neighbors;
+  double fit_radius, fit_outlier_factor; int fit_min_points;
+  double z_min, z_max, roll_max, pitch_max, wheel_distance_max;
+} rolo_priorpose_params;
+typedef struct rolo_priorpose_result {
+  double z, roll, pitch, R[9], cost; double wheel_distance[ROLO_PRIOR_MAX_WHEELS]; double lidar_pose[6];   /* x y z roll pitch yaw */
+  int iterations, end_reason, success, status;
+} rolo_priorpose_result;
+/* hits: the radius search's count; inliers: after the cut (0 when the fit ended before it); fallback: ROLO_PRIOR_FIT_*; point: the ground point the residual
+ * would use, the fit's (x, y, height) or the nearest point; nearest: that point's index, -1 when the fit held */
+typedef struct rolo_priorpose_fit { int hits, inliers, fallback, nearest; double point[3]; } rolo_priorpose_fit;
+/* the values of config/prior_pose_params.yaml (its four wheels), fit radius 0.6, outlier factor 3, minimum points 15 */
+void rolo_priorpose_default_params(rolo_priorpose_params* p);
+int rolo_priorpose_solve(rolo_ground* g, const rolo_priorpose_params* params, const double* xyyaw, int B, rolo_priorpose_result* out);
+/* the fit alone at nq <= ROLO_GROUND_MAX_QUERIES double queries (x y) */
+int rolo_priorpose_fit_surface(rolo_ground* g, const rolo_priorpose_params* params, const double* xy, int nq, rolo_priorpose_fit* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,23 @@ class LoopIcpTraceRec(C.Structure):
     _fields_ = [("n", C.c_int), ("mse", C.c_double), ("sums", C.c_double * 17), ("increment", C.c_float * 16)]
 
 
+class PriorPoseParams(C.Structure):
+    _fields_ = [("n_wheels", C.c_int), ("wheel_xy", C.c_double * 16), ("vehicle_com_z", C.c_double), ("body_to_lidar_t", C.c_double * 3), ("body_to_lidar_R", C.c_double * 9),
+                ("k_spring", C.c_double), ("g", C.c_double), ("max_iters", C.c_int), ("lm_lambda", C.c_double), ("tol_cost", C.c_double), ("tol_step", C.c_double),
+                ("ground_avg_radius", C.c_double), ("ground_min_neighbors", C.c_int), ("fit_radius", C.c_double), ("fit_outlier_factor", C.c_double),
+                ("fit_min_points", C.c_int), ("z_min", C.c_double), ("z_max", C.c_double), ("roll_max", C.c_double), ("pitch_max", C.c_double),
+                ("wheel_distance_max", C.c_double)]
+
+
+class PriorPoseResult(C.Structure):
+    _fields_ = [("z", C.c_double), ("roll", C.c_double), ("pitch", C.c_double), ("R", C.c_double * 9), ("cost", C.c_double), ("wheel_distance", C.c_double * 8),
+                ("lidar_pose", C.c_double * 6), ("iterations", C.c_int), ("end_reason", C.c_int), ("success", C.c_int), ("status", C.c_int)]
+
+
+class PriorPoseFit(C.Structure):
+    _fields_ = [("hits", C.c_int), ("inliers", C.c_int), ("fallback", C.c_int), ("nearest", C.c_int), ("point", C.c_double * 3)]
+
+
 class EskfOptions(C.Structure):   # include/rolo_fusion.h
     _fields_ = [(k, C.c_double) for k in ("max_dt", "q_linear_jerk_std", "q_angular_jerk_std", "r_position_std", "r_rotation_std", "init_position_std",
                                           "init_rotation_std", "init_velocity_std", "init_angular_velocity_std", "init_acceleration_std",
@@ -220,6 +237,18 @@ SYMBOLS = {
     "rolo_keymap_global_info": (C.c_int, [vp, C.POINTER(C.c_longlong), C.c_int]),
     "rolo_keymap_global_last_ms": (C.c_int, [vp, fp]),
     "rolo_keymap_global_cloud": (C.c_longlong, [vp, ip, C.c_int, fp, C.c_longlong]),
+    "rolo_ground_create": (C.c_int, [C.c_int, C.POINTER(vp)]),
+    "rolo_ground_destroy": (None, [vp]),
+    "rolo_ground_set_grid": (C.c_int, [vp, C.c_float, C.c_int]),
+    "rolo_ground_set_cloud": (C.c_int, [vp, fp, C.c_int, C.c_int]),
+    "rolo_ground_info": (C.c_int, [vp, C.POINTER(C.c_longlong), C.c_int]),
+    "rolo_ground_nearest_xy": (C.c_int, [vp, fp, C.c_int, ip, fp]),
+    "rolo_ground_radius_xy": (C.c_int, [vp, fp, C.c_int, C.c_double, C.c_int, ip, ip, fp]),
+    "rolo_ground_extract_patch": (C.c_int, [vp, C.c_double, C.c_double, C.c_double, fp, fp, C.c_int, C.POINTER(C.c_int)]),
+    "rolo_ground_last_ms": (C.c_int, [vp, fp]),
+    "rolo_priorpose_default_params": (None, [C.POINTER(PriorPoseParams)]),
+    "rolo_priorpose_solve": (C.c_int, [vp, C.POINTER(PriorPoseParams), dp, C.c_int, C.POINTER(PriorPoseResult)]),
+    "rolo_priorpose_fit_surface": (C.c_int, [vp, C.POINTER(PriorPoseParams), dp, C.c_int, C.POINTER(PriorPoseFit)]),
     "rolo_num_voxels": (C.c_int, [vp]),
     "rolo_num_edge_points": (C.c_int, [vp]),
     "rolo_get_voxels": (C.c_int, [vp, ip, ip, dp, dp]),

@@ -2,14 +2,14 @@
 device-resident key frames with sub-map assembly (:558-678) over rolo_keymap_*, Scan Context loop detection (src/scancontext/Scancontext.cpp) over
 rolo_keymap_sc_*, the loop closure's clouds, radius-search detector and ICP (:2307-2624) over rolo_keymap_loop_* / rolo_loopicp_*, the factor graph
 (:1222-1320) as a batch pose-graph optimisation over rolo_pgo_*, and the clouds of the exports (publishGlobalMap :1611-1665, cloudGlobal.pcd :1546-1557) over
-rolo_keymap_global_*."""
+rolo_keymap_global_*, and the ground prior (src/prior_pose/pose_solver.cpp, prior_pose_node.cpp:164-233) over rolo_ground_* / rolo_priorpose_*."""
 from __future__ import annotations
 
 import ctypes as C
 
 import numpy as np
 
-from ._lib import lib, check, Scan2MapStats, ScParams, ScResult, LoopIcpParams, LoopIcpResult, LoopIcpTraceRec, PgoParams, PgoResult, PgoTraceRec
+from ._lib import lib, check, Scan2MapStats, ScParams, ScResult, LoopIcpParams, LoopIcpResult, LoopIcpTraceRec, PgoParams, PgoResult, PgoTraceRec, PriorPoseParams, PriorPoseResult, PriorPoseFit
 from .rotvgicp import RotVGICP
 
 
@@ -647,3 +647,138 @@ class PoseGraph:
         d = np.zeros(6 * max(n, 1)); its = C.c_int(0); res = C.c_double(0.0)
         check(lib().rolo_pgo_solve_linear(self._h, lambda_, pcg_tol, pcg_max, d.ctypes.data_as(C.POINTER(C.c_double)), C.byref(its), C.byref(res)), "rolo_pgo_solve_linear")
         return d[:6 * n], its.value, res.value
+
+
+def prior_pose_params(wheel_xy=None, square_size=None, **kw) -> PriorPoseParams:
+    """config/prior_pose_params.yaml's values; wheel_xy (k x 2, body frame) or square_size (VehicleModel::FromSquare's four corners) replace its wheels; fields of
+    rolo_priorpose_params by keyword (body_to_lidar_t: 3, body_to_lidar_R: 3 x 3 row-major)"""
+    p = PriorPoseParams()
+    lib().rolo_priorpose_default_params(C.byref(p))
+    if square_size is not None:
+        h = square_size / 2.0
+        wheel_xy = [(-h, h), (h, h), (h, -h), (-h, -h)]
+    if wheel_xy is not None:
+        w = np.asarray(wheel_xy, np.float64).reshape(-1, 2)
+        p.n_wheels = w.shape[0]
+        for k in range(min(w.shape[0], 8)):   # more than 8: n_wheels says so and the call refuses it
+            p.wheel_xy[2 * k], p.wheel_xy[2 * k + 1] = w[k]
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        if k in ("body_to_lidar_t", "body_to_lidar_R"):
+            v = np.asarray(v, np.float64).reshape(-1)
+            for i in range(v.shape[0]):
+                getattr(p, k)[i] = v[i]
+        else:
+            setattr(p, k, v)
+    return p
+
+
+class GroundModel:
+    """ground_factor::GroundModel (pose_solver.cpp:120-376) resident on the device: the ground cloud (n x stride floats, x y z first, 3 <= stride <= 8), its x-y
+    queries and ExtractPatch."""
+
+    def __init__(self, device: int = 0):
+        self._h = C.c_void_p()
+        check(lib().rolo_ground_create(device, C.byref(self._h)), "rolo_ground_create")
+
+    def close(self):
+        if self._h:
+            lib().rolo_ground_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def setGrid(self, cell_size: float = 0.6, max_cells: int = 1 << 22):
+        check(lib().rolo_ground_set_grid(self._h, cell_size, max_cells), "rolo_ground_set_grid")
+
+    def setCloud(self, cloud):
+        """UpdateFromCloud. An empty cloud empties the model"""
+        a = np.ascontiguousarray(cloud, np.float32)
+        a = a.reshape(-1, a.shape[-1] if a.ndim > 1 else 4)
+        check(lib().rolo_ground_set_cloud(self._h, a.ctypes.data_as(C.POINTER(C.c_float)), a.shape[0], a.shape[1]), "rolo_ground_set_cloud")
+
+    def info(self) -> dict:
+        v = (C.c_longlong * 5)()
+        check(lib().rolo_ground_info(self._h, v, 5), "rolo_ground_info")
+        return dict(points=v[0], nx=v[1], ny=v[2], doubled=v[3], stride=v[4])
+
+    def nearestXY(self, xy):
+        """test hook -> (index, d2) per query (n x 2, taken as float)"""
+        q = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        idx = np.zeros(q.shape[0], np.int32); d2 = np.zeros(q.shape[0], np.float32)
+        check(lib().rolo_ground_nearest_xy(self._h, q.ctypes.data_as(C.POINTER(C.c_float)), q.shape[0], idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                           d2.ctypes.data_as(C.POINTER(C.c_float))), "rolo_ground_nearest_xy")
+        return idx, d2
+
+    def radiusXY(self, xy, radius: float, cap: int = 4096):
+        """test hook -> per query (count, indices, d2) of the sorted radius search; the lists are empty when count exceeds 4096, cut at cap otherwise"""
+        q = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        nq = q.shape[0]
+        cnt = np.zeros(nq, np.int32); idx = np.zeros((nq, max(cap, 1)), np.int32); d2 = np.zeros((nq, max(cap, 1)), np.float32)
+        check(lib().rolo_ground_radius_xy(self._h, q.ctypes.data_as(C.POINTER(C.c_float)), nq, radius, cap, cnt.ctypes.data_as(C.POINTER(C.c_int32)),
+                                          idx.ctypes.data_as(C.POINTER(C.c_int32)), d2.ctypes.data_as(C.POINTER(C.c_float))), "rolo_ground_radius_xy")
+        out = []
+        for k in range(nq):
+            m = min(int(cnt[k]), cap) if cnt[k] <= 4096 else 0
+            out.append((int(cnt[k]), idx[k, :m].copy(), d2[k, :m].copy()))
+        return out
+
+    def extractPatch(self, cx: float, cy: float, patch_size: float, T=None):
+        """ExtractPatch, then (T given, 4 x 4) pcl::transformPointCloud in float: the kept records in the cloud's order, possibly none"""
+        st = self.info()
+        n, stride = st["points"], st["stride"]
+        out = np.zeros((max(n, 1), max(stride, 3)), np.float32)
+        m = C.c_int(0)
+        keep, t = _guess_ptr(T)
+        check(lib().rolo_ground_extract_patch(self._h, cx, cy, patch_size, t, out.ctypes.data_as(C.POINTER(C.c_float)), n, C.byref(m)), "rolo_ground_extract_patch")
+        return out[:m.value].copy()
+
+    def lastMs(self):
+        """device milliseconds of the last grid build, patch and solve"""
+        ms = np.zeros(3, np.float32)
+        check(lib().rolo_ground_last_ms(self._h, ms.ctypes.data_as(C.POINTER(C.c_float))), "rolo_ground_last_ms")
+        return ms
+
+
+class PriorPoseSolver:
+    """ground_factor::PoseSolver (pose_solver.cpp:379-679) over a resident GroundModel, for whole arrays of poses, and what PriorPoseNode::HandlePose
+    (prior_pose_node.cpp:164-233) publishes from one."""
+    END_REASONS = ("converged", "max_iters")
+    FALLBACKS = ("fit", "few_hits", "few_inliers", "no_plane", "vertical", "overflow")
+
+    def __init__(self, ground: GroundModel, params: PriorPoseParams = None, groundPatchSize: float = 20.0):
+        self.ground = ground
+        self.params = params if params is not None else prior_pose_params()
+        self.patch_size = groundPatchSize
+
+    def solve(self, xyyaw) -> dict:
+        """(B x 3) poses -> arrays per field: z, roll, pitch, R (B x 3 x 3), cost, wheel_distance (B x wheels), lidar_pose (B x 6: x y z roll pitch yaw),
+        iterations, end_reason, success, status"""
+        q = np.ascontiguousarray(xyyaw, np.float64).reshape(-1, 3)
+        B = q.shape[0]
+        res = (PriorPoseResult * max(B, 1))()
+        check(lib().rolo_priorpose_solve(self.ground._h, C.byref(self.params), q.ctypes.data_as(C.POINTER(C.c_double)), B, res), "rolo_priorpose_solve")
+        W = self.params.n_wheels
+        return dict(z=np.array([r.z for r in res]), roll=np.array([r.roll for r in res]), pitch=np.array([r.pitch for r in res]),
+                    R=np.array([list(r.R) for r in res]).reshape(B, 3, 3), cost=np.array([r.cost for r in res]),
+                    wheel_distance=np.array([list(r.wheel_distance)[:W] for r in res]), lidar_pose=np.array([list(r.lidar_pose) for r in res]),
+                    iterations=np.array([r.iterations for r in res], np.int32), end_reason=np.array([r.end_reason for r in res], np.int32),
+                    success=np.array([bool(r.success) for r in res]), status=np.array([r.status for r in res], np.int32))
+
+    def fitSurface(self, xy) -> dict:
+        """test hook: FitLocalSurface (or its nearest-point fall-back) at (n x 2) double queries -> hits, inliers, fallback, nearest, point (n x 3)"""
+        q = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+        res = (PriorPoseFit * max(q.shape[0], 1))()
+        check(lib().rolo_priorpose_fit_surface(self.ground._h, C.byref(self.params), q.ctypes.data_as(C.POINTER(C.c_double)), q.shape[0], res), "rolo_priorpose_fit_surface")
+        return dict(hits=np.array([r.hits for r in res], np.int32), inliers=np.array([r.inliers for r in res], np.int32),
+                    fallback=np.array([r.fallback for r in res], np.int32), nearest=np.array([r.nearest for r in res], np.int32),
+                    point=np.array([list(r.point) for r in res]))
+
+    def handlePose(self, x: float, y: float, yaw: float):
+        """HandlePose: None unless the solve succeeds; else (initialGuess X Y Z Roll Pitch Yaw as float32, the ground patch around the lidar's x y in the lidar
+        pose's frame). The patch's transform is T_world_lidar^-1 inverted in double and cast to float, as the reference casts it."""
+        r = self.solve([[x, y, yaw]])
+        if not r["success"][0]:
+            return None
+        lp = r["lidar_pose"][0]
+        T = pose6_to_T([lp[3], lp[4], lp[5], lp[0], lp[1], lp[2]], np.float64)
+        patch = self.ground.extractPatch(lp[0], lp[1], float(self.patch_size), np.linalg.inv(T).astype(np.float32))
+        return lp.astype(np.float32), patch
