@@ -621,6 +621,22 @@ int rolo_loopicp_associate(rolo_ctx* ctx, const float* source, int n_source, con
  * rolo_keymap_loop_last_ms adds ms6[4] / ms6[5]: the last rolo_keymap_loop_cloud of slot 0 / slot 1 */
 int rolo_loopicp_last_ms(rolo_ctx* ctx, float* ms4);
 int rolo_keymap_loop_last_ms(rolo_keymap* km, float* ms6);
+/* The ground-prior association's form (performPriorAssociation, :1943-2158: one ICP per stored patch against the same ground cloud): B sources against ONE target.
+ * sources holds the clouds one after another (n_source[b] points of 4 floats each), guess16 B row-major 4 x 4 matrices or NULL, out B results. out[b] and
+ * candidate b's trace are those of rolo_loopicp_align(source b, target, params, guess b), bit for bit: the same sort and 256-point workgroups per candidate, the
+ * same sums in the same order, the same host step. What differs is the schedule: every candidate's association runs in one launch per iteration, the increment
+ * of the previous iteration is applied when that launch loads a point, and the host is waited for once per iteration for all candidates; a candidate that has left
+ * the loop gets its fitness pass in the next launch and rests after it. Launches: the largest iteration count + 1, not the sum.
+ * B <= ROLO_LOOPICP_MAX_BATCH; the target and the sum of the sources are each at most ROLO_KEYMAP_MAX_POINTS. B == 0 is ROLO_OK and touches nothing; an empty
+ * source, or an empty target, gives that candidate NO_CORRESPONDENCES. Null pointers, a negative count or sizes past the limits are ROLO_EINVAL. */
+#define ROLO_LOOPICP_MAX_BATCH 256
+int rolo_loopicp_align_batch(rolo_ctx* ctx, const float* sources, const int* n_source, int B, const float* target, int n_target, const rolo_loopicp_params* params,
+                             const float* guess16_or_null, rolo_loopicp_result* out);
+/* candidate b's associations of the last batch call, as rolo_loopicp_get_trace; b outside the last batch is ROLO_EINVAL */
+int rolo_loopicp_get_trace_batch(rolo_ctx* ctx, int b, rolo_loopicp_trace_rec* out, int cap);
+/* device time of the last batch call in milliseconds between HIP events: ms4[0] set-up (guesses, sorts, tree, tables), [1] all iterations with the fitness passes,
+ * [2] 0, [3] the whole call */
+int rolo_loopicp_batch_last_ms(rolo_ctx* ctx, float* ms4);
 
 /* ---- back end: the global map (publishGlobalMap, src/backMapping.cpp:1611-1665; saveGlobalPCDs' cloudGlobal.pcd, :1546-1557) --------------------------
  * rolo_keymap_global_map: for every listed key frame, in list order and with repeats, its corner and then its surface cloud moved by the frame's current pose

@@ -212,6 +212,9 @@ SYMBOLS = {
     "rolo_keymap_loop_trace": (C.c_int, [vp, C.POINTER(LoopIcpTraceRec), C.c_int]),
     "rolo_loopicp_associate": (C.c_int, [vp, fp, C.c_int, fp, C.c_int, fp, C.c_double, ip, fp]),
     "rolo_loopicp_last_ms": (C.c_int, [vp, fp]),
+    "rolo_loopicp_align_batch": (C.c_int, [vp, fp, C.POINTER(C.c_int), C.c_int, fp, C.c_int, C.POINTER(LoopIcpParams), fp, C.POINTER(LoopIcpResult)]),
+    "rolo_loopicp_get_trace_batch": (C.c_int, [vp, C.c_int, C.POINTER(LoopIcpTraceRec), C.c_int]),
+    "rolo_loopicp_batch_last_ms": (C.c_int, [vp, fp]),
     "rolo_pgo_create": (C.c_int, [C.c_int, C.POINTER(vp)]),
     "rolo_pgo_destroy": (None, [vp]),
     "rolo_pgo_default_params": (None, [C.POINTER(PgoParams)]),

@@ -156,6 +156,35 @@ class LoopIcp:
         check(lib().rolo_loopicp_last_ms(self.reg._h, ms.ctypes.data_as(C.POINTER(C.c_float))), "rolo_loopicp_last_ms")
         return ms
 
+    MAX_BATCH = 256   # ROLO_LOOPICP_MAX_BATCH
+
+    def alignBatch(self, sources, target, params: LoopIcpParams = None, guesses=None) -> list:
+        """align(sources[b], target, params, guesses[b]) for every b, bit for bit, with all candidates' associations in one launch per iteration"""
+        fp = C.POINTER(C.c_float)
+        srcs = [np.ascontiguousarray(x, np.float32).reshape(-1, 4) for x in sources]
+        B = len(srcs)
+        tgt = np.ascontiguousarray(target, np.float32).reshape(-1, 4)
+        cat = np.ascontiguousarray(np.concatenate(srcs, 0) if B else np.zeros((0, 4), np.float32))
+        ns = np.array([s.shape[0] for s in srcs], np.int32)
+        g = None
+        if guesses is not None:
+            g = np.ascontiguousarray(guesses, np.float32).reshape(B, 16)
+        res = (LoopIcpResult * max(B, 1))()
+        check(lib().rolo_loopicp_align_batch(self.reg._h, cat.ctypes.data_as(fp), ns.ctypes.data_as(C.POINTER(C.c_int)), B, tgt.ctypes.data_as(fp), tgt.shape[0],
+                                             C.byref(params if params is not None else loop_icp_params()), g.ctypes.data_as(fp) if g is not None else None, res),
+              "rolo_loopicp_align_batch")
+        return [_icp_result(res[b]) for b in range(B)]
+
+    def traceBatch(self, b: int):
+        """candidate b's records of the last alignBatch, as trace()"""
+        return _icp_trace(lambda h, out, cap: lib().rolo_loopicp_get_trace_batch(h, b, out, cap), self.reg._h)
+
+    def batchLastMs(self):
+        """device milliseconds of the last alignBatch: set-up, iterations with the fitness passes, 0, whole call"""
+        ms = np.zeros(4, np.float32)
+        check(lib().rolo_loopicp_batch_last_ms(self.reg._h, ms.ctypes.data_as(C.POINTER(C.c_float))), "rolo_loopicp_batch_last_ms")
+        return ms
+
 
 class KeyFrameMap:
     """cornerCloudKeyFrames / surfCloudKeyFrames / cloudKeyPoses6D on the device, with extractSurroundingKeyFrames and downsampleCurrentScan"""
@@ -568,6 +597,12 @@ class PoseGraph:
         Z = np.linalg.inv(np.asarray(pose_from, np.float64)) @ np.asarray(pose_to, np.float64)
         self.addBetween(int(cur), int(pre), Z, np.full(6, float(noise)), cauchy=getattr(loop, "robust", None))
 
+    def addPriorFactor(self, f):
+        """addPriorFactor (:1266-1284) for one PriorFactor of GroundPriorCloser: between(linked, current, poseFrom^-1 poseTo, its six variances), plain noise"""
+        linked, current, pose_from, pose_to, variances = f
+        Z = np.linalg.inv(np.asarray(pose_from, np.float64)) @ np.asarray(pose_to, np.float64)
+        self.addBetween(int(linked), int(current), Z, np.asarray(variances, np.float64))
+
     def optimize(self, params: PgoParams = None) -> dict:
         res = PgoResult()
         check(lib().rolo_pgo_optimize(self._h, C.byref(params if params is not None else pgo_params()), C.byref(res)), "rolo_pgo_optimize")
@@ -782,3 +817,276 @@ class PriorPoseSolver:
         T = pose6_to_T([lp[3], lp[4], lp[5], lp[0], lp[1], lp[2]], np.float64)
         patch = self.ground.extractPatch(lp[0], lp[1], float(self.patch_size), np.linalg.inv(T).astype(np.float32))
         return lp.astype(np.float32), patch
+
+
+# ---- the ground prior's association (performPriorAssociation, src/backMapping.cpp:1943-2158) ------------------------------------------------------------------
+_f32 = np.float32
+
+
+def _mul34(a, b):
+    """Affine3f a * b in float32: linear = La Lb, translation = La tb + ta (each entry a0 b0 + a1 b1 + a2 b2, left to right)"""
+    a, b = np.asarray(a, _f32), np.asarray(b, _f32)
+    o = np.eye(4, dtype=_f32)
+    for i in range(3):
+        for j in range(4):
+            x = a[i, 0] * b[0, j]
+            x = _f32(x + a[i, 1] * b[1, j])
+            x = _f32(x + a[i, 2] * b[2, j])
+            o[i, j] = _f32(x + a[i, 3]) if j == 3 else x
+    return o
+
+
+def _inv34(a):
+    """Affine3f::inverse() in float32: the 3 x 3 inverse by cofactors over the determinant (Eigen's compute_inverse<3>), translation = -(L^-1 t)"""
+    a = np.asarray(a, _f32)
+    m = a[:3, :3]
+    cof = lambda i, j: _f32(m[(i + 1) % 3, (j + 1) % 3] * m[(i + 2) % 3, (j + 2) % 3] - m[(i + 1) % 3, (j + 2) % 3] * m[(i + 2) % 3, (j + 1) % 3])
+    c0 = [cof(0, 0), cof(1, 0), cof(2, 0)]   # the first column of the inverse, before the division
+    det = _f32(_f32(m[0, 0] * c0[0] + m[1, 0] * c0[1]) + m[2, 0] * c0[2])
+    inv = _f32(1.0) / det
+    o = np.eye(4, dtype=_f32)
+    for i in range(3):
+        for j in range(3):
+            o[i, j] = cof(j, i) * inv
+    for i in range(3):
+        o[i, 3] = -_f32(_f32(o[i, 0] * a[0, 3] + o[i, 1] * a[1, 3]) + o[i, 2] * a[2, 3])
+    return o
+
+
+def _euler34(T):
+    """pcl::getTranslationAndEulerAngles in float32 -> (x, y, z, roll, pitch, yaw)"""
+    T = np.asarray(T, _f32)
+    return T[0, 3], T[1, 3], T[2, 3], np.arctan2(T[2, 1], T[2, 2]), np.arcsin(-T[2, 0]), np.arctan2(T[1, 0], T[0, 0])
+
+
+def _quat_from_R(m):
+    """Eigen::Quaternionf(Matrix3f) in float32 -> (w, x, y, z)"""
+    m = np.asarray(m, _f32)
+    t = _f32(_f32(m[0, 0] + m[1, 1]) + m[2, 2])
+    q = np.zeros(4, _f32)
+    if t > 0:
+        t = np.sqrt(_f32(t + _f32(1.0)))
+        q[0] = _f32(0.5) * t
+        t = _f32(0.5) / t
+        q[1], q[2], q[3] = (m[2, 1] - m[1, 2]) * t, (m[0, 2] - m[2, 0]) * t, (m[1, 0] - m[0, 1]) * t
+    else:
+        i = 0
+        if m[1, 1] > m[0, 0]:
+            i = 1
+        if m[2, 2] > m[i, i]:
+            i = 2
+        j, k = (i + 1) % 3, (i + 2) % 3
+        t = np.sqrt(_f32(_f32(_f32(m[i, i] - m[j, j]) - m[k, k]) + _f32(1.0)))
+        q[1 + i] = _f32(0.5) * t
+        t = _f32(0.5) / t
+        q[0] = (m[k, j] - m[j, k]) * t
+        q[1 + j] = (m[j, i] + m[i, j]) * t
+        q[1 + k] = (m[k, i] + m[i, k]) * t
+    return q
+
+
+def _quat_norm(q):
+    n = np.sqrt(_f32(_f32(_f32(q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]))
+    return (q / n).astype(_f32)
+
+
+def _quat_mul(a, b):
+    """Hamilton product in float32, (w, x, y, z)"""
+    aw, ax, ay, az = a
+    bw, bx, by, bz = b
+    return np.array([aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by, aw * by + ay * bw + az * bx - ax * bz,
+                     aw * bz + az * bw + ax * by - ay * bx], _f32)
+
+
+def _quat_axis(angle, axis):
+    """Quaternionf(AngleAxisf(angle, unit axis `axis`))"""
+    h = _f32(0.5) * _f32(angle)
+    q = np.zeros(4, _f32)
+    q[0], q[1 + axis] = np.cos(h), np.sin(h)
+    return q
+
+
+def _quat_slerp(a, t, b):
+    """Eigen's QuaternionBase::slerp in float32: the linear branch at |a . b| >= 1 - epsilon, the second weight negated for a negative dot"""
+    t = _f32(t)
+    d = _f32(_f32(_f32(a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]) + a[3] * b[3])
+    ad = np.abs(d)
+    if ad >= _f32(1.0) - np.finfo(_f32).eps:
+        s0, s1 = _f32(1.0) - t, t
+    else:
+        th = np.arccos(ad)
+        st = np.sin(th)
+        s0, s1 = np.sin(_f32(_f32(1.0) - t) * th) / st, np.sin(t * th) / st
+    if d < 0:
+        s1 = -s1
+    return (_f32(s0) * a + _f32(s1) * b).astype(_f32)
+
+
+def _quat_to_R(q):
+    """Quaternionf::toRotationMatrix in float32"""
+    w, x, y, z = (_f32(v) for v in q)
+    tx, ty, tz = _f32(2.0) * x, _f32(2.0) * y, _f32(2.0) * z
+    twx, twy, twz = tx * w, ty * w, tz * w
+    txx, txy, txz = tx * x, ty * x, tz * x
+    tyy, tyz, tzz = ty * y, tz * y, tz * z
+    one = _f32(1.0)
+    return np.array([[one - (tyy + tzz), txy - twz, txz + twy], [txy + twz, one - (txx + tzz), tyz - twx], [txz - twy, tyz + twx, one - (txx + tyy)]], _f32)
+
+
+def _wrap_abs(a):
+    """|atan2(sin a, cos a)| in float32 (:2089-2090)"""
+    a = _f32(a)
+    return np.abs(np.arctan2(np.sin(a), np.cos(a)))
+
+
+PRIOR_WEIGHT = 0.2   # priorWeight, :2067
+
+
+def prior_association_gates(linked_key_pose, current_key_pose, relative_prior_pose, T, fitness, priorRotDiffTolerance, priorTransDiffTolerance=1.0,
+                            priorFactorWeight=100.0):
+    """performPriorAssociation from the accepted ICP to the factor (:2054-2125) in float32, host only. The three poses and the ICP's T are 4 x 4 (Affine3f);
+    priorRotDiffTolerance is in RADIANS here (the reference converts its parameter on loading, utility.h:368; GroundPriorCloser takes degrees as the parameter file
+    does). Returns a dict: `rejected` is None, "z", "roll" or "pitch" (the first failing gate in the reference's order of tests); `diff` = (diff_z, diff_roll,
+    diff_pitch); `odom` / `prior` = (dx, dy, dz, roll, pitch, yaw) of tbbPrevToCur / tbbPrevToCur_prior; and, when nothing rejected, priorTrans (4 x 4 float32),
+    poseFrom, poseTo (4 x 4 float64: RzRyRx of the float Euler angles, as gtsam builds them) and variances (6 float64: s, s, 1e-6f, 1e-6f, 1e-6f, s).
+    Where Eigen takes a Transform's rotation() through an SVD (Affine mode), this takes linear(): the poses are rigid up to float rounding."""
+    linked, current, relative = (np.asarray(x, _f32).reshape(4, 4) for x in (linked_key_pose, current_key_pose, relative_prior_pose))
+    Tf = np.asarray(T, np.float64).reshape(4, 4).astype(_f32)   # getFinalTransformation().cast<double>().cast<float>()
+    prev_to_cur = _mul34(current, _inv34(linked))               # :2064
+    prev_to_cur_prior = _mul34(Tf, relative)                    # :2065
+    odom_q = _quat_norm(_quat_from_R(prev_to_cur[:3, :3]))
+    odom = _euler34(prev_to_cur)
+    prior = _euler34(prev_to_cur_prior)
+    diff_z = np.abs(_f32(odom[2] - prior[2]))
+    diff_roll = _wrap_abs(odom[3] - prior[3])
+    diff_pitch = _wrap_abs(odom[4] - prior[4])
+    out = dict(rejected=None, diff=(diff_z, diff_roll, diff_pitch), odom=odom, prior=prior)
+    rot_tol, trans_tol = _f32(priorRotDiffTolerance), _f32(priorTransDiffTolerance)
+    if diff_z > trans_tol:
+        out["rejected"] = "z"
+    elif diff_roll > rot_tol:
+        out["rejected"] = "roll"
+    elif diff_pitch > rot_tol:
+        out["rejected"] = "pitch"
+    if out["rejected"] is not None:
+        return out
+    target_q = _quat_norm(_quat_mul(_quat_mul(_quat_axis(odom[5], 2), _quat_axis(prior[4], 1)), _quat_axis(prior[3], 0)))   # Rz(odom yaw) Ry(prior pitch) Rx(prior roll)
+    blended_q = _quat_norm(_quat_slerp(odom_q, PRIOR_WEIGHT, target_q))
+    prior_trans = np.eye(4, dtype=_f32)
+    prior_trans[:3, :3] = _quat_to_R(blended_q)
+    prior_trans[:3, 3] = prev_to_cur[:3, 3]   # the odometry's translation: the z blend is commented out (:2071)
+    x, y, z, r, p, yw = _euler34(linked)
+    pose_from = pose6_to_T([float(r), float(p), float(yw), float(x), float(y), float(z)], np.float64)
+    x, y, z, r, p, yw = _euler34(_mul34(prior_trans, linked))   # :2117
+    pose_to = pose6_to_T([float(r), float(p), float(yw), float(x), float(y), float(z)], np.float64)
+    s = max(_f32(fitness), _f32(1e-6)) * _f32(priorFactorWeight)
+    small = np.float64(_f32(1e-6))
+    out.update(priorTrans=prior_trans, poseFrom=pose_from, poseTo=pose_to, variances=np.array([s, s, small, small, small, s], np.float64))
+    return out
+
+
+class PriorFactor(tuple):
+    """(linked_key, current_key, poseFrom 4 x 4, poseTo 4 x 4, variances6) as GroundPriorCloser returns it: the constraint is poseFrom.between(poseTo) from the
+    linked key pose to the current one. PoseGraph.addPriorFactor takes it as it is."""
+    def __new__(cls, linked_key, current_key, poseFrom, poseTo, variances6):
+        return super().__new__(cls, (linked_key, current_key, poseFrom, poseTo, variances6))
+
+    linked_key = property(lambda self: self[0])
+    current_key = property(lambda self: self[1])
+    poseFrom = property(lambda self: self[2])
+    poseTo = property(lambda self: self[3])
+    variances = property(lambda self: self[4])
+
+
+class GroundPriorCloser:
+    """priorInfoHandler (:459-513) and performPriorAssociation (:1943-2158) over a key map's poses: the history of (prior pose, ground patch) entries, the
+    candidates near the last key pose, their ICPs against the laser's ground cloud, `batch` at a time through LoopIcp.alignBatch, the gates and the factor.
+    The history is never pruned, as in the reference (priorFilter is commented out there). Not here: the ROS thread and its rate, visualizePrior, priorFilter."""
+
+    def __init__(self, keymap, icp: LoopIcp = None, groundPatchSize: float = 2.0, nearPriorRadius: float = 1.0, priorFitnessScore: float = 0.01,
+                 priorRotDiffTolerance: float = 5.0, priorTransDiffTolerance: float = 1.0, priorFactorWeight: float = 100.0, priorSyncedInterval: float = 0.0,
+                 batch: int = 8):
+        """priorRotDiffTolerance in degrees, as the parameter file has it. keymap: anything with `poses` (pose6 per key frame) and `times`; icp: a LoopIcp
+        (made on first use when None). batch: candidates per alignBatch call; 1 runs them one launch set each. The default of 8 is from profiles/r18/priorassoc.json: a
+        chunk of eight costs about what two to three ICPs cost one after another; raise it where long runs of rejections are the rule."""
+        assert 1 <= batch <= LoopIcp.MAX_BATCH
+        self.km, self.icp, self._own_icp = keymap, icp, False
+        self.patch_size, self.radius, self.fitness_score = _f32(groundPatchSize), _f32(nearPriorRadius), _f32(priorFitnessScore)
+        self.rot_tol = _f32(_f32(priorRotDiffTolerance) * np.pi / _f32(180.0))   # utility.h:368 (float * double / float -> float)
+        self.trans_tol, self.weight, self.synced_interval = _f32(priorTransDiffTolerance), _f32(priorFactorWeight), _f32(priorSyncedInterval)
+        self.batch = int(batch)
+        self.priorPosePatchHistory, self.priorTimeKeyQueue = [], []
+        self.ground_cloud = np.zeros((0, 4), np.float32)
+        self.priorVisContainer = {}
+        # per candidate the last performPriorAssociation aligned, in history order: dict(entry, linked_key, icp, rejected, gates); rejected is None (the factor's),
+        # "fitness", "z", "roll", "pitch", or "unused" for what shared the accepted candidate's chunk behind it and was never judged
+        self.last = []
+
+    def close(self):
+        if self._own_icp and self.icp is not None:
+            self.icp.close()
+            self.icp = None
+
+    def priorInfoHandler(self, msg_time: float, prior_pose6, patch) -> bool:
+        """prior_pose6: initialGuess roll, pitch, yaw, x, y, z. True when the entry was stored"""
+        if len(self.km.poses) == 0:
+            return False
+        latest_time, latest_id = self.km.times[-1], len(self.km.poses) - 1
+        if latest_id <= 9 or abs(float(msg_time) - latest_time) >= 1e-2:
+            return False
+        if self.priorTimeKeyQueue and self.synced_interval > 0.0:
+            if float(msg_time) - self.priorTimeKeyQueue[-1][0] < float(self.synced_interval):
+                return False
+        pose = np.asarray(prior_pose6, np.float32).reshape(6).astype(np.float64)   # priorPoseCur is float[6]
+        self.priorPosePatchHistory.append((pose, np.ascontiguousarray(patch, np.float32).reshape(-1, 4).copy()))
+        self.priorTimeKeyQueue.append((float(msg_time), latest_id))
+        return True
+
+    def setGroundCloud(self, patch):
+        """GroundCloudFromlaser (groundMapHandler): the ICPs' target, e.g. GroundModel.extractPatch(0, 0, groundPatchSize)"""
+        self.ground_cloud = np.ascontiguousarray(patch, np.float32).reshape(-1, 4).copy()
+
+    def candidates(self):
+        """the history entries the reference would run an ICP for, in order: (entry index, linked key, linked pose, relative prior pose), all float32 4 x 4"""
+        out = []
+        if len(self.km.poses) == 0:
+            return out
+        current = pose6_to_T(self.km.poses[-1])
+        for e, ((pose, patch), (_, linked_id)) in enumerate(zip(self.priorPosePatchHistory, self.priorTimeKeyQueue)):
+            linked = pose6_to_T(self.km.poses[linked_id])
+            relative = pose6_to_T(pose.astype(np.float32))   # pcl::getTransformation takes floats
+            g = _mul34(linked, relative)
+            dx, dy = _f32(g[0, 3] - current[0, 3]), _f32(g[1, 3] - current[1, 3])
+            dist = float(np.sqrt(_f32(dx * dx + dy * dy)))
+            if dist < float(self.radius) and patch.shape[0] > 0 and self.ground_cloud.shape[0] > 0:
+                out.append((e, linked_id, linked, relative))
+        return out
+
+    def performPriorAssociation(self):
+        self.last = []
+        if len(self.km.poses) == 0 or not self.priorPosePatchHistory:
+            return None
+        if self.icp is None:
+            self.icp, self._own_icp = LoopIcp(), True
+        current_id = len(self.km.poses) - 1
+        current = pose6_to_T(self.km.poses[-1])
+        cands = self.candidates()
+        params = loop_icp_params(float(self.patch_size), max_iterations=100, transformation_epsilon=1e-6, euclidean_fitness_epsilon=1e-6)
+        for c0 in range(0, len(cands), self.batch):
+            chunk = cands[c0:c0 + self.batch]
+            results = self.icp.alignBatch([self.priorPosePatchHistory[e][1] for e, _, _, _ in chunk], self.ground_cloud, params)
+            for k, ((e, linked_id, linked, relative), res) in enumerate(zip(chunk, results)):
+                rec = dict(entry=e, linked_key=linked_id, icp=res, rejected=None, gates=None)
+                self.last.append(rec)
+                if not res["converged"] or res["fitness"] > float(self.fitness_score):   # :2048
+                    rec["rejected"] = "fitness"
+                    continue
+                g = prior_association_gates(linked, current, relative, res["T"], res["fitness"], self.rot_tol, self.trans_tol, self.weight)
+                rec["gates"], rec["rejected"] = g, g["rejected"]
+                if g["rejected"] is not None:
+                    continue
+                self.priorVisContainer[current_id] = (linked_id, self.priorPosePatchHistory[e][0].astype(np.float32))   # :2142
+                # "Matching only one prior at a time" (:2145): what the chunk aligned behind it is never judged
+                self.last += [dict(entry=e2, linked_key=l2, icp=r2, rejected="unused", gates=None) for (e2, l2, _, _), r2 in zip(chunk[k + 1:], results[k + 1:])]
+                return PriorFactor(linked_id, current_id, g["poseFrom"], g["poseTo"], g["variances"])
+        return None

@@ -1,4 +1,5 @@
-// Device-side row helpers of the back end (scan2map.hip, submap.hip, loopicp.hip): the fixed-order sum of per-workgroup rows and the float row transform.
+// Device-side row helpers of the back end (scan2map.hip, submap.hip, loopicp.hip): the fixed-order sum of per-workgroup rows, its segmented form and the float
+// row transform.
 #pragma once
 #include "dev_math.hpp"
 
@@ -29,6 +30,30 @@ __global__ __launch_bounds__(256) void sum_rows(const double* __restrict__ parti
 #pragma unroll
     for (int k = 0; k < 8; k++) t += part[k][threadIdx.x];
     out[threadIdx.x] = t;
+  }
+}
+
+// sum_rows<NV, 1> once per segment in one launch: workgroup g adds rows [seg[g].x, seg[g].x + seg[g].y) in exactly that order into out + g * NV (pinned host
+// memory). A segment whose skip word (skip[g * skip_stride]) equals skip_value is neither read nor written.
+template <int NV>
+__global__ __launch_bounds__(256) void sum_rows_segmented(const double* __restrict__ partials, const int2* __restrict__ seg, const int* __restrict__ skip, int skip_stride,
+                                                          int skip_value, double* __restrict__ out) {
+  __shared__ double part[8][32];
+  const int g = blockIdx.x;
+  if (skip[(size_t)g * skip_stride] == skip_value) return;   // (workgroup-uniform)
+  const int2 sg = seg[g];
+  const double* __restrict__ rows = partials + (size_t)sg.x * NV;
+  const int v = threadIdx.x & 31, q = threadIdx.x >> 5;
+  double s = 0;
+  if (v < NV)
+    for (int b = q; b < sg.y; b += 8) s += rows[(size_t)b * NV + v];
+  part[q][v] = s;
+  __syncthreads();
+  if (threadIdx.x < NV) {
+    double t = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) t += part[k][threadIdx.x];
+    out[(size_t)g * NV + threadIdx.x] = t;
   }
 }
 

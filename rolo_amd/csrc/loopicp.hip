@@ -11,11 +11,18 @@
 // workgroup; sum_rows (dev_rows.hpp) adds the workgroups' rows in a fixed order into pinned host memory (one 136-byte read-back per iteration, the precedent of scan2map.hip).
 // The 3 x 3 SVD and the convergence tests run on the host in double; icp_transform_kernel (transform12) multiplies the resident source by the float increment.
 // The tree and the walk live in a registration context (its stream, its builder); the scratch hangs off that context, only grows and is freed with it.
+//
+// The batched form (rolo_loopicp_align_batch: the ground prior's association, performPriorAssociation :1943-2158, one ICP per stored patch near the current key
+// pose, all against the same ground patch): patch-sized clouds leave most of the device idle and pay the per-iteration launches and the host exchange once per
+// candidate and iteration. There every candidate owns whole workgroups of one `cur`, ONE launch of icp_assoc_batch_kernel per iteration serves all of them — it
+// applies the previous iteration's increment when it loads a point, so no transform launch — sum_rows_segmented adds each candidate's rows, and the host waits
+// once per iteration for the batch and runs the single form's step (loop_host_step) per candidate. Each candidate's bits are the single form's.
 #include "keymap.hpp"
 #include "knn_packet.hpp"
 #include "dev_rows.hpp"
 #include <cfloat>
 #include <climits>
+#include <cstddef>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -41,69 +48,56 @@ struct IcpArgs {
 
 ROLO_DEV unsigned long long icp_key(float d2, int idx) { return ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)idx; }
 
-__global__ __launch_bounds__(ICP_THREADS) void icp_assoc_kernel(IcpArgs A) {
-  __shared__ int stk_[ICP_THREADS / 64][WALK_STACK];
-  __shared__ double red[ICP_THREADS / 64][ICP_NV];
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int j = blockIdx.x * ICP_THREADS + threadIdx.x;
-  float4 qs = make_float4(0.f, 0.f, 0.f, __int_as_float(INT_MAX));
-  if (j < A.n_sorted) qs = A.cur[j];
-  const int qidx = __float_as_int(qs.w);
-  const bool active = qidx != INT_MAX;
-  const float4 q = make_float4(active ? qs.x : 0.f, active ? qs.y : 0.f, active ? qs.z : 0.f, 0.f);
+// one wavefront's walk of the target's tree for its 64 queries: the best key per lane, started at the cap
+ROLO_DEV unsigned long long icp_walk(const float4* __restrict__ sorted, const float4* __restrict__ boxes, int P, int n_leaves, float4 q, bool active, float cap2, lds_int* stk) {
   // a real candidate's index is below INT_MAX: a pair at exactly the cap sorts below this key and is kept; an idle lane accepts nothing
-  unsigned long long best = active ? icp_key(A.cap2, INT_MAX) : 0ull;
-  float bd = active ? A.cap2 : -1.0f;
-  {
-    const float4* __restrict__ sorted = A.tsorted;
-    const float4* __restrict__ boxes = A.tboxes;
-    const int P = A.P, n_leaves = A.n_leaves;
-    lds_int* stk = (lds_int*)&stk_[wv][0];
-    int sp = 0, h = 1;
-    while (true) {   // (no store ahead of or inside this loop: the node and leaf fetches stay scalar, knn_packet.hpp's clobber rule)
-      h = __builtin_amdgcn_readfirstlane(h);
-      if (h < P) {
-        float4 llo, lhi, rlo, rhi;
-        sload_node(boxes + 4 * (size_t)h, llo, lhi, rlo, rhi);
-        const box_f2 bd2 = box_d2_pair(llo, lhi, rlo, rhi, q);
-        const float bl = bd2[0], br = bd2[1];
-        const bool okl = (bl <= bd) && (bl < INFINITY), okr = (br <= bd) && (br < INFINITY);   // "<=": an equal distance may hide a smaller index
-        const unsigned long long ml = __ballot(okl), mr = __ballot(okr);
-        if (ml != 0ull && mr != 0ull) {
-          const unsigned long long pref = __ballot((okl || okr) && (bl <= br));
-          const bool left_first = 2 * __popcll(pref) >= __popcll(ml | mr);
-          if (sp < WALK_STACK) { stk[sp] = left_first ? 2 * h + 1 : 2 * h; sp++; }
-          h = left_first ? 2 * h : 2 * h + 1;
-          continue;
-        }
-        if (ml != 0ull) { h = 2 * h; continue; }
-        if (mr != 0ull) { h = 2 * h + 1; continue; }
-      } else if (h - P < n_leaves) {
-        float4 pts[KNN_LEAF];
-        sload_leaf(sorted + KNN_LEAF * (size_t)(h - P), pts);
-#pragma unroll
-        for (int u = 0; u < KNN_LEAF; u++) {
-          const float4 c = pts[u];
-          const float dx = q.x - c.x, dy = q.y - c.y, dz = q.z - c.z;
-          const float cd = ((dx * dx) + (dy * dy)) + (dz * dz);   // (-ffp-contract=off)
-          const unsigned long long ck = icp_key(cd, __float_as_int(c.w));   // (a padding point: +infinity, INT_MAX — never below the start key)
-          best = ck < best ? ck : best;
-        }
-        bd = active ? __uint_as_float((unsigned)(best >> 32)) : -1.0f;
+  unsigned long long best = active ? icp_key(cap2, INT_MAX) : 0ull;
+  float bd = active ? cap2 : -1.0f;
+  int sp = 0, h = 1;
+  while (true) {   // (no store ahead of or inside this loop: the node and leaf fetches stay scalar, knn_packet.hpp's clobber rule)
+    h = __builtin_amdgcn_readfirstlane(h);
+    if (h < P) {
+      float4 llo, lhi, rlo, rhi;
+      sload_node(boxes + 4 * (size_t)h, llo, lhi, rlo, rhi);
+      const box_f2 bd2 = box_d2_pair(llo, lhi, rlo, rhi, q);
+      const float bl = bd2[0], br = bd2[1];
+      const bool okl = (bl <= bd) && (bl < INFINITY), okr = (br <= bd) && (br < INFINITY);   // "<=": an equal distance may hide a smaller index
+      const unsigned long long ml = __ballot(okl), mr = __ballot(okr);
+      if (ml != 0ull && mr != 0ull) {
+        const unsigned long long pref = __ballot((okl || okr) && (bl <= br));
+        const bool left_first = 2 * __popcll(pref) >= __popcll(ml | mr);
+        if (sp < WALK_STACK) { stk[sp] = left_first ? 2 * h + 1 : 2 * h; sp++; }
+        h = left_first ? 2 * h : 2 * h + 1;
+        continue;
       }
-      if (sp == 0) break;
-      sp--;
-      h = stk[sp];
+      if (ml != 0ull) { h = 2 * h; continue; }
+      if (mr != 0ull) { h = 2 * h + 1; continue; }
+    } else if (h - P < n_leaves) {
+      float4 pts[KNN_LEAF];
+      sload_leaf(sorted + KNN_LEAF * (size_t)(h - P), pts);
+#pragma unroll
+      for (int u = 0; u < KNN_LEAF; u++) {
+        const float4 c = pts[u];
+        const float dx = q.x - c.x, dy = q.y - c.y, dz = q.z - c.z;
+        const float cd = ((dx * dx) + (dy * dy)) + (dz * dz);   // (-ffp-contract=off)
+        const unsigned long long ck = icp_key(cd, __float_as_int(c.w));   // (a padding point: +infinity, INT_MAX — never below the start key)
+        best = ck < best ? ck : best;
+      }
+      bd = active ? __uint_as_float((unsigned)(best >> 32)) : -1.0f;
     }
+    if (sp == 0) break;
+    sp--;
+    h = stk[sp];
   }
-  const int ti = (int)(unsigned)(best & 0xffffffffull);
-  const bool kept = active && ti != INT_MAX;
-  const float d2 = __uint_as_float((unsigned)(best >> 32));
-  double acc[ICP_NV];
+  return best;
+}
+
+// the 17 terms of one lane's pair (zeros when it kept none)
+ROLO_DEV void icp_pair_terms(bool kept, float4 qs, float d2, int ti, const float4* __restrict__ txyz, double* acc) {
 #pragma unroll
   for (int v = 0; v < ICP_NV; v++) acc[v] = 0.0;
   if (kept) {
-    const float4 t = A.txyz[ti];
+    const float4 t = txyz[ti];
     const double p[3] = {(double)qs.x, (double)qs.y, (double)qs.z}, qq[3] = {(double)t.x, (double)t.y, (double)t.z};
     acc[0] = 1.0; acc[1] = (double)d2;
 #pragma unroll
@@ -113,8 +107,10 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_assoc_kernel(IcpArgs A) {
       for (int c = 0; c < 3; c++) acc[8 + 3 * r + c] = p[r] * qq[c];
     }
   }
-  if (active && A.idx_out) { A.idx_out[qidx] = kept ? ti : -1; A.d2_out[qidx] = kept ? d2 : INFINITY; }
-  // workgroup sum, fixed order
+}
+
+// workgroup sum, fixed order, into this workgroup's row
+ROLO_DEV void icp_block_row(const double* acc, double (*red)[ICP_NV], int wv, int lane, double* __restrict__ row) {
 #pragma unroll
   for (int v = 0; v < ICP_NV; v++) {
     double x = acc[v];
@@ -127,8 +123,85 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_assoc_kernel(IcpArgs A) {
     double s = 0;
 #pragma unroll
     for (int w = 0; w < ICP_THREADS / 64; w++) s += red[w][threadIdx.x];
-    A.partials[(size_t)blockIdx.x * ICP_NV + threadIdx.x] = s;
+    row[threadIdx.x] = s;
   }
+}
+
+__global__ __launch_bounds__(ICP_THREADS) void icp_assoc_kernel(IcpArgs A) {
+  __shared__ int stk_[ICP_THREADS / 64][WALK_STACK];
+  __shared__ double red[ICP_THREADS / 64][ICP_NV];
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int j = blockIdx.x * ICP_THREADS + threadIdx.x;
+  float4 qs = make_float4(0.f, 0.f, 0.f, __int_as_float(INT_MAX));
+  if (j < A.n_sorted) qs = A.cur[j];
+  const int qidx = __float_as_int(qs.w);
+  const bool active = qidx != INT_MAX;
+  const float4 q = make_float4(active ? qs.x : 0.f, active ? qs.y : 0.f, active ? qs.z : 0.f, 0.f);
+  const unsigned long long best = icp_walk(A.tsorted, A.tboxes, A.P, A.n_leaves, q, active, A.cap2, (lds_int*)&stk_[wv][0]);
+  const int ti = (int)(unsigned)(best & 0xffffffffull);
+  const bool kept = active && ti != INT_MAX;
+  const float d2 = __uint_as_float((unsigned)(best >> 32));
+  double acc[ICP_NV];
+  icp_pair_terms(kept, qs, d2, ti, A.txyz, acc);
+  if (active && A.idx_out) { A.idx_out[qidx] = kept ? ti : -1; A.d2_out[qidx] = kept ? d2 : INFINITY; }
+  icp_block_row(acc, red, wv, lane, A.partials + (size_t)blockIdx.x * ICP_NV);
+}
+
+// ---- the batched form: B sources against one target, every candidate's association in ONE launch per iteration ------------------------------------
+// Candidate b owns the workgroups [seg[b].x, seg[b].x + seg[b].y) of `cur` (its sorted source as loop_setup leaves it, padded to whole workgroups with
+// INT_MAX slots: the 256-point partition of the single form); a workgroup reads its candidate's control record, which the host rewrites between launches.
+constexpr int ICP_MODE_ITERATE = 0, ICP_MODE_FITNESS = 1, ICP_MODE_IDLE = 2;   // the kernel treats ITERATE and FITNESS alike: they differ in cap2 and on the host
+constexpr int ICP_MODE_MOVE = 4;                                              // bit: apply `inc` on load (absent in a candidate's first launch: the points stay as they are, signed zeros too)
+struct IcpCtl { float inc[12]; float cap2; int mode; };
+constexpr int ICP_CTL_WORDS = (int)(sizeof(IcpCtl) / sizeof(int)), ICP_CTL_MODE_WORD = 13;
+static_assert(sizeof(IcpCtl) == 56 && offsetof(IcpCtl, mode) == 4 * ICP_CTL_MODE_WORD, "control record layout");
+
+struct IcpBatchArgs {
+  float4* cur;             // all candidates' segments
+  const int* blk_cand;     // workgroup -> candidate
+  const IcpCtl* ctl;       // per candidate
+  const float4* tsorted;
+  const float4* tboxes;
+  const float4* txyz;
+  int P, n_leaves;
+  double* partials;        // grid x ICP_NV
+};
+
+__global__ __launch_bounds__(ICP_THREADS) void icp_assoc_batch_kernel(IcpBatchArgs A) {
+  __shared__ int stk_[ICP_THREADS / 64][WALK_STACK];
+  __shared__ double red[ICP_THREADS / 64][ICP_NV];
+  const int b = A.blk_cand[blockIdx.x];
+  const IcpCtl* __restrict__ ctl = A.ctl + b;
+  const int mode = ctl->mode;
+  if ((mode & 3) == ICP_MODE_IDLE) return;   // (workgroup-uniform)
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const size_t j = (size_t)blockIdx.x * ICP_THREADS + threadIdx.x;   // (segments are whole workgroups: always inside `cur`)
+  float4 qs = A.cur[j];
+  const int qidx = __float_as_int(qs.w);
+  const bool active = qidx != INT_MAX;
+  if (mode & ICP_MODE_MOVE) {   // the increment of the previous iteration, in place of a launch of icp_transform_kernel<true>
+    float T[12];
+#pragma unroll
+    for (int i = 0; i < 12; i++) T[i] = ctl->inc[i];
+    const float4 m = transform12(T, qs);
+    if (active) qs = m;
+  }
+  const float4 q = make_float4(active ? qs.x : 0.f, active ? qs.y : 0.f, active ? qs.z : 0.f, 0.f);
+  const unsigned long long best = icp_walk(A.tsorted, A.tboxes, A.P, A.n_leaves, q, active, ctl->cap2, (lds_int*)&stk_[wv][0]);
+  if (active && (mode & ICP_MODE_MOVE)) A.cur[j] = qs;   // (after the walk: the clobber rule)
+  const int ti = (int)(unsigned)(best & 0xffffffffull);
+  const bool kept = active && ti != INT_MAX;
+  const float d2 = __uint_as_float((unsigned)(best >> 32));
+  double acc[ICP_NV];
+  icp_pair_terms(kept, qs, d2, ti, A.txyz, acc);
+  icp_block_row(acc, red, wv, lane, A.partials + (size_t)blockIdx.x * ICP_NV);
+}
+
+// a candidate's sorted source into its segment of `cur`; the slots behind it, up to whole workgroups, become padding
+__global__ __launch_bounds__(256) void icp_segment_kernel(const float4* __restrict__ sorted, int n_sorted, float4* __restrict__ seg, int n_seg) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_seg) return;
+  seg[i] = i < n_sorted ? sorted[i] : make_float4(0.f, 0.f, 0.f, __int_as_float(INT_MAX));
 }
 
 struct Rows12 { float T[12]; };
@@ -230,6 +303,16 @@ struct LoopIcp {
   float ms[4] = {0.f, 0.f, 0.f, 0.f};
   DevStore store{nullptr, "loop ICP"};   // grows the buffers above (nothing is kept across a growth: no stream); what they outgrew is freed with the context
   std::vector<rolo_loopicp_trace_rec> trace;
+  // the batched form (loop_align_batch)
+  float4* bsrc = nullptr; size_t bsrc_cap = 0;       // the concatenated sources in the caller's order
+  int* blk_cand = nullptr; size_t blk_cand_cap = 0;
+  int2* seg = nullptr; size_t seg_cap = 0;
+  IcpCtl* ctl = nullptr; size_t ctl_cap = 0;
+  IcpCtl* h_ctl = nullptr; size_t h_ctl_cap = 0;     // pinned: the control table as the next launch reads it
+  double* h_bsum = nullptr; size_t h_bsum_cap = 0;   // pinned: B x 17 sums, written by sum_rows_segmented
+  hipEvent_t bev[3] = {nullptr, nullptr, nullptr};
+  float bms[4] = {0.f, 0.f, 0.f, 0.f};
+  std::vector<std::vector<rolo_loopicp_trace_rec>> btrace;
 };
 
 int loop_state(rolo_ctx* c, LoopIcp** out) {
@@ -240,6 +323,7 @@ int loop_state(rolo_ctx* c, LoopIcp** out) {
     HIPCHK(hipSetDevice(ctx_device(c)));
     HIPCHK(hipHostMalloc((void**)&W->h_sum, sizeof(double) * ICP_NV));
     for (int i = 0; i < 4; i++) HIPCHK(hipEventCreate(&W->ev[i]));
+    for (int i = 0; i < 3; i++) HIPCHK(hipEventCreate(&W->bev[i]));
   }
   *out = W;
   return ROLO_OK;
@@ -250,8 +334,8 @@ bool is_identity16(const float* T) {
   return true;
 }
 
-// the moved source sorted along the target's curve and the target's tree; d_src / d_tgt: device clouds of float4
-int loop_setup(rolo_ctx* c, LoopIcp* W, const float4* d_src, int ns, const float4* d_tgt, int nt, const float* T16, IcpArgs* A, int* grid) {
+// the target's tree (pair->c[0]) and the source, moved by T16, sorted along the same curve (pair->c[1]); d_src / d_tgt: device clouds of float4
+int loop_sorted(rolo_ctx* c, LoopIcp* W, const float4* d_src, int ns, const float4* d_tgt, int nt, const float* T16, KnnPair* pair) {
   hipStream_t s = ctx_stream(c);
   int rc;
   const float4* moved = d_src;
@@ -262,8 +346,16 @@ int loop_setup(rolo_ctx* c, LoopIcp* W, const float4* d_src, int ns, const float
     HIPCHK(hipGetLastError());
     moved = W->srcg;
   }
+  *pair = KnnPair{};
+  return ctx_build_map_trees(c, reinterpret_cast<const float*>(d_tgt), nt, reinterpret_cast<const float*>(moved), ns, 4, pair, true);
+}
+
+// the moved source sorted along the target's curve, in W->cur, and the target's tree
+int loop_setup(rolo_ctx* c, LoopIcp* W, const float4* d_src, int ns, const float4* d_tgt, int nt, const float* T16, IcpArgs* A, int* grid) {
+  hipStream_t s = ctx_stream(c);
+  int rc;
   KnnPair pair{};
-  if ((rc = ctx_build_map_trees(c, reinterpret_cast<const float*>(d_tgt), nt, reinterpret_cast<const float*>(moved), ns, 4, &pair, true))) return rc;
+  if ((rc = loop_sorted(c, W, d_src, ns, d_tgt, nt, T16, &pair))) return rc;
   const int n_sorted = pair.c[1].n_sorted;
   *grid = (n_sorted + ICP_THREADS - 1) / ICP_THREADS;
   if ((rc = W->store.grow(W->cur, W->cur_cap, (size_t)n_sorted))) return rc;
@@ -297,6 +389,47 @@ void matmul4f(const float* a, const float* b, float* o) {   // o = a b, each ent
   std::memcpy(o, r, sizeof(r));
 }
 
+// The host's share of one iteration, from the 17 sums of its association: the trace record, the increment (have_inc: the source is to be moved by it), the pose
+// and the exit tests in pcl's order. True when the alignment has ended (res.state says how).
+bool loop_host_step(const double* h, const rolo_loopicp_params* P, double rot_thr, rolo_loopicp_result& res, double& prev, std::vector<rolo_loopicp_trace_rec>& trace,
+                    float* inc /* 16 */, bool* have_inc) {
+  *have_inc = false;
+  rolo_loopicp_trace_rec tr{};
+  const int n = (int)(h[0] + 0.5);
+  tr.n = n; tr.mse = n > 0 ? h[1] / n : 0.0;
+  std::memcpy(tr.sums, h, sizeof(tr.sums));
+  res.n_last = n;
+  if (n < P->min_correspondences || n < 1) { trace.push_back(tr); res.state = ROLO_ICP_NO_CORRESPONDENCES; res.converged = 0; return true; }
+  double R[9], t[3];
+  umeyama(h, R, t);
+  const float incv[16] = {(float)R[0], (float)R[1], (float)R[2], (float)t[0], (float)R[3], (float)R[4], (float)R[5], (float)t[1],
+                          (float)R[6], (float)R[7], (float)R[8], (float)t[2], 0.f, 0.f, 0.f, 1.f};
+  std::memcpy(inc, incv, sizeof(incv));
+  std::memcpy(tr.increment, inc, sizeof(incv));
+  trace.push_back(tr);
+  *have_inc = true;
+  matmul4f(inc, res.T, res.T);
+  res.iterations++;
+  const double cosa = 0.5 * ((double)inc[0] + (double)inc[5] + (double)inc[10] - 1.0);
+  const double tsq = (double)inc[3] * (double)inc[3] + (double)inc[7] * (double)inc[7] + (double)inc[11] * (double)inc[11];
+  const double mse = tr.mse;
+  if (res.iterations >= P->max_iterations) { res.state = ROLO_ICP_ITERATIONS; res.converged = 1; return true; }
+  if (cosa >= rot_thr && tsq <= P->transformation_epsilon) { res.state = ROLO_ICP_TRANSFORM; res.converged = 1; return true; }
+  if (mse < 1e-12) { res.state = ROLO_ICP_ABS_MSE; res.converged = 1; return true; }
+  if (std::fabs(mse - prev) / prev < P->euclidean_fitness_epsilon) { res.state = ROLO_ICP_REL_MSE; res.converged = 1; return true; }
+  prev = mse;
+  return false;
+}
+
+// getFitnessScore() from the sums of the association without a cap
+void loop_host_fitness(const double* h, rolo_loopicp_result& res, std::vector<rolo_loopicp_trace_rec>& trace) {
+  rolo_loopicp_trace_rec tr{};
+  tr.n = (int)(h[0] + 0.5); tr.mse = tr.n > 0 ? h[1] / tr.n : 0.0;
+  std::memcpy(tr.sums, h, sizeof(tr.sums));
+  trace.push_back(tr);
+  res.fitness = tr.n > 0 ? tr.mse : DBL_MAX;
+}
+
 int loop_align(rolo_ctx* c, const float4* d_src, int ns, const float4* d_tgt, int nt, const rolo_loopicp_params* P, const float* guess16, rolo_loopicp_result* out) {
   LoopIcp* W = nullptr;
   int rc = loop_state(c, &W);
@@ -321,41 +454,21 @@ int loop_align(rolo_ctx* c, const float4* d_src, int ns, const float4* d_tgt, in
   const double* h = W->h_sum;
   while (true) {
     if ((rc = loop_associate(c, W, A, grid))) return rc;
-    rolo_loopicp_trace_rec tr{};
-    const int n = (int)(h[0] + 0.5);
-    tr.n = n; tr.mse = n > 0 ? h[1] / n : 0.0;
-    std::memcpy(tr.sums, h, sizeof(tr.sums));
-    res.n_last = n;
-    if (n < P->min_correspondences || n < 1) { W->trace.push_back(tr); res.state = ROLO_ICP_NO_CORRESPONDENCES; res.converged = 0; break; }
-    double R[9], t[3];
-    umeyama(h, R, t);
-    float inc[16] = {(float)R[0], (float)R[1], (float)R[2], (float)t[0], (float)R[3], (float)R[4], (float)R[5], (float)t[1],
-                     (float)R[6], (float)R[7], (float)R[8], (float)t[2], 0.f, 0.f, 0.f, 1.f};
-    std::memcpy(tr.increment, inc, sizeof(inc));
-    W->trace.push_back(tr);
-    Rows12 Rw; std::memcpy(Rw.T, inc, sizeof(Rw.T));
-    icp_transform_kernel<true><<<(A.n_sorted + 255) / 256, 256, 0, s>>>(W->cur, W->cur, A.n_sorted, Rw);
-    HIPCHK(hipGetLastError());
-    matmul4f(inc, res.T, res.T);
-    res.iterations++;
-    const double cosa = 0.5 * ((double)inc[0] + (double)inc[5] + (double)inc[10] - 1.0);
-    const double tsq = (double)inc[3] * (double)inc[3] + (double)inc[7] * (double)inc[7] + (double)inc[11] * (double)inc[11];
-    const double mse = tr.mse;
-    if (res.iterations >= P->max_iterations) { res.state = ROLO_ICP_ITERATIONS; res.converged = 1; break; }
-    if (cosa >= rot_thr && tsq <= P->transformation_epsilon) { res.state = ROLO_ICP_TRANSFORM; res.converged = 1; break; }
-    if (mse < 1e-12) { res.state = ROLO_ICP_ABS_MSE; res.converged = 1; break; }
-    if (std::fabs(mse - prev) / prev < P->euclidean_fitness_epsilon) { res.state = ROLO_ICP_REL_MSE; res.converged = 1; break; }
-    prev = mse;
+    float inc[16];
+    bool have_inc = false;
+    const bool done = loop_host_step(h, P, rot_thr, res, prev, W->trace, inc, &have_inc);
+    if (have_inc) {
+      Rows12 Rw; std::memcpy(Rw.T, inc, sizeof(Rw.T));
+      icp_transform_kernel<true><<<(A.n_sorted + 255) / 256, 256, 0, s>>>(W->cur, W->cur, A.n_sorted, Rw);
+      HIPCHK(hipGetLastError());
+    }
+    if (done) break;
   }
   HIPCHK(hipEventRecord(W->ev[2], s));
   {   // getFitnessScore(): the moved source as it stands, no cap
     A.cap2 = INFINITY;
     if ((rc = loop_associate(c, W, A, grid))) return rc;
-    rolo_loopicp_trace_rec tr{};
-    tr.n = (int)(h[0] + 0.5); tr.mse = tr.n > 0 ? h[1] / tr.n : 0.0;
-    std::memcpy(tr.sums, h, sizeof(tr.sums));
-    W->trace.push_back(tr);
-    res.fitness = tr.n > 0 ? tr.mse : DBL_MAX;
+    loop_host_fitness(h, res, W->trace);
   }
   HIPCHK(hipEventRecord(W->ev[3], s));
   HIPCHK(hipEventSynchronize(W->ev[3]));
@@ -374,6 +487,107 @@ int loop_upload(rolo_ctx* c, LoopIcp* W, const float* src, int ns, const float* 
   hipStream_t s = ctx_stream(c);
   if (ns > 0) HIPCHK(hipMemcpyAsync(W->src, src, sizeof(float4) * (size_t)ns, hipMemcpyHostToDevice, s));
   if (nt > 0) HIPCHK(hipMemcpyAsync(W->tgt, tgt, sizeof(float4) * (size_t)nt, hipMemcpyHostToDevice, s));
+  return ROLO_OK;
+}
+
+// B sources (concatenated at d_srcs, ns[b] points each) against one target: loop_align per candidate, with every candidate's association in one launch per
+// iteration and one exchange with the host per iteration for all of them. Candidate b's results are those of loop_align(source b, target), bit for bit: its
+// sorted order and 256-point workgroups are the single form's (the same builder, once per candidate; the target's tree of the last build serves all, a tree's
+// shape never changes an association's result), its rows are added in sum_rows' order, and the host step is the same code.
+int loop_align_batch(rolo_ctx* c, LoopIcp* W, const float4* d_srcs, const int* ns, int B, const float4* d_tgt, int nt, const rolo_loopicp_params* P, const float* guess16,
+                     rolo_loopicp_result* out) {
+  if (!(P->max_correspondence_distance >= 0.0) || P->max_iterations < 0) { ctx_set_error("loop ICP: bad parameters"); return ROLO_EINVAL; }
+  int rc;
+  HIPCHK(hipSetDevice(ctx_device(c)));
+  hipStream_t s = ctx_stream(c);
+  W->btrace.assign((size_t)B, {});
+  for (float& m : W->bms) m = 0.f;
+  std::vector<double> prev((size_t)B, DBL_MAX);
+  std::vector<int2> seg((size_t)B);
+  int total_blocks = 0, n_live = 0;
+  for (int b = 0; b < B; b++) {
+    rolo_loopicp_result& res = out[b];
+    res = rolo_loopicp_result{};
+    for (int i = 0; i < 16; i++) res.T[i] = guess16 ? guess16[16 * (size_t)b + i] : ((i % 5 == 0) ? 1.f : 0.f);
+    res.n_source = ns[b]; res.n_target = nt; res.fitness = DBL_MAX; res.state = ROLO_ICP_NOT_CONVERGED;
+    const bool live = ns[b] > 0 && nt > 0;
+    if (!live) res.state = ROLO_ICP_NO_CORRESPONDENCES;
+    const int n_sorted = live ? KNN_LEAF * ((ns[b] + KNN_LEAF - 1) / KNN_LEAF) : 0;   // (the builder's: KnnCloud::n_sorted)
+    seg[b] = make_int2(total_blocks, (n_sorted + ICP_THREADS - 1) / ICP_THREADS);
+    total_blocks += seg[b].y;
+    n_live += live ? 1 : 0;
+  }
+  if (n_live == 0) return ROLO_OK;
+  HIPCHK(hipEventRecord(W->bev[0], s));
+  // ---- setup: every candidate's segment, the tables ----
+  if ((rc = W->store.grow(W->cur, W->cur_cap, (size_t)total_blocks * ICP_THREADS))) return rc;
+  if ((rc = W->store.grow(W->part, W->part_cap, (size_t)total_blocks * ICP_NV))) return rc;
+  if ((rc = W->store.grow(W->blk_cand, W->blk_cand_cap, (size_t)total_blocks))) return rc;
+  if ((rc = W->store.grow(W->seg, W->seg_cap, (size_t)B))) return rc;
+  if ((rc = W->store.grow(W->ctl, W->ctl_cap, (size_t)B))) return rc;
+  if ((rc = W->store.grow_pinned(W->h_ctl, W->h_ctl_cap, (size_t)B, 16))) return rc;
+  if ((rc = W->store.grow_pinned(W->h_bsum, W->h_bsum_cap, (size_t)B * ICP_NV, 16 * ICP_NV))) return rc;
+  IcpBatchArgs A{};
+  {
+    size_t off = 0;
+    for (int b = 0; b < B; b++) {
+      if (seg[b].y > 0) {
+        KnnPair pair{};
+        if ((rc = loop_sorted(c, W, d_srcs + off, ns[b], d_tgt, nt, guess16 ? guess16 + 16 * (size_t)b : nullptr, &pair))) return rc;
+        if (pair.c[1].n_sorted > seg[b].y * ICP_THREADS) { ctx_set_error("loop ICP: the builder's sorted size is not the expected one"); return ROLO_ESTATE; }
+        const int n_seg = seg[b].y * ICP_THREADS;
+        icp_segment_kernel<<<seg[b].y, 256, 0, s>>>(pair.c[1].sorted, pair.c[1].n_sorted, W->cur + (size_t)seg[b].x * ICP_THREADS, n_seg);
+        HIPCHK(hipGetLastError());
+        A.tsorted = pair.c[0].sorted; A.tboxes = pair.c[0].boxes; A.txyz = pair.c[0].xyz; A.P = pair.c[0].P; A.n_leaves = pair.c[0].n_leaves;
+      }
+      off += (size_t)ns[b];
+    }
+  }
+  std::vector<int> blk((size_t)total_blocks);   // (blk and seg outlive the first wait for the stream below)
+  for (int b = 0; b < B; b++) for (int k = 0; k < seg[b].y; k++) blk[(size_t)seg[b].x + k] = b;
+  HIPCHK(hipMemcpyAsync(W->blk_cand, blk.data(), sizeof(int) * (size_t)total_blocks, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(W->seg, seg.data(), sizeof(int2) * (size_t)B, hipMemcpyHostToDevice, s));
+  A.cur = W->cur; A.blk_cand = W->blk_cand; A.ctl = W->ctl; A.partials = W->part;
+  const float cap2 = cap2_float(P->max_correspondence_distance);
+  for (int b = 0; b < B; b++) {
+    IcpCtl& k = W->h_ctl[b];
+    std::memset(&k, 0, sizeof(k));
+    k.cap2 = cap2;
+    k.mode = seg[b].y > 0 ? ICP_MODE_ITERATE : ICP_MODE_IDLE;
+  }
+  HIPCHK(hipEventRecord(W->bev[1], s));
+  // ---- iterations: one launch, one segmented sum, one wait for all candidates ----
+  const double rot_thr = P->rotation_epsilon > 0 ? P->rotation_epsilon : 1.0 - P->transformation_epsilon;
+  while (n_live > 0) {
+    HIPCHK(hipMemcpyAsync(W->ctl, W->h_ctl, sizeof(IcpCtl) * (size_t)B, hipMemcpyHostToDevice, s));
+    icp_assoc_batch_kernel<<<total_blocks, ICP_THREADS, 0, s>>>(A);
+    HIPCHK(hipGetLastError());
+    sum_rows_segmented<ICP_NV><<<B, 256, 0, s>>>(W->part, W->seg, reinterpret_cast<const int*>(W->ctl) + ICP_CTL_MODE_WORD, ICP_CTL_WORDS, ICP_MODE_IDLE, W->h_bsum);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    for (int b = 0; b < B; b++) {
+      IcpCtl& k = W->h_ctl[b];
+      if (k.mode == ICP_MODE_IDLE) continue;
+      const double* h = W->h_bsum + (size_t)b * ICP_NV;
+      if ((k.mode & 3) == ICP_MODE_FITNESS) {   // getFitnessScore(): the moved source as it stood, no cap
+        loop_host_fitness(h, out[b], W->btrace[b]);
+        k.mode = ICP_MODE_IDLE;
+        n_live--;
+        continue;
+      }
+      float inc[16];
+      bool have_inc = false;
+      const bool done = loop_host_step(h, P, rot_thr, out[b], prev[b], W->btrace[b], inc, &have_inc);
+      if (have_inc) std::memcpy(k.inc, inc, sizeof(k.inc));
+      k.mode = (done ? ICP_MODE_FITNESS : ICP_MODE_ITERATE) | (have_inc ? ICP_MODE_MOVE : 0);   // the next launch applies the increment on load
+      if (done) k.cap2 = INFINITY;
+    }
+  }
+  HIPCHK(hipEventRecord(W->bev[2], s));
+  HIPCHK(hipEventSynchronize(W->bev[2]));
+  (void)hipEventElapsedTime(&W->bms[0], W->bev[0], W->bev[1]);
+  (void)hipEventElapsedTime(&W->bms[1], W->bev[1], W->bev[2]);
+  (void)hipEventElapsedTime(&W->bms[3], W->bev[0], W->bev[2]);
   return ROLO_OK;
 }
 
@@ -398,7 +612,11 @@ void rolo_loopicp_destroy(rolo_ctx* c) {   // called by rolo_ctx_destroy
   for (void* p : {(void*)W->src, (void*)W->tgt, (void*)W->srcg, (void*)W->cur, (void*)W->part, (void*)W->idx, (void*)W->d2}) if (p) (void)hipFree(p);
   W->store.release();
   if (W->h_sum) (void)hipHostFree(W->h_sum);
+  for (void* p : {(void*)W->bsrc, (void*)W->blk_cand, (void*)W->seg, (void*)W->ctl}) if (p) (void)hipFree(p);
+  if (W->h_ctl) (void)hipHostFree(W->h_ctl);
+  if (W->h_bsum) (void)hipHostFree(W->h_bsum);
   for (hipEvent_t e : W->ev) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : W->bev) if (e) (void)hipEventDestroy(e);
   delete W;
   *ctx_loop_slot(c) = nullptr;
 }
@@ -439,6 +657,47 @@ int rolo_keymap_loop_icp(rolo_keymap* km, const rolo_loopicp_params* params, con
 int rolo_loopicp_get_trace(rolo_ctx* c, rolo_loopicp_trace_rec* out, int cap) {
   if (!c || cap < 0 || (cap && !out)) return ROLO_EINVAL;
   return copy_trace(c, out, cap);
+}
+
+int rolo_loopicp_align_batch(rolo_ctx* c, const float* sources, const int* n_source, int B, const float* target, int n_target, const rolo_loopicp_params* params,
+                             const float* guess16, rolo_loopicp_result* out) {
+  if (!c || !params || B < 0 || B > ROLO_LOOPICP_MAX_BATCH || n_target < 0 || (n_target && !target) || n_target > ROLO_KEYMAP_MAX_POINTS) return ROLO_EINVAL;
+  if (B == 0) return ROLO_OK;
+  if (!n_source || !out) return ROLO_EINVAL;
+  long long total = 0;
+  for (int b = 0; b < B; b++) {
+    if (n_source[b] < 0) return ROLO_EINVAL;
+    total += n_source[b];
+  }
+  if (total > ROLO_KEYMAP_MAX_POINTS || (total && !sources)) return ROLO_EINVAL;
+  LoopIcp* W = nullptr;
+  int rc = loop_state(c, &W);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(ctx_device(c)));
+  hipStream_t s = ctx_stream(c);
+  if ((rc = W->store.grow(W->bsrc, W->bsrc_cap, (size_t)std::max(total, 1ll)))) return rc;
+  if ((rc = W->store.grow(W->tgt, W->tgt_cap, (size_t)std::max(n_target, 1)))) return rc;
+  if (total > 0) HIPCHK(hipMemcpyAsync(W->bsrc, sources, sizeof(float4) * (size_t)total, hipMemcpyHostToDevice, s));
+  if (n_target > 0) HIPCHK(hipMemcpyAsync(W->tgt, target, sizeof(float4) * (size_t)n_target, hipMemcpyHostToDevice, s));
+  rc = loop_align_batch(c, W, W->bsrc, n_source, B, W->tgt, n_target, params, guess16, out);
+  if (rc) (void)hipStreamSynchronize(s);   // the caller's arrays are free again, whatever happened
+  return rc;
+}
+
+int rolo_loopicp_get_trace_batch(rolo_ctx* c, int b, rolo_loopicp_trace_rec* out, int cap) {
+  if (!c || b < 0 || cap < 0 || (cap && !out)) return ROLO_EINVAL;
+  LoopIcp* W = static_cast<LoopIcp*>(*ctx_loop_slot(c));
+  if (!W || b >= (int)W->btrace.size()) return ROLO_EINVAL;
+  const int m = (int)W->btrace[b].size();
+  for (int i = 0; i < std::min(m, cap); i++) out[i] = W->btrace[b][i];
+  return m;
+}
+
+int rolo_loopicp_batch_last_ms(rolo_ctx* c, float* ms4) {
+  if (!c || !ms4) return ROLO_EINVAL;
+  LoopIcp* W = static_cast<LoopIcp*>(*ctx_loop_slot(c));
+  for (int i = 0; i < 4; i++) ms4[i] = W ? W->bms[i] : 0.f;
+  return ROLO_OK;
 }
 
 int rolo_keymap_loop_trace(rolo_keymap* km, rolo_loopicp_trace_rec* out, int cap) {
