@@ -3,7 +3,7 @@
 The reference itself cannot be built for the tests (it needs Eigen, PCL and OpenCV), so THIS twin is the parity target of tests/test_gpu_scancontext.py: the
 same arithmetic as the HIP kernels, written independently of them from the reference's text. Expression types are the reference's: float32 where it computes
 in float, float64 where an operand is a double (Python floats in the inner loops: the same IEEE doubles), every sum taken serially in index order in a Python
-loop (Eigen's own order is not known: parity unpinned), atan through math.atan (the platform's libm, fp64). Operations that are independent per point or per
+loop (Eigen's own order is not known: parity unpinned), atan through math.atan (the platform's libm, fp64) unless a caller passes another (tests/sc_cases.py: a correctly rounded one). Operations that are independent per point or per
 searched key are written element-wise on arrays; nothing is ever summed by numpy."""
 import math
 
@@ -21,17 +21,19 @@ def _atan(q):
     return np.array([math.atan(v) if v == v else math.nan for v in np.asarray(q, f64).tolist()], f64)
 
 
-def xy2theta(x, y):
-    """:23-36, element-wise on float32 arrays: the quotient is a float, atan and the rest fp64, the return value float"""
+def xy2theta(x, y, atan=None):
+    """:23-36, element-wise on float32 arrays: the quotient is a float, atan and the rest fp64, the return value float. `atan` replaces the platform libm's
+    (an fp64 array in, an fp64 array out): tests/sc_cases.py runs the same expression on a correctly rounded one"""
+    at = atan or _atan
     x, y = np.atleast_1d(np.asarray(x, f32)), np.atleast_1d(np.asarray(y, f32))
     K = f64(180.0) / f64(math.pi)
     out = np.zeros(x.shape, f32)
     with np.errstate(all="ignore"):
         b1 = (x >= 0) & (y >= 0); b2 = (x < 0) & (y >= 0); b3 = (x < 0) & (y < 0); b4 = (x >= 0) & (y < 0)
-        out[b1] = (K * _atan(y[b1] / x[b1])).astype(f32)
-        out[b2] = (f64(180.0) - (K * _atan(y[b2] / (-x[b2])))).astype(f32)
-        out[b3] = (f64(180.0) + (K * _atan(y[b3] / x[b3]))).astype(f32)
-        out[b4] = (f64(360.0) - (K * _atan((-y[b4]) / x[b4]))).astype(f32)
+        out[b1] = (K * at(y[b1] / x[b1])).astype(f32)
+        out[b2] = (f64(180.0) - (K * at(y[b2] / (-x[b2])))).astype(f32)
+        out[b3] = (f64(180.0) + (K * at(y[b3] / x[b3]))).astype(f32)
+        out[b4] = (f64(360.0) - (K * at((-y[b4]) / x[b4]))).astype(f32)
     return out
 
 
@@ -42,9 +44,9 @@ def _clamp_ceil(v, hi):
         return np.where(c != c, 1.0, np.clip(c, 1.0, float(hi))).astype(np.int64)
 
 
-def make_scancontext(pts, P=DEFAULTS):
+def make_scancontext(pts, P=DEFAULTS, atan=None):
     """:151-195. Returns the num_ring x num_sector float64 matrix (float32 values) or None for an empty cloud. The per-point arithmetic is element-wise on
-    arrays (the same IEEE operations as on scalars); the maximum per bin is exact in any order"""
+    arrays (the same IEEE operations as on scalars); the maximum per bin is exact in any order. `atan`: see xy2theta"""
     pts = np.asarray(pts, f32).reshape(-1, 4)
     if len(pts) == 0:
         return None
@@ -55,7 +57,7 @@ def make_scancontext(pts, P=DEFAULTS):
         zf = (z.astype(f64) + h).astype(f32)                 # :168
         r = np.sqrt(x * x + y * y)                            # :171, float
         assert r.dtype == f32
-        th = xy2theta(x, y)                                   # :172
+        th = xy2theta(x, y, atan)                             # :172
         keep = ~(r.astype(f64) > maxr)                        # :175
         ring = _clamp_ceil((r.astype(f64) / maxr) * f64(R), R)             # :178
         sector = _clamp_ceil((th.astype(f64) / f64(360.0)) * f64(S), S)    # :179
@@ -175,9 +177,10 @@ class Store:
     def __init__(self, **kw):
         self.P = dict(DEFAULTS); self.P.update(kw)
         self.entries = []
+        self.atan = None   # the platform libm's; see xy2theta
 
     def add(self, pts):
-        desc = make_scancontext(pts, self.P)
+        desc = make_scancontext(pts, self.P, self.atan)
         if desc is None:
             return -1
         self.entries.append((desc,) + keys(desc))
