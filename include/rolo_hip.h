@@ -305,6 +305,10 @@ int rolo_ctx_lm_form(rolo_ctx* ctx, int* out, int n);
 #define ROLO_VOXBUILD_SEARCH 2
 #define ROLO_VOXBUILD_FRAME 3
 int rolo_debug_voxel_build(rolo_ctx* ctx, int32_t out[4]);
+/* test hook: the source covariances' PLANE short form, C_A = I - m m^T, as the passes would read it: m (n x 3, row per point), m.x NaN where the neighbourhood's
+ * SVD did not leave that form (the passes then read the point's six entries). n must be the source's size. ROLO_ESTATE when the passes would not read the form at all:
+ * a regularisation other than PLANE, handed-in covariances, ROLO_PASS_NRM=0, or covariances not computed. */
+int rolo_debug_source_plane_form(rolo_ctx* ctx, double* m /* n x 3 */, int n);
 /* device buffer (re)allocations made so far by the registration contexts of this process (every hipMalloc behind a rolo_ctx's buffers; a captured hipGraph is keyed on it):
  * a steady-state frame loop must stop moving it */
 long long rolo_alloc_count(void);

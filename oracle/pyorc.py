@@ -74,6 +74,7 @@ def lib():
         for f in (L.orc_reg_get_source_covs, L.orc_reg_get_target_covs):
             f.argtypes = [C.c_void_p, dp]
         L.orc_reg_set_source_covs.argtypes = [C.c_void_p, dp]
+        L.orc_reg_set_target_covs.argtypes = [C.c_void_p, dp]
         L.orc_reg_get_voxels.argtypes = [C.c_void_p, ip, ip, dp, dp]
         L.orc_reg_so3_linearize.restype = C.c_double
         L.orc_reg_so3_linearize.argtypes = [C.c_void_p, dp, dp, dp]
@@ -183,6 +184,10 @@ class Reg:
     def set_source_covs(self, covs):
         a = np.ascontiguousarray(covs, np.float64).reshape(self.ns, 16)
         assert lib().orc_reg_set_source_covs(self.h, _d(a)) == 0
+
+    def set_target_covs(self, covs):
+        a = np.ascontiguousarray(covs, np.float64).reshape(self.nt, 16)
+        assert lib().orc_reg_set_target_covs(self.h, _d(a)) == 0
 
     def target_covs(self):
         out = np.zeros((self.nt, 4, 4))

@@ -668,6 +668,13 @@ int orc_reg_set_source_covs(orc_reg* r, const double* covs) {
   r->have_scov = true;
   return 0;
 }
+int orc_reg_set_target_covs(orc_reg* r, const double* covs) {
+  r->target_covs.resize(r->target.size());
+  for (size_t i = 0; i < r->target.size(); i++) for (int a = 0; a < 3; a++) for (int b = 0; b < 3; b++) r->target_covs[i].a[a][b] = covs[i * 16 + a * 4 + b];
+  r->have_tcov = true; r->have_map = false;
+  r->corr_src.clear(); r->corr_vox.clear(); r->mahal.clear();
+  return 0;
+}
 int orc_reg_build_voxelmap(orc_reg* r) { int rc = orc_reg_compute_covariances(r); if (rc) return rc; return build_map(r); }
 int orc_reg_num_voxels(orc_reg* r) { return r->have_map ? (int)r->voxels.size() : -1; }
 int orc_reg_get_voxels(orc_reg* r, int32_t* keys, int32_t* counts, double* means, double* covs) {

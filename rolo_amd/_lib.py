@@ -294,6 +294,7 @@ SYMBOLS = {
     "rolo_ctx_lm_form": (C.c_int, [vp, C.POINTER(C.c_int), C.c_int]),
     "rolo_debug_chain": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "rolo_debug_voxel_build": (C.c_int, [vp, ip]),
+    "rolo_debug_source_plane_form": (C.c_int, [vp, dp, C.c_int]),
     "rolo_alloc_count": (C.c_longlong, []),
     "rolo_prof_enable": (C.c_int, [vp, C.c_int]),
     "rolo_prof_read": (C.c_int, [vp, C.c_int, fp, C.c_int]),

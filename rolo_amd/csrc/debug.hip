@@ -145,6 +145,22 @@ int rolo_debug_voxel_build(rolo_ctx* c, int32_t out[4]) {
   return ROLO_OK;
 }
 
+// the source's PLANE short form as prepare_pass hands it to the passes (schedule.hip: PassArgs::nrm), row per point; m.x is NaN where the tail poisoned it
+int rolo_debug_source_plane_form(rolo_ctx* c, double* m, int n) {
+  if (!c || !m) return ROLO_EINVAL;
+  if (c->async_pending) { g_err = "a registration is in flight on this context"; return ROLO_ESTATE; }
+  int rc = set_device(c); if (rc) return rc;
+  if (!(switches().pass_nrm && c->src.have_cov && c->src.have_nrm && !c->src.cov_user && c->src.nrm && c->P.regularization == ROLO_REG_PLANE)) {
+    g_err = "the passes do not read the source's plane form (not PLANE, handed-in covariances, ROLO_PASS_NRM=0, or not computed)"; return ROLO_ESTATE;
+  }
+  if (n != c->src.n) { g_err = "rolo_debug_source_plane_form: n is not the source's size"; return ROLO_EINVAL; }
+  std::vector<double> soa(3 * (size_t)n);
+  HIPCHK(hipMemcpyAsync(soa.data(), c->src.nrm, sizeof(double) * soa.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int i = 0; i < n; i++) for (int d = 0; d < 3; d++) m[(size_t)i * 3 + d] = soa[(size_t)d * n + i];
+  return ROLO_OK;
+}
+
 int rolo_prof_enable(rolo_ctx* c, int on) {
   if (!c) return ROLO_EINVAL;
   c->prof_on = on != 0;

@@ -511,6 +511,7 @@ ROLO_DEV void inv3(const double (&A)[9], double (&o)[9]) {
 ROLO_DEV void knn_covariance_finish(double cxx, double cxy, double cxz, double cyy, double cyz, double czz, int n, int qi, int reg,
                                     double* __restrict__ cov, double (&c6)[6], double* __restrict__ nrm = nullptr) {
   double out[9];
+  double U[9], V[9];   // (of the SVD rules; PLANE's epilogue below reads them)
 
   if (reg == ROLO_REG_NONE) {
     out[0] = cxx; out[1] = cxy; out[2] = cxz; out[3] = cxy; out[4] = cyy; out[5] = cyz; out[6] = cxz; out[7] = cyz; out[8] = czz;
@@ -526,33 +527,52 @@ ROLO_DEV void knn_covariance_finish(double cxx, double cxy, double cxz, double c
     inv3(Ci, out);
   } else {
     const double A[9] = {cxx, cxy, cxz, cxy, cyy, cyz, cxz, cyz, czz};
-    double U[9], V[9], sv[3];
+    double sv[3];
     jacobi_svd3(A, U, sv, V);
     double v0 = 1, v1 = 1, v2 = 1e-3;
     if (reg == ROLO_REG_MIN_EIG) { v0 = fmax(sv[0], 1e-3); v1 = fmax(sv[1], 1e-3); v2 = fmax(sv[2], 1e-3); }
-    else if (reg == ROLO_REG_NORMALIZED_MIN_EIG) { double m = fmax(sv[0], fmax(sv[1], sv[2])); v0 = fmax(sv[0] / m, 1e-3); v1 = fmax(sv[1] / m, 1e-3); v2 = fmax(sv[2] / m, 1e-3); }
+    else if (reg == ROLO_REG_NORMALIZED_MIN_EIG) {
+      // (x < 1e-3 ? 1e-3 : x, not fmax: coincident neighbours make 0 / 0, and the reference's std::max keeps that NaN — rot_vgicp_impl.hpp:482-483 — where fmax drops it)
+      const double m = fmax(sv[0], fmax(sv[1], sv[2])), q0 = sv[0] / m, q1 = sv[1] / m, q2 = sv[2] / m;
+      v0 = q0 < 1e-3 ? 1e-3 : q0; v1 = q1 < 1e-3 ? 1e-3 : q1; v2 = q2 < 1e-3 ? 1e-3 : q2;
+    }
     else if (reg == ROLO_REG_PLANE_S) { double s = sv[0] + sv[1] + sv[2]; v0 = sv[0] / s; v1 = sv[1] / s; v2 = 1e-3; }
 #pragma unroll
     for (int a = 0; a < 3; a++)
 #pragma unroll
       for (int b = 0; b < 3; b++) out[a * 3 + b] = (U[a * 3 + 0] * v0) * V[b * 3 + 0] + (U[a * 3 + 1] * v1) * V[b * 3 + 1] + (U[a * 3 + 2] * v2) * V[b * 3 + 2];
-    if (nrm && reg == ROLO_REG_PLANE) {
-      // U diag(1, 1, 1e-3) V^T with orthonormal V and U = V up to the sign fix of each column: u0 u0^T + u1 u1^T + s 1e-3 u2 u2^T = I - (1 - s 1e-3) u2 u2^T,
-      // s = U's sign on the third column (-1 only for a rank-deficient neighbourhood whose zero singular value came out of the sweep with a minus sign)
-      const double s3 = U[0 * 3 + 2] * V[0 * 3 + 2] + U[1 * 3 + 2] * V[1 * 3 + 2] + U[2 * 3 + 2] * V[2 * 3 + 2];   // +-1 to rounding
-      const double al = sqrt(1.0 - (s3 < 0 ? -1e-3 : 1e-3));
-      // The identity needs u0 = v0 and u1 = v1. A neighbourhood of rank <= 1 (collinear or coincident neighbours: TWO singular values ~ 0) can leave the sweep with the
-      // sign fix on the second column as well (or, for coincident points, on all three): the six entries above are then NOT I - m m^T, and they are what the voxel map
-      // and every getter see. Such a point is poisoned — NaN in m.x — and the passes take its six entries instead (passes.hip load_pt / rotated_cov): advisor, round 5.
-      const double s1 = U[0 * 3 + 0] * V[0 * 3 + 0] + U[1 * 3 + 0] * V[1 * 3 + 0] + U[2 * 3 + 0] * V[2 * 3 + 0];
-      const double s2 = U[0 * 3 + 1] * V[0 * 3 + 1] + U[1 * 3 + 1] * V[1 * 3 + 1] + U[2 * 3 + 1] * V[2 * 3 + 1];
-      const bool plane_form = s1 > 0 && s2 > 0;
-      const size_t pn = (size_t)n;
-      nrm[qi] = plane_form ? al * V[0 * 3 + 2] : __builtin_nan(""); nrm[pn + qi] = al * V[1 * 3 + 2]; nrm[2 * pn + qi] = al * V[2 * 3 + 2];
-    }
   }
   const size_t pitch = (size_t)n;
   c6[0] = out[0]; c6[1] = 0.5 * (out[1] + out[3]); c6[2] = 0.5 * (out[2] + out[6]); c6[3] = out[4]; c6[4] = 0.5 * (out[5] + out[7]); c6[5] = out[8];
+  if (reg == ROLO_REG_PLANE) {
+    // U diag(1, 1, 1e-3) V^T with orthonormal V and U = V up to the sign fix of each column: u0 u0^T + u1 u1^T + s 1e-3 u2 u2^T = I - (1 - s 1e-3) u2 u2^T,
+    // s = U's sign on the third column (-1 only for a rank-deficient neighbourhood whose zero singular value came out of the sweep with a minus sign)
+    const double s3 = U[0 * 3 + 2] * V[0 * 3 + 2] + U[1 * 3 + 2] * V[1 * 3 + 2] + U[2 * 3 + 2] * V[2 * 3 + 2];   // +-1 to rounding
+    const double al = sqrt(1.0 - (s3 < 0 ? -1e-3 : 1e-3));
+    const double mx = al * V[0 * 3 + 2], my = al * V[1 * 3 + 2], mz = al * V[2 * 3 + 2];
+    // The identity needs u0 = v0 and u1 = v1. A neighbourhood of rank <= 1 (collinear or coincident neighbours: TWO singular values ~ 0) can leave the sweep with the
+    // sign fix on the second column as well (or, for coincident points, on all three): the six entries above are then NOT I - m m^T, and they are what the voxel map
+    // and every getter see. Such a point is poisoned — NaN in m.x — and the passes take its six entries instead (passes.hip load_pt / rotated_cov): advisor, round 5.
+    const double s1 = U[0 * 3 + 0] * V[0 * 3 + 0] + U[1 * 3 + 0] * V[1 * 3 + 0] + U[2 * 3 + 0] * V[2 * 3 + 0];
+    const double s2 = U[0 * 3 + 1] * V[0 * 3 + 1] + U[1 * 3 + 1] * V[1 * 3 + 1] + U[2 * 3 + 1] * V[2 * 3 + 1];
+    const bool plane_form = s1 > 0 && s2 > 0;
+    // Positive cosines are not u = v: two singular values that are tiny but NOT zero (a line rounded to float32: ~1e-15 of the first) leave the sweep with U and V a
+    // rotation of ~1e-6 apart inside that plane. The symmetric part of U diag V^T is then 1e-7 away from I - m m^T, and its own singular values are no longer
+    // (1, 1, 1e-3). Where the six entries are not I - m m^T to 2^-46 (every other neighbourhood is: < 4e-15 on 14 400 points of a VLP-16 frame) they BECOME I - m m^T:
+    // V diag(1, 1, 1e-3) V^T, a matrix with exactly those singular values — so the passes, the voxel map and the getters hold one matrix for the point. Whether a
+    // plane-form buffer is written or not makes no difference to the six entries.
+    if (plane_form) {
+      const double p6[6] = {1.0 - mx * mx, -(mx * my), -(mx * mz), 1.0 - my * my, -(my * mz), 1.0 - mz * mz};
+      double dev = 0;
+#pragma unroll
+      for (int d = 0; d < 6; d++) dev = fmax(dev, fabs(c6[d] - p6[d]));
+      if (!(dev <= 0x1p-46)) {
+#pragma unroll
+        for (int d = 0; d < 6; d++) c6[d] = p6[d];
+      }
+    }
+    if (nrm) { nrm[qi] = plane_form ? mx : __builtin_nan(""); nrm[pitch + qi] = my; nrm[2 * pitch + qi] = mz; }
+  }
 #pragma unroll
   for (int d = 0; d < 6; d++) cov[d * pitch + qi] = c6[d];
 }

@@ -247,6 +247,13 @@ class RotVGICP:
         check(lib().rolo_debug_voxel_build(self._h, _i(out)), "rolo_debug_voxel_build")
         return tuple(int(v) for v in out)
 
+    def sourcePlaneForm(self):
+        """Test hook (rolo_debug_source_plane_form): m (n, 3) with C_A = I - m m^T as the passes read the source's PLANE covariances; m[:, 0] is NaN where they
+        take the six entries instead. RoloError (ROLO_ESTATE) when they would not read the form at all."""
+        m = np.zeros((self._ns, 3))
+        check(lib().rolo_debug_source_plane_form(self._h, _d(m), self._ns), "rolo_debug_source_plane_form")
+        return m
+
     def targetVoxelKeys(self):
         keys = np.zeros((self._nt, 3), np.int32)
         check(lib().rolo_get_target_voxel_keys(self._h, _i(keys)), "rolo_get_target_voxel_keys")

@@ -5,7 +5,8 @@ cut from synth.dense_pair("vlp16") (1 024 of the source, 1 024 of the target) an
 _degenerate_cloud (exact ties, zero distances, rank-1 neighbourhoods: two singular values zero, the sign fixes of the SVD decided by its last bits).
 
 Both forms of the walk's epilogue (ROLO_KNN_MOMENTS = 1 / 0) are run, each in its own process (the switch is read once per process); they must agree bit for bit before
-anything is written. Run from the repository root at the PARENT of a change, on the GPU:   python tests/golden/make_golden_cov_bits.py"""
+anything is written. Run from the repository root at the PARENT of a change, on the GPU:   python tests/golden/make_golden_cov_bits.py
+(A change that moves bits on purpose records with its own library, after the arrays it does not mean to move compared equal to the earlier recording.)"""
 import os
 import subprocess
 import sys

@@ -5,6 +5,9 @@ to make_jacobi / jacobi_pair / jacobi_svd3 that claims to keep every bit: it com
 
 The clouds (rebuilt here by the generator's own cov_bits_clouds): 2 048 points cut from synth.dense_pair("vlp16"), and a line, a duplicates and a lattice cloud of 200 / 217
 points — rank-1 neighbourhoods whose SVD sign fixes hang on the last bits, zero distances, exact ties and exactly zero moments (which take the plain-division path).
+Re-recorded once, with the library of the commit that made the six entries of a plane-form point I - m m^T where they were not (knn_covariance_finish; tests/test_gpu_cov_cases.py):
+8 + 21 points of the line cloud, whose y is rounded (two singular values tiny, not zero), and with them its pose (by 1.1e-8), changed on purpose; the other nine arrays were
+compared with the earlier recording first and kept every bit.
 Both forms of the walk's epilogue (ROLO_KNN_MOMENTS = 1 / 0), and the 64-query packets (ROLO_KNN_SUB = 0) beside the walk picked by size, each in its own process
 (the switches are read once per process)."""
 import os
