@@ -42,22 +42,31 @@ inline int fail_hip(hipError_t e, const char* what) {
 }
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) return rolo::fail_hip(_e, #x); } while (0)
 
-// Device (and pinned host) buffers that only grow, counted in elements. An outgrown buffer is retired, not freed, until release(): a hipFree is a device-wide
-// synchronisation that would stall the frames other contexts have in flight, and work queued on the owner's stream may still read the old buffer. Sizes grow by
-// half, so the retired buffers together stay below twice the live one. The owner frees its live buffers itself, after it has drained its stream.
+// Device (and pinned host) buffers, counted in elements: the ones that only grow, and the fixed-size ones an owner creates once (alloc). The store remembers every
+// allocation it makes and release() frees them all, the live ones and the outgrown ones: an owner keeps no list of its own. An outgrown buffer stays allocated
+// until then: a hipFree is a device-wide synchronisation that would stall the frames other contexts have in flight, and work queued on the owner's stream may
+// still read the old buffer. Sizes grow by half, so the outgrown buffers together stay below twice the live one. The owner drains its stream, then calls release().
 struct DevStore {
   hipStream_t stream = nullptr;   // carries the copy of the `keep` elements
   const char* who = "";           // names the unit in the allocation's error message
   size_t slack = 256;             // elements a buffer gets beyond one and a half times the need
-  std::vector<void*> retired, retired_host;
+  std::vector<void*> dev, pinned; // everything allocated since the last release()
 
-  // exactly n elements, the first `keep` of the old buffer copied over on the stream
+  // exactly n elements of device memory; with p set before, the first `keep` of the old buffer copied over on the stream
   template <typename T>
-  int replace(T*& p, size_t n, size_t keep = 0) {
+  int alloc(T*& p, size_t n, size_t keep = 0) {
     T* q = nullptr;
     if (hipMalloc((void**)&q, n * sizeof(T)) != hipSuccess) { ctx_set_error((std::string("hipMalloc failed (") + who + ")").c_str()); return ROLO_EHIP; }
+    dev.push_back(q);
     if (p && keep) HIPCHK(hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, stream));
-    retire(p);
+    p = q;
+    return ROLO_OK;
+  }
+  template <typename T>
+  int alloc_pinned(T*& p, size_t n) {
+    T* q = nullptr;
+    if (hipHostMalloc((void**)&q, n * sizeof(T)) != hipSuccess) { ctx_set_error((std::string("hipHostMalloc failed (") + who + ")").c_str()); return ROLO_EHIP; }
+    pinned.push_back(q);
     p = q;
     return ROLO_OK;
   }
@@ -65,7 +74,7 @@ struct DevStore {
   int grow(T*& p, size_t& cap, size_t need, size_t keep = 0) {
     if (need <= cap && p) return ROLO_OK;
     const size_t want = need + need / 2 + slack;
-    const int rc = replace(p, want, keep);
+    const int rc = alloc(p, want, keep);
     if (rc == ROLO_OK) cap = want;
     return rc;
   }
@@ -73,17 +82,14 @@ struct DevStore {
   int grow_pinned(T*& p, size_t& cap, size_t need, size_t pinned_slack) {
     if (need <= cap && p) return ROLO_OK;
     const size_t want = need + need / 2 + pinned_slack;
-    T* q = nullptr;
-    if (hipHostMalloc((void**)&q, want * sizeof(T)) != hipSuccess) { ctx_set_error((std::string("hipHostMalloc failed (") + who + ")").c_str()); return ROLO_EHIP; }
-    if (p) retired_host.push_back(p);
-    p = q; cap = want;
-    return ROLO_OK;
+    const int rc = alloc_pinned(p, want);
+    if (rc == ROLO_OK) cap = want;
+    return rc;
   }
-  void retire(void* p) { if (p) retired.push_back(p); }
-  void release() {
-    for (void* p : retired) (void)hipFree(p);
-    for (void* p : retired_host) (void)hipHostFree(p);
-    retired.clear(); retired_host.clear();
+  void release() {   // (the owner's pointers dangle from here on)
+    for (void* p : dev) (void)hipFree(p);
+    for (void* p : pinned) (void)hipHostFree(p);
+    dev.clear(); pinned.clear();
   }
 };
 

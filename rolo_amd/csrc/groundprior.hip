@@ -38,11 +38,7 @@ struct rolo_ground {
   float4* pts = nullptr; size_t pts_cap = 0;         // x y z 0 in the caller's order
   float4* spts = nullptr; size_t spts_cap = 0;       // x y z (index bits), sorted by cell
   int* cell_start = nullptr; size_t cell_start_cap = 0;   // [cells + 1]
-  // sort scratch (as the key map's)
-  unsigned* keys[2] = {nullptr, nullptr}; size_t keys_cap[2] = {0, 0};
-  int* vals[2] = {nullptr, nullptr}; size_t vals_cap[2] = {0, 0};
-  unsigned* hist = nullptr; size_t hist_cap = 0;
-  unsigned* dtot = nullptr; size_t dtot_cap = 0;
+  rolo::SortScratch sort;                            // the sort of (cell, point index)
   float* box_part = nullptr; size_t box_part_cap = 0;
   unsigned* bcnt = nullptr; size_t bcnt_cap = 0;     // the patch's kept points per workgroup, then their scan
   float* patch = nullptr; size_t patch_cap = 0;
@@ -750,12 +746,13 @@ int rolo_ground_create(int device, rolo_ground** out) {
   HIPCHK(hipSetDevice(device));
   rolo_ground* g = new rolo_ground();
   g->device = device;
-  hipError_t e = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&g->h_box, sizeof(float) * 8);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&g->h_m, sizeof(int) * 2);
-  if (e == hipSuccess) e = hipMalloc((void**)&g->d_m, sizeof(int) * 2);
+  const hipError_t e = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking);
   if (e != hipSuccess) { ctx_set_error((std::string("rolo_ground_create: ") + hipGetErrorString(e)).c_str()); rolo_ground_destroy(g); return ROLO_EHIP; }
   g->store.stream = g->stream; g->store.who = "ground";
+  int rc = g->store.alloc_pinned(g->h_box, 8);
+  if (!rc) rc = g->store.alloc_pinned(g->h_m, 2);
+  if (!rc) rc = g->store.alloc(g->d_m, 2);
+  if (rc) { rolo_ground_destroy(g); return rc; }
   *out = g;
   return ROLO_OK;
 }
@@ -765,10 +762,6 @@ void rolo_ground_destroy(rolo_ground* g) {
   (void)hipSetDevice(g->device);
   if (g->stream) (void)hipStreamSynchronize(g->stream);
   g->store.release();
-  for (void* p : {(void*)g->rec, (void*)g->pts, (void*)g->spts, (void*)g->cell_start, (void*)g->keys[0], (void*)g->keys[1], (void*)g->vals[0], (void*)g->vals[1], (void*)g->hist,
-                  (void*)g->dtot, (void*)g->box_part, (void*)g->bcnt, (void*)g->patch, (void*)g->d_m, (void*)g->d_q, (void*)g->d_out})
-    if (p) (void)hipFree(p);
-  for (void* p : {(void*)g->h_box, (void*)g->h_m}) if (p) (void)hipHostFree(p);
   for (hipEvent_t e : g->ev) if (e) (void)hipEventDestroy(e);
   if (g->stream) (void)hipStreamDestroy(g->stream);
   delete g;
@@ -798,25 +791,15 @@ int rolo_ground_set_cloud(rolo_ground* g, const float* pts, int n, int stride) {
   hipStream_t s = g->stream;
   int rc;
   if ((rc = ensure_events(g))) return rc;
-  const int nblocks = (n + SORT_TILE - 1) / SORT_TILE;
   if ((rc = g->store.grow(g->rec, g->rec_cap, (size_t)n * stride))) return rc;
   if ((rc = g->store.grow(g->pts, g->pts_cap, (size_t)n))) return rc;
   if ((rc = g->store.grow(g->spts, g->spts_cap, (size_t)n))) return rc;
-  for (int b = 0; b < 2; b++) {
-    if ((rc = g->store.grow(g->keys[b], g->keys_cap[b], (size_t)n))) return rc;
-    if ((rc = g->store.grow(g->vals[b], g->vals_cap[b], (size_t)n))) return rc;
-  }
-  if ((rc = g->store.grow(g->hist, g->hist_cap, 256 * (size_t)nblocks))) return rc;
-  if ((rc = g->store.grow(g->dtot, g->dtot_cap, (size_t)4 * 256))) return rc;
+  if ((rc = g->sort.reserve(g->store, (size_t)n))) return rc;
   if ((rc = g->store.grow(g->box_part, g->box_part_cap, 8 * (size_t)BOX_BLOCKS_MAX))) return rc;
   HIPCHK(hipMemcpyAsync(g->rec, pts, sizeof(float) * (size_t)n * stride, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(g->pts, p4.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, s));
   HIPCHK(hipEventRecord(g->ev[0], s));
-  const int bblocks = std::min((n + SM_THREADS - 1) / SM_THREADS, BOX_BLOCKS_MAX);
-  vg_box_kernel<<<bblocks, SM_THREADS, 0, s>>>(g->pts, n, g->box_part);
-  HIPCHK(hipGetLastError());
-  vg_box_final_kernel<<<1, SM_THREADS, 0, s>>>(g->box_part, bblocks, g->h_box);
-  HIPCHK(hipGetLastError());
+  if ((rc = enqueue_box(s, g->pts, n, g->box_part, g->h_box))) return rc;
   HIPCHK(hipStreamSynchronize(s));
   const float minx = g->h_box[0], miny = g->h_box[1], maxx = g->h_box[3], maxy = g->h_box[4];
   // the cell size: doubled until no side and not the whole grid is over its limit
@@ -836,25 +819,13 @@ int rolo_ground_set_cloud(rolo_ground* g, const float* pts, int n, int stride) {
   if ((rc = g->store.grow(g->cell_start, g->cell_start_cap, (size_t)cells + 1))) return rc;
   g->n = n;
   const GpGrid G = grid_of(g);
-  gp_key_kernel<<<(n + SM_THREADS - 1) / SM_THREADS, SM_THREADS, 0, s>>>(g->pts, n, G, g->keys[0], g->vals[0]);
+  gp_key_kernel<<<(n + SM_THREADS - 1) / SM_THREADS, SM_THREADS, 0, s>>>(g->pts, n, G, g->sort.keys[0], g->sort.vals[0]);
   HIPCHK(hipGetLastError());
-  int bits = 1;
-  while (bits < 31 && (1ll << bits) < cells) bits++;
   int cur = 0;
-  HIPCHK(hipMemsetAsync(g->dtot, 0, sizeof(unsigned) * 4 * 256, s));
-  for (int shift = 0; shift < bits; shift += 8) {
-    unsigned* dtot = g->dtot + 256 * (shift / 8);
-    sort_hist_kernel<<<nblocks, SM_THREADS, 0, s>>>(g->keys[cur], n, shift, g->hist, nblocks, dtot);
-    HIPCHK(hipGetLastError());
-    sort_scan_kernel<<<256, SM_THREADS, 0, s>>>(g->hist, nblocks, dtot);
-    HIPCHK(hipGetLastError());
-    sort_scatter_kernel<<<nblocks, SM_THREADS, 0, s>>>(g->keys[cur], g->vals[cur], g->keys[cur ^ 1], g->vals[cur ^ 1], n, shift, g->hist, nblocks);
-    HIPCHK(hipGetLastError());
-    cur ^= 1;
-  }
-  gp_cell_start_kernel<<<(cells + 1 + SM_THREADS - 1) / SM_THREADS, SM_THREADS, 0, s>>>(g->keys[cur], n, cells, g->cell_start);
+  if ((rc = g->sort.sort_pairs(s, n, sort_bits_for_cells(cells), &cur))) return rc;
+  gp_cell_start_kernel<<<(cells + 1 + SM_THREADS - 1) / SM_THREADS, SM_THREADS, 0, s>>>(g->sort.keys[cur], n, cells, g->cell_start);
   HIPCHK(hipGetLastError());
-  gp_sorted_points_kernel<<<(n + SM_THREADS - 1) / SM_THREADS, SM_THREADS, 0, s>>>(g->pts, g->vals[cur], n, g->spts);
+  gp_sorted_points_kernel<<<(n + SM_THREADS - 1) / SM_THREADS, SM_THREADS, 0, s>>>(g->pts, g->sort.vals[cur], n, g->spts);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(g->ev[1], s));
   HIPCHK(hipStreamSynchronize(s));

@@ -2,6 +2,7 @@
 // descriptors of the same key frames). One rule for both: the key map's own stream, buffers that only grow (km->store), nothing freed before rolo_keymap_destroy.
 #pragma once
 #include "ctx_access.hpp"
+#include "sort_dev.hpp"
 
 namespace rolo {
 struct Seg { const float4* src; int n; int dst; float T[12]; };   // one key frame's cloud in the concatenation
@@ -24,10 +25,7 @@ struct rolo_keymap {
   float4* cat[2] = {nullptr, nullptr}; size_t cat_cap[2] = {0, 0};       // the concatenated, transformed clouds (corner, surface); cat[0] also stages rolo_keymap_downsample's input
   float4* sub[2] = {nullptr, nullptr}; size_t sub_cap[2] = {0, 0};       // the sub-map (laserCloud*FromMapDS)
   float4* ds_out = nullptr; size_t ds_cap = 0;                           // rolo_keymap_downsample's result
-  unsigned* keys[2] = {nullptr, nullptr}; size_t keys_cap[2] = {0, 0};
-  int* vals[2] = {nullptr, nullptr}; size_t vals_cap[2] = {0, 0};
-  unsigned* hist = nullptr; size_t hist_cap = 0;
-  unsigned* dtot = nullptr; size_t dtot_cap = 0;   // [4 passes][256 digits]
+  rolo::SortScratch sort;            // the voxel filter's sort of (cell, point index)
   unsigned* bcnt = nullptr; size_t bcnt_cap = 0;
   int* starts = nullptr; size_t starts_cap = 0;
   float* box_part = nullptr; size_t box_part_cap = 0;
@@ -36,7 +34,7 @@ struct rolo_keymap {
   float* h_box = nullptr;            // pinned [2][8]
   int* h_m = nullptr;                // pinned [2]
   rolo::Seg* h_segs = nullptr; size_t h_segs_cap = 0;   // pinned staging of the segment table
-  rolo::DevStore store;              // grows the scratch on the key map's stream; its retired buffers are freed by rolo_keymap_destroy
+  rolo::DevStore store;              // every buffer here and in `sc` is its allocation, on the key map's stream; rolo_keymap_destroy releases it
   int m_sub[2] = {0, 0};
   bool have_submap = false;
   rolo::ScStore* sc = nullptr;       // the Scan Context descriptors (scancontext.hip), created by the first rolo_keymap_sc_* call

@@ -8,15 +8,17 @@
 // iterations: one wavefront walks the target's tree once for its 64 queries (ballot-driven descent, node boxes and leaves through wave-uniform fetches, as
 // knn_packet.hpp's walk) with ONE best key per lane, (d2, index) packed so that an integer minimum is the nearest point with the smallest index. The search starts
 // at the correspondence cap, so a source point beyond it leaves the tree at the root. The same kernel forms the 17 fp64 sums of the kept pairs and reduces them per
-// workgroup; sum_rows (dev_rows.hpp) adds the workgroups' rows in a fixed order into pinned host memory (one 136-byte read-back per iteration, the precedent of scan2map.hip).
-// The 3 x 3 SVD and the convergence tests run on the host in double; icp_transform_kernel (transform12) multiplies the resident source by the float increment.
-// The tree and the walk live in a registration context (its stream, its builder); the scratch hangs off that context, only grows and is freed with it.
+// workgroup; sum_rows_segmented (dev_rows.hpp) adds the workgroups' rows in a fixed order into pinned host memory (one 136-byte read-back per iteration, the precedent of scan2map.hip).
+// The 3 x 3 SVD and the convergence tests run on the host in double; the float increment goes into a 56-byte control record in pinned host memory, which the next
+// launch reads in place and applies to the resident source when it loads a point: no transform launch, no copy. The tree and the walk live in a registration context (its stream, its builder); the scratch
+// hangs off that context, only grows and is freed with it.
 //
-// The batched form (rolo_loopicp_align_batch: the ground prior's association, performPriorAssociation :1943-2158, one ICP per stored patch near the current key
-// pose, all against the same ground patch): patch-sized clouds leave most of the device idle and pay the per-iteration launches and the host exchange once per
-// candidate and iteration. There every candidate owns whole workgroups of one `cur`, ONE launch of icp_assoc_batch_kernel per iteration serves all of them — it
-// applies the previous iteration's increment when it loads a point, so no transform launch — sum_rows_segmented adds each candidate's rows, and the host waits
-// once per iteration for the batch and runs the single form's step (loop_host_step) per candidate. Each candidate's bits are the single form's.
+// ONE loop serves one source and many (loop_align_batch; rolo_loopicp_align_batch is the ground prior's association, performPriorAssociation :1943-2158, one ICP
+// per stored patch near the current key pose, all against the same ground patch): patch-sized clouds leave most of the device idle and would pay the
+// per-iteration launches and the host exchange once per candidate and iteration. Every candidate owns whole workgroups of one `cur`, ONE launch of
+// icp_assoc_batch_kernel per iteration serves all of them, sum_rows_segmented adds each candidate's rows, and the host waits once per iteration for the batch and
+// runs loop_host_step per candidate. A candidate's bits depend on its own source, the target and the settings alone; the single entry points (loop_align:
+// rolo_loopicp_align, rolo_keymap_loop_icp) are a batch of one, and rolo_loopicp_associate is one launch of it with the per-point outputs switched on.
 #include "keymap.hpp"
 #include "knn_packet.hpp"
 #include "dev_rows.hpp"
@@ -32,19 +34,6 @@ namespace {
 
 constexpr int ICP_THREADS = 256;
 constexpr int ICP_NV = 17;   // n, sum d2, sum p (3), sum q (3), sum p q^T (9, row = p, column = q)
-
-struct IcpArgs {
-  const float4* cur;       // the moved source in curve order: x, y, z, bits(index in the caller's order); padding: index INT_MAX
-  int n_sorted;
-  const float4* tsorted;   // the target's tree
-  const float4* tboxes;
-  const float4* txyz;      // the target in the caller's order
-  int P, n_leaves;
-  float cap2;              // the largest float whose double is <= max_correspondence_distance^2
-  double* partials;        // grid x ICP_NV
-  int32_t* idx_out;        // per source point in the caller's order (tests), or nullptr
-  float* d2_out;
-};
 
 ROLO_DEV unsigned long long icp_key(float d2, int idx) { return ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)idx; }
 
@@ -127,29 +116,9 @@ ROLO_DEV void icp_block_row(const double* acc, double (*red)[ICP_NV], int wv, in
   }
 }
 
-__global__ __launch_bounds__(ICP_THREADS) void icp_assoc_kernel(IcpArgs A) {
-  __shared__ int stk_[ICP_THREADS / 64][WALK_STACK];
-  __shared__ double red[ICP_THREADS / 64][ICP_NV];
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int j = blockIdx.x * ICP_THREADS + threadIdx.x;
-  float4 qs = make_float4(0.f, 0.f, 0.f, __int_as_float(INT_MAX));
-  if (j < A.n_sorted) qs = A.cur[j];
-  const int qidx = __float_as_int(qs.w);
-  const bool active = qidx != INT_MAX;
-  const float4 q = make_float4(active ? qs.x : 0.f, active ? qs.y : 0.f, active ? qs.z : 0.f, 0.f);
-  const unsigned long long best = icp_walk(A.tsorted, A.tboxes, A.P, A.n_leaves, q, active, A.cap2, (lds_int*)&stk_[wv][0]);
-  const int ti = (int)(unsigned)(best & 0xffffffffull);
-  const bool kept = active && ti != INT_MAX;
-  const float d2 = __uint_as_float((unsigned)(best >> 32));
-  double acc[ICP_NV];
-  icp_pair_terms(kept, qs, d2, ti, A.txyz, acc);
-  if (active && A.idx_out) { A.idx_out[qidx] = kept ? ti : -1; A.d2_out[qidx] = kept ? d2 : INFINITY; }
-  icp_block_row(acc, red, wv, lane, A.partials + (size_t)blockIdx.x * ICP_NV);
-}
-
-// ---- the batched form: B sources against one target, every candidate's association in ONE launch per iteration ------------------------------------
-// Candidate b owns the workgroups [seg[b].x, seg[b].x + seg[b].y) of `cur` (its sorted source as loop_setup leaves it, padded to whole workgroups with
-// INT_MAX slots: the 256-point partition of the single form); a workgroup reads its candidate's control record, which the host rewrites between launches.
+// ---- B sources against one target, every candidate's association in ONE launch per iteration ---------------------------------------------------------
+// Candidate b owns the workgroups [seg[b].x, seg[b].x + seg[b].y) of `cur` (its source, moved by its guess and sorted along the target's curve, padded to whole
+// workgroups with INT_MAX slots); a workgroup reads its candidate's control record, which the host rewrites between launches.
 constexpr int ICP_MODE_ITERATE = 0, ICP_MODE_FITNESS = 1, ICP_MODE_IDLE = 2;   // the kernel treats ITERATE and FITNESS alike: they differ in cap2 and on the host
 constexpr int ICP_MODE_MOVE = 4;                                              // bit: apply `inc` on load (absent in a candidate's first launch: the points stay as they are, signed zeros too)
 struct IcpCtl { float inc[12]; float cap2; int mode; };
@@ -157,14 +126,16 @@ constexpr int ICP_CTL_WORDS = (int)(sizeof(IcpCtl) / sizeof(int)), ICP_CTL_MODE_
 static_assert(sizeof(IcpCtl) == 56 && offsetof(IcpCtl, mode) == 4 * ICP_CTL_MODE_WORD, "control record layout");
 
 struct IcpBatchArgs {
-  float4* cur;             // all candidates' segments
+  float4* cur;             // all candidates' segments: x, y, z, bits(index in the caller's order); padding: index INT_MAX
   const int* blk_cand;     // workgroup -> candidate
-  const IcpCtl* ctl;       // per candidate
+  const IcpCtl* ctl;       // per candidate, in pinned host memory
   const float4* tsorted;
   const float4* tboxes;
   const float4* txyz;
   int P, n_leaves;
   double* partials;        // grid x ICP_NV
+  int32_t* idx_out;        // rolo_loopicp_associate: per point of ONE candidate in the caller's order; nullptr otherwise
+  float* d2_out;
 };
 
 __global__ __launch_bounds__(ICP_THREADS) void icp_assoc_batch_kernel(IcpBatchArgs A) {
@@ -179,7 +150,7 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_assoc_batch_kernel(IcpBatchAr
   float4 qs = A.cur[j];
   const int qidx = __float_as_int(qs.w);
   const bool active = qidx != INT_MAX;
-  if (mode & ICP_MODE_MOVE) {   // the increment of the previous iteration, in place of a launch of icp_transform_kernel<true>
+  if (mode & ICP_MODE_MOVE) {   // the increment of the previous iteration
     float T[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) T[i] = ctl->inc[i];
@@ -194,25 +165,25 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_assoc_batch_kernel(IcpBatchAr
   const float d2 = __uint_as_float((unsigned)(best >> 32));
   double acc[ICP_NV];
   icp_pair_terms(kept, qs, d2, ti, A.txyz, acc);
+  if (active && A.idx_out) { A.idx_out[qidx] = kept ? ti : -1; A.d2_out[qidx] = kept ? d2 : INFINITY; }
   icp_block_row(acc, red, wv, lane, A.partials + (size_t)blockIdx.x * ICP_NV);
 }
 
-// a candidate's sorted source into its segment of `cur`; the slots behind it, up to whole workgroups, become padding
-__global__ __launch_bounds__(256) void icp_segment_kernel(const float4* __restrict__ sorted, int n_sorted, float4* __restrict__ seg, int n_seg) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_seg) return;
-  seg[i] = i < n_sorted ? sorted[i] : make_float4(0.f, 0.f, 0.f, __int_as_float(INT_MAX));
+// candidate b's sorted source into its segment of `cur`, one workgroup of this launch per workgroup of the segment; the slots behind the source become
+// padding. The launch writes the candidate's entries of the two tables too: no table travels from the host.
+__global__ __launch_bounds__(ICP_THREADS) void icp_segment_kernel(const float4* __restrict__ sorted, int n_sorted, float4* __restrict__ cur, int2 sg, int b,
+                                                                  int* __restrict__ blk_cand, int2* __restrict__ seg) {
+  const int i = blockIdx.x * ICP_THREADS + threadIdx.x;   // (gridDim.x = sg.y)
+  cur[(size_t)sg.x * ICP_THREADS + i] = i < n_sorted ? sorted[i] : make_float4(0.f, 0.f, 0.f, __int_as_float(INT_MAX));
+  if (threadIdx.x == 0) { blk_cand[sg.x + blockIdx.x] = b; if (blockIdx.x == 0) seg[b] = sg; }
 }
 
 struct Rows12 { float T[12]; };
-// out = T * in (transform12); a padding slot (KEEP_PAD, index INT_MAX) stays as it is
-template <bool KEEP_PAD>
-__global__ __launch_bounds__(256) void icp_transform_kernel(const float4* in, float4* out /* may be in */, int n, Rows12 R) {
+// out = T * in (transform12): the guess, ahead of the sort
+__global__ __launch_bounds__(256) void icp_transform_kernel(const float4* in, float4* out, int n, Rows12 R) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const float4 p = in[i];
-  if (KEEP_PAD && __float_as_int(p.w) == INT_MAX) { out[i] = p; return; }
-  out[i] = transform12(R.T, p);
+  out[i] = transform12(R.T, in[i]);
 }
 
 // ---- host: Umeyama without scaling, in double ------------------------------------------------------------------------------------------------
@@ -294,25 +265,20 @@ inline float cap2_float(double max_dist) {   // the largest float f with (double
 }
 
 struct LoopIcp {
-  float4 *src = nullptr, *tgt = nullptr, *srcg = nullptr, *cur = nullptr; size_t src_cap = 0, tgt_cap = 0, srcg_cap = 0, cur_cap = 0;
+  float4 *src = nullptr, *tgt = nullptr, *srcg = nullptr, *cur = nullptr; size_t src_cap = 0, tgt_cap = 0, srcg_cap = 0, cur_cap = 0;   // src: the (concatenated) sources in the caller's order
   double* part = nullptr; size_t part_cap = 0;
   int32_t* idx = nullptr; size_t idx_cap = 0;
   float* d2 = nullptr; size_t d2_cap = 0;
-  double* h_sum = nullptr;          // pinned: the 17 sums of an association, written by sum_rows
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  float ms[4] = {0.f, 0.f, 0.f, 0.f};
-  DevStore store{nullptr, "loop ICP"};   // grows the buffers above (nothing is kept across a growth: no stream); what they outgrew is freed with the context
-  std::vector<rolo_loopicp_trace_rec> trace;
-  // the batched form (loop_align_batch)
-  float4* bsrc = nullptr; size_t bsrc_cap = 0;       // the concatenated sources in the caller's order
   int* blk_cand = nullptr; size_t blk_cand_cap = 0;
-  int2* seg = nullptr; size_t seg_cap = 0;
-  IcpCtl* ctl = nullptr; size_t ctl_cap = 0;
-  IcpCtl* h_ctl = nullptr; size_t h_ctl_cap = 0;     // pinned: the control table as the next launch reads it
-  double* h_bsum = nullptr; size_t h_bsum_cap = 0;   // pinned: B x 17 sums, written by sum_rows_segmented
-  hipEvent_t bev[3] = {nullptr, nullptr, nullptr};
-  float bms[4] = {0.f, 0.f, 0.f, 0.f};
-  std::vector<std::vector<rolo_loopicp_trace_rec>> btrace;
+  int2* seg = nullptr; size_t seg_cap = 0;           // (an empty candidate's entry is never written, nor read: it is IDLE from the start)
+  IcpCtl* h_ctl = nullptr; size_t h_ctl_cap = 0;   // pinned: the control table, which the kernels read where it lies (no copy per launch); the host rewrites it
+                                                   // only between a wait for the stream and the next launch
+  double* h_sum = nullptr; size_t h_sum_cap = 0;   // pinned: B x 17 sums, written by sum_rows_segmented
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // start, set-up done, the single form's fitness pass begins, end
+  DevStore store{nullptr, "loop ICP"};   // every buffer above (nothing is kept across a growth: no stream); freed with the context
+  // per call kind: the last single alignment's (or association's) times and records, the last batch call's
+  float ms[4] = {0.f, 0.f, 0.f, 0.f}, bms[4] = {0.f, 0.f, 0.f, 0.f};
+  std::vector<std::vector<rolo_loopicp_trace_rec>> trace, btrace;   // (trace: no or one candidate)
 };
 
 int loop_state(rolo_ctx* c, LoopIcp** out) {
@@ -321,9 +287,7 @@ int loop_state(rolo_ctx* c, LoopIcp** out) {
     W = new LoopIcp();
     *ctx_loop_slot(c) = W;
     HIPCHK(hipSetDevice(ctx_device(c)));
-    HIPCHK(hipHostMalloc((void**)&W->h_sum, sizeof(double) * ICP_NV));
     for (int i = 0; i < 4; i++) HIPCHK(hipEventCreate(&W->ev[i]));
-    for (int i = 0; i < 3; i++) HIPCHK(hipEventCreate(&W->bev[i]));
   }
   *out = W;
   return ROLO_OK;
@@ -342,40 +306,12 @@ int loop_sorted(rolo_ctx* c, LoopIcp* W, const float4* d_src, int ns, const floa
   if (T16 && !is_identity16(T16)) {
     if ((rc = W->store.grow(W->srcg, W->srcg_cap, (size_t)ns))) return rc;
     Rows12 R; std::memcpy(R.T, T16, sizeof(R.T));
-    icp_transform_kernel<false><<<(ns + 255) / 256, 256, 0, s>>>(d_src, W->srcg, ns, R);
+    icp_transform_kernel<<<(ns + 255) / 256, 256, 0, s>>>(d_src, W->srcg, ns, R);
     HIPCHK(hipGetLastError());
     moved = W->srcg;
   }
   *pair = KnnPair{};
   return ctx_build_map_trees(c, reinterpret_cast<const float*>(d_tgt), nt, reinterpret_cast<const float*>(moved), ns, 4, pair, true);
-}
-
-// the moved source sorted along the target's curve, in W->cur, and the target's tree
-int loop_setup(rolo_ctx* c, LoopIcp* W, const float4* d_src, int ns, const float4* d_tgt, int nt, const float* T16, IcpArgs* A, int* grid) {
-  hipStream_t s = ctx_stream(c);
-  int rc;
-  KnnPair pair{};
-  if ((rc = loop_sorted(c, W, d_src, ns, d_tgt, nt, T16, &pair))) return rc;
-  const int n_sorted = pair.c[1].n_sorted;
-  *grid = (n_sorted + ICP_THREADS - 1) / ICP_THREADS;
-  if ((rc = W->store.grow(W->cur, W->cur_cap, (size_t)n_sorted))) return rc;
-  if ((rc = W->store.grow(W->part, W->part_cap, (size_t)*grid * ICP_NV))) return rc;
-  HIPCHK(hipMemcpyAsync(W->cur, pair.c[1].sorted, sizeof(float4) * (size_t)n_sorted, hipMemcpyDeviceToDevice, s));
-  *A = IcpArgs{};
-  A->cur = W->cur; A->n_sorted = n_sorted; A->tsorted = pair.c[0].sorted; A->tboxes = pair.c[0].boxes; A->txyz = pair.c[0].xyz; A->P = pair.c[0].P;
-  A->n_leaves = pair.c[0].n_leaves; A->partials = W->part;
-  return ROLO_OK;
-}
-
-// one association on the stream, its 17 sums in W->h_sum when this returns
-int loop_associate(rolo_ctx* c, LoopIcp* W, const IcpArgs& A, int grid) {
-  hipStream_t s = ctx_stream(c);
-  icp_assoc_kernel<<<grid, ICP_THREADS, 0, s>>>(A);
-  HIPCHK(hipGetLastError());
-  sum_rows<ICP_NV, 1><<<1, 256, 0, s>>>(A.partials, grid, W->h_sum);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(s));
-  return ROLO_OK;
 }
 
 void matmul4f(const float* a, const float* b, float* o) {   // o = a b, each entry a0 b0 + a1 b1 + a2 b2 + a3 b3 left to right
@@ -430,59 +366,9 @@ void loop_host_fitness(const double* h, rolo_loopicp_result& res, std::vector<ro
   res.fitness = tr.n > 0 ? tr.mse : DBL_MAX;
 }
 
-int loop_align(rolo_ctx* c, const float4* d_src, int ns, const float4* d_tgt, int nt, const rolo_loopicp_params* P, const float* guess16, rolo_loopicp_result* out) {
-  LoopIcp* W = nullptr;
-  int rc = loop_state(c, &W);
-  if (rc) return rc;
-  if (!(P->max_correspondence_distance >= 0.0) || P->max_iterations < 0) { ctx_set_error("loop ICP: bad parameters"); return ROLO_EINVAL; }
-  HIPCHK(hipSetDevice(ctx_device(c)));
-  hipStream_t s = ctx_stream(c);
-  rolo_loopicp_result res{};
-  for (int i = 0; i < 16; i++) res.T[i] = guess16 ? guess16[i] : ((i % 5 == 0) ? 1.f : 0.f);
-  res.n_source = ns; res.n_target = nt; res.fitness = DBL_MAX; res.state = ROLO_ICP_NOT_CONVERGED;
-  W->trace.clear();
-  for (float& m : W->ms) m = 0.f;
-  if (ns <= 0 || nt <= 0) { res.state = ROLO_ICP_NO_CORRESPONDENCES; *out = res; return ROLO_OK; }
-  HIPCHK(hipEventRecord(W->ev[0], s));
-  IcpArgs A{};
-  int grid = 0;
-  if ((rc = loop_setup(c, W, d_src, ns, d_tgt, nt, guess16, &A, &grid))) return rc;
-  HIPCHK(hipEventRecord(W->ev[1], s));
-  A.cap2 = cap2_float(P->max_correspondence_distance);
-  const double rot_thr = P->rotation_epsilon > 0 ? P->rotation_epsilon : 1.0 - P->transformation_epsilon;
-  double prev = DBL_MAX;
-  const double* h = W->h_sum;
-  while (true) {
-    if ((rc = loop_associate(c, W, A, grid))) return rc;
-    float inc[16];
-    bool have_inc = false;
-    const bool done = loop_host_step(h, P, rot_thr, res, prev, W->trace, inc, &have_inc);
-    if (have_inc) {
-      Rows12 Rw; std::memcpy(Rw.T, inc, sizeof(Rw.T));
-      icp_transform_kernel<true><<<(A.n_sorted + 255) / 256, 256, 0, s>>>(W->cur, W->cur, A.n_sorted, Rw);
-      HIPCHK(hipGetLastError());
-    }
-    if (done) break;
-  }
-  HIPCHK(hipEventRecord(W->ev[2], s));
-  {   // getFitnessScore(): the moved source as it stands, no cap
-    A.cap2 = INFINITY;
-    if ((rc = loop_associate(c, W, A, grid))) return rc;
-    loop_host_fitness(h, res, W->trace);
-  }
-  HIPCHK(hipEventRecord(W->ev[3], s));
-  HIPCHK(hipEventSynchronize(W->ev[3]));
-  (void)hipEventElapsedTime(&W->ms[0], W->ev[0], W->ev[1]);
-  (void)hipEventElapsedTime(&W->ms[1], W->ev[1], W->ev[2]);
-  (void)hipEventElapsedTime(&W->ms[2], W->ev[2], W->ev[3]);
-  (void)hipEventElapsedTime(&W->ms[3], W->ev[0], W->ev[3]);
-  *out = res;
-  return ROLO_OK;
-}
-
-int loop_upload(rolo_ctx* c, LoopIcp* W, const float* src, int ns, const float* tgt, int nt) {
+int loop_upload(rolo_ctx* c, LoopIcp* W, const float* src, long long ns, const float* tgt, int nt) {
   int rc;
-  if ((rc = W->store.grow(W->src, W->src_cap, (size_t)std::max(ns, 1)))) return rc;
+  if ((rc = W->store.grow(W->src, W->src_cap, (size_t)std::max(ns, 1ll)))) return rc;
   if ((rc = W->store.grow(W->tgt, W->tgt_cap, (size_t)std::max(nt, 1)))) return rc;
   hipStream_t s = ctx_stream(c);
   if (ns > 0) HIPCHK(hipMemcpyAsync(W->src, src, sizeof(float4) * (size_t)ns, hipMemcpyHostToDevice, s));
@@ -490,113 +376,139 @@ int loop_upload(rolo_ctx* c, LoopIcp* W, const float* src, int ns, const float* 
   return ROLO_OK;
 }
 
-// B sources (concatenated at d_srcs, ns[b] points each) against one target: loop_align per candidate, with every candidate's association in one launch per
-// iteration and one exchange with the host per iteration for all of them. Candidate b's results are those of loop_align(source b, target), bit for bit: its
-// sorted order and 256-point workgroups are the single form's (the same builder, once per candidate; the target's tree of the last build serves all, a tree's
-// shape never changes an association's result), its rows are added in sum_rows' order, and the host step is the same code.
-int loop_align_batch(rolo_ctx* c, LoopIcp* W, const float4* d_srcs, const int* ns, int B, const float4* d_tgt, int nt, const rolo_loopicp_params* P, const float* guess16,
-                     rolo_loopicp_result* out) {
-  if (!(P->max_correspondence_distance >= 0.0) || P->max_iterations < 0) { ctx_set_error("loop ICP: bad parameters"); return ROLO_EINVAL; }
-  int rc;
-  HIPCHK(hipSetDevice(ctx_device(c)));
+// Set-up for B sources (concatenated at d_srcs, ns[b] points each) against one target: every live candidate's segment of W->cur (the builder's sort, once per
+// candidate; the target's tree of the last build serves all, a tree's shape never changes an association's result), the tables, and the control records in
+// ITERATE mode at cap2. *n_live = 0 (an empty target, or no source with a point): nothing was touched on the device.
+int loop_segments(rolo_ctx* c, LoopIcp* W, const float4* d_srcs, const int* ns, int B, const float4* d_tgt, int nt, const float* guess16, float cap2, IcpBatchArgs* A,
+                  int* total_blocks_out, int* n_live_out) {
   hipStream_t s = ctx_stream(c);
-  W->btrace.assign((size_t)B, {});
-  for (float& m : W->bms) m = 0.f;
-  std::vector<double> prev((size_t)B, DBL_MAX);
+  int rc, total_blocks = 0, n_live = 0;
   std::vector<int2> seg((size_t)B);
-  int total_blocks = 0, n_live = 0;
   for (int b = 0; b < B; b++) {
-    rolo_loopicp_result& res = out[b];
-    res = rolo_loopicp_result{};
-    for (int i = 0; i < 16; i++) res.T[i] = guess16 ? guess16[16 * (size_t)b + i] : ((i % 5 == 0) ? 1.f : 0.f);
-    res.n_source = ns[b]; res.n_target = nt; res.fitness = DBL_MAX; res.state = ROLO_ICP_NOT_CONVERGED;
     const bool live = ns[b] > 0 && nt > 0;
-    if (!live) res.state = ROLO_ICP_NO_CORRESPONDENCES;
     const int n_sorted = live ? KNN_LEAF * ((ns[b] + KNN_LEAF - 1) / KNN_LEAF) : 0;   // (the builder's: KnnCloud::n_sorted)
     seg[b] = make_int2(total_blocks, (n_sorted + ICP_THREADS - 1) / ICP_THREADS);
     total_blocks += seg[b].y;
     n_live += live ? 1 : 0;
   }
+  *total_blocks_out = total_blocks; *n_live_out = n_live;
   if (n_live == 0) return ROLO_OK;
-  HIPCHK(hipEventRecord(W->bev[0], s));
-  // ---- setup: every candidate's segment, the tables ----
+  HIPCHK(hipEventRecord(W->ev[0], s));
   if ((rc = W->store.grow(W->cur, W->cur_cap, (size_t)total_blocks * ICP_THREADS))) return rc;
   if ((rc = W->store.grow(W->part, W->part_cap, (size_t)total_blocks * ICP_NV))) return rc;
   if ((rc = W->store.grow(W->blk_cand, W->blk_cand_cap, (size_t)total_blocks))) return rc;
   if ((rc = W->store.grow(W->seg, W->seg_cap, (size_t)B))) return rc;
-  if ((rc = W->store.grow(W->ctl, W->ctl_cap, (size_t)B))) return rc;
   if ((rc = W->store.grow_pinned(W->h_ctl, W->h_ctl_cap, (size_t)B, 16))) return rc;
-  if ((rc = W->store.grow_pinned(W->h_bsum, W->h_bsum_cap, (size_t)B * ICP_NV, 16 * ICP_NV))) return rc;
-  IcpBatchArgs A{};
-  {
-    size_t off = 0;
-    for (int b = 0; b < B; b++) {
-      if (seg[b].y > 0) {
-        KnnPair pair{};
-        if ((rc = loop_sorted(c, W, d_srcs + off, ns[b], d_tgt, nt, guess16 ? guess16 + 16 * (size_t)b : nullptr, &pair))) return rc;
-        if (pair.c[1].n_sorted > seg[b].y * ICP_THREADS) { ctx_set_error("loop ICP: the builder's sorted size is not the expected one"); return ROLO_ESTATE; }
-        const int n_seg = seg[b].y * ICP_THREADS;
-        icp_segment_kernel<<<seg[b].y, 256, 0, s>>>(pair.c[1].sorted, pair.c[1].n_sorted, W->cur + (size_t)seg[b].x * ICP_THREADS, n_seg);
-        HIPCHK(hipGetLastError());
-        A.tsorted = pair.c[0].sorted; A.tboxes = pair.c[0].boxes; A.txyz = pair.c[0].xyz; A.P = pair.c[0].P; A.n_leaves = pair.c[0].n_leaves;
-      }
-      off += (size_t)ns[b];
+  if ((rc = W->store.grow_pinned(W->h_sum, W->h_sum_cap, (size_t)B * ICP_NV, 16 * ICP_NV))) return rc;
+  *A = IcpBatchArgs{};
+  size_t off = 0;
+  for (int b = 0; b < B; b++) {
+    if (seg[b].y > 0) {
+      KnnPair pair{};
+      if ((rc = loop_sorted(c, W, d_srcs + off, ns[b], d_tgt, nt, guess16 ? guess16 + 16 * (size_t)b : nullptr, &pair))) return rc;
+      if (pair.c[1].n_sorted > seg[b].y * ICP_THREADS) { ctx_set_error("loop ICP: the builder's sorted size is not the expected one"); return ROLO_ESTATE; }
+      icp_segment_kernel<<<seg[b].y, ICP_THREADS, 0, s>>>(pair.c[1].sorted, pair.c[1].n_sorted, W->cur, seg[b], b, W->blk_cand, W->seg);
+      HIPCHK(hipGetLastError());
+      A->tsorted = pair.c[0].sorted; A->tboxes = pair.c[0].boxes; A->txyz = pair.c[0].xyz; A->P = pair.c[0].P; A->n_leaves = pair.c[0].n_leaves;
     }
+    off += (size_t)ns[b];
   }
-  std::vector<int> blk((size_t)total_blocks);   // (blk and seg outlive the first wait for the stream below)
-  for (int b = 0; b < B; b++) for (int k = 0; k < seg[b].y; k++) blk[(size_t)seg[b].x + k] = b;
-  HIPCHK(hipMemcpyAsync(W->blk_cand, blk.data(), sizeof(int) * (size_t)total_blocks, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(W->seg, seg.data(), sizeof(int2) * (size_t)B, hipMemcpyHostToDevice, s));
-  A.cur = W->cur; A.blk_cand = W->blk_cand; A.ctl = W->ctl; A.partials = W->part;
-  const float cap2 = cap2_float(P->max_correspondence_distance);
+  A->cur = W->cur; A->blk_cand = W->blk_cand; A->ctl = W->h_ctl; A->partials = W->part;
   for (int b = 0; b < B; b++) {
     IcpCtl& k = W->h_ctl[b];
     std::memset(&k, 0, sizeof(k));
     k.cap2 = cap2;
     k.mode = seg[b].y > 0 ? ICP_MODE_ITERATE : ICP_MODE_IDLE;
   }
-  HIPCHK(hipEventRecord(W->bev[1], s));
-  // ---- iterations: one launch, one segmented sum, one wait for all candidates ----
+  return ROLO_OK;
+}
+
+// one launch for all candidates as W->h_ctl stands, every live candidate's 17 sums in W->h_sum when this returns
+int loop_associate(rolo_ctx* c, LoopIcp* W, const IcpBatchArgs& A, int total_blocks, int B) {
+  hipStream_t s = ctx_stream(c);
+  icp_assoc_batch_kernel<<<total_blocks, ICP_THREADS, 0, s>>>(A);
+  HIPCHK(hipGetLastError());
+  sum_rows_segmented<ICP_NV><<<B, 256, 0, s>>>(W->part, W->seg, reinterpret_cast<const int*>(A.ctl) + ICP_CTL_MODE_WORD, ICP_CTL_WORDS, ICP_MODE_IDLE, W->h_sum);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(s));
+  return ROLO_OK;
+}
+
+// The ICP of B sources against one target, with every candidate's association in one launch per iteration and one exchange with the host per iteration for all
+// of them. Candidate b's results depend on nothing but its own source, the target, the settings and its guess: its sorted order and 256-point workgroups are its
+// own, its rows are added in a fixed order, and the host step is per candidate. traces[b] takes candidate b's records; ms4: set-up, iterations, the fitness pass
+// when split_fitness (B == 1: the host knows the launch at which the one candidate turns FITNESS) and 0 otherwise (then the iterations carry the fitness
+// passes), the whole call.
+int loop_align_batch(rolo_ctx* c, LoopIcp* W, const float4* d_srcs, const int* ns, int B, const float4* d_tgt, int nt, const rolo_loopicp_params* P, const float* guess16,
+                     rolo_loopicp_result* out, std::vector<std::vector<rolo_loopicp_trace_rec>>& traces, float* ms4, bool split_fitness) {
+  if (!(P->max_correspondence_distance >= 0.0) || P->max_iterations < 0) { ctx_set_error("loop ICP: bad parameters"); return ROLO_EINVAL; }
+  int rc;
+  HIPCHK(hipSetDevice(ctx_device(c)));
+  hipStream_t s = ctx_stream(c);
+  traces.assign((size_t)B, {});
+  for (int i = 0; i < 4; i++) ms4[i] = 0.f;
+  std::vector<double> prev((size_t)B, DBL_MAX);
+  for (int b = 0; b < B; b++) {
+    rolo_loopicp_result& res = out[b];
+    res = rolo_loopicp_result{};
+    for (int i = 0; i < 16; i++) res.T[i] = guess16 ? guess16[16 * (size_t)b + i] : ((i % 5 == 0) ? 1.f : 0.f);
+    res.n_source = ns[b]; res.n_target = nt; res.fitness = DBL_MAX;
+    res.state = ns[b] > 0 && nt > 0 ? ROLO_ICP_NOT_CONVERGED : ROLO_ICP_NO_CORRESPONDENCES;
+  }
+  IcpBatchArgs A{};
+  int total_blocks = 0, n_live = 0;
+  if ((rc = loop_segments(c, W, d_srcs, ns, B, d_tgt, nt, guess16, cap2_float(P->max_correspondence_distance), &A, &total_blocks, &n_live))) return rc;
+  if (n_live == 0) return ROLO_OK;
+  HIPCHK(hipEventRecord(W->ev[1], s));
   const double rot_thr = P->rotation_epsilon > 0 ? P->rotation_epsilon : 1.0 - P->transformation_epsilon;
   while (n_live > 0) {
-    HIPCHK(hipMemcpyAsync(W->ctl, W->h_ctl, sizeof(IcpCtl) * (size_t)B, hipMemcpyHostToDevice, s));
-    icp_assoc_batch_kernel<<<total_blocks, ICP_THREADS, 0, s>>>(A);
-    HIPCHK(hipGetLastError());
-    sum_rows_segmented<ICP_NV><<<B, 256, 0, s>>>(W->part, W->seg, reinterpret_cast<const int*>(W->ctl) + ICP_CTL_MODE_WORD, ICP_CTL_WORDS, ICP_MODE_IDLE, W->h_bsum);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));
+    if ((rc = loop_associate(c, W, A, total_blocks, B))) return rc;
     for (int b = 0; b < B; b++) {
       IcpCtl& k = W->h_ctl[b];
       if (k.mode == ICP_MODE_IDLE) continue;
-      const double* h = W->h_bsum + (size_t)b * ICP_NV;
+      const double* h = W->h_sum + (size_t)b * ICP_NV;
       if ((k.mode & 3) == ICP_MODE_FITNESS) {   // getFitnessScore(): the moved source as it stood, no cap
-        loop_host_fitness(h, out[b], W->btrace[b]);
+        loop_host_fitness(h, out[b], traces[b]);
         k.mode = ICP_MODE_IDLE;
         n_live--;
         continue;
       }
       float inc[16];
       bool have_inc = false;
-      const bool done = loop_host_step(h, P, rot_thr, out[b], prev[b], W->btrace[b], inc, &have_inc);
+      const bool done = loop_host_step(h, P, rot_thr, out[b], prev[b], traces[b], inc, &have_inc);
       if (have_inc) std::memcpy(k.inc, inc, sizeof(k.inc));
       k.mode = (done ? ICP_MODE_FITNESS : ICP_MODE_ITERATE) | (have_inc ? ICP_MODE_MOVE : 0);   // the next launch applies the increment on load
       if (done) k.cap2 = INFINITY;
+      if (done && split_fitness) HIPCHK(hipEventRecord(W->ev[2], s));
     }
   }
-  HIPCHK(hipEventRecord(W->bev[2], s));
-  HIPCHK(hipEventSynchronize(W->bev[2]));
-  (void)hipEventElapsedTime(&W->bms[0], W->bev[0], W->bev[1]);
-  (void)hipEventElapsedTime(&W->bms[1], W->bev[1], W->bev[2]);
-  (void)hipEventElapsedTime(&W->bms[3], W->bev[0], W->bev[2]);
+  HIPCHK(hipEventRecord(W->ev[3], s));
+  HIPCHK(hipEventSynchronize(W->ev[3]));
+  (void)hipEventElapsedTime(&ms4[0], W->ev[0], W->ev[1]);
+  (void)hipEventElapsedTime(&ms4[1], W->ev[1], split_fitness ? W->ev[2] : W->ev[3]);
+  if (split_fitness) (void)hipEventElapsedTime(&ms4[2], W->ev[2], W->ev[3]);
+  (void)hipEventElapsedTime(&ms4[3], W->ev[0], W->ev[3]);
   return ROLO_OK;
 }
 
-int copy_trace(rolo_ctx* c, rolo_loopicp_trace_rec* out, int cap) {
+// one source: a batch of one, its records and times kept apart from the batch calls'
+int loop_align(rolo_ctx* c, const float4* d_src, int ns, const float4* d_tgt, int nt, const rolo_loopicp_params* P, const float* guess16, rolo_loopicp_result* out) {
+  LoopIcp* W = nullptr;
+  int rc = loop_state(c, &W);
+  if (rc) return rc;
+  rolo_loopicp_result res{};
+  if ((rc = loop_align_batch(c, W, d_src, &ns, 1, d_tgt, nt, P, guess16, &res, W->trace, W->ms, true))) return rc;
+  *out = res;
+  return ROLO_OK;
+}
+
+int copy_records(const std::vector<rolo_loopicp_trace_rec>& t, rolo_loopicp_trace_rec* out, int cap) {
+  for (int i = 0; i < std::min((int)t.size(), cap); i++) out[i] = t[i];
+  return (int)t.size();
+}
+int copy_trace(rolo_ctx* c, rolo_loopicp_trace_rec* out, int cap) {   // the last single alignment's or association's
   LoopIcp* W = static_cast<LoopIcp*>(*ctx_loop_slot(c));
-  if (!W) return 0;
-  const int m = (int)W->trace.size();
-  for (int i = 0; i < std::min(m, cap); i++) out[i] = W->trace[i];
-  return m;
+  return !W || W->trace.empty() ? 0 : copy_records(W->trace[0], out, cap);
 }
 
 }  // namespace
@@ -609,14 +521,10 @@ extern "C" {
 void rolo_loopicp_destroy(rolo_ctx* c) {   // called by rolo_ctx_destroy
   LoopIcp* W = static_cast<LoopIcp*>(*ctx_loop_slot(c));
   if (!W) return;
-  for (void* p : {(void*)W->src, (void*)W->tgt, (void*)W->srcg, (void*)W->cur, (void*)W->part, (void*)W->idx, (void*)W->d2}) if (p) (void)hipFree(p);
+  (void)hipSetDevice(ctx_device(c));
+  (void)hipStreamSynchronize(ctx_stream(c));
   W->store.release();
-  if (W->h_sum) (void)hipHostFree(W->h_sum);
-  for (void* p : {(void*)W->bsrc, (void*)W->blk_cand, (void*)W->seg, (void*)W->ctl}) if (p) (void)hipFree(p);
-  if (W->h_ctl) (void)hipHostFree(W->h_ctl);
-  if (W->h_bsum) (void)hipHostFree(W->h_bsum);
   for (hipEvent_t e : W->ev) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : W->bev) if (e) (void)hipEventDestroy(e);
   delete W;
   *ctx_loop_slot(c) = nullptr;
 }
@@ -674,13 +582,9 @@ int rolo_loopicp_align_batch(rolo_ctx* c, const float* sources, const int* n_sou
   int rc = loop_state(c, &W);
   if (rc) return rc;
   HIPCHK(hipSetDevice(ctx_device(c)));
-  hipStream_t s = ctx_stream(c);
-  if ((rc = W->store.grow(W->bsrc, W->bsrc_cap, (size_t)std::max(total, 1ll)))) return rc;
-  if ((rc = W->store.grow(W->tgt, W->tgt_cap, (size_t)std::max(n_target, 1)))) return rc;
-  if (total > 0) HIPCHK(hipMemcpyAsync(W->bsrc, sources, sizeof(float4) * (size_t)total, hipMemcpyHostToDevice, s));
-  if (n_target > 0) HIPCHK(hipMemcpyAsync(W->tgt, target, sizeof(float4) * (size_t)n_target, hipMemcpyHostToDevice, s));
-  rc = loop_align_batch(c, W, W->bsrc, n_source, B, W->tgt, n_target, params, guess16, out);
-  if (rc) (void)hipStreamSynchronize(s);   // the caller's arrays are free again, whatever happened
+  if ((rc = loop_upload(c, W, sources, total, target, n_target))) return rc;
+  rc = loop_align_batch(c, W, W->src, n_source, B, W->tgt, n_target, params, guess16, out, W->btrace, W->bms, false);
+  if (rc) (void)hipStreamSynchronize(ctx_stream(c));   // the caller's arrays are free again, whatever happened
   return rc;
 }
 
@@ -688,9 +592,7 @@ int rolo_loopicp_get_trace_batch(rolo_ctx* c, int b, rolo_loopicp_trace_rec* out
   if (!c || b < 0 || cap < 0 || (cap && !out)) return ROLO_EINVAL;
   LoopIcp* W = static_cast<LoopIcp*>(*ctx_loop_slot(c));
   if (!W || b >= (int)W->btrace.size()) return ROLO_EINVAL;
-  const int m = (int)W->btrace[b].size();
-  for (int i = 0; i < std::min(m, cap); i++) out[i] = W->btrace[b][i];
-  return m;
+  return copy_records(W->btrace[b], out, cap);
 }
 
 int rolo_loopicp_batch_last_ms(rolo_ctx* c, float* ms4) {
@@ -718,18 +620,15 @@ int rolo_loopicp_associate(rolo_ctx* c, const float* source, int n_source, const
   if ((rc = loop_upload(c, W, source, n_source, target, n_target))) return rc;
   if ((rc = W->store.grow(W->idx, W->idx_cap, (size_t)n_source))) return rc;
   if ((rc = W->store.grow(W->d2, W->d2_cap, (size_t)n_source))) return rc;
-  IcpArgs A{};
-  int grid = 0;
-  W->trace.clear();
-  rc = loop_setup(c, W, W->src, n_source, W->tgt, n_target, T16, &A, &grid);
+  IcpBatchArgs A{};
+  int total_blocks = 0, n_live = 0;
+  W->trace.assign(1, {});
+  rc = loop_segments(c, W, W->src, &n_source, 1, W->tgt, n_target, T16, cap2_float(max_correspondence_distance), &A, &total_blocks, &n_live);
   if (rc) { (void)hipStreamSynchronize(s); return rc; }
-  A.cap2 = cap2_float(max_correspondence_distance);
   A.idx_out = W->idx; A.d2_out = W->d2;
-  if ((rc = loop_associate(c, W, A, grid))) return rc;
-  rolo_loopicp_trace_rec tr{};
-  tr.n = (int)(W->h_sum[0] + 0.5); tr.mse = tr.n > 0 ? W->h_sum[1] / tr.n : 0.0;
-  std::memcpy(tr.sums, W->h_sum, sizeof(tr.sums));
-  W->trace.push_back(tr);
+  if ((rc = loop_associate(c, W, A, total_blocks, 1))) return rc;
+  rolo_loopicp_result unused{};
+  loop_host_fitness(W->h_sum, unused, W->trace[0]);
   HIPCHK(hipMemcpyAsync(index_out, W->idx, sizeof(int32_t) * (size_t)n_source, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(d2_out, W->d2, sizeof(float) * (size_t)n_source, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));

@@ -1104,13 +1104,13 @@ int rolo_pgo_create(int device, rolo_pgo** out) {
   int khz = 0;
   if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) g->wall_khz = (double)khz;
   if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&g->ev[0]) != hipSuccess || hipEventCreate(&g->ev[1]) != hipSuccess ||
-      hipEventCreate(&g->gev[0]) != hipSuccess || hipEventCreate(&g->gev[1]) != hipSuccess || hipEventCreate(&g->gev[2]) != hipSuccess ||
-      hipHostMalloc((void**)&g->h_info, sizeof(double) * 8) != hipSuccess) {
-    ctx_set_error("rolo_pgo_create: stream, events or pinned memory");
+      hipEventCreate(&g->gev[0]) != hipSuccess || hipEventCreate(&g->gev[1]) != hipSuccess || hipEventCreate(&g->gev[2]) != hipSuccess) {
+    ctx_set_error("rolo_pgo_create: stream or events");
     rolo_pgo_destroy(g);
     return ROLO_EHIP;
   }
   g->store.stream = g->stream; g->store.who = "pose graph"; g->store.slack = 64;
+  if (const int rc = g->store.alloc_pinned(g->h_info, 8)) { rolo_pgo_destroy(g); return rc; }
   *out = g;
   return ROLO_OK;
 }
@@ -1119,13 +1119,7 @@ void rolo_pgo_destroy(rolo_pgo* g) {
   if (!g) return;
   (void)hipSetDevice(g->device);
   if (g->stream) (void)hipStreamSynchronize(g->stream);
-  for (void* p : {(void*)g->poses, (void*)g->trial, (void*)g->d_factors, (void*)g->slots, (void*)g->rowptr, (void*)g->entries, (void*)g->diag, (void*)g->chain, (void*)g->grad,
-                  (void*)g->chordH, (void*)g->d_chord_factor, (void*)g->d_chord_ij, (void*)g->touched, (void*)g->touched_ptr, (void*)g->touched_ent, (void*)g->LD, (void*)g->LU,
-                  (void*)g->LW, (void*)g->B, (void*)g->X, (void*)g->vec[0], (void*)g->vec[1], (void*)g->vec[2], (void*)g->vec[3], (void*)g->vec[4], (void*)g->cscr, (void*)g->delta,
-                  (void*)g->partials, (void*)g->ferr, (void*)g->gst})
-    if (p) (void)hipFree(p);
   g->store.release();
-  if (g->h_info) (void)hipHostFree(g->h_info);
   for (hipEvent_t e : g->ev) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : g->gev) if (e) (void)hipEventDestroy(e);
   if (g->stream) (void)hipStreamDestroy(g->stream);

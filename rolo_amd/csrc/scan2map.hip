@@ -594,7 +594,8 @@ using namespace rolo;
 namespace rolo {
 struct S2mScratch { float4* feat = nullptr; double* part = nullptr; unsigned char* sel = nullptr; float4* coeff = nullptr;
                     size_t feat_cap = 0, part_cap = 0, sel_cap = 0, coeff_cap = 0;
-                    DevStore store{nullptr, "scan2map"};   // grows the four above (nothing is kept across a growth: no stream); what they outgrew is freed with the context
+                    int4* wstats = nullptr; size_t wstats_cap = 0;   // the per-wavefront counters of a statistics run
+                    DevStore store{nullptr, "scan2map"};   // allocates the four above and h_sum (nothing is kept across a growth: no stream); freed with the context
                     KnnPair maps{}; int m_corner = 0, m_surf = 0; bool have_maps = false;   // the resident sub-map (rolo_scan2map_set_submap): trees of the context's two clouds
                     bool map_set = false; unsigned long long maps_epoch = 0;   // a sub-map was handed in (possibly too small to search); the context's cloud epoch when its trees were built —
                                                                                // any later upload into the context (rolo_set_input_*, a registration, the pool) makes the raw pointers in `maps` stale
@@ -604,10 +605,10 @@ struct S2mScratch { float4* feat = nullptr; double* part = nullptr; unsigned cha
 extern "C" void rolo_s2m_destroy(rolo_ctx* c) {   // called by rolo_ctx_destroy
   S2mScratch* W = static_cast<S2mScratch*>(*ctx_s2m_slot(c));
   if (!W) return;
-  for (void* p : {(void*)W->feat, (void*)W->part, (void*)W->sel, (void*)W->coeff}) if (p) (void)hipFree(p);
+  (void)hipSetDevice(ctx_device(c));
+  (void)hipStreamSynchronize(ctx_stream(c));
   W->store.release();
   if (W->qev) (void)hipEventDestroy(W->qev);
-  if (W->h_sum) (void)hipHostFree(W->h_sum);
   rolo_ctx* q = W->qctx;
   delete W; *ctx_s2m_slot(c) = nullptr;
   if (q) rolo_ctx_release(q);
@@ -725,11 +726,11 @@ extern "C" int rolo_scan2map_optimize(rolo_ctx* c, const float* corner, int n_co
   A.qry[0] = qp.c[0]; A.qry[1] = qp.c[1];
   const char* stats_path = switches().s2m_stats;
   int4* d_wstats = nullptr;
-  if (stats_path && use_packets) { HIPCHK(hipMalloc((void**)&d_wstats, sizeof(int4) * 4 * (size_t)grid)); HIPCHK(hipMemsetAsync(d_wstats, 0, sizeof(int4) * 4 * (size_t)grid, s)); A.wstats = d_wstats; }
+  if (stats_path && use_packets) { if ((rg = W->store.grow(W->wstats, W->wstats_cap, 4 * (size_t)grid))) return rg; d_wstats = W->wstats; HIPCHK(hipMemsetAsync(d_wstats, 0, sizeof(int4) * 4 * (size_t)grid, s)); A.wstats = d_wstats; }
   float* tf = transformTobeMapped;
   bool isDegenerate = false;
   float matP[36]; for (int i = 0; i < 36; i++) matP[i] = (i % 7 == 0) ? 1.f : 0.f;
-  if (!W->h_sum) HIPCHK(hipHostMalloc((void**)&W->h_sum, sizeof(double) * S2M_NV));
+  if (!W->h_sum && (rg = W->store.alloc_pinned(W->h_sum, S2M_NV))) return rg;
   double* h_sum = W->h_sum;
   for (int iterCount = 0; iterCount < 30; iterCount++) {
     // trans2Affine3f :339-342 = pcl::getTransformation(x, y, z, roll, pitch, yaw), float
@@ -777,7 +778,6 @@ extern "C" int rolo_scan2map_optimize(rolo_ctx* c, const float* corner, int n_co
     std::vector<int4> hw(4 * (size_t)grid);
     HIPCHK(hipMemcpy(hw.data(), d_wstats, sizeof(int4) * hw.size(), hipMemcpyDeviceToHost));
     if (FILE* f = fopen(stats_path, "w")) { for (const int4& r : hw) fprintf(f, "%d %d %d %d\n", r.x, r.y, r.z, r.w); fclose(f); }
-    (void)hipFree(d_wstats);
   }
   st.degenerate = isDegenerate ? 1 : 0;
   if (selected_out) HIPCHK(hipMemcpy(selected_out, d_sel, (size_t)n, hipMemcpyDeviceToHost));

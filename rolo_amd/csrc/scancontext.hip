@@ -280,12 +280,8 @@ struct ScStore {
   float last_ms = 0.f;
 };
 
-void sc_store_destroy(ScStore* sc) {
+void sc_store_destroy(ScStore* sc) {   // (every buffer is the key map's store's)
   if (!sc) return;
-  for (void* p : {(void*)sc->desc, (void*)sc->colnorm, (void*)sc->seckey, (void*)sc->ringkey, (void*)sc->keys, (void*)sc->part, (void*)sc->cdist, (void*)sc->calign})
-    if (p) (void)hipFree(p);
-  if (sc->h_flag) (void)hipHostFree(sc->h_flag);
-  if (sc->h_best) (void)hipHostFree(sc->h_best);
   if (sc->t0) (void)hipEventDestroy(sc->t0);
   if (sc->t1) (void)hipEventDestroy(sc->t1);
   delete sc;
@@ -303,9 +299,10 @@ int sc_store(rolo_keymap* km, ScStore** out) {
     HIPCHK(hipSetDevice(km->device));
     ScStore* sc = new ScStore();
     sc_defaults(&sc->P);
-    hipError_t e = hipHostMalloc((void**)&sc->h_flag, sizeof(int));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&sc->h_best, sizeof(ScBest));
-    if (e == hipSuccess) e = hipEventCreate(&sc->t0);
+    int rc = km->store.alloc_pinned(sc->h_flag, 1);
+    if (!rc) rc = km->store.alloc_pinned(sc->h_best, 1);
+    if (rc) { sc_store_destroy(sc); return rc; }
+    hipError_t e = hipEventCreate(&sc->t0);
     if (e == hipSuccess) e = hipEventCreate(&sc->t1);
     if (e != hipSuccess) { ctx_set_error((std::string("rolo_keymap_sc: ") + hipGetErrorString(e)).c_str()); sc_store_destroy(sc); return ROLO_EHIP; }
     km->sc = sc;
@@ -315,16 +312,16 @@ int sc_store(rolo_keymap* km, ScStore** out) {
 }
 
 // room for one more descriptor: four larger arrays (sc->cap counts descriptors, so the sizes are given outright), the stored descriptors copied on the key map's
-// stream, the outgrown arrays retired
+// stream
 int sc_reserve(rolo_keymap* km, ScStore* sc) {
   if ((size_t)sc->n < sc->cap) return ROLO_OK;
   const size_t want = sc->cap + sc->cap / 2 + 64;
   const size_t R = (size_t)sc->P.num_ring, S = (size_t)sc->P.num_sector, n = (size_t)sc->n;
   int rc;
-  if ((rc = km->store.replace(sc->desc, want * R * S, n * R * S))) return rc;
-  if ((rc = km->store.replace(sc->colnorm, want * S, n * S))) return rc;
-  if ((rc = km->store.replace(sc->seckey, want * S, n * S))) return rc;
-  if ((rc = km->store.replace(sc->ringkey, want * R, n * R))) return rc;
+  if ((rc = km->store.alloc(sc->desc, want * R * S, n * R * S))) return rc;
+  if ((rc = km->store.alloc(sc->colnorm, want * S, n * S))) return rc;
+  if ((rc = km->store.alloc(sc->seckey, want * S, n * S))) return rc;
+  if ((rc = km->store.alloc(sc->ringkey, want * R, n * R))) return rc;
   sc->cap = want;
   return ROLO_OK;
 }
@@ -371,8 +368,7 @@ int rolo_keymap_sc_set_params(rolo_keymap* km, const rolo_sc_params* p) {
     return ROLO_ESTATE;
   }
   if (sc->cap > 0 && (p->num_ring != sc->P.num_ring || p->num_sector != sc->P.num_sector)) {
-    // no descriptor is stored, but an add that failed (a non-finite coordinate) has already sized the arrays for the old geometry: retire them, the next add allocates anew
-    for (void* q : {(void*)sc->desc, (void*)sc->colnorm, (void*)sc->seckey, (void*)sc->ringkey}) km->store.retire(q);
+    // no descriptor is stored, but an add that failed (a non-finite coordinate) has already sized the arrays for the old geometry: the next add allocates anew (the store frees these with the rest)
     sc->desc = nullptr; sc->colnorm = nullptr; sc->seckey = nullptr; sc->ringkey = nullptr;
     sc->cap = 0;
   }

@@ -1,8 +1,11 @@
 // Device kernels shared by the units that bin points into grid cells: submap.hip (pcl::VoxelGrid's cells) and groundprior.hip (the ground model's x-y grid).
 // The box of a cloud, the stable LSD radix sort of (cell, point index), the one-workgroup exclusive scan and the lower bound in a sorted array. Each unit that
-// includes this gets its own copy (unnamed namespace); the units are built without contraction.
+// includes this gets its own copy (unnamed namespace); the units are built without contraction. Behind the kernels, the host's one rule for launching them:
+// the sort's scratch and pass loop (SortScratch), the key width for a number of cells, the box pass.
 #pragma once
+#include "ctx_access.hpp"
 #include "dev_math.hpp"
+#include <algorithm>
 #include <cfloat>
 
 namespace rolo {
@@ -185,6 +188,62 @@ __device__ __forceinline__ int lower_bound_u32(const unsigned* __restrict__ a, i
   int lo = 0, hi = n;
   while (lo < hi) { const int mid = lo + ((hi - lo) >> 1); if (a[mid] < key) lo = mid + 1; else hi = mid; }
   return lo;
+}
+
+// ---- host: how the kernels above are launched -----------------------------------------------------------------------------------------------------------------
+// the sort's two key / value buffers, the tiles' digit counts and the digit totals of its four passes; they only grow, in the owner's store
+struct SortScratch {
+  unsigned* keys[2] = {nullptr, nullptr}; size_t keys_cap[2] = {0, 0};
+  int* vals[2] = {nullptr, nullptr}; size_t vals_cap[2] = {0, 0};
+  unsigned* hist = nullptr; size_t hist_cap = 0;
+  unsigned* dtot = nullptr; size_t dtot_cap = 0;   // [4 passes][256 digits]
+
+  int reserve(DevStore& store, size_t n) {
+    const size_t nblocks = (n + SORT_TILE - 1) / SORT_TILE;
+    int rc;
+    for (int b = 0; b < 2; b++) {
+      if ((rc = store.grow(keys[b], keys_cap[b], n))) return rc;
+      if ((rc = store.grow(vals[b], vals_cap[b], n))) return rc;
+    }
+    if ((rc = store.grow(hist, hist_cap, 256 * nblocks))) return rc;
+    return store.grow(dtot, dtot_cap, (size_t)4 * 256);
+  }
+  // the stable sort of keys[0] / vals[0] (n pairs) by the keys' low `bits` bits, 8 per pass: the result in keys[*cur] / vals[*cur]
+  int sort_pairs(hipStream_t s, int n, int bits, int* cur_out) {
+    const int nblocks = (n + SORT_TILE - 1) / SORT_TILE;
+    int cur = 0;
+    HIPCHK(hipMemsetAsync(dtot, 0, sizeof(unsigned) * 4 * 256, s));
+    for (int shift = 0; shift < bits; shift += 8) {
+      unsigned* dt = dtot + 256 * (shift / 8);
+      sort_hist_kernel<<<nblocks, SM_THREADS, 0, s>>>(keys[cur], n, shift, hist, nblocks, dt);
+      HIPCHK(hipGetLastError());
+      sort_scan_kernel<<<256, SM_THREADS, 0, s>>>(hist, nblocks, dt);
+      HIPCHK(hipGetLastError());
+      sort_scatter_kernel<<<nblocks, SM_THREADS, 0, s>>>(keys[cur], vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, shift, hist, nblocks);
+      HIPCHK(hipGetLastError());
+      cur ^= 1;
+    }
+    *cur_out = cur;
+    return ROLO_OK;
+  }
+};
+
+// key bits the sort has to look at for cells 0 .. cells - 1
+inline int sort_bits_for_cells(long long cells) {
+  int bits = 1;
+  while (bits < 31 && (1ll << bits) < cells) bits++;
+  return bits;
+}
+
+// the box of pts[0 .. n) into h_box[0..6] (pinned; valid after the stream has been waited for); box_part: 8 * BOX_BLOCKS_MAX floats
+inline int enqueue_box(hipStream_t s, const float4* pts, int n, float* box_part, float* h_box) {
+  if (n <= 0) return ROLO_OK;
+  const int blocks = std::min((n + SM_THREADS - 1) / SM_THREADS, BOX_BLOCKS_MAX);
+  vg_box_kernel<<<blocks, SM_THREADS, 0, s>>>(pts, n, box_part);
+  HIPCHK(hipGetLastError());
+  vg_box_final_kernel<<<1, SM_THREADS, 0, s>>>(box_part, blocks, h_box);
+  HIPCHK(hipGetLastError());
+  return ROLO_OK;
 }
 
 }  // namespace

@@ -228,29 +228,17 @@ using namespace rolo;
 namespace {
 
 int km_sort_scratch(rolo_keymap* km, int n) {
-  const int nblocks = (n + SORT_TILE - 1) / SORT_TILE, nrun = (n + RUN_TILE - 1) / RUN_TILE;
+  const int nrun = (n + RUN_TILE - 1) / RUN_TILE;
   int rc;
-  for (int b = 0; b < 2; b++) {
-    if ((rc = km->store.grow(km->keys[b], km->keys_cap[b], (size_t)n))) return rc;
-    if ((rc = km->store.grow(km->vals[b], km->vals_cap[b], (size_t)n))) return rc;
-  }
-  if ((rc = km->store.grow(km->hist, km->hist_cap, 256 * (size_t)nblocks))) return rc;
-  if ((rc = km->store.grow(km->dtot, km->dtot_cap, (size_t)4 * 256))) return rc;
+  if ((rc = km->sort.reserve(km->store, (size_t)n))) return rc;
   if ((rc = km->store.grow(km->bcnt, km->bcnt_cap, (size_t)nrun))) return rc;
   if ((rc = km->store.grow(km->starts, km->starts_cap, (size_t)n))) return rc;
-  if ((rc = km->store.grow(km->box_part, km->box_part_cap, 2 * 8 * (size_t)BOX_BLOCKS_MAX))) return rc;
-  return ROLO_OK;
+  return km->store.grow(km->box_part, km->box_part_cap, 2 * 8 * (size_t)BOX_BLOCKS_MAX);
 }
 
 // first half of the filter: the cloud's box into h_box[slot] (valid after the stream has been waited for)
 int vg_enqueue_box(rolo_keymap* km, const float4* pts, int n, int slot) {
-  if (n <= 0) return ROLO_OK;
-  const int blocks = std::min((n + SM_THREADS - 1) / SM_THREADS, BOX_BLOCKS_MAX);
-  vg_box_kernel<<<blocks, SM_THREADS, 0, km->stream>>>(pts, n, km->box_part + 8 * (size_t)BOX_BLOCKS_MAX * slot);
-  HIPCHK(hipGetLastError());
-  vg_box_final_kernel<<<1, SM_THREADS, 0, km->stream>>>(km->box_part + 8 * (size_t)BOX_BLOCKS_MAX * slot, blocks, km->h_box + 8 * slot);
-  HIPCHK(hipGetLastError());
-  return ROLO_OK;
+  return enqueue_box(km->stream, pts, n, km->box_part + 8 * (size_t)BOX_BLOCKS_MAX * slot, km->h_box + 8 * slot);
 }
 
 // the grid of a box (h_box's 7 floats) at a leaf: false for PCL's "leaf size is too small" (more than INT32_MAX cells by the extents). *bits: what the sort needs
@@ -266,35 +254,25 @@ bool vg_grid_of_box(const float* hb, float leaf, VgGrid* G, int* bits) {
   G->mul[0] = 1u; G->mul[1] = (unsigned)div[0]; G->mul[2] = (unsigned)div[0] * (unsigned)div[1];
   const long long cells = (long long)div[0] * div[1] * div[2];
   *bits = 32;
-  if (cells <= (long long)INT32_MAX) { *bits = 1; while (*bits < 31 && (1ll << *bits) < cells) (*bits)++; G->flip = 0u; }
+  if (cells <= (long long)INT32_MAX) { *bits = sort_bits_for_cells(cells); G->flip = 0u; }
   else G->flip = 0x80000000u;   // div_b's product wraps the int (the extents' product did not): signed order through the flipped sign bit
   return true;
 }
 
-// keys of pts[0 .. n), the stable sort by cell, the run heads: sorted keys / point indices in km->keys[*cur] / km->vals[*cur], km->starts, the number of runs in
+// keys of pts[0 .. n), the stable sort by cell, the run heads: sorted keys / point indices in km->sort.keys[*cur] / km->sort.vals[*cur], km->starts, the number of runs in
 // d_m[slot] and h_m[slot] (valid after the stream has been waited for)
 int vg_enqueue_sort_runs(rolo_keymap* km, const float4* pts, int n, const VgGrid& G, int bits, int slot, int* cur_out) {
   hipStream_t s = km->stream;
-  const int nblocks = (n + SORT_TILE - 1) / SORT_TILE, nrun = (n + RUN_TILE - 1) / RUN_TILE;
-  vg_key_kernel<<<(n + SM_THREADS - 1) / SM_THREADS, SM_THREADS, 0, s>>>(pts, n, G, km->keys[0], km->vals[0]);
+  const int nrun = (n + RUN_TILE - 1) / RUN_TILE;
+  vg_key_kernel<<<(n + SM_THREADS - 1) / SM_THREADS, SM_THREADS, 0, s>>>(pts, n, G, km->sort.keys[0], km->sort.vals[0]);
   HIPCHK(hipGetLastError());
-  int cur = 0;
-  HIPCHK(hipMemsetAsync(km->dtot, 0, sizeof(unsigned) * 4 * 256, s));
-  for (int shift = 0; shift < bits; shift += 8) {
-    unsigned* dtot = km->dtot + 256 * (shift / 8);
-    sort_hist_kernel<<<nblocks, SM_THREADS, 0, s>>>(km->keys[cur], n, shift, km->hist, nblocks, dtot);
-    HIPCHK(hipGetLastError());
-    sort_scan_kernel<<<256, SM_THREADS, 0, s>>>(km->hist, nblocks, dtot);
-    HIPCHK(hipGetLastError());
-    sort_scatter_kernel<<<nblocks, SM_THREADS, 0, s>>>(km->keys[cur], km->vals[cur], km->keys[cur ^ 1], km->vals[cur ^ 1], n, shift, km->hist, nblocks);
-    HIPCHK(hipGetLastError());
-    cur ^= 1;
-  }
-  run_heads_kernel<0><<<nrun, SM_THREADS, 0, s>>>(km->keys[cur], n, km->bcnt, km->starts);
+  int cur = 0, rc;
+  if ((rc = km->sort.sort_pairs(s, n, bits, &cur))) return rc;
+  run_heads_kernel<0><<<nrun, SM_THREADS, 0, s>>>(km->sort.keys[cur], n, km->bcnt, km->starts);
   HIPCHK(hipGetLastError());
   scan_excl_kernel<<<1, 1024, 0, s>>>(km->bcnt, nrun, km->d_m + slot, km->h_m + slot);
   HIPCHK(hipGetLastError());
-  run_heads_kernel<1><<<nrun, SM_THREADS, 0, s>>>(km->keys[cur], n, km->bcnt, km->starts);
+  run_heads_kernel<1><<<nrun, SM_THREADS, 0, s>>>(km->sort.keys[cur], n, km->bcnt, km->starts);
   HIPCHK(hipGetLastError());
   *cur_out = cur;
   return ROLO_OK;
@@ -316,7 +294,7 @@ int vg_enqueue_filter(rolo_keymap* km, const float4* pts, int n, float leaf, int
   int cur = 0;
   const int rc = vg_enqueue_sort_runs(km, pts, n, G, bits, slot, &cur);
   if (rc) return rc;
-  vg_runsum_kernel<<<(n + SM_THREADS - 1) / SM_THREADS, SM_THREADS, 0, km->stream>>>(pts, km->vals[cur], km->starts, km->d_m + slot, n, out);
+  vg_runsum_kernel<<<(n + SM_THREADS - 1) / SM_THREADS, SM_THREADS, 0, km->stream>>>(pts, km->sort.vals[cur], km->starts, km->d_m + slot, n, out);
   HIPCHK(hipGetLastError());
   return ROLO_OK;
 }
@@ -448,9 +426,9 @@ int gm_streamed(rolo_keymap* km, const std::vector<GmPiece>& pieces, long long t
     int cur = 0;
     if ((rc = vg_enqueue_sort_runs(km, km->cat[0], nb, G, bits, 0, &cur))) return rc;
     const int blocks = (nb + SM_THREADS - 1) / SM_THREADS;
-    unsigned* rkey = km->keys[cur ^ 1];   // the sort's other pair is free now: the runs' cells and their lower bounds
-    int* lbv = km->vals[cur ^ 1];
-    gm_find_kernel<<<blocks, SM_THREADS, 0, s>>>(km->keys[cur], km->starts, km->d_m, km->gt_key[tcur], m_tab, rkey, lbv, km->gm_ncnt);
+    unsigned* rkey = km->sort.keys[cur ^ 1];   // the sort's other pair is free now: the runs' cells and their lower bounds
+    int* lbv = km->sort.vals[cur ^ 1];
+    gm_find_kernel<<<blocks, SM_THREADS, 0, s>>>(km->sort.keys[cur], km->starts, km->d_m, km->gt_key[tcur], m_tab, rkey, lbv, km->gm_ncnt);
     HIPCHK(hipGetLastError());
     scan_excl_kernel<<<1, 1024, 0, s>>>(km->gm_ncnt, blocks, km->gm_d, km->gm_h);
     HIPCHK(hipGetLastError());
@@ -465,7 +443,7 @@ int gm_streamed(rolo_keymap* km, const std::vector<GmPiece>& pieces, long long t
     if ((rc = km->store.grow(km->gt_sum[tn], km->gt_sum_cap[tn], m_new))) return rc;
     if ((rc = km->store.grow(km->gt_cnt[tn], km->gt_cnt_cap[tn], m_new))) return rc;
     const GmTable told{km->gt_key[tcur], km->gt_sum[tcur], km->gt_cnt[tcur]}, tnew{km->gt_key[tn], km->gt_sum[tn], km->gt_cnt[tn]};
-    gm_merge_runs_kernel<<<blocks, SM_THREADS, 0, s>>>(km->cat[0], km->vals[cur], km->starts, km->d_m, nb, rkey, lbv, km->gm_ncnt, told, tnew, km->gm_npre);
+    gm_merge_runs_kernel<<<blocks, SM_THREADS, 0, s>>>(km->cat[0], km->sort.vals[cur], km->starts, km->d_m, nb, rkey, lbv, km->gm_ncnt, told, tnew, km->gm_npre);
     HIPCHK(hipGetLastError());
     if (m_tab > 0) {
       gm_move_old_kernel<<<(m_tab + SM_THREADS - 1) / SM_THREADS, SM_THREADS, 0, s>>>(told, m_tab, rkey, km->d_m, km->gm_npre, tnew);
@@ -537,13 +515,14 @@ int rolo_keymap_create(int device, rolo_keymap** out) {
   hipError_t e = hipStreamCreateWithFlags(&km->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&km->ready, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&km->consumed, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&km->h_box, sizeof(float) * 16);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&km->h_m, sizeof(int) * 2);
-  if (e == hipSuccess) e = hipMalloc((void**)&km->d_m, sizeof(int) * 2);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&km->gm_h, sizeof(int) * 2);
-  if (e == hipSuccess) e = hipMalloc((void**)&km->gm_d, sizeof(int) * 2);
   if (e != hipSuccess) { ctx_set_error((std::string("rolo_keymap_create: ") + hipGetErrorString(e)).c_str()); rolo_keymap_destroy(km); return ROLO_EHIP; }
   km->store.stream = km->stream; km->store.who = "keymap";
+  int rc = km->store.alloc_pinned(km->h_box, 16);
+  if (!rc) rc = km->store.alloc_pinned(km->h_m, 2);
+  if (!rc) rc = km->store.alloc(km->d_m, 2);
+  if (!rc) rc = km->store.alloc_pinned(km->gm_h, 2);
+  if (!rc) rc = km->store.alloc(km->gm_d, 2);
+  if (rc) { rolo_keymap_destroy(km); return rc; }
   *out = km;
   return ROLO_OK;
 }
@@ -557,12 +536,6 @@ void rolo_keymap_destroy(rolo_keymap* km) {
   if (km->loop_ctx) { rolo_ctx_release(km->loop_ctx); km->loop_ctx = nullptr; }
   for (auto& c : km->chunks) (void)hipFree(c.p);
   km->store.release();
-  for (void* p : {(void*)km->cat[0], (void*)km->cat[1], (void*)km->sub[0], (void*)km->sub[1], (void*)km->ds_out, (void*)km->keys[0], (void*)km->keys[1], (void*)km->vals[0],
-                  (void*)km->vals[1], (void*)km->hist, (void*)km->dtot, (void*)km->bcnt, (void*)km->starts, (void*)km->box_part, (void*)km->segs, (void*)km->d_m, (void*)km->loop[0], (void*)km->loop[1],
-                  (void*)km->gmap, (void*)km->gt_key[0], (void*)km->gt_key[1], (void*)km->gt_sum[0], (void*)km->gt_sum[1], (void*)km->gt_cnt[0], (void*)km->gt_cnt[1], (void*)km->gm_ncnt,
-                  (void*)km->gm_npre, (void*)km->gm_d})
-    if (p) (void)hipFree(p);
-  for (void* p : {(void*)km->h_box, (void*)km->h_m, (void*)km->h_segs, (void*)km->gm_h}) if (p) (void)hipHostFree(p);
   if (km->ready) (void)hipEventDestroy(km->ready);
   if (km->consumed) (void)hipEventDestroy(km->consumed);
   if (km->loop_t0) (void)hipEventDestroy(km->loop_t0);

@@ -175,6 +175,26 @@ def test_alignment_is_bit_reproducible(icp):
     assert runs[0] == runs[1]
 
 
+def test_single_form_bits_are_the_recorded_ones(golden_dir):
+    """LoopIcp.align + trace() on the inputs of test_gpu_loopicp_batch.py's "batch equals single" comparisons (loopicp_bits_cases.py) against the bytes recorded
+    on an MI355X at the commit the file's meta names (profiles/tools/record_loopicp_bits.py): the single form was an ICP loop of its own then, so the batch
+    tests' comparisons with it say something about a single form that is a batch of one"""
+    import os
+    import loopicp_bits_cases as rec
+    want = np.load(os.path.join(golden_dir, rec.FILE))
+    print(str(want["meta"]))
+    h = LoopIcp()   # a fresh context, as the recorder's
+    try:
+        got = rec.run(h)
+    finally:
+        h.close()
+    assert sorted(got) == sorted(k for k in want.files if k != "meta")
+    assert got["names"].tolist() == want["names"].tolist() and len(got["names"]) == 2 * 2 * 7 + 2 * 5
+    for k in got:
+        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, k
+        assert np.array_equal(rec.raw(got[k]), rec.raw(want[k])), (k, np.flatnonzero(np.any((rec.raw(got[k]) != rec.raw(want[k])).reshape(len(got[k]), -1), axis=1))[:8])
+
+
 # ---- 3. whole alignments against the twin -----------------------------------------------------------------------------------------------------------------------
 def against_twin(icp, src, tgt, guess=None, **kw):
     want = T.icp(src, tgt, guess, **kw)

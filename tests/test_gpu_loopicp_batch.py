@@ -218,3 +218,70 @@ def test_empty_batch_and_bad_arguments(icp):
     # an empty target: every candidate NO_CORRESPONDENCES, as the single form
     rs = icp.alignBatch([src, src[:0]], tgt[:0], P)
     assert [r["state"] for r in rs] == [T.NO_CORRESPONDENCES] * 2 and not any(r["converged"] for r in rs)
+
+
+def trace_bits(trace):
+    return bits(dict(T=np.zeros(16, f32), fitness=0.0, state=0, iterations=0, n_last=0, converged=0, n_source=0, n_target=0), trace)[8]
+
+
+def test_one_context_serves_both_call_kinds():
+    """align, alignBatch, align, associate in ONE context, whose scratch, events and control records the call kinds share: every result is a fresh context's,
+    the single form's records survive a batch call and the batch's survive a single call"""
+    rng = np.random.default_rng(78)
+    tgt = rng.uniform(-5, 5, (900, 3)).astype(f32)
+    one = rng.uniform(-5, 5, (70, 3)).astype(f32)
+    srcs = [rng.uniform(-5, 5, (n, 3)).astype(f32) for n in (3, 257, 2000)]
+    P = loop_icp_params(3.0, max_iterations=6)
+    Tm = motion((0.01, -0.02, 0.03), (0.1, -0.2, 0.05)).astype(f32)
+    h, fresh = LoopIcp(), LoopIcp()
+    try:
+        want = run_single(fresh, one, tgt, P)
+        want_i, want_d = fresh.associate(xyzi(one), xyzi(tgt), Tm, 3.0)
+        want_sums = fresh.trace()[-1]["sums"].tobytes()
+        first = run_single(h, one, tgt, P)
+        assert_same(first, want, "first align")
+        batch = run_batch(h, srcs, tgt, P)
+        assert trace_bits(h.trace()) == first[8]                      # read after the batch call: still the first align's
+        second = run_single(h, one, tgt, P)
+        assert_same(second, want, "align after a batch")
+        for b in range(len(srcs)):                                    # the batch's records are unchanged by the later align
+            assert trace_bits(h.traceBatch(b)) == batch[b][8], b
+            fresh2 = LoopIcp()                                        # each candidate against a context that has seen nothing else
+            try:
+                assert_same(batch[b], run_single(fresh2, srcs[b], tgt, P), "candidate %d" % b)
+            finally:
+                fresh2.close()
+        got_i, got_d = h.associate(xyzi(one), xyzi(tgt), Tm, 3.0)
+        assert np.array_equal(got_i, want_i) and got_d.tobytes() == want_d.tobytes()
+        assert len(h.trace()) == 1 and h.trace()[-1]["sums"].tobytes() == want_sums
+        for b in range(len(srcs)):                                    # ... nor by the association
+            assert trace_bits(h.traceBatch(b)) == batch[b][8], b
+        assert len(first[8]) >= 2 and all(len(g[8]) >= 2 for g in batch)   # of the test's own inputs: every alignment associated at least twice
+    finally:
+        h.close(); fresh.close()
+
+
+def test_times_keep_their_meaning():
+    """lastMs: set-up, iterations, fitness pass, whole call of the last align; batchLastMs: set-up, iterations with the fitness passes, 0, whole call. The 1 %
+    is slack for the float rounding of the event times, not a performance bound."""
+    rng = np.random.default_rng(79)
+    tgt = rng.uniform(-5, 5, (900, 3)).astype(f32)
+    src = rng.uniform(-5, 5, (300, 3)).astype(f32)
+    P = loop_icp_params(3.0, max_iterations=5)
+    h = LoopIcp()
+    try:
+        r = h.align(xyzi(src), xyzi(tgt), P)
+        ms = h.lastMs().astype(np.float64)
+        print("single", r["iterations"], "iterations, ms", ms)
+        assert ms.shape == (4,) and np.all(np.isfinite(ms)) and np.all(ms > 0)
+        assert ms[0] + ms[1] + ms[2] <= ms[3] * 1.01
+        h.align(xyzi(src[:0]), xyzi(tgt), P)
+        assert np.array_equal(h.lastMs(), np.zeros(4, f32))
+        h.alignBatch([xyzi(src), xyzi(src[:100])], xyzi(tgt), P)
+        bms = h.batchLastMs().astype(np.float64)
+        print("batch ms", bms)
+        assert np.all(np.isfinite(bms)) and bms[2] == 0 and bms[0] > 0 and bms[1] > 0 and bms[3] > 0
+        assert bms[0] + bms[1] <= bms[3] * 1.01
+        assert np.array_equal(h.lastMs(), np.zeros(4, f32))   # the batch call left the single form's times alone
+    finally:
+        h.close()
