@@ -20,17 +20,17 @@ std::atomic<unsigned long long> g_alloc_epoch{0};
 
 static int upload_cloud(rolo_ctx* c, CloudDev& cl, size_t& xyz_cap, const float* pts, int n, int stride, bool on_device) {
   if (n < 0 || stride < 3 || (n > 0 && !pts)) { g_err = "bad cloud arguments"; return ROLO_EINVAL; }
-  int rc = ensure(cl.xyz, xyz_cap, (size_t)std::max(n, 1));
+  int rc = c->store.grow(cl.xyz, xyz_cap, (size_t)std::max(n, 1));
   if (rc) return rc;
   const float* dsrc = pts;
   if (!on_device && n > 0) {
-    rc = ensure(c->stage_in, c->stage_in_cap, (size_t)n * stride);
+    rc = c->store.grow(c->stage_in, c->stage_in_cap, (size_t)n * stride);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(c->stage_in, pts, sizeof(float) * (size_t)n * stride, hipMemcpyHostToDevice, c->stream));
     dsrc = c->stage_in;
   }
   const int nparts = (n + 255) / 256;
-  if ((rc = ensure(cl.bbox_part, cl.bbox_part_cap, (size_t)std::max(nparts, 1) * 6))) return rc;
+  if ((rc = c->store.grow(cl.bbox_part, cl.bbox_part_cap, (size_t)std::max(nparts, 1) * 6))) return rc;
   HIPCHK(launch_pack_xyz(dsrc, stride, cl.xyz, n, c->stream, cl.bbox_part));
   cl.n_bbox_part = nparts;
   cl.n = n;
@@ -50,13 +50,13 @@ static int prepare_cloud(rolo_ctx* c, CloudDev& cl, size_t& cov_cap, size_t& sor
   int P = 2; while (P < cl.n_leaves) P <<= 1;
   cl.P = P;
   int rc;
-  if ((rc = ensure(cl.cov, cov_cap, 6 * (size_t)n))) return rc;
-  if (!tree_only && (rc = ensure(cl.nrm, cl.nrm_cap, 3 * (size_t)n))) return rc;
-  if ((rc = ensure(cl.sorted, sorted_cap, KNN_LEAF * (size_t)cl.n_leaves))) return rc;
-  if ((rc = ensure(cl.boxes, boxes_cap, 4 * (size_t)P))) return rc;
+  if ((rc = c->store.grow(cl.cov, cov_cap, 6 * (size_t)n))) return rc;
+  if (!tree_only && (rc = c->store.grow(cl.nrm, cl.nrm_cap, 3 * (size_t)n))) return rc;
+  if ((rc = c->store.grow(cl.sorted, sorted_cap, KNN_LEAF * (size_t)cl.n_leaves))) return rc;
+  if ((rc = c->store.grow(cl.boxes, boxes_cap, 4 * (size_t)P))) return rc;
   if (c->want_knn_lists) {
-    if ((rc = ensure(cl.knn_idx, knn_cap, (size_t)n * k))) return rc;
-    if ((rc = ensure(cl.knn_d2, knnd_cap, (size_t)n * k))) return rc;
+    if ((rc = c->store.grow(cl.knn_idx, knn_cap, (size_t)n * k))) return rc;
+    if ((rc = c->store.grow(cl.knn_d2, knnd_cap, (size_t)n * k))) return rc;
   }
   out.xyz = cl.xyz; out.sorted = cl.sorted; out.boxes = cl.boxes; out.cov = cl.cov; out.nrm = tree_only ? nullptr : cl.nrm;
   out.knn_idx = c->want_knn_lists ? cl.knn_idx : nullptr; out.knn_d2 = c->want_knn_lists ? cl.knn_d2 : nullptr;
@@ -77,22 +77,22 @@ int build_clouds(rolo_ctx* c, bool do_src, bool do_tgt, hipStream_t stream, bool
   A.n_clouds = nc;
   const size_t n_total = (size_t)A.c[0].n + (nc > 1 ? (size_t)A.c[1].n : 0);
   rolo_ctx::KnnScratch& S = c->ks[(do_tgt && !do_src) ? 1 : 0];
-  if ((rc = ensure(S.keys0, S.keys0_cap, n_total))) return rc;
-  if ((rc = ensure(S.keys1, S.keys1_cap, n_total))) return rc;
-  if ((rc = ensure(S.vals0, S.vals0_cap, n_total))) return rc;
-  if ((rc = ensure(S.vals1, S.vals1_cap, n_total))) return rc;
-  if ((rc = ensure(S.bbox, S.bbox_cap, knn_bbox_ints()))) return rc;
+  if ((rc = c->store.grow(S.keys0, S.keys0_cap, n_total))) return rc;
+  if ((rc = c->store.grow(S.keys1, S.keys1_cap, n_total))) return rc;
+  if ((rc = c->store.grow(S.vals0, S.vals0_cap, n_total))) return rc;
+  if ((rc = c->store.grow(S.vals1, S.vals1_cap, n_total))) return rc;
+  if ((rc = c->store.grow(S.bbox, S.bbox_cap, knn_bbox_ints()))) return rc;
   const int kc = tree_only ? 1 : c->P.k_correspondences;
   const size_t kslots = kc > 64 ? 64 * (((size_t)kc + 63) / 64) : (kc > 32 ? 64 : 32);   // slot-major neighbour lists: KMAX slots per sorted position (k > 64: rounds of 64)
-  if ((rc = ensure(S.nbr, S.nbr_cap, kslots * ((size_t)A.c[0].n_sorted + (nc > 1 ? (size_t)A.c[1].n_sorted : 0))))) return rc;
+  if ((rc = c->store.grow(S.nbr, S.nbr_cap, kslots * ((size_t)A.c[0].n_sorted + (nc > 1 ? (size_t)A.c[1].n_sorted : 0))))) return rc;
   A.c[0].nbr = S.nbr; if (nc > 1) A.c[1].nbr = S.nbr + kslots * (size_t)A.c[0].n_sorted;
   for (int i = 0; i < 2; i++) { A.c[i].lower = nullptr; A.c[i].slot0 = 0; A.c[i].k_total = 0; }
   if (kc > 64) {   // one key per sorted position: where the next round of 64 starts
-    if ((rc = ensure(S.lower, S.lower_cap, (size_t)A.c[0].n_sorted + (nc > 1 ? (size_t)A.c[1].n_sorted : 0)))) return rc;
+    if ((rc = c->store.grow(S.lower, S.lower_cap, (size_t)A.c[0].n_sorted + (nc > 1 ? (size_t)A.c[1].n_sorted : 0)))) return rc;
     A.c[0].lower = S.lower; if (nc > 1) A.c[1].lower = S.lower + A.c[0].n_sorted;
   }
   const size_t tmp = knn_sort_temp_bytes((int)n_total);
-  if ((rc = ensure(S.sort_tmp, S.sort_tmp_cap, tmp + 256))) return rc;
+  if ((rc = c->store.grow(S.sort_tmp, S.sort_tmp_cap, tmp + 256))) return rc;
   // Multi-GPU ("K5 shards by query point with the full cloud replicated"): every rank sorts and builds the BVH of the whole
   // cloud (cheap, identical on all ranks), searches only its slice of the Morton-sorted queries — whole 256-query workgroups, equal
   // slices — and the 48-byte covariances are all-gathered once per frame in sorted order, then scattered to cov[] by original index.
@@ -117,7 +117,7 @@ int build_clouds(rolo_ctx* c, bool do_src, bool do_tgt, hipStream_t stream, bool
       stage = reinterpret_cast<double*>(static_cast<char*>(c->peer.base) + PEER_STAGE_OFFSET);
       stage_epoch = static_cast<const unsigned long long*>(c->peer.base) + PEER_W_COV_EPOCH; stage_alt = c->peer.area_bytes / sizeof(double);
     } else {
-      if ((rc = ensure(S.stage, S.stage_cap, seg * (size_t)c->world))) return rc;
+      if ((rc = c->store.grow(S.stage, S.stage_cap, seg * (size_t)c->world))) return rc;
       stage = S.stage;
     }
     for (int i = 0; i < nc; i++) { A.c[i].seg = seg; A.c[i].stage = stage; A.c[i].stage_epoch = stage_epoch; A.c[i].stage_alt = stage_alt; }
@@ -206,12 +206,12 @@ int size_voxel_table(rolo_ctx* c) {
   const int n = c->tgt.n;
   int rc;
   size_t capslots = 1024; while (capslots < 2 * (size_t)n) capslots <<= 1;
-  if ((rc = ensure(c->tab.keys, c->tab_keys_cap, 2 * capslots))) return rc;   // 16 bytes per slot: key + id
-  if ((rc = ensure(c->tab.rec, c->tab_rec_cap, (size_t)n * REC_DOUBLES))) return rc;
-  if ((rc = ensure(c->tab.id_keys, c->tab_idk_cap, (size_t)n))) return rc;
-  if ((rc = ensure(c->tgt_keys, c->tgt_keys_cap, (size_t)n))) return rc;
-  if ((rc = ensure(c->tgt_slot, c->tgt_slot_cap, (size_t)n + KNN_LEAF))) return rc;
-  if ((rc = ensure(c->counters, c->counters_cap, 4))) return rc;
+  if ((rc = c->store.grow(c->tab.keys, c->tab_keys_cap, 2 * capslots))) return rc;   // 16 bytes per slot: key + id
+  if ((rc = c->store.grow(c->tab.rec, c->tab_rec_cap, (size_t)n * REC_DOUBLES))) return rc;
+  if ((rc = c->store.grow(c->tab.id_keys, c->tab_idk_cap, (size_t)n))) return rc;
+  if ((rc = c->store.grow(c->tgt_keys, c->tgt_keys_cap, (size_t)n))) return rc;
+  if ((rc = c->store.grow(c->tgt_slot, c->tgt_slot_cap, (size_t)n + KNN_LEAF))) return rc;
+  if (!c->counters && (rc = c->store.alloc(c->counters, 4))) return rc;
   c->tab.mask = (unsigned)(capslots - 1);
   fill_table_params(c);
   return ROLO_OK;
@@ -265,8 +265,8 @@ int ctx_set_pair_device(rolo_ctx* c, const float* d_src, int n_src, int stride_s
   size_t* cap[2] = {&c->src_xyz_cap, &c->tgt_xyz_cap};
   const int n[2] = {n_src, n_tgt};
   for (int i = 0; i < 2; i++) {
-    if ((rc = ensure(cl[i]->xyz, *cap[i], (size_t)n[i]))) return rc;
-    if ((rc = ensure(cl[i]->bbox_part, cl[i]->bbox_part_cap, (size_t)((n[i] + 255) / 256) * 6))) return rc;
+    if ((rc = c->store.grow(cl[i]->xyz, *cap[i], (size_t)n[i]))) return rc;
+    if ((rc = c->store.grow(cl[i]->bbox_part, cl[i]->bbox_part_cap, (size_t)((n[i] + 255) / 256) * 6))) return rc;
   }
   HIPCHK(launch_pack_pair(d_src, stride_src, c->src.xyz, n_src, c->src.bbox_part, T16_host_or_null, d_tgt, stride_tgt, c->tgt.xyz, n_tgt, c->tgt.bbox_part, c->stream));
   for (int i = 0; i < 2; i++) { cl[i]->n_bbox_part = (n[i] + 255) / 256; cl[i]->n = n[i]; cl[i]->have_cov = false; cl[i]->have_nrm = false; cl[i]->have_sorted = false; cl[i]->bbox6 = nullptr; }
@@ -394,13 +394,16 @@ static int ctx_create_impl(int device, bool high_priority, rolo_ctx** out) {
   } else if (ok) ok = bank_acquire_pair(device, &c->stream, &c->stream2, &c->bank_slot) == ROLO_OK;
   if (!ok || hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess || hipEventCreate(&c->ev_done) != hipSuccess || hipEventCreate(&c->ev_start) != hipSuccess) { rolo_ctx_destroy(c); g_err = "hipStreamCreate failed"; return ROLO_EHIP; }
-  if (hipHostMalloc((void**)&c->h_state, sizeof(LmState)) != hipSuccess || hipHostMalloc((void**)&c->h_sums, sizeof(double) * NV_MAX) != hipSuccess ||
-      hipHostMalloc((void**)&c->h_counters, sizeof(int) * 4) != hipSuccess || hipHostMalloc((void**)&c->h_args, sizeof(FrameArgs)) != hipSuccess) { rolo_ctx_destroy(c); g_err = "hipHostMalloc failed"; return ROLO_EHIP; }
-  memset(c->h_state, 0, sizeof(LmState));
-  int rc = ensure(c->state, c->state_cap, 2);   // [0] the state every entry point sees; [1] the other half of the fused launches' double buffer
-  if (!rc) rc = ensure(c->sums, c->sums_cap, NV_MAX);
-  if (!rc) rc = ensure(c->trace, c->trace_cap, TRACE_CAP);
-  if (!rc) rc = ensure(c->d_args, c->d_args_cap, 1);
+  c->store.stream = c->stream; c->store.who = "context"; c->store.epoch = &g_alloc_epoch;
+  int rc = c->store.alloc_pinned(c->h_state, 1);
+  if (!rc) rc = c->store.alloc_pinned(c->h_sums, NV_MAX);
+  if (!rc) rc = c->store.alloc_pinned(c->h_counters, 4);
+  if (!rc) rc = c->store.alloc_pinned(c->h_args, 1);
+  if (!rc) memset(c->h_state, 0, sizeof(LmState));
+  if (!rc) rc = c->store.alloc(c->state, 2);   // [0] the state every entry point sees; [1] the other half of the fused launches' double buffer
+  if (!rc) rc = c->store.alloc(c->sums, NV_MAX);
+  if (!rc) rc = c->store.alloc(c->trace, TRACE_CAP);
+  if (!rc) rc = c->store.alloc(c->d_args, 1);
   if (!rc && hipMemsetAsync(c->state, 0, 2 * sizeof(LmState), c->stream) != hipSuccess) rc = ROLO_EHIP;
   if (rc) { rolo_ctx_destroy(c); return rc; }
   *out = c;
@@ -417,23 +420,13 @@ void rolo_ctx_destroy(rolo_ctx* c) {
   rolo_loopicp_destroy(c);
   peer_release(c);
   if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
-  void* bufs[] = {c->src.nrm, c->tgt.nrm, c->src.bbox_part, c->tgt.bbox_part, c->src.xyz, c->src.cov, c->src.sorted, c->src.boxes, c->src.knn_idx, c->src.knn_d2, c->tgt.xyz, c->tgt.cov, c->tgt.sorted,
-                  c->tgt.boxes, c->tgt.knn_idx, c->tgt.knn_d2, c->ks[0].sort_tmp, c->ks[0].keys0, c->ks[0].keys1, c->ks[0].vals0, c->ks[0].vals1, c->ks[0].bbox,
-                  c->ks[1].sort_tmp, c->ks[1].keys0, c->ks[1].keys1, c->ks[1].vals0, c->ks[1].vals1, c->ks[1].bbox, c->ks[0].nbr, c->ks[1].nbr, c->ks[0].stage, c->ks[1].stage, c->ks[0].lower, c->ks[1].lower, c->tab.keys,
-                  c->tab.rec, c->tab.id_keys, c->tgt_keys, c->tgt_slot, c->counters, c->corr[0], c->corr[1], c->partials, c->sums,
-                  c->state, c->trace, c->stage_in, c->stage_out, c->stage_d, c->stage_i, c->xbuf, c->stamps};
-  for (void* b : bufs) if (b) (void)hipFree(b);
   c->sched.release();
   if (c->galt.exec) (void)hipGraphExecDestroy(c->galt.exec);
   if (c->galt.graph) (void)hipGraphDestroy(c->galt.graph);
   if (c->dbg_chain_exec) (void)hipGraphExecDestroy(c->dbg_chain_exec);
-  if (c->h_args) (void)hipHostFree(c->h_args);
-  if (c->h_stamps) (void)hipHostFree(c->h_stamps);
-  if (c->d_args) (void)hipFree(c->d_args);
-  if (c->h_state) (void)hipHostFree(c->h_state);
-  if (c->h_sums) (void)hipHostFree(c->h_sums);
-  if (c->h_counters) (void)hipHostFree(c->h_counters);
-  if (c->stream2) { (void)hipStreamSynchronize(c->stream2); if (c->bank_slot < 0) (void)hipStreamDestroy(c->stream2); }
+  if (c->stream2) (void)hipStreamSynchronize(c->stream2);
+  c->store.release();   // both streams are drained
+  if (c->stream2 && c->bank_slot < 0) (void)hipStreamDestroy(c->stream2);
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
   if (c->ev_done) (void)hipEventDestroy(c->ev_done);
@@ -580,7 +573,7 @@ int rolo_compute_covariances(rolo_ctx* c) {
 static int get_covs(rolo_ctx* c, CloudDev& cl, double* covs) {
   if (!covs) return ROLO_EINVAL;
   if (!cl.have_cov) { g_err = "covariances not computed"; return ROLO_ESTATE; }
-  int rc = ensure(c->stage_d, c->stage_d_cap, (size_t)cl.n * 16);
+  int rc = c->store.grow(c->stage_d, c->stage_d_cap, (size_t)cl.n * 16);
   if (rc) return rc;
   HIPCHK(launch_cov_unpack(cl.cov, cl.n, c->stage_d, c->stream));
   HIPCHK(hipMemcpyAsync(covs, c->stage_d, sizeof(double) * 16 * (size_t)cl.n, hipMemcpyDeviceToHost, c->stream));
@@ -592,8 +585,8 @@ int rolo_get_target_covariances(rolo_ctx* c, double* covs) { if (!c) return ROLO
 
 static int set_covs(rolo_ctx* c, CloudDev& cl, size_t& cov_cap, const double* covs) {
   if (!covs || cl.n <= 0) return ROLO_EINVAL;
-  int rc = ensure(cl.cov, cov_cap, 6 * (size_t)cl.n);
-  if (!rc) rc = ensure(c->stage_d, c->stage_d_cap, (size_t)cl.n * 16);
+  int rc = c->store.grow(cl.cov, cov_cap, 6 * (size_t)cl.n);
+  if (!rc) rc = c->store.grow(c->stage_d, c->stage_d_cap, (size_t)cl.n * 16);
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(c->stage_d, covs, sizeof(double) * 16 * (size_t)cl.n, hipMemcpyHostToDevice, c->stream));
   HIPCHK(launch_cov_pack(c->stage_d, cl.n, cl.cov, c->stream));
@@ -662,7 +655,7 @@ int rolo_get_target_voxel_keys(rolo_ctx* c, int32_t* keys) {
   if (!c || !keys) return ROLO_EINVAL;
   if (c->tgt.n <= 0) return ROLO_ESTATE;
   int rc = set_device(c); if (rc) return rc;
-  rc = ensure(c->stage_i, c->stage_i_cap, 3 * (size_t)c->tgt.n);
+  rc = c->store.grow(c->stage_i, c->stage_i_cap, 3 * (size_t)c->tgt.n);
   if (rc) return rc;
   fill_table_params(c);
   HIPCHK(launch_voxel_keys(c->tgt.xyz, c->tgt.n, c->tab, c->stage_i, c->stream));
@@ -781,8 +774,8 @@ int rolo_transform_cloud(rolo_ctx* c, const float* in, float* out, int n, int st
   if (!c || !in || !out || !T16 || n < 0 || stride < 3) return ROLO_EINVAL;
   int rc = set_device(c); if (rc) return rc;
   if (n == 0) return ROLO_OK;
-  if ((rc = ensure(c->stage_in, c->stage_in_cap, (size_t)n * stride))) return rc;
-  if ((rc = ensure(c->stage_out, c->stage_out_cap, (size_t)n * stride))) return rc;
+  if ((rc = c->store.grow(c->stage_in, c->stage_in_cap, (size_t)n * stride))) return rc;
+  if ((rc = c->store.grow(c->stage_out, c->stage_out_cap, (size_t)n * stride))) return rc;
   HIPCHK(hipMemcpyAsync(c->stage_in, in, sizeof(float) * (size_t)n * stride, hipMemcpyHostToDevice, c->stream));
   HIPCHK(launch_transform_cloud(c->stage_in, c->stage_out, n, stride, nullptr, T16, c->stream));
   HIPCHK(hipMemcpyAsync(out, c->stage_out, sizeof(float) * (size_t)n * stride, hipMemcpyDeviceToHost, c->stream));

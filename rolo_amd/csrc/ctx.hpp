@@ -17,19 +17,7 @@ namespace rolo {
 
 extern thread_local std::string g_err;   // rolo_last_error (api.hip)
 
-extern std::atomic<unsigned long long> g_alloc_epoch;  // bumped on every (re)allocation: captured graphs hold raw device pointers (api.hip)
-
-template <typename T>
-int ensure(T*& p, size_t& cap, size_t need) {
-  if (need <= cap && p) return ROLO_OK;
-  g_alloc_epoch++;
-  if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) return fail_hip(e, "hipFree"); p = nullptr; }
-  size_t ncap = std::max<size_t>(need + need / 4, 1024);
-  hipError_t e = hipMalloc((void**)&p, ncap * sizeof(T));
-  if (e != hipSuccess) { cap = 0; return fail_hip(e, "hipMalloc"); }
-  cap = ncap;
-  return ROLO_OK;
-}
+extern std::atomic<unsigned long long> g_alloc_epoch;  // bumped on every (re)allocation of a context buffer (rolo_ctx::store): captured graphs hold raw device pointers (api.hip)
 
 // ---- RCCL through dlopen (only multi-GPU runs need it; peer.hip) ----
 struct Uid { char internal[128]; };
@@ -83,6 +71,7 @@ struct rolo_peer_state {
 struct rolo_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
+  rolo::DevStore store;   // every device and pinned buffer below: grown here, freed by rolo_ctx_destroy's release() and nowhere else
   rolo_params P;
   rolo::CloudDev src, tgt;
   size_t src_xyz_cap = 0, src_cov_cap = 0, tgt_xyz_cap = 0, tgt_cov_cap = 0;
@@ -115,10 +104,10 @@ struct rolo_ctx {
   size_t tab_keys_cap = 0, tab_rec_cap = 0, tab_idk_cap = 0;
   unsigned long long* tgt_keys = nullptr; size_t tgt_keys_cap = 0;
   int* tgt_slot = nullptr; size_t tgt_slot_cap = 0;
-  int* counters = nullptr; size_t counters_cap = 0;
+  int* counters = nullptr;
   bool have_map = false;
   int n_voxels = 0;
-  unsigned long long* stamps = nullptr; size_t stamps_cap = 0; unsigned long long* h_stamps = nullptr;   // ROLO_STAMP=1 debug timeline (pinned)
+  unsigned long long* stamps = nullptr; unsigned long long* h_stamps = nullptr;   // ROLO_STAMP=1 debug timeline (pinned)
   rolo::VoxelFuse vf{};     // enqueue_frame arms it before the search when the map can be built inside the search's launches
   bool vf_done = false;     // the search just enqueued did carry the map build
   int vox_build[4] = {-1, 0, 0, 0};   // the last map build as enqueued (rolo_debug_voxel_build): form, fixed-point covariances, scale from the points, slots
@@ -130,9 +119,9 @@ struct rolo_ctx {
   unsigned long long* xbuf = nullptr; size_t xbuf_cap = 0;   // row exchange of the resident LM kernel (fused_lm = 2): header + 2 parities x workgroups x 64 words, zeroed when (re)allocated
   int lmp_rows = 1, lmp_ppt = 1, lmp_threads = 512;   // its grid, the points per thread and the workgroup size
   rolo::LmpForm lmp_form{};   // the form of its last launch (rolo_ctx_lm_form); all zero after a chain of the other launch forms
-  double* sums = nullptr; size_t sums_cap = 0;
-  rolo::LmState* state = nullptr; size_t state_cap = 0;
-  rolo_trace_rec* trace = nullptr; size_t trace_cap = 0;
+  double* sums = nullptr;
+  rolo::LmState* state = nullptr;
+  rolo_trace_rec* trace = nullptr;
   bool have_corr = false;
   // staging
   float* stage_in = nullptr; size_t stage_in_cap = 0;
@@ -158,7 +147,7 @@ struct rolo_ctx {
   hipGraphExec_t dbg_chain_exec = nullptr; int dbg_chain_key[3] = {-1, -1, -1};   // rolo_debug_chain: the captured chain and its (kind, n_pairs, grid)
   // hipGraph of one whole frame (rolo_register_async): captured on the second frame with an unchanged key, replayed after
   rolo::FrameArgs* h_args = nullptr;   // pinned; a captured H2D copy refreshes d_args on every replay
-  rolo::FrameArgs* d_args = nullptr; size_t d_args_cap = 0;
+  rolo::FrameArgs* d_args = nullptr;
   using GraphKey = rolo::GraphKey;
   rolo::CapturedSchedule<GraphKey> sched;
   bool device_busy = false;   // other contexts of this device had frames in flight when this frame was enqueued (picks the walk kernel of large launches: knn_cov.hip launch_knn_walk)
@@ -196,6 +185,7 @@ struct rolo_batch {
   hipEvent_t ev_fork = nullptr;
   std::vector<hipEvent_t> ev_join;   // member front work done (recorded inside the captured schedule)
   std::vector<hipEvent_t> ev_in;     // member stream's earlier work (cloud packing) done — recorded outside the graph
+  rolo::DevStore store;                    // the four buffers below
   rolo::BatchSlot* h_slots = nullptr;      // pinned
   rolo::BatchSlot* d_slots = nullptr;
   rolo::FrameArgs* h_args = nullptr;       // pinned, n entries

@@ -3,6 +3,7 @@
 // scan2map.hip, submap.hip, scancontext.hip, loopicp.hip) as well as by their users: the compiler checks every definition against the declaration here.
 #pragma once
 #include "rolo_internal.hpp"
+#include <atomic>
 #include <string>
 #include <vector>
 
@@ -50,6 +51,7 @@ struct DevStore {
   hipStream_t stream = nullptr;   // carries the copy of the `keep` elements
   const char* who = "";           // names the unit in the allocation's error message
   size_t slack = 256;             // elements a buffer gets beyond one and a half times the need
+  std::atomic<unsigned long long>* epoch = nullptr;   // counts the device allocations, where captured frames are keyed on them (a context's buffers)
   std::vector<void*> dev, pinned; // everything allocated since the last release()
 
   // exactly n elements of device memory; with p set before, the first `keep` of the old buffer copied over on the stream
@@ -58,6 +60,7 @@ struct DevStore {
     T* q = nullptr;
     if (hipMalloc((void**)&q, n * sizeof(T)) != hipSuccess) { ctx_set_error((std::string("hipMalloc failed (") + who + ")").c_str()); return ROLO_EHIP; }
     dev.push_back(q);
+    if (epoch) ++*epoch;
     if (p && keep) HIPCHK(hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, stream));
     p = q;
     return ROLO_OK;

@@ -7,7 +7,7 @@ using namespace rolo;
 // ---- test hook: the controller kernels on scripted pass results (include/rolo_hip.h rolo_lm_script) -------------------------------------------
 static int script_stage(rolo_ctx* c, const rolo_lm_script* S, int stage, int dof, int generic_ctrl) {
   if (!S || S->n_outer < 1 || S->n_trial < 1 || !S->lin_y || !S->lin_H || !S->lin_b || !S->lin_n || !S->err_y) { g_err = "bad LM script"; return ROLO_EINVAL; }
-  int rc = ensure(c->partials, c->partials_cap, (size_t)NV_MAX);
+  int rc = c->store.grow(c->partials, c->partials_cap, (size_t)NV_MAX);
   if (rc) return rc;
   const int hard_cap = (std::max(c->P.max_iterations, c->P.fixed_iterations) + 2) * (std::max(c->P.lm_max_iterations, 0) + 2) + 8;
   for (int it = 0; it <= hard_cap; it++) {

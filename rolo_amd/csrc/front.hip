@@ -977,8 +977,9 @@ __global__ void fill_int_kernel(int* p, int n, int v) {
 
 struct Front {
   int device = 0;
-  size_t cap_raw = 0, cap_raw_pts = 0, cap_pix = 0, cap_scan = 0;
-  float* raw = nullptr; unsigned short* ring = nullptr;
+  DevStore store;   // every buffer below; none of them is part of a captured frame
+  size_t cap_pix = 0, cap_scan = 0;   // the pixel and the ring group: set once every buffer of the group is allocated
+  float* raw = nullptr; size_t cap_raw = 0; unsigned short* ring = nullptr; size_t cap_ring = 0;   // staged records (floats) and their rings (points)
   int *owner = nullptr, *local_idx = nullptr, *ring_count = nullptr, *start_ring = nullptr, *end_ring = nullptr, *counters = nullptr;
   float4* extracted = nullptr; int* col = nullptr; float* range = nullptr; float* range_mat = nullptr;
   float* curv = nullptr; int *picked = nullptr, *label = nullptr;
@@ -999,67 +1000,62 @@ struct Front {
   bool deskew_from_msg = false;                      // armed without times: the next message brings them
   // message-level entry: raw payload and what the unpack kernel makes of it
   unsigned char* msg_raw = nullptr; size_t cap_msg = 0;
-  float* msg_xyz = nullptr; unsigned short* msg_ring = nullptr; float* msg_time = nullptr; size_t cap_msg_pts = 0;
+  float* msg_xyz = nullptr; unsigned short* msg_ring = nullptr; float* msg_time = nullptr; size_t cap_msg_xyz = 0, cap_msg_ring = 0, cap_msg_time = 0;
 };
 
 thread_local std::string g_ferr;
 
-template <typename T>
-bool dev_alloc(T*& p, size_t count) {
-  if (p) { (void)hipFree(p); p = nullptr; }
-  return hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T)) == hipSuccess;
-}
-
-void front_free(Front* f) {
-  void* bufs[] = {f->raw, f->ring, f->owner, f->local_idx, f->ring_count, f->start_ring, f->end_ring, f->counters, f->extracted, f->col, f->range,
-                  f->range_mat, f->curv, f->picked, f->label, f->corner_stage, f->surf_stage, f->corner_out, f->surf_out, f->corner_cnt, f->surf_cnt, f->paths, f->big, f->rel_time, f->msg_raw, f->msg_xyz, f->msg_ring, f->msg_time};
-  for (void* b : bufs) if (b) (void)hipFree(b);
-}
-
 }  // namespace
 
 namespace {
+
+// the front-end state of a context, created on first use
+Front* front_of(rolo_ctx* c) {
+  void** slot = ctx_front_slot(c);
+  if (!*slot) {
+    Front* f = new Front();
+    f->store.stream = ctx_stream(c); f->store.who = "front end";
+    *slot = f;
+  }
+  return static_cast<Front*>(*slot);
+}
 
 // device buffers for frames of up to n_raw points / n_scan x horizon_scan pixels
 int front_prepare(rolo_ctx* c, const rolo_front_params* P, int n_raw, int stride, bool stage_raw, Front** out) {
   if (P->n_scan <= 0 || P->horizon_scan <= 0 || P->downsample_rate <= 0) { ctx_set_error("bad front params"); return ROLO_EINVAL; }
   if (P->horizon_scan > FRONT_MAX_H_BIG) { ctx_set_error("Horizon_SCAN above the limit of this build (4096)"); return ROLO_EUNSUPPORTED; }
   HIPCHK(hipSetDevice(ctx_device(c)));
-  void** slot = ctx_front_slot(c);
-  if (!*slot) *slot = new Front();
-  Front* f = static_cast<Front*>(*slot);
+  Front* f = front_of(c);
   f->device = ctx_device(c);
+  f->projected = false; f->paths_valid = false; f->last_times = nullptr;   // (before the buffers change: what an earlier frame left is gone either way)
   const int NS = P->n_scan, H = P->horizon_scan;
   const size_t npix = (size_t)NS * H;
-  bool ok = true;
+  DevStore& st = f->store;
+  int rc;
   // two capacities: floats of the staged records (n_raw * stride) and points (ring) — a later frame with a smaller stride can hold
   // more points inside the same float capacity
-  if (stage_raw && ((size_t)n_raw * stride > f->cap_raw || !f->raw)) {
-    ok = ok && dev_alloc(f->raw, (size_t)n_raw * stride);
-    f->cap_raw = ok ? (size_t)n_raw * stride : 0;
-  }
-  if (stage_raw && ((size_t)n_raw > f->cap_raw_pts || !f->ring)) {
-    ok = ok && dev_alloc(f->ring, (size_t)n_raw);
-    f->cap_raw_pts = ok ? (size_t)n_raw : 0;
-  }
-  if (npix > f->cap_pix || !f->owner) {
+  if (stage_raw && ((rc = st.grow(f->raw, f->cap_raw, (size_t)n_raw * stride)) || (rc = st.grow(f->ring, f->cap_ring, (size_t)n_raw)))) return rc;
+  // a group's capacity is set once every buffer of the group is there: after a failed allocation the next call allocates the group again
+  if (npix > f->cap_pix) {
     const size_t np = npix + 2 * FRONT_GUARD;
-    ok = ok && dev_alloc(f->owner, npix) && dev_alloc(f->local_idx, npix) && dev_alloc(f->extracted, np) && dev_alloc(f->col, np) && dev_alloc(f->range, np) &&
-         dev_alloc(f->range_mat, npix) && dev_alloc(f->curv, np) && dev_alloc(f->picked, np) && dev_alloc(f->label, np) && dev_alloc(f->corner_out, npix) &&
-         dev_alloc(f->surf_out, npix);
-    f->cap_pix = npix; f->precleared_np = 0;   // fresh buffers: not cleared
+    f->cap_pix = 0; f->precleared_np = 0;   // fresh buffers: not cleared
+    if ((rc = st.alloc(f->owner, npix)) || (rc = st.alloc(f->local_idx, npix)) || (rc = st.alloc(f->extracted, np)) || (rc = st.alloc(f->col, np)) ||
+        (rc = st.alloc(f->range, np)) || (rc = st.alloc(f->range_mat, npix)) || (rc = st.alloc(f->curv, np)) || (rc = st.alloc(f->picked, np)) ||
+        (rc = st.alloc(f->label, np)) || (rc = st.alloc(f->corner_out, npix)) || (rc = st.alloc(f->surf_out, npix))) return rc;
+    f->cap_pix = npix;
   }
   const int maxh = H > FRONT_MAX_H ? FRONT_MAX_H_BIG : FRONT_MAX_H;   // pitch of the per-ring staging rows, and which extract kernel runs
-  if ((size_t)NS > f->cap_scan || !f->ring_count || maxh > f->cap_maxh) {
-    ok = ok && dev_alloc(f->ring_count, NS) && dev_alloc(f->start_ring, NS) && dev_alloc(f->end_ring, NS) && dev_alloc(f->counters, 8) &&
-         dev_alloc(f->corner_stage, (size_t)NS * 6 * 20) && dev_alloc(f->corner_cnt, (size_t)NS * 6) && dev_alloc(f->surf_stage, (size_t)NS * maxh) &&
-         dev_alloc(f->surf_cnt, NS) && dev_alloc(f->paths, NS);
-    if (maxh > FRONT_MAX_H) ok = ok && dev_alloc(f->big, (size_t)NS * front_ring_bytes(FRONT_MAX_H_BIG));
-    f->cap_scan = ok ? NS : 0; f->cap_maxh = ok ? maxh : 0;
+  if ((size_t)NS > f->cap_scan || maxh > f->cap_maxh) {
+    const size_t ns = (size_t)NS;
+    f->cap_scan = 0; f->cap_maxh = 0;
+    if ((rc = st.alloc(f->ring_count, ns)) || (rc = st.alloc(f->start_ring, ns)) || (rc = st.alloc(f->end_ring, ns)) || (rc = st.alloc(f->counters, 8)) ||
+        (rc = st.alloc(f->corner_stage, ns * 6 * 20)) || (rc = st.alloc(f->corner_cnt, ns * 6)) || (rc = st.alloc(f->surf_stage, ns * maxh)) ||
+        (rc = st.alloc(f->surf_cnt, ns)) || (rc = st.alloc(f->paths, ns)) ||
+        (maxh > FRONT_MAX_H && (rc = st.alloc(f->big, ns * front_ring_bytes(FRONT_MAX_H_BIG))))) return rc;
+    f->cap_scan = ns; f->cap_maxh = maxh;
   }
   f->maxh = maxh;
-  if (!ok) { ctx_set_error("hipMalloc failed (front end)"); return ROLO_EHIP; }
-  f->n_scan = NS; f->H = H; f->projected = false; f->paths_valid = false; f->last_times = nullptr;
+  f->n_scan = NS; f->H = H;
   *out = f;
   return ROLO_OK;
 }
@@ -1073,10 +1069,7 @@ int front_project_enqueue(Front* f, const rolo_front_params* P, const float* d_p
   if (f->deskew_from_msg) {   // armed without times and no time field came with the points: interpolate them from the azimuth
     f->deskew_from_msg = false;
     if (n_raw > 0) {
-      if ((size_t)n_raw > f->cap_time || !f->rel_time) {
-        if (!dev_alloc(f->rel_time, (size_t)n_raw)) { ctx_set_error("hipMalloc failed (de-skew times)"); return ROLO_EHIP; }
-        f->cap_time = (size_t)n_raw;
-      }
+      if (int rc = f->store.grow(f->rel_time, f->cap_time, (size_t)n_raw)) return rc;
       fill_int_kernel<<<1, 64, 0, s>>>(f->counters + 4, 1, INT_MAX);
       azimuth_flag_kernel<<<(n_raw + 255) / 256, 256, 0, s>>>(d_pts, stride, n_raw, f->counters + 4);
       azimuth_time_kernel<<<(n_raw + 255) / 256, 256, 0, s>>>(d_pts, stride, n_raw, f->deskew.scan_period, f->counters + 4, f->rel_time);
@@ -1194,13 +1187,11 @@ int front_frame_features_from_msg(rolo_ctx* c, const rolo_front_params* P, const
   if (rc) return rc;
   hipStream_t s = ctx_stream(c);
   const size_t bytes = (size_t)n_raw * L->point_step;
-  if ((size_t)n_raw > f->cap_msg_pts || !f->msg_xyz) {
-    if (!dev_alloc(f->msg_xyz, 3 * (size_t)n_raw) || !dev_alloc(f->msg_ring, (size_t)n_raw) || !dev_alloc(f->msg_time, (size_t)n_raw)) { ctx_set_error("hipMalloc failed (message buffers)"); return ROLO_EHIP; }
-    f->cap_msg_pts = (size_t)n_raw;
-  }
+  if ((rc = f->store.grow(f->msg_xyz, f->cap_msg_xyz, 3 * (size_t)n_raw)) || (rc = f->store.grow(f->msg_ring, f->cap_msg_ring, (size_t)n_raw)) ||
+      (rc = f->store.grow(f->msg_time, f->cap_msg_time, (size_t)n_raw))) return rc;
   const unsigned char* d_data = data;
   if (!on_device) {
-    if (bytes > f->cap_msg || !f->msg_raw) { if (!dev_alloc(f->msg_raw, bytes)) { ctx_set_error("hipMalloc failed (message payload)"); return ROLO_EHIP; } f->cap_msg = bytes; }
+    if ((rc = f->store.grow(f->msg_raw, f->cap_msg, bytes))) return rc;
     HIPCHK(hipMemcpyAsync(f->msg_raw, data, bytes, hipMemcpyHostToDevice, s));
     d_data = f->msg_raw;
   }
@@ -1235,15 +1226,13 @@ extern "C" {
 
 void rolo_front_destroy(rolo_ctx* c) {
   void** slot = ctx_front_slot(c);
-  if (*slot) { Front* f = static_cast<Front*>(*slot); front_free(f); delete f; *slot = nullptr; }
+  if (*slot) { Front* f = static_cast<Front*>(*slot); f->store.release(); delete f; *slot = nullptr; }   // (rolo_ctx_destroy has drained the stream)
 }
 
 int rolo_front_set_deskew(rolo_ctx* c, const rolo_deskew* d, const float* rel_time, int n_raw, int on_device) {
   if (!c || !d) return ROLO_EINVAL;
   HIPCHK(hipSetDevice(ctx_device(c)));
-  void** slot = ctx_front_slot(c);
-  if (!*slot) *slot = new Front();
-  Front* f = static_cast<Front*>(*slot);
+  Front* f = front_of(c);
   f->deskew_armed = false; f->deskew_from_msg = false;
   if (!d->enabled) return ROLO_OK;   // deskewPoint returns the point as is (:371-372)
   if (!(d->odom_time_diff != 0.0) || !(d->scan_period != 0.f)) { ctx_set_error("de-skew: zero scan period / odometry time difference"); return ROLO_EINVAL; }
@@ -1255,10 +1244,7 @@ int rolo_front_set_deskew(rolo_ctx* c, const rolo_deskew* d, const float* rel_ti
   if (n_raw < 0) { ctx_set_error("de-skew needs the per-point times"); return ROLO_EINVAL; }
   const float* dt = rel_time;
   if (!on_device) {
-    if ((size_t)n_raw > f->cap_time || !f->rel_time) {
-      if (!dev_alloc(f->rel_time, (size_t)n_raw)) { ctx_set_error("hipMalloc failed (de-skew times)"); return ROLO_EHIP; }
-      f->cap_time = (size_t)n_raw;
-    }
+    if (int rc = f->store.grow(f->rel_time, f->cap_time, (size_t)n_raw)) return rc;
     HIPCHK(hipMemcpyAsync(f->rel_time, rel_time, sizeof(float) * (size_t)n_raw, hipMemcpyHostToDevice, ctx_stream(c)));
     dt = f->rel_time;
   }

@@ -78,6 +78,7 @@ struct rolo_odom {
   float4* d_feat[3] = {nullptr, nullptr, nullptr};  // ring: [old] = previous features, [old+1], [old+2] = submitted frames
   float4* d_prop = nullptr;
   size_t d_cap = 0;
+  rolo::DevStore store;   // d_feat, d_prop and the slots' pinned counts
   int old_buf = 0, nOld = 0;
   int nCornerOld = 0;   // corners lead the feature cloud of the last collected frame
   struct Slot { double stamp = 0; int* h_counts = nullptr; hipEvent_t done = nullptr; } q[2];
@@ -119,6 +120,7 @@ int rolo_odom_create(rolo_ctx* ctx, float ct_lambda, rolo_odom** out) {
   if (!ctx || !out) return ROLO_EINVAL;
   rolo_odom* o = new rolo_odom();
   o->ctx = ctx; o->ct_lambda = ct_lambda;
+  o->store.who = "odometry";
   o->early_source_enabled = rolo::odom_early_source_now(o->early_source_enabled);   // A/B runs (ROLO_ODOM_EARLY_SOURCE, read per driver)
   // (rolo_params.fused_lm is NOT switched behind the caller's back here: the driver asserts its own option right before every registration it
   // enqueues — a later rolo_set_params with the caller's own parameter block cannot silently revert it, nor does creating a driver change
@@ -129,9 +131,8 @@ int rolo_odom_create(rolo_ctx* ctx, float ct_lambda, rolo_odom** out) {
 void rolo_odom_destroy(rolo_odom* o) {
   if (!o) return;
   if (o->fctx) rolo_ctx_destroy(o->fctx);  // synchronises its stream
-  for (float4* b : o->d_feat) if (b) (void)hipFree(b);
-  if (o->d_prop) (void)hipFree(o->d_prop);
-  for (auto& sl : o->q) { if (sl.h_counts) (void)hipHostFree(sl.h_counts); if (sl.done) (void)hipEventDestroy(sl.done); }
+  o->store.release();
+  for (auto& sl : o->q) if (sl.done) (void)hipEventDestroy(sl.done);
   delete o;
 }
 
@@ -153,9 +154,8 @@ static int ensure_front_ctx(rolo_odom* o) {
   int rc = plain ? rolo_ctx_create(rolo::ctx_device(o->ctx), &o->fctx) : rolo::ctx_create_high_priority(rolo::ctx_device(o->ctx), &o->fctx);
   if (rc) return rc;
   for (auto& sl : o->q) {
-    if (hipHostMalloc((void**)&sl.h_counts, 4 * sizeof(int)) != hipSuccess || hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) != hipSuccess) {
-      rolo::ctx_set_error("pinned buffer / event creation failed"); return ROLO_EHIP;
-    }
+    if ((rc = o->store.alloc_pinned(sl.h_counts, 4))) return rc;
+    if (hipEventCreateWithFlags(&sl.done, hipEventDisableTiming) != hipSuccess) { rolo::ctx_set_error("event creation failed"); return ROLO_EHIP; }
   }
   return ROLO_OK;
 }
@@ -257,11 +257,8 @@ static int submit_common(rolo_odom* o, const rolo_front_params* P, double stamp,
   const size_t cap = rolo::front_feature_capacity(P);
   if (cap > o->d_cap) {
     if (o->nOld > 0 || o->q_len > 0) { rolo::ctx_set_error("front parameters grew between frames"); return ROLO_ESTATE; }
-    float4** bufs[4] = {&o->d_feat[0], &o->d_feat[1], &o->d_feat[2], &o->d_prop};
-    for (float4** b : bufs) {
-      if (*b) { (void)hipFree(*b); *b = nullptr; }
-      if (hipMalloc((void**)b, sizeof(float4) * cap) != hipSuccess) { rolo::ctx_set_error("hipMalloc failed (odometry feature buffers)"); return ROLO_EHIP; }
-    }
+    o->d_cap = 0;   // (set again once all four are there)
+    for (float4** b : {&o->d_feat[0], &o->d_feat[1], &o->d_feat[2], &o->d_prop}) if ((rc = o->store.alloc(*b, cap))) return rc;
     o->d_cap = cap;
   }
   const int buf = (o->old_buf + 1 + o->q_len) % 3;

@@ -618,7 +618,7 @@ extern "C" void rolo_s2m_forget(rolo_ctx* c) {   // called by rolo_ctx_release b
   if (!W) return;
   W->have_maps = false; W->map_set = false; W->m_corner = W->m_surf = 0; W->maps = KnnPair{};
   rolo_ctx* q = W->qctx; W->qctx = nullptr;
-  if (q) rolo_ctx_release(q);   // (the scratch buffers stay: they only grow, and a hipFree would stall every context's frames in flight)
+  if (q) rolo_ctx_release(q);   // (the scratch buffers stay: they only grow, and freeing one would stall every context's frames in flight)
 }
 
 // kdtreeCornerFromMap->setInputCloud(laserCloudCornerFromMapDS) / kdtreeSurfFromMap->setInputCloud(laserCloudSurfFromMapDS) (:690-691) as a call of its own: the

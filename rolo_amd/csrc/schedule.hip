@@ -36,11 +36,11 @@ static unsigned long long lm_persist_timeout_ticks() { return (unsigned long lon
 int prepare_pass(rolo_ctx* c, PassArgs& a, int& grid) {
   const int noff = n_offsets(c->P);
   int rc;
-  for (int b = 0; b < 2; b++) if ((rc = ensure(c->corr[b], c->corr_cap[b], (size_t)c->src.n * noff))) return rc;
+  for (int b = 0; b < 2; b++) if ((rc = c->store.grow(c->corr[b], c->corr_cap[b], (size_t)c->src.n * noff))) return rc;
   int begin, end; shard(c, begin, end);
   grid = std::max(1, (end - begin + PASS_THREADS - 1) / PASS_THREADS);
   c->lm_rows = std::max(1, (end - begin + lm_threads() * lm_ppt() - 1) / (lm_threads() * lm_ppt()));
-  if ((rc = ensure(c->partials, c->partials_cap, std::max((size_t)grid, 2 * (size_t)c->lm_rows) * NV_MAX))) return rc;
+  if ((rc = c->store.grow(c->partials, c->partials_cap, std::max((size_t)grid, 2 * (size_t)c->lm_rows) * NV_MAX))) return rc;
   if (lm_persist(c)) {
     // ROLO_LM_PERSIST_BUSY_THREADS=256 (A/B): with other frames in flight twice the workgroups of half the size — the same registers held, on twice the CUs, half of each
     int T = c->device_busy ? switches().lm_persist_busy_threads : 512;
@@ -57,7 +57,7 @@ int prepare_pass(rolo_ctx* c, PassArgs& a, int& grid) {
     c->lmp_rows = (npts + T * c->lmp_ppt - 1) / (T * c->lmp_ppt);
     const size_t need = lm_persist_words(256);   // sized for the largest grid once: the epochs in it must survive a change of the cloud size
     if (!c->xbuf || c->xbuf_cap < need) {
-      if ((rc = ensure(c->xbuf, c->xbuf_cap, need))) return rc;
+      if ((rc = c->store.grow(c->xbuf, c->xbuf_cap, need))) return rc;
       HIPCHK(hipMemsetAsync(c->xbuf, 0, c->xbuf_cap * sizeof(unsigned long long), c->stream));
     }
   } else {
@@ -350,8 +350,8 @@ static int enqueue_frame(rolo_ctx* c, bool with_trans) {   // with_trans = false
   int rc;
   if (c->src.n <= 0 || c->tgt.n <= 0) { g_err = "source/target not set"; return ROLO_ESTATE; }
   if (stamp_env()) {
-    if ((rc = ensure(c->stamps, c->stamps_cap, 8))) return rc;
-    if (!c->h_stamps) HIPCHK(hipHostMalloc((void**)&c->h_stamps, sizeof(unsigned long long) * 8));
+    if (!c->stamps && (rc = c->store.alloc(c->stamps, 8))) return rc;
+    if (!c->h_stamps && (rc = c->store.alloc_pinned(c->h_stamps, 8))) return rc;
   }
   STAMP(0);
   // voxel map without the host round trip of ensure_map(): errors are picked up in rolo_register_wait. The table is sized first: when
@@ -522,11 +522,15 @@ int rolo_batch_create(int device, int n_members, rolo_batch** out) {
     if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { g_err = "event creation failed"; rolo_batch_destroy(b); return ROLO_EHIP; }
     b->ev_in.push_back(e);
   }
-  if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming) != hipSuccess ||
-      hipHostMalloc((void**)&b->h_slots, sizeof(BatchSlot) * n_members) != hipSuccess || hipHostMalloc((void**)&b->h_args, sizeof(FrameArgs) * n_members) != hipSuccess ||
-      hipMalloc((void**)&b->d_slots, sizeof(BatchSlot) * n_members) != hipSuccess || hipMalloc((void**)&b->d_args, sizeof(FrameArgs) * n_members) != hipSuccess) {
-    g_err = "batch allocation failed"; rolo_batch_destroy(b); return ROLO_EHIP;
+  if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming) != hipSuccess) {
+    g_err = "batch stream / event creation failed"; rolo_batch_destroy(b); return ROLO_EHIP;
   }
+  b->store.stream = b->stream; b->store.who = "batch";
+  int rc = b->store.alloc_pinned(b->h_slots, (size_t)n_members);
+  if (!rc) rc = b->store.alloc_pinned(b->h_args, (size_t)n_members);
+  if (!rc) rc = b->store.alloc(b->d_slots, (size_t)n_members);
+  if (!rc) rc = b->store.alloc(b->d_args, (size_t)n_members);
+  if (rc) { rolo_batch_destroy(b); return rc; }
   *out = b;
   return ROLO_OK;
 }
@@ -541,10 +545,7 @@ void rolo_batch_destroy(rolo_batch* b) {
   for (hipEvent_t e : b->ev_in) (void)hipEventDestroy(e);
   if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
   if (b->stream) (void)hipStreamDestroy(b->stream);
-  if (b->h_slots) (void)hipHostFree(b->h_slots);
-  if (b->h_args) (void)hipHostFree(b->h_args);
-  if (b->d_slots) (void)hipFree(b->d_slots);
-  if (b->d_args) (void)hipFree(b->d_args);
+  b->store.release();
   delete b;
 }
 

@@ -321,7 +321,7 @@ int km_alloc_points(rolo_keymap* km, size_t n, float4** out) {
   if (n == 0) return ROLO_OK;
   if (km->chunks.empty() || km->chunks.back().cap - km->chunks.back().used < n) {
     rolo_keymap::Chunk c{nullptr, std::max(CHUNK_POINTS, n), 0};
-    if (hipMalloc((void**)&c.p, c.cap * sizeof(float4)) != hipSuccess) { ctx_set_error("hipMalloc failed (key-frame store)"); return ROLO_EHIP; }
+    if (const int rc = km->store.alloc(c.p, c.cap)) return rc;
     km->chunks.push_back(c);
   }
   rolo_keymap::Chunk& c = km->chunks.back();
@@ -534,7 +534,6 @@ void rolo_keymap_destroy(rolo_keymap* km) {
   if (km->consumer_pending && km->consumed) (void)hipEventSynchronize(km->consumed);
   if (km->sc) { sc_store_destroy(km->sc); km->sc = nullptr; }
   if (km->loop_ctx) { rolo_ctx_release(km->loop_ctx); km->loop_ctx = nullptr; }
-  for (auto& c : km->chunks) (void)hipFree(c.p);
   km->store.release();
   if (km->ready) (void)hipEventDestroy(km->ready);
   if (km->consumed) (void)hipEventDestroy(km->consumed);

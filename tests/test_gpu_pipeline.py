@@ -318,6 +318,6 @@ def test_pipeline_50_frames():
         assert c[-1]["topup_frames"] <= 3, c[-1]
         assert c[-1]["sync_chunks"] <= 8, c[-1]
         assert c[-1]["hint_rot"] == c[20]["hint_rot"] and c[-1]["hint_trans"] <= c[20]["hint_trans"] + 2   # the schedule hints settled in the first twenty frames
-    # device allocations stop: buffers grow by a quarter beyond what a frame needs, so the count of (re)allocations is the same after frame 25 and after frame 50
+    # device allocations stop: buffers grow by half (and 256 elements) beyond what a frame needs, so the count of (re)allocations is the same after frame 25 and after frame 50
     assert counters[-1][2] == counters[25][2], (counters[25][2], counters[-1][2])
     staged.close(); fused.close()
