@@ -847,6 +847,92 @@ int rolo_priorpose_solve(rolo_ground* g, const rolo_priorpose_params* params, co
 /* the fit alone at nq <= ROLO_GROUND_MAX_QUERIES double queries (x y) */
 int rolo_priorpose_fit_surface(rolo_ground* g, const rolo_priorpose_params* params, const double* xy, int nq, rolo_priorpose_fit* out);
 
+/* ---- back end: the mapping node's per-scan step as one device-resident call ---------------------------------------------------------------
+ * laserCloudInfoHandler (src/backMapping.cpp:420-457) for one CloudInfoStamp: the interval gate (:436), updateInitialGuess (:516-555), extractSurroundingKeyFrames
+ * (:558-663), downsampleCurrentScan (:666-678), scan2MapOptimization (:681-711) with transformUpdate (:1060-1068), saveKeyFramesAndFactor (:1094-1221), correctPoses
+ * (:1287-1320), the incremental pose of publishOdometry (:1361-1389) and the clouds of publishFrames (:1405-1424), in that order. A mapper owns a key map, a pooled
+ * context for the scan-to-submap registration and a pose graph, and composes the calls above: every result is the bits of the call-by-call route (INTEGRATION.md,
+ * "Back end"). What it adds is residence: the scan is uploaded once (or handed over as device clouds), its two filtered clouds stay in slots of their own in the key
+ * map, the registration packs its features from there behind an event, and a saved scan is appended to the key-frame store device to device.
+ *   pose      transformTobeMapped = (roll, pitch, yaw, x, y, z) in float, as everywhere in this header. The node's Affine3f bookkeeping is restated in float:
+ *             pcl::getTransformation, pcl::getTranslationAndEulerAngles, Affine3f::inverse() as the cofactor inverse of the linear part with -L^-1 t, products as
+ *             sums over k left to right (Eigen's own order is unpinned).
+ *   sub-map   rolo_keyposes_select_nearby on the key map's poses and stamps (10 s of recent poses), rolo_keymap_extract, rolo_scan2map_set_submap_keymap. The
+ *             sub-map of the last scan is kept (submap_rebuilt = 0) exactly when the listed indices equal the last list and no key pose has been set since (by the
+ *             mapper or through the borrowed key map); nothing transformed is cached, so keeping and rebuilding give the same bits. (A rolo_keymap_extract of the caller's own
+ *             through the borrowed key map replaces what rolo_keymap_get_submap returns, not what the registration searches: its trees live in the mapper's context.)
+ *   too few   with n_corner_ds <= edgeFeatureMinValidNum or n_surf_ds <= surfFeatureMinValidNum the pose stays the guess, transformUpdate does not run and
+ *             incrementalOdometryAffineBack keeps the PREVIOUS scan's value, as in the reference (:687-710): the incremental pose then advances by the previous scan's
+ *             step measured from this scan's front. Before transformUpdate has ever run the reference reads an unset matrix; here it is the identity.
+ *   graph     key 0 gets the prior (:1229-1233), every later key the odometry factor from the key map's last pose (:1235-1241), then the queued loop factors
+ *             (cauchy_k > 0: rolo_pgo_add_between_robust) and prior factors in queue order, ONE rolo_pgo_optimize with the default parameters, and
+ *             transformTobeMapped from the newest pose's pose6. poseCovariance (:1161) is not provided: it is read nowhere. A queued factor whose keys are not
+ *             in the graph when it is added is ROLO_EINVAL, and the queues keep it.
+ *   errors    a non-finite coordinate (ROLO_ENONFINITE) or any other error before saveKeyFramesAndFactor leaves the mapper exactly as it was: pose, odometry
+ *             memory, time gate, key frames, graph, queues (the next scan rebuilds its sub-map). saveKeyFramesAndFactor first reserves room in the key map, the
+ *             descriptor store and the graph, then computes the descriptor, then changes the three: they grow together or not at all.
+ * A mapper is single-threaded like a context: the reference's mtx is the caller's business. Publishing stays with the caller. */
+typedef struct rolo_mapper rolo_mapper;
+typedef struct rolo_mapper_params {           /* utility.h:320-343 */
+  double mappingProcessInterval;              /* 0.15 */
+  float  mappingCornerLeafSize, mappingSurfLeafSize;                                       /* 0.2, 0.2 */
+  float  surroundingKeyframeSearchRadius, surroundingKeyframeDensity;                      /* 50, 1 */
+  float  surroundingkeyframeAddingDistThreshold, surroundingkeyframeAddingAngleThreshold;  /* 1.0, 0.2 */
+  int    edgeFeatureMinValidNum, surfFeatureMinValidNum;                                   /* 10, 100 */
+  float  z_tollerance, rotation_tollerance;                                                /* FLT_MAX */
+  int    sc_input;                            /* 0 none, 1 scan_feat (:1213), 2 scan_raw (:1186-1196) */
+  float  sc_leaf;                             /* downSizeFilterSC of scan_raw: 0.5 */
+} rolo_mapper_params;
+typedef struct rolo_mapper_result {
+  int processed;                              /* 0: the interval gate (:436) held the scan back; nothing else is filled */
+  float transformTobeMapped[6], incremental6[6];   /* :1348-1351 and :1372-1384 (x y z roll pitch yaw of increOdomAffine) */
+  int s2m_ran;                                /* 0: no key frame yet (:684) */
+  rolo_scan2map_stats s2m;
+  int n_corner_ds, n_surf_ds, m_corner, m_surf, n_listed, submap_rebuilt;
+  int keyframe;                               /* index of the key frame this scan became, -1: saveFrame said no */
+  int loops_added, priors_added, poses_corrected;   /* poses_corrected 1: correctPoses rewrote the key map */
+  int sc_index;                               /* descriptor stored for this key frame, -1 none */
+  rolo_pgo_result pgo;                        /* of the optimise behind isam->update, zeroed when keyframe < 0 */
+} rolo_mapper_result;
+void rolo_mapper_default_params(rolo_mapper_params* p);
+int rolo_mapper_create(int device, const rolo_mapper_params* params /* NULL: the defaults */, rolo_mapper** out);
+void rolo_mapper_destroy(rolo_mapper* m);
+/* borrowed, never destroyed by the caller: for the loop-closure, Scan Context, global-map and ground-prior calls between scans */
+rolo_keymap* rolo_mapper_keymap(rolo_mapper* m);
+rolo_pgo* rolo_mapper_pgo(rolo_mapper* m);
+/* one CloudInfoStamp. corner, surf: n x 4 floats (surf = extracted_surface ++ extracted_normal, :430); raw: cloud_projected (for sc_input 2 and
+ * rolo_mapper_get_registered_raw), may be NULL; clouds_on_device != 0: all three are device pointers on the mapper's device whose writers the caller has waited for.
+ * initialGuess6: initialGuessRoll / Pitch / Yaw / X / Y / Z, read when odomAvailable != 0. */
+int rolo_mapper_scan(rolo_mapper* m, double stamp, const float* corner, int n_corner, const float* surf, int n_surf, const float* raw, int n_raw, int clouds_on_device,
+                     const float* initialGuess6, int odomAvailable, rolo_mapper_result* out);
+/* loopIndexQueue / loopPoseQueue / loopNoiseQueue .push_back (:2388-2392, :2472-2476): between(from, to, T16, Variances(var6)), under Cauchy(cauchy_k) when cauchy_k > 0.
+ * T16, var6 and cauchy_k are checked here as rolo_pgo_add_between[_robust] checks them; the keys when the factor is added */
+int rolo_mapper_queue_loop(rolo_mapper* m, int from, int to, const double* T16, const double* var6, double cauchy_k);
+/* priorIndexQueue &c (:2129-2133) */
+int rolo_mapper_queue_prior(rolo_mapper* m, int from, int to, const double* T16, const double* var6);
+/* laserCloudCornerLastDS / laserCloudSurfLastDS of the last processed scan; either output may be NULL to read the sizes; counts2 (optional): the two sizes */
+int rolo_mapper_get_scan(rolo_mapper* m, float* corner_ds, int cap_corner, float* surf_ds, int cap_surf, int* counts2);
+/* publishFrames :1405-1414: corner_ds ++ surf_ds moved to transformTobeMapped, each row T0 x + (T1 y + (T2 z + T3)) as the key map moves its clouds; returns the size */
+int rolo_mapper_get_registered(rolo_mapper* m, float* out, int cap);
+/* :1416-1424: the raw cloud of the last processed scan moved the same way; ROLO_ESTATE when that scan came without one */
+int rolo_mapper_get_registered_raw(rolo_mapper* m, float* out, int cap);
+/* the key poses (n x 6 floats) and stamps of the mapper's key map, the first min(n, cap); returns n */
+int rolo_mapper_get_keyposes(rolo_mapper* m, float* pose6, double* times, int cap);
+/* device milliseconds of the last processed scan between HIP events: ms6[0] down-sample, [1] sub-map (extraction and hand-over), [2] scan2map, [3] key-frame commit
+ * (descriptor and append), [4] graph (rolo_pgo_last_ms summed), [5] the whole call, first event to last */
+int rolo_mapper_last_ms(rolo_mapper* m, float* ms6);
+/* the node's float bookkeeping, host only (no device needed):
+ * updateInitialGuess (:516-555) after incrementalOdometryAffineFront has been taken. tf6_out = tf6_in, with roll = pitch = yaw = 0 while there is no key frame
+ * (:524-531); else, when odomAvailable: the first guess is only stored (:540-543), a later one moves the pose by lastOdom^-1 guess (:545-551). lastOdom12 (rows 0..2 of
+ * lastOdomTransformation, row-major 3 x 4) and *lastOdomAvailable are read and updated. */
+int rolo_mapper_initial_guess(const float* tf6_in, int have_keyposes, const float* guess6, int odomAvailable, float* lastOdom12, int* lastOdomAvailable, float* tf6_out);
+/* saveFrame (:1071-1091): 1 save, 0 not; last_keypose6 NULL: no key frame yet, 1 */
+int rolo_mapper_save_frame(const float* last_keypose6, const float* tf6, float dist_thr, float angle_thr);
+/* publishOdometry :1361-1389. started == 0 (lastIncreOdomPubFlag false): incre12 = trans2Affine3f(tf6). Otherwise incre12 <- incre12 (front^-1 back) with front =
+ * trans2Affine3f(front6), the pose before updateInitialGuess (:519), and back = trans2Affine3f(back6), the pose transformUpdate last wrote (:1067). pose6_out =
+ * x y z roll pitch yaw of incre12. */
+int rolo_mapper_incremental(const float* front6, const float* back6, const float* tf6, int started, float* incre12, float* pose6_out);
+
 #ifdef __cplusplus
 }
 #endif

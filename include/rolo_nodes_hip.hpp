@@ -7,6 +7,8 @@
 //                                                                                     src/featureExtraction.cpp:87-266
 //   rolo::LidarOdometry      odometryHandler() / cloudHandler()                       src/lidarOdometry.cpp:440-446, 503-570
 //                            + the fused device-resident path frame() / submit() / collect() (rolo_odom_frame & co)
+// and of the back end's mapping node:
+//   rolo::MapOptimization    laserCloudInfoHandler()                                  src/backMapping.cpp:420-457 (rolo_mapper_scan)
 //
 // Data are plain arrays with the layout of rolo/CloudInfoStamp (msg/CloudInfoStamp.msg:1-28): int32 startRingIndex /
 // endRingIndex / pointColInd, float32 pointRange, feature clouds as n x 4 floats (x, y, z, intensity).
@@ -156,6 +158,90 @@ public:
 private:
   Context& ctx_;
   rolo_odom* odom_ = nullptr;
+};
+
+// rolo/mapping* of include/rolo/utility.h:320-343 under their own names
+struct MapperParams : rolo_mapper_params {
+  MapperParams() { rolo_mapper_default_params(this); }
+};
+
+// mapOptimization (src/backMapping.cpp): laserCloudInfoHandler :420-457 as one call per CloudInfoStamp (rolo_mapper_scan). The key map, the scan-to-submap
+// context and the pose graph belong to the object; keymap() / graph() lend them to the loop-closure, Scan Context, global-map and ground-prior calls between
+// scans. The reference's mtx stays with the node: one thread at a time.
+class MapOptimization {
+public:
+  explicit MapOptimization(int device = 0, const MapperParams& params = MapperParams()) { check(rolo_mapper_create(device, &params, &mapper_), "rolo_mapper_create"); }
+  ~MapOptimization() { rolo_mapper_destroy(mapper_); }
+  MapOptimization(const MapOptimization&) = delete;
+  MapOptimization& operator=(const MapOptimization&) = delete;
+
+  // :420-457 between fromROSMsg and the publishers. laserCloudCornerLast / laserCloudSurfLast (extracted_surface ++ extracted_normal, :430): n x 4 floats;
+  // cloud_projected may be empty; initialGuess = initialGuessRoll / Pitch / Yaw / X / Y / Z when odomAvailable. Returns false when the interval gate held the scan
+  bool laserCloudInfoHandler(double timeLaserInfoCur, const std::vector<float>& laserCloudCornerLast, const std::vector<float>& laserCloudSurfLast,
+                             const std::vector<float>& cloud_projected = {}, const float* initialGuess = nullptr, bool odomAvailable = false) {
+    check(rolo_mapper_scan(mapper_, timeLaserInfoCur, laserCloudCornerLast.data(), (int)(laserCloudCornerLast.size() / 4), laserCloudSurfLast.data(),
+                           (int)(laserCloudSurfLast.size() / 4), cloud_projected.empty() ? nullptr : cloud_projected.data(), (int)(cloud_projected.size() / 4), 0,
+                           initialGuess, odomAvailable ? 1 : 0, &result), "rolo_mapper_scan");
+    if (!result.processed) return false;
+    for (int k = 0; k < 6; k++) transformTobeMapped[k] = result.transformTobeMapped[k];
+    isDegenerate = result.s2m.degenerate != 0;
+    return true;
+  }
+  // the same on device clouds of the mapper's device whose writers the caller has waited for
+  bool laserCloudInfoHandlerDevice(double timeLaserInfoCur, const float* d_corner, int n_corner, const float* d_surf, int n_surf, const float* d_raw, int n_raw,
+                                   const float* initialGuess = nullptr, bool odomAvailable = false) {
+    check(rolo_mapper_scan(mapper_, timeLaserInfoCur, d_corner, n_corner, d_surf, n_surf, d_raw, n_raw, 1, initialGuess, odomAvailable ? 1 : 0, &result), "rolo_mapper_scan");
+    if (!result.processed) return false;
+    for (int k = 0; k < 6; k++) transformTobeMapped[k] = result.transformTobeMapped[k];
+    isDegenerate = result.s2m.degenerate != 0;
+    return true;
+  }
+  // loopIndexQueue / loopPoseQueue / loopNoiseQueue .push_back (:2388-2392; cauchy_k > 0: the Robust noise of :2468-2470), priorIndexQueue &c (:2129-2133)
+  void queueLoop(int indexFrom, int indexTo, const double poseBetween[16], const double variances[6], double cauchy_k = 0.0) {
+    check(rolo_mapper_queue_loop(mapper_, indexFrom, indexTo, poseBetween, variances, cauchy_k), "rolo_mapper_queue_loop");
+  }
+  void queuePrior(int indexFrom, int indexTo, const double poseBetween[16], const double variances[6]) {
+    check(rolo_mapper_queue_prior(mapper_, indexFrom, indexTo, poseBetween, variances), "rolo_mapper_queue_prior");
+  }
+  // cloudKeyPoses6D: n x 6 floats (roll, pitch, yaw, x, y, z) and the stamps
+  int cloudKeyPoses6D(std::vector<float>& pose6, std::vector<double>& time) {
+    const int n = check(rolo_mapper_get_keyposes(mapper_, nullptr, nullptr, 0), "rolo_mapper_get_keyposes");
+    pose6.assign((size_t)(n > 0 ? n : 1) * 6, 0.f); time.assign((size_t)(n > 0 ? n : 1), 0.0);
+    check(rolo_mapper_get_keyposes(mapper_, pose6.data(), time.data(), n), "rolo_mapper_get_keyposes");
+    pose6.resize((size_t)n * 6); time.resize((size_t)n);
+    return n;
+  }
+  // laserCloudCornerLastDS / laserCloudSurfLastDS of the last processed scan
+  void lastScanDS(std::vector<float>& laserCloudCornerLastDS, std::vector<float>& laserCloudSurfLastDS) {
+    int cnt[2] = {0, 0};
+    check(rolo_mapper_get_scan(mapper_, nullptr, 0, nullptr, 0, cnt), "rolo_mapper_get_scan");
+    laserCloudCornerLastDS.assign((size_t)(cnt[0] > 0 ? cnt[0] : 1) * 4, 0.f); laserCloudSurfLastDS.assign((size_t)(cnt[1] > 0 ? cnt[1] : 1) * 4, 0.f);
+    check(rolo_mapper_get_scan(mapper_, laserCloudCornerLastDS.data(), cnt[0], laserCloudSurfLastDS.data(), cnt[1], nullptr), "rolo_mapper_get_scan");
+    laserCloudCornerLastDS.resize((size_t)cnt[0] * 4); laserCloudSurfLastDS.resize((size_t)cnt[1] * 4);
+  }
+  // publishFrames :1405-1414 — what pubRecentKeyFrame gets
+  void registeredKeyFrame(std::vector<float>& cloudOut) {
+    int cnt[2] = {0, 0};
+    check(rolo_mapper_get_scan(mapper_, nullptr, 0, nullptr, 0, cnt), "rolo_mapper_get_scan");
+    cloudOut.assign((size_t)(cnt[0] + cnt[1] > 0 ? cnt[0] + cnt[1] : 1) * 4, 0.f);
+    const int n = check(rolo_mapper_get_registered(mapper_, cloudOut.data(), cnt[0] + cnt[1]), "rolo_mapper_get_registered");
+    cloudOut.resize((size_t)n * 4);
+  }
+  // :1416-1424 — what pubCloudRegisteredRaw gets; n_raw: the size of the cloud_projected handed to the last scan
+  void registeredRaw(std::vector<float>& cloudOut, int n_raw) {
+    cloudOut.assign((size_t)(n_raw > 0 ? n_raw : 1) * 4, 0.f);
+    const int n = check(rolo_mapper_get_registered_raw(mapper_, cloudOut.data(), n_raw), "rolo_mapper_get_registered_raw");
+    cloudOut.resize((size_t)n * 4);
+  }
+  rolo_keymap* keymap() const { return rolo_mapper_keymap(mapper_); }   // borrowed
+  rolo_pgo* graph() const { return rolo_mapper_pgo(mapper_); }          // borrowed
+  rolo_mapper* get() const { return mapper_; }
+
+  std::array<float, 6> transformTobeMapped{};   // roll, pitch, yaw, x, y, z
+  bool isDegenerate = false;
+  rolo_mapper_result result{};                  // of the last laserCloudInfoHandler: incremental6, the stats, the key frame, the graph's optimise
+private:
+  rolo_mapper* mapper_ = nullptr;
 };
 
 }  // namespace rolo

@@ -112,6 +112,20 @@ class PriorPoseFit(C.Structure):
     _fields_ = [("hits", C.c_int), ("inliers", C.c_int), ("fallback", C.c_int), ("nearest", C.c_int), ("point", C.c_double * 3)]
 
 
+class MapperParams(C.Structure):
+    _fields_ = [("mappingProcessInterval", C.c_double), ("mappingCornerLeafSize", C.c_float), ("mappingSurfLeafSize", C.c_float),
+                ("surroundingKeyframeSearchRadius", C.c_float), ("surroundingKeyframeDensity", C.c_float),
+                ("surroundingkeyframeAddingDistThreshold", C.c_float), ("surroundingkeyframeAddingAngleThreshold", C.c_float),
+                ("edgeFeatureMinValidNum", C.c_int), ("surfFeatureMinValidNum", C.c_int), ("z_tollerance", C.c_float), ("rotation_tollerance", C.c_float),
+                ("sc_input", C.c_int), ("sc_leaf", C.c_float)]
+
+
+class MapperResult(C.Structure):
+    _fields_ = [("processed", C.c_int), ("transformTobeMapped", C.c_float * 6), ("incremental6", C.c_float * 6), ("s2m_ran", C.c_int), ("s2m", Scan2MapStats),
+                ("n_corner_ds", C.c_int), ("n_surf_ds", C.c_int), ("m_corner", C.c_int), ("m_surf", C.c_int), ("n_listed", C.c_int), ("submap_rebuilt", C.c_int),
+                ("keyframe", C.c_int), ("loops_added", C.c_int), ("priors_added", C.c_int), ("poses_corrected", C.c_int), ("sc_index", C.c_int), ("pgo", PgoResult)]
+
+
 class EskfOptions(C.Structure):   # include/rolo_fusion.h
     _fields_ = [(k, C.c_double) for k in ("max_dt", "q_linear_jerk_std", "q_angular_jerk_std", "r_position_std", "r_rotation_std", "init_position_std",
                                           "init_rotation_std", "init_velocity_std", "init_angular_velocity_std", "init_acceleration_std",
@@ -252,6 +266,22 @@ SYMBOLS = {
     "rolo_priorpose_default_params": (None, [C.POINTER(PriorPoseParams)]),
     "rolo_priorpose_solve": (C.c_int, [vp, C.POINTER(PriorPoseParams), dp, C.c_int, C.POINTER(PriorPoseResult)]),
     "rolo_priorpose_fit_surface": (C.c_int, [vp, C.POINTER(PriorPoseParams), dp, C.c_int, C.POINTER(PriorPoseFit)]),
+    "rolo_mapper_default_params": (None, [C.POINTER(MapperParams)]),
+    "rolo_mapper_create": (C.c_int, [C.c_int, C.POINTER(MapperParams), C.POINTER(vp)]),
+    "rolo_mapper_destroy": (None, [vp]),
+    "rolo_mapper_keymap": (vp, [vp]),
+    "rolo_mapper_pgo": (vp, [vp]),
+    "rolo_mapper_scan": (C.c_int, [vp, C.c_double, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, fp, C.c_int, C.POINTER(MapperResult)]),
+    "rolo_mapper_queue_loop": (C.c_int, [vp, C.c_int, C.c_int, dp, dp, C.c_double]),
+    "rolo_mapper_queue_prior": (C.c_int, [vp, C.c_int, C.c_int, dp, dp]),
+    "rolo_mapper_get_scan": (C.c_int, [vp, fp, C.c_int, fp, C.c_int, C.POINTER(C.c_int)]),
+    "rolo_mapper_get_registered": (C.c_int, [vp, fp, C.c_int]),
+    "rolo_mapper_get_registered_raw": (C.c_int, [vp, fp, C.c_int]),
+    "rolo_mapper_get_keyposes": (C.c_int, [vp, fp, dp, C.c_int]),
+    "rolo_mapper_last_ms": (C.c_int, [vp, fp]),
+    "rolo_mapper_initial_guess": (C.c_int, [fp, C.c_int, fp, C.c_int, fp, C.POINTER(C.c_int), fp]),
+    "rolo_mapper_save_frame": (C.c_int, [fp, fp, C.c_float, C.c_float]),
+    "rolo_mapper_incremental": (C.c_int, [fp, fp, fp, C.c_int, fp, fp]),
     "rolo_num_voxels": (C.c_int, [vp]),
     "rolo_num_edge_points": (C.c_int, [vp]),
     "rolo_get_voxels": (C.c_int, [vp, ip, ip, dp, dp]),

@@ -2,14 +2,15 @@
 device-resident key frames with sub-map assembly (:558-678) over rolo_keymap_*, Scan Context loop detection (src/scancontext/Scancontext.cpp) over
 rolo_keymap_sc_*, the loop closure's clouds, radius-search detector and ICP (:2307-2624) over rolo_keymap_loop_* / rolo_loopicp_*, the factor graph
 (:1222-1320) as a batch pose-graph optimisation over rolo_pgo_*, and the clouds of the exports (publishGlobalMap :1611-1665, cloudGlobal.pcd :1546-1557) over
-rolo_keymap_global_*, and the ground prior (src/prior_pose/pose_solver.cpp, prior_pose_node.cpp:164-233) over rolo_ground_* / rolo_priorpose_*."""
+rolo_keymap_global_*, and the ground prior (src/prior_pose/pose_solver.cpp, prior_pose_node.cpp:164-233) over rolo_ground_* / rolo_priorpose_*; and the node's
+per-scan step laserCloudInfoHandler (:420-457) as one call over all of them: MapOptimization over rolo_mapper_*."""
 from __future__ import annotations
 
 import ctypes as C
 
 import numpy as np
 
-from ._lib import lib, check, Scan2MapStats, ScParams, ScResult, LoopIcpParams, LoopIcpResult, LoopIcpTraceRec, PgoParams, PgoResult, PgoTraceRec, PriorPoseParams, PriorPoseResult, PriorPoseFit
+from ._lib import lib, check, Scan2MapStats, ScParams, ScResult, LoopIcpParams, LoopIcpResult, LoopIcpTraceRec, PgoParams, PgoResult, PgoTraceRec, PriorPoseParams, PriorPoseResult, PriorPoseFit, MapperParams, MapperResult
 from .rotvgicp import RotVGICP
 
 
@@ -1090,3 +1091,211 @@ class GroundPriorCloser:
                 self.last += [dict(entry=e2, linked_key=l2, icp=r2, rejected="unused", gates=None) for (e2, l2, _, _), r2 in zip(chunk[k + 1:], results[k + 1:])]
                 return PriorFactor(linked_id, current_id, g["poseFrom"], g["poseTo"], g["variances"])
         return None
+
+
+def mapper_params(**kw) -> MapperParams:
+    """utility.h:320-343's defaults (rolo_mapper_default_params); fields of rolo_mapper_params by keyword. sc_input: 0 none, 1 scan_feat, 2 scan_raw"""
+    p = MapperParams()
+    lib().rolo_mapper_default_params(C.byref(p))
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+class _BorrowedKeyFrameMap(KeyFrameMap):
+    """a mapper's key map under KeyFrameMap's calls: the handle is the mapper's, close() leaves it alone, and the key poses and stamps are read from the library"""
+
+    def __init__(self, owner: "MapOptimization"):
+        self._owner = owner
+        self._h = C.c_void_p(lib().rolo_mapper_keymap(owner._h))
+        self.corner_leaf, self.surf_leaf = owner.params.mappingCornerLeafSize, owner.params.mappingSurfLeafSize
+        self.m_corner = self.m_surf = self.m_global = 0
+
+    def close(self):
+        pass
+
+    poses = property(lambda self: list(self._owner.keyPoses()[0]))
+    times = property(lambda self: list(self._owner.keyPoses()[1]))
+    _sizes = property(lambda self: self._owner._sizes)
+
+
+class _BorrowedPoseGraph(PoseGraph):
+    """a mapper's graph under PoseGraph's calls; close() leaves it alone. addOdomFactor belongs to the mapper's scans and is not offered"""
+
+    def __init__(self, owner: "MapOptimization"):
+        self._h = C.c_void_p(lib().rolo_mapper_pgo(owner._h))
+        self._last = None
+        self.last = None
+
+    def close(self):
+        pass
+
+    def addOdomFactor(self, pose6):
+        raise RuntimeError("a mapper adds its own odometry factors: call MapOptimization.scan")
+
+
+class MapOptimization:
+    """mapOptimization::laserCloudInfoHandler (:420-457) as one call per CloudInfoStamp over rolo_mapper_*: the key map, the scan-to-submap context and the pose
+    graph belong to the mapper; `keymap` and `graph` lend them to LoopCloser, ScanContextManager, GroundPriorCloser and the exports between scans."""
+
+    def __init__(self, device: int = 0, params: MapperParams = None, **kw):
+        self.params = params if params is not None else mapper_params(**kw)
+        self.device = device
+        self._h = C.c_void_p()
+        check(lib().rolo_mapper_create(device, C.byref(self.params), C.byref(self._h)), "rolo_mapper_create")
+        self._sizes = []
+        self._keymap = self._graph = None
+        self.last = None
+
+    def close(self):
+        if self._h:
+            lib().rolo_mapper_destroy(self._h)
+            self._h = C.c_void_p()
+
+    @property
+    def keymap(self) -> KeyFrameMap:
+        if self._keymap is None:
+            self._keymap = _BorrowedKeyFrameMap(self)
+        return self._keymap
+
+    @property
+    def graph(self) -> PoseGraph:
+        if self._graph is None:
+            self._graph = _BorrowedPoseGraph(self)
+        return self._graph
+
+    @staticmethod
+    def _cloud(x):
+        """(keep-alive, address, points, on device) of an n x 4 float32 cloud: a numpy array, or a torch tensor on the mapper's device"""
+        if x is None:
+            return None, None, 0, None
+        if hasattr(x, "data_ptr"):   # torch
+            import torch
+            t = x.reshape(-1, 4).contiguous()
+            assert t.dtype == torch.float32
+            if t.is_cuda:
+                return t, t.data_ptr() if t.shape[0] else None, t.shape[0], True
+            x = t.numpy()
+        a = np.ascontiguousarray(x, np.float32).reshape(-1, 4)
+        return a, a.ctypes.data if a.shape[0] else None, a.shape[0], False
+
+    def scan(self, stamp: float, corner, surf, raw=None, initialGuess=None) -> dict:
+        """one CloudInfoStamp: corner = extracted_corner, surf = extracted_surface ++ extracted_normal, raw = cloud_projected (optional), initialGuess =
+        (roll, pitch, yaw, x, y, z) when odomAvailable. All clouds numpy, or all torch tensors on the device (handed over without a copy through the host)."""
+        cl = [self._cloud(x) for x in (corner, surf, raw)]
+        where = {c[3] for c in cl if c[2]}
+        assert len(where) <= 1, "host and device clouds in one scan"
+        on_device = bool(where and where.pop())
+        if on_device:
+            import torch
+            torch.cuda.synchronize(self.device)   # the clouds' writers
+        g = None if initialGuess is None else np.ascontiguousarray(initialGuess, np.float32).reshape(6)
+        res = MapperResult()
+        check(lib().rolo_mapper_scan(self._h, float(stamp), cl[0][1], cl[0][2], cl[1][1], cl[1][2], cl[2][1], cl[2][2], 1 if on_device else 0,
+                                     None if g is None else g.ctypes.data_as(C.POINTER(C.c_float)), 0 if g is None else 1, C.byref(res)), "rolo_mapper_scan")
+        if res.keyframe >= 0:
+            self._sizes.append(res.n_corner_ds + res.n_surf_ds)
+        if res.s2m_ran:   # the borrowed key map's submap() sizes its arrays by these
+            self.keymap.m_corner, self.keymap.m_surf = res.m_corner, res.m_surf
+        s = res.s2m
+        self.last = dict(processed=bool(res.processed), transformTobeMapped=np.array(res.transformTobeMapped, np.float32), incremental6=np.array(res.incremental6, np.float32),
+                         s2m_ran=bool(res.s2m_ran), s2m=(s.skipped, s.iterations, s.converged, s.degenerate, s.n_selected), n_corner_ds=res.n_corner_ds,
+                         n_surf_ds=res.n_surf_ds, m_corner=res.m_corner, m_surf=res.m_surf, n_listed=res.n_listed, submap_rebuilt=bool(res.submap_rebuilt),
+                         keyframe=res.keyframe, loops_added=res.loops_added, priors_added=res.priors_added, poses_corrected=bool(res.poses_corrected),
+                         sc_index=res.sc_index, pgo=dict(state=res.pgo.state, iterations=res.pgo.iterations, trials=res.pgo.trials, initial_cost=res.pgo.initial_cost,
+                                                         final_cost=res.pgo.final_cost, lambda_=res.pgo.lambda_, pcg_iterations=res.pgo.pcg_iterations))
+        return self.last
+
+    @staticmethod
+    def _between(f):
+        Z = np.linalg.inv(np.asarray(f[2], np.float64)) @ np.asarray(f[3], np.float64)
+        return np.ascontiguousarray(Z, np.float64).reshape(16)
+
+    def queueLoop(self, loop):
+        """loopIndexQueue &c .push_back for a LoopFactor of LoopCloser: between(cur, pre, poseFrom^-1 poseTo, noise on all six), under Cauchy(robust) when it has one"""
+        cur, pre, _, _, noise = loop
+        Z = self._between(loop)
+        v = np.full(6, float(noise), np.float64)
+        k = getattr(loop, "robust", None)
+        dp = C.POINTER(C.c_double)
+        check(lib().rolo_mapper_queue_loop(self._h, int(cur), int(pre), Z.ctypes.data_as(dp), v.ctypes.data_as(dp), 0.0 if k is None else float(k)), "rolo_mapper_queue_loop")
+
+    def queueLoopBetween(self, i: int, j: int, T, variances, cauchy=None):
+        """the same from the measurement itself (4 x 4) and its six variances"""
+        Z = np.ascontiguousarray(T, np.float64).reshape(16); v = np.ascontiguousarray(variances, np.float64).reshape(6)
+        dp = C.POINTER(C.c_double)
+        check(lib().rolo_mapper_queue_loop(self._h, i, j, Z.ctypes.data_as(dp), v.ctypes.data_as(dp), 0.0 if cauchy is None else float(cauchy)), "rolo_mapper_queue_loop")
+
+    def queuePrior(self, f):
+        """priorIndexQueue &c .push_back for a PriorFactor of GroundPriorCloser"""
+        Z = self._between(f)
+        v = np.ascontiguousarray(f[4], np.float64).reshape(6)
+        dp = C.POINTER(C.c_double)
+        check(lib().rolo_mapper_queue_prior(self._h, int(f[0]), int(f[1]), Z.ctypes.data_as(dp), v.ctypes.data_as(dp)), "rolo_mapper_queue_prior")
+
+    def keyPoses(self):
+        """(n x 6 float32 key poses in transformTobeMapped order, n stamps): cloudKeyPoses6D"""
+        n = check(lib().rolo_mapper_get_keyposes(self._h, None, None, 0), "rolo_mapper_get_keyposes")
+        p = np.zeros((max(n, 1), 6), np.float32); t = np.zeros(max(n, 1), np.float64)
+        check(lib().rolo_mapper_get_keyposes(self._h, p.ctypes.data_as(C.POINTER(C.c_float)), t.ctypes.data_as(C.POINTER(C.c_double)), n), "rolo_mapper_get_keyposes")
+        return p[:n], t[:n]
+
+    def lastScan(self):
+        """laserCloudCornerLastDS, laserCloudSurfLastDS of the last processed scan"""
+        fp = C.POINTER(C.c_float)
+        cnt = (C.c_int * 2)()
+        check(lib().rolo_mapper_get_scan(self._h, None, 0, None, 0, cnt), "rolo_mapper_get_scan")
+        c = np.zeros((cnt[0], 4), np.float32); s = np.zeros((cnt[1], 4), np.float32)
+        check(lib().rolo_mapper_get_scan(self._h, c.ctypes.data_as(fp), cnt[0], s.ctypes.data_as(fp), cnt[1], None), "rolo_mapper_get_scan")
+        return c, s
+
+    def registered(self):
+        """publishFrames :1405-1414: the last scan's two filtered clouds at transformTobeMapped, corners first"""
+        cnt = (C.c_int * 2)()
+        check(lib().rolo_mapper_get_scan(self._h, None, 0, None, 0, cnt), "rolo_mapper_get_scan")
+        out = np.zeros((cnt[0] + cnt[1], 4), np.float32)
+        n = check(lib().rolo_mapper_get_registered(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.shape[0]), "rolo_mapper_get_registered")
+        return out[:n]
+
+    def registeredRaw(self, n_raw: int):
+        """:1416-1424: the last scan's raw cloud (n_raw points, as handed to scan) at transformTobeMapped"""
+        out = np.zeros((n_raw, 4), np.float32)
+        n = check(lib().rolo_mapper_get_registered_raw(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), n_raw), "rolo_mapper_get_registered_raw")
+        return out[:n]
+
+    def lastMs(self):
+        """device milliseconds of the last processed scan: down-sample, sub-map, scan2map, key-frame commit, graph, whole call"""
+        ms = np.zeros(6, np.float32)
+        check(lib().rolo_mapper_last_ms(self._h, ms.ctypes.data_as(C.POINTER(C.c_float))), "rolo_mapper_last_ms")
+        return ms
+
+
+def mapper_initial_guess(tf6, have_keyposes: bool, guess6, last_odom12, last_odom_available: bool):
+    """updateInitialGuess (:516-555) -> (tf6, lastOdom12, lastOdomAvailable); guess6 None: odomAvailable false. Host only."""
+    fp = C.POINTER(C.c_float)
+    tf = np.ascontiguousarray(tf6, np.float32).reshape(6); out = np.zeros(6, np.float32)
+    lo = np.ascontiguousarray(last_odom12, np.float32).reshape(12).copy()
+    g = None if guess6 is None else np.ascontiguousarray(guess6, np.float32).reshape(6)
+    flag = C.c_int(1 if last_odom_available else 0)
+    check(lib().rolo_mapper_initial_guess(tf.ctypes.data_as(fp), 1 if have_keyposes else 0, None if g is None else g.ctypes.data_as(fp), 0 if g is None else 1,
+                                          lo.ctypes.data_as(fp), C.byref(flag), out.ctypes.data_as(fp)), "rolo_mapper_initial_guess")
+    return out, lo, bool(flag.value)
+
+
+def mapper_save_frame(last_keypose6, tf6, dist_thr: float = 1.0, angle_thr: float = 0.2) -> bool:
+    """saveFrame (:1071-1091); last_keypose6 None: no key frame yet. Host only."""
+    fp = C.POINTER(C.c_float)
+    a = None if last_keypose6 is None else np.ascontiguousarray(last_keypose6, np.float32).reshape(6)
+    b = np.ascontiguousarray(tf6, np.float32).reshape(6)
+    return check(lib().rolo_mapper_save_frame(None if a is None else a.ctypes.data_as(fp), b.ctypes.data_as(fp), dist_thr, angle_thr), "rolo_mapper_save_frame") == 1
+
+
+def mapper_incremental(front6, back6, tf6, started: bool, incre12):
+    """publishOdometry's incremental pose (:1361-1389) -> (incre12, x y z roll pitch yaw). Host only."""
+    fp = C.POINTER(C.c_float)
+    a = [np.ascontiguousarray(x, np.float32).reshape(6) for x in (front6, back6, tf6)]
+    inc = np.ascontiguousarray(incre12, np.float32).reshape(12).copy(); out = np.zeros(6, np.float32)
+    check(lib().rolo_mapper_incremental(a[0].ctypes.data_as(fp), a[1].ctypes.data_as(fp), a[2].ctypes.data_as(fp), 1 if started else 0, inc.ctypes.data_as(fp),
+                                        out.ctypes.data_as(fp)), "rolo_mapper_incremental")
+    return inc, out

@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librolo_hip.so")
-SOURCES = ["api.hip", "schedule.hip", "debug.hip", "knn_cov.hip", "voxelmap.hip", "passes.hip", "misc.hip", "front.hip", "odometry.hip", "fusion.hip", "scan2map.hip", "submap.hip", "scancontext.hip", "loopicp.hip", "posegraph.hip", "peer.hip", "groundprior.hip"]
+SOURCES = ["api.hip", "schedule.hip", "debug.hip", "knn_cov.hip", "voxelmap.hip", "passes.hip", "misc.hip", "front.hip", "odometry.hip", "fusion.hip", "scan2map.hip", "submap.hip", "scancontext.hip", "loopicp.hip", "posegraph.hip", "peer.hip", "groundprior.hip", "mapper.hip"]
 # every unit is rebuilt when any header changes: the private ones are whatever *.hpp csrc/ holds (a hand-kept list that misses one leaves stale objects linked in silently)
 HEADERS = sorted(h for h in os.listdir(CSRC) if h.endswith(".hpp")) + [os.path.join("..", "..", "include", "rolo_hip.h"), os.path.join("..", "..", "include", "rolo_fusion.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -24,7 +24,7 @@ FLAGS = os.environ.get("ROLO_EXTRA_FLAGS", "").split() + ["--offload-arch=gfx950
 # pcl::transformPointCloud, range-image projection, curvature): no FMA contraction (HIP's __fmul_rn/__fadd_rn are
 # plain operators that the compiler is otherwise free to fuse)
 EXTRA = {"knn_cov.hip": ["-ffp-contract=off"], "scan2map.hip": ["-ffp-contract=off"], "misc.hip": ["-ffp-contract=off"], "front.hip": ["-ffp-contract=off"],
-         "submap.hip": ["-ffp-contract=off"], "scancontext.hip": ["-ffp-contract=off"], "loopicp.hip": ["-ffp-contract=off"], "groundprior.hip": ["-ffp-contract=off"]}
+         "submap.hip": ["-ffp-contract=off"], "scancontext.hip": ["-ffp-contract=off"], "loopicp.hip": ["-ffp-contract=off"], "groundprior.hip": ["-ffp-contract=off"], "mapper.hip": ["-ffp-contract=off"]}
 # (front.hip was built at -O2 through round 3: hipcc 7.2 -O3 died in the backend — "Illegal instruction detected: Operand has incorrect register class" — on the
 # round-1 form of extract_kernel's serial greedy walk; that function was rewritten in rounds 2-3 and the file has compiled at -O3 since: profiles/tools/README.md)
 

@@ -25,6 +25,12 @@ void front_reset_object_state(rolo_ctx* c);
 // ---- submap.hip: the resident sub-map as device clouds (n x 4 floats), the event a reader's stream waits for and the one it records when it has read them ----
 int keymap_device_submap(rolo_keymap* km, const float** d_corner, int* m_corner, const float** d_surf, int* m_surf, hipEvent_t* ready, hipEvent_t* consumed, int* device);
 void keymap_mark_consumed(rolo_keymap* km);
+// ---- scan2map.hip: the body of rolo_scan2map_optimize; feat_on_device: corner / surf are device clouds that are complete once feat_ready (may be null) has passed ----
+int s2m_optimize_core(rolo_ctx* c, const float* corner, int n_corner, const float* surf, int n_surf, bool feat_on_device, hipEvent_t feat_ready, const float* map_corner,
+                      int m_corner, const float* map_surf, int m_surf, float* transformTobeMapped, int edge_min, int surf_min, rolo_scan2map_stats* stats,
+                      unsigned char* selected_out, float* coeff_out);
+// ---- posegraph.hip: device room for more_poses poses, more_factors factors and more_chords chords beyond what the graph holds: the next optimise allocates nothing ----
+int pgo_reserve(rolo_pgo* g, int more_poses, int more_factors, int more_chords);
 }  // namespace rolo
 
 extern "C" {   // called by rolo_ctx_destroy / rolo_ctx_release (api.hip); no part of include/rolo_hip.h

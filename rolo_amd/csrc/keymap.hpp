@@ -25,6 +25,14 @@ struct rolo_keymap {
   float4* cat[2] = {nullptr, nullptr}; size_t cat_cap[2] = {0, 0};       // the concatenated, transformed clouds (corner, surface); cat[0] also stages rolo_keymap_downsample's input
   float4* sub[2] = {nullptr, nullptr}; size_t sub_cap[2] = {0, 0};       // the sub-map (laserCloud*FromMapDS)
   float4* ds_out = nullptr; size_t ds_cap = 0;                           // rolo_keymap_downsample's result
+  // the current scan of a mapper (mapper.hip), resident from its upload to its place in the store: laserCloudCornerLastDS / laserCloudSurfLastDS in slots of
+  // their own, the raw cloud (cloud_projected) when one was given, and the scratch of the registered clouds (publishFrames)
+  float4* scan_ds[2] = {nullptr, nullptr}; size_t scan_ds_cap[2] = {0, 0};
+  int n_scan_ds[2] = {0, 0};
+  float4* scan_raw = nullptr; size_t scan_raw_cap = 0; int n_scan_raw = 0;
+  float4* reg = nullptr; size_t reg_cap = 0;
+  hipEvent_t scan_ready = nullptr;   // recorded after the scan's two filters: what the scan-to-submap helper context's stream waits for; created by the first scan
+  unsigned long long pose_epoch = 0; // counts rolo_keymap_set_pose / _set_poses: a mapper keeps its sub-map only while this stands still
   rolo::SortScratch sort;            // the voxel filter's sort of (cell, point index)
   unsigned* bcnt = nullptr; size_t bcnt_cap = 0;
   int* starts = nullptr; size_t starts_cap = 0;
@@ -69,5 +77,23 @@ namespace rolo {
 // filter (vg_enqueue_box / vg_enqueue_filter) without leaving the device. *d_out (n_out points) is valid on the key map's stream until the next call that
 // uses the scratch. The stream has been waited for when this returns: the caller's array is free again.
 int keymap_stage_cloud(rolo_keymap* km, const float* pts, int n, float leaf, const float4** d_out, int* n_out);
+
+// ---- submap.hip, for mapper.hip: the current scan without a host round trip. on_device: the clouds are device memory whose writers the caller has waited for ----
+// downsampleCurrentScan (:666-678): both clouds staged (cat[0], cat[1]) and filtered into scan_ds[0] / scan_ds[1]; raw (may be NULL) is copied into scan_raw as it
+// is. Two host waits for the pair, as rolo_keymap_extract has for its pair; scan_ready is recorded behind the filters. An error leaves n_scan_ds as it was.
+int keymap_scan_downsample(rolo_keymap* km, const float* corner, int n_corner, float corner_leaf, const float* surf, int n_surf, float surf_leaf, const float* raw,
+                           int n_raw, bool on_device);
+// the voxel filter on a cloud that is resident already and ordered on the key map's stream, into ds_out (keymap_stage_cloud's result slot)
+int keymap_filter_resident(rolo_keymap* km, const float4* pts, int n, float leaf, const float4** d_out, int* n_out);
+// room in the store for one more key frame of these sizes: after it keymap_append_scan cannot fail for want of memory
+int keymap_reserve_keyframe(rolo_keymap* km, int n_corner, int n_surf);
+// cornerCloudKeyFrames / surfCloudKeyFrames .push_back of scan_ds[0] / scan_ds[1], device to device on the key map's stream; returns the key frame's index
+int keymap_append_scan(rolo_keymap* km, const float* pose6, double time);
+// publishFrames :1405-1424: pieces[k] (n[k] points each, k < count <= 2) moved by pose6 into `reg` one after another and downloaded into out; the transform is
+// km_transform_kernel's, T0 x + (T1 y + (T2 z + T3)) per row
+int keymap_registered(rolo_keymap* km, const float4* const* pieces, const int* n, int count, const float* pose6, float* out);
+// scancontext.hip: room for one more descriptor (creates the store), and the descriptor of a resident cloud on the key map's stream; returns its index
+int keymap_sc_reserve(rolo_keymap* km);
+int keymap_sc_add_resident(rolo_keymap* km, const float4* d_pts, int n);
 
 }  // namespace rolo

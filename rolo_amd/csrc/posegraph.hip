@@ -950,6 +950,45 @@ int pgo_sync_graph(rolo_pgo* g) {
   return ROLO_OK;
 }
 
+// every buffer pgo_sync_graph would grow for a graph larger by these counts, grown now: what the device holds is carried over (poses, factors, the incidence list,
+// the chord tables), the rest is scratch of one linearisation or one solve
+int pgo_reserve_impl(rolo_pgo* g, int more_poses, int more_factors, int more_chords) {
+  HIPCHK(hipSetDevice(g->device));
+  const size_t N = (size_t)g->N + (size_t)more_poses, F = g->factors.size() + (size_t)more_factors, nc0 = g->chord_factor.size(), nc = nc0 + (size_t)more_chords;
+  const size_t F1 = std::max<size_t>(F, 1), nc1 = std::max<size_t>(nc, 1), have_chords = g->d_chord_factor ? nc0 : 0, have_touched = g->touched ? (size_t)g->n_touched : 0;
+  int rc;
+  g->linearized = false;
+  if ((rc = g->store.grow(g->poses, g->poses_cap, 12 * N, 12 * (size_t)g->up_poses))) return rc;
+  if ((rc = g->store.grow(g->trial, g->trial_cap, 12 * N))) return rc;
+  if ((rc = g->store.grow(g->d_factors, g->factors_cap, F1, (size_t)g->up_factors))) return rc;
+  if ((rc = g->store.grow(g->slots, g->slots_cap, (size_t)PGO_SLOT * F1))) return rc;
+  if ((rc = g->store.grow(g->rowptr, g->rowptr_cap, N + 1, g->rowptr ? g->h_rowptr.size() : 0))) return rc;
+  if ((rc = g->store.grow(g->entries, g->entries_cap, 2 * F1, g->entries ? g->h_entries.size() : 0))) return rc;
+  if (nc) {
+    if ((rc = g->store.grow(g->d_chord_factor, g->d_chord_factor_cap, nc, have_chords))) return rc;
+    if ((rc = g->store.grow(g->d_chord_ij, g->d_chord_ij_cap, 2 * nc, 2 * have_chords))) return rc;
+    if ((rc = g->store.grow(g->touched, g->touched_cap, 2 * nc, have_touched))) return rc;
+    if ((rc = g->store.grow(g->touched_ptr, g->touched_ptr_cap, 2 * nc + 1, have_touched ? have_touched + 1 : 0))) return rc;
+    if ((rc = g->store.grow(g->touched_ent, g->touched_ent_cap, 2 * nc, 2 * have_chords))) return rc;
+  }
+  if ((rc = g->store.grow(g->chordH, g->chordH_cap, 36 * nc1))) return rc;
+  if ((rc = g->store.grow(g->cscr, g->cscr_cap, 12 * nc1))) return rc;
+  if ((rc = g->store.grow(g->diag, g->diag_cap, 36 * N))) return rc;
+  if ((rc = g->store.grow(g->chain, g->chain_cap, 36 * N))) return rc;
+  if ((rc = g->store.grow(g->grad, g->grad_cap, 6 * N))) return rc;
+  if ((rc = g->store.grow(g->delta, g->delta_cap, 6 * N))) return rc;
+  for (int v = 0; v < 5; v++) if ((rc = g->store.grow(g->vec[v], g->vec_cap[v], 6 * N))) return rc;
+  size_t M = 1;
+  while (M < N) M <<= 1;
+  if ((rc = g->store.grow(g->LD, g->LD_cap, 72 * M))) return rc;
+  if ((rc = g->store.grow(g->LU, g->LU_cap, 72 * M))) return rc;
+  if ((rc = g->store.grow(g->LW, g->LW_cap, 72 * M))) return rc;
+  if ((rc = g->store.grow(g->B, g->B_cap, 12 * M))) return rc;
+  if ((rc = g->store.grow(g->X, g->X_cap, 12 * M))) return rc;
+  if ((rc = g->store.grow(g->gst, g->gst_cap, (size_t)PGO_ST_WORDS + PGO_SOLVE_THREADS))) return rc;
+  return g->store.grow(g->partials, g->partials_cap, (std::max(N, F) + PGO_FACTOR_THREADS - 1) / PGO_FACTOR_THREADS + 1);
+}
+
 // linearise at g->poses: slots, the assembled blocks, the cost into h_info[0] (valid after the stream has been waited for)
 int pgo_enqueue_linearize(rolo_pgo* g) {
   hipStream_t s = g->stream;
@@ -1090,6 +1129,14 @@ void pgo_fill_factor(PgoFactor& f, int i, int j, const double* T, const double* 
 bool pgo_finite_T(const double* T) { for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) if (!std::isfinite(T[4 * r + c])) return false; return true; }
 
 }  // namespace
+
+namespace rolo {
+int pgo_reserve(rolo_pgo* g, int more_poses, int more_factors, int more_chords) {
+  if (!g || more_poses < 0 || more_factors < 0 || more_chords < 0) return ROLO_EINVAL;
+  if (g->N + more_poses > ROLO_PGO_MAX_POSES) { ctx_set_error("pose graph: more than ROLO_PGO_MAX_POSES poses"); return ROLO_EINVAL; }
+  return pgo_reserve_impl(g, more_poses, more_factors, more_chords);
+}
+}  // namespace rolo
 
 extern "C" {
 

@@ -665,9 +665,12 @@ extern "C" int rolo_scan2map_set_submap_keymap(rolo_ctx* c, rolo_keymap* km) {
   return ROLO_OK;
 }
 
-extern "C" int rolo_scan2map_optimize(rolo_ctx* c, const float* corner, int n_corner, const float* surf, int n_surf, const float* map_corner, int m_corner,
-                                      const float* map_surf, int m_surf, float* transformTobeMapped, int edge_min, int surf_min, rolo_scan2map_stats* stats,
-                                      unsigned char* selected_out, float* coeff_out) {
+// scan2MapOptimization's body, the one statement behind both entries. rolo_scan2map_optimize hands in host arrays (feat_on_device false, no event);
+// rolo_mapper_scan (mapper.hip) hands in the key map's resident scan: device clouds that the first stream to read them reaches only behind feat_ready
+namespace rolo {
+int s2m_optimize_core(rolo_ctx* c, const float* corner, int n_corner, const float* surf, int n_surf, bool feat_on_device, hipEvent_t feat_ready, const float* map_corner,
+                      int m_corner, const float* map_surf, int m_surf, float* transformTobeMapped, int edge_min, int surf_min, rolo_scan2map_stats* stats,
+                      unsigned char* selected_out, float* coeff_out) {
   if (!c || !transformTobeMapped || n_corner < 0 || n_surf < 0 || m_corner < 0 || m_surf < 0 || (n_corner && !corner) || (n_surf && !surf) ||
       (m_corner && !map_corner) || (m_surf && !map_surf))
     return ROLO_EINVAL;
@@ -704,7 +707,8 @@ extern "C" int rolo_scan2map_optimize(rolo_ctx* c, const float* corner, int n_co
   if (use_packets) {
     S2mScratch* Wq = static_cast<S2mScratch*>(*ctx_s2m_slot(c));
     if (!Wq->qctx) { if (rolo_ctx_acquire(ctx_device(c), &Wq->qctx) != ROLO_OK) return ROLO_EHIP; HIPCHK(hipEventCreateWithFlags(&Wq->qev, hipEventDisableTiming)); }
-    const int rq = ctx_build_map_trees(Wq->qctx, corner, n_corner, surf, n_surf, 4, &qp);   // upload + Hilbert sort (+ a tree nobody walks) on the helper's stream
+    if (feat_ready) HIPCHK(hipStreamWaitEvent(ctx_stream(Wq->qctx), feat_ready, 0));
+    const int rq = ctx_build_map_trees(Wq->qctx, corner, n_corner, surf, n_surf, 4, &qp, feat_on_device);   // upload (or pack from the device) + Hilbert sort (+ a tree nobody walks) on the helper's stream
     if (rq) return rq;
     HIPCHK(hipEventRecord(Wq->qev, ctx_stream(Wq->qctx)));
     HIPCHK(hipStreamWaitEvent(s, Wq->qev, 0));
@@ -718,9 +722,11 @@ extern "C" int rolo_scan2map_optimize(rolo_ctx* c, const float* corner, int n_co
   if ((rg = W->store.grow(W->feat, W->feat_cap, (size_t)n)) || (rg = W->store.grow(W->part, W->part_cap, S2M_NV * (size_t)grid)) ||
       (selected_out && (rg = W->store.grow(W->sel, W->sel_cap, (size_t)n))) || (coeff_out && (rg = W->store.grow(W->coeff, W->coeff_cap, (size_t)n)))) return rg;
   float4* d_feat = W->feat; double* d_part = W->part; unsigned char* d_sel = selected_out ? W->sel : nullptr; float4* d_coeff = coeff_out ? W->coeff : nullptr;
+  const hipMemcpyKind feat_kind = feat_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  if (!use_packets && feat_ready) HIPCHK(hipStreamWaitEvent(s, feat_ready, 0));
   if (!use_packets &&   // (s2m_assoc_kernel reads the features from the helper context's sorted clouds)
-      (hipMemcpyAsync(d_feat, corner, sizeof(float4) * (size_t)n_corner, hipMemcpyHostToDevice, s) != hipSuccess ||
-       hipMemcpyAsync(d_feat + n_corner, surf, sizeof(float4) * (size_t)n_surf, hipMemcpyHostToDevice, s) != hipSuccess)) { ctx_set_error("upload failed (scan2map)"); return ROLO_EHIP; }
+      (hipMemcpyAsync(d_feat, corner, sizeof(float4) * (size_t)n_corner, feat_kind, s) != hipSuccess ||
+       hipMemcpyAsync(d_feat + n_corner, surf, sizeof(float4) * (size_t)n_surf, feat_kind, s) != hipSuccess)) { ctx_set_error("upload failed (scan2map)"); return ROLO_EHIP; }
   S2mArgs A{};
   A.feat = d_feat; A.n_corner = n_corner; A.n_surf = n_surf; A.map[0] = maps.c[0]; A.map[1] = maps.c[1]; A.partials = d_part; A.selected = d_sel; A.coeff = d_coeff;
   A.qry[0] = qp.c[0]; A.qry[1] = qp.c[1];
@@ -784,4 +790,12 @@ extern "C" int rolo_scan2map_optimize(rolo_ctx* c, const float* corner, int n_co
   if (coeff_out) HIPCHK(hipMemcpy(coeff_out, d_coeff, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost));
   if (stats) *stats = st;
   return ROLO_OK;
+}
+}  // namespace rolo
+
+extern "C" int rolo_scan2map_optimize(rolo_ctx* c, const float* corner, int n_corner, const float* surf, int n_surf, const float* map_corner, int m_corner,
+                                      const float* map_surf, int m_surf, float* transformTobeMapped, int edge_min, int surf_min, rolo_scan2map_stats* stats,
+                                      unsigned char* selected_out, float* coeff_out) {
+  return s2m_optimize_core(c, corner, n_corner, surf, n_surf, false, nullptr, map_corner, m_corner, map_surf, m_surf, transformTobeMapped, edge_min, surf_min, stats,
+                           selected_out, coeff_out);
 }

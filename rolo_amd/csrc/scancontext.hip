@@ -342,6 +342,22 @@ int sc_add_device(rolo_keymap* km, ScStore* sc, const float4* d_pts, int n) {
 }
 
 }  // namespace
+
+// for mapper.hip: the reservation ahead of a key frame, and the descriptor of a cloud that is resident already (the scan's surface cloud, or the filtered raw cloud)
+int keymap_sc_reserve(rolo_keymap* km) {
+  ScStore* sc;
+  if (const int rc = sc_store(km, &sc)) return rc;
+  HIPCHK(hipSetDevice(km->device));
+  return sc_reserve(km, sc);
+}
+int keymap_sc_add_resident(rolo_keymap* km, const float4* d_pts, int n) {
+  if (n <= 0) { ctx_set_error("Scan Context: empty cloud"); return ROLO_EINVAL; }
+  ScStore* sc;
+  if (const int rc = sc_store(km, &sc)) return rc;
+  HIPCHK(hipSetDevice(km->device));
+  HIPCHK(hipEventRecord(sc->t0, km->stream));
+  return sc_add_device(km, sc, d_pts, n);
+}
 }  // namespace rolo
 
 using namespace rolo;

@@ -499,6 +499,119 @@ int keymap_stage_cloud(rolo_keymap* km, const float* pts, int n, float leaf, con
   *d_out = km->ds_out; *n_out = mm;
   return ROLO_OK;
 }
+
+int keymap_filter_resident(rolo_keymap* km, const float4* pts, int n, float leaf, const float4** d_out, int* n_out) {
+  HIPCHK(hipSetDevice(km->device));
+  hipStream_t s = km->stream;
+  int rc;
+  if ((rc = km_sort_scratch(km, n))) return rc;
+  if ((rc = km->store.grow(km->ds_out, km->ds_cap, (size_t)n))) return rc;
+  if ((rc = vg_enqueue_box(km, pts, n, 0))) return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  bool direct; int m_direct = 0;
+  if ((rc = vg_enqueue_filter(km, pts, n, leaf, 0, km->ds_out, &direct, &m_direct))) return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  const int mm = direct ? m_direct : km->h_m[0];
+  if (mm < 0 || mm > n) { ctx_set_error("the key map's voxel filter returned an inconsistent cell count"); return ROLO_ESTATE; }
+  *d_out = km->ds_out; *n_out = mm;
+  return ROLO_OK;
+}
+
+int keymap_scan_downsample(rolo_keymap* km, const float* corner, int n_corner, float corner_leaf, const float* surf, int n_surf, float surf_leaf, const float* raw,
+                           int n_raw, bool on_device) {
+  if (n_corner < 0 || n_surf < 0 || n_raw < 0 || (n_corner && !corner) || (n_surf && !surf) || n_corner > KM_MAX_POINTS || n_surf > KM_MAX_POINTS || n_raw > KM_MAX_POINTS ||
+      !(corner_leaf > 0.f) || !(surf_leaf > 0.f))
+    return ROLO_EINVAL;
+  HIPCHK(hipSetDevice(km->device));
+  hipStream_t s = km->stream;
+  if (!km->scan_ready) HIPCHK(hipEventCreateWithFlags(&km->scan_ready, hipEventDisableTiming));
+  const float* src[2] = {corner, surf};
+  const int n[2] = {n_corner, n_surf};
+  const float leaf[2] = {corner_leaf, surf_leaf};
+  const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  int rc;
+  if (std::max(n[0], n[1]) > 0 && (rc = km_sort_scratch(km, std::max(n[0], n[1])))) return rc;
+  for (int t = 0; t < 2; t++) {
+    if ((rc = km->store.grow(km->cat[t], km->cat_cap[t], (size_t)std::max(n[t], 1)))) return rc;
+    if ((rc = km->store.grow(km->scan_ds[t], km->scan_ds_cap[t], (size_t)std::max(n[t], 1)))) return rc;
+  }
+  if (raw && n_raw && (rc = km->store.grow(km->scan_raw, km->scan_raw_cap, (size_t)n_raw))) return rc;
+  for (int t = 0; t < 2; t++) {
+    if (n[t]) HIPCHK(hipMemcpyAsync(km->cat[t], src[t], sizeof(float4) * (size_t)n[t], kind, s));
+    if ((rc = vg_enqueue_box(km, km->cat[t], n[t], t))) return rc;
+  }
+  if (raw && n_raw) HIPCHK(hipMemcpyAsync(km->scan_raw, raw, sizeof(float4) * (size_t)n_raw, kind, s));
+  HIPCHK(hipStreamSynchronize(s));   // the boxes are on the host, and the caller's arrays are free again
+  bool direct[2]; int m_direct[2] = {0, 0};
+  for (int t = 0; t < 2; t++)
+    if ((rc = vg_enqueue_filter(km, km->cat[t], n[t], leaf[t], t, km->scan_ds[t], &direct[t], &m_direct[t]))) return rc;
+  HIPCHK(hipEventRecord(km->scan_ready, s));
+  HIPCHK(hipStreamSynchronize(s));
+  int mm[2];
+  for (int t = 0; t < 2; t++) {
+    mm[t] = direct[t] ? m_direct[t] : km->h_m[t];
+    if (mm[t] < 0 || mm[t] > n[t]) { ctx_set_error("the key map's voxel filter returned an inconsistent cell count"); return ROLO_ESTATE; }
+  }
+  km->n_scan_ds[0] = mm[0]; km->n_scan_ds[1] = mm[1];
+  km->n_scan_raw = raw ? n_raw : 0;
+  return ROLO_OK;
+}
+
+int keymap_reserve_keyframe(rolo_keymap* km, int n_corner, int n_surf) {
+  if (km->frames.size() >= (size_t)INT_MAX) return ROLO_EINVAL;
+  HIPCHK(hipSetDevice(km->device));
+  const size_t need = (size_t)n_corner + (size_t)n_surf;
+  if (need && (km->chunks.empty() || km->chunks.back().cap - km->chunks.back().used < need)) {
+    rolo_keymap::Chunk c{nullptr, std::max(CHUNK_POINTS, need), 0};
+    if (const int rc = km->store.alloc(c.p, c.cap)) return rc;
+    km->chunks.push_back(c);
+  }
+  km->frames.reserve(km->frames.size() + 1);
+  return ROLO_OK;
+}
+
+int keymap_append_scan(rolo_keymap* km, const float* pose6, double time) {
+  HIPCHK(hipSetDevice(km->device));
+  rolo_keymap::Frame f{};
+  for (int t = 0; t < 2; t++) {
+    float4* d = nullptr;
+    const int rc = km_alloc_points(km, (size_t)km->n_scan_ds[t], &d);
+    if (rc) return rc;
+    if (km->n_scan_ds[t]) HIPCHK(hipMemcpyAsync(d, km->scan_ds[t], sizeof(float4) * (size_t)km->n_scan_ds[t], hipMemcpyDeviceToDevice, km->stream));
+    f.pts[t] = d; f.n[t] = km->n_scan_ds[t];
+  }
+  std::memcpy(f.pose, pose6, sizeof(f.pose));
+  f.time = time;
+  km->frames.push_back(f);   // (the copies are ordered before every later reader on the key map's stream: no host wait)
+  return (int)km->frames.size() - 1;
+}
+
+int keymap_registered(rolo_keymap* km, const float4* const* pieces, const int* n, int count, const float* pose6, float* out) {
+  HIPCHK(hipSetDevice(km->device));
+  hipStream_t s = km->stream;
+  size_t total = 0, nsegs = 0;
+  int max_n = 1;
+  for (int k = 0; k < count; k++) { total += (size_t)n[k]; max_n = std::max(max_n, n[k]); }
+  if (total == 0) return ROLO_OK;
+  int rc;
+  if ((rc = km->store.grow_pinned(km->h_segs, km->h_segs_cap, (size_t)count, 64))) return rc;
+  if ((rc = km->store.grow(km->segs, km->segs_cap, (size_t)count))) return rc;
+  if ((rc = km->store.grow(km->reg, km->reg_cap, total))) return rc;
+  int dst = 0;
+  for (int k = 0; k < count; k++) {
+    if (!n[k]) continue;
+    Seg& g = km->h_segs[nsegs++];
+    g.src = pieces[k]; g.n = n[k]; g.dst = dst;
+    pose_to_T(pose6, g.T);
+    dst += n[k];
+  }
+  HIPCHK(hipMemcpyAsync(km->segs, km->h_segs, nsegs * sizeof(Seg), hipMemcpyHostToDevice, s));
+  km_transform_kernel<<<dim3(std::min((max_n + SM_THREADS - 1) / SM_THREADS, 128), (unsigned)nsegs), SM_THREADS, 0, s>>>(km->segs, km->reg);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, km->reg, sizeof(float4) * total, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return ROLO_OK;
+}
 }  // namespace rolo
 
 extern "C" {
@@ -537,6 +650,7 @@ void rolo_keymap_destroy(rolo_keymap* km) {
   km->store.release();
   if (km->ready) (void)hipEventDestroy(km->ready);
   if (km->consumed) (void)hipEventDestroy(km->consumed);
+  if (km->scan_ready) (void)hipEventDestroy(km->scan_ready);
   if (km->loop_t0) (void)hipEventDestroy(km->loop_t0);
   if (km->loop_t1) (void)hipEventDestroy(km->loop_t1);
   for (hipEvent_t e : km->gm_ev) if (e) (void)hipEventDestroy(e);
@@ -570,12 +684,14 @@ int rolo_keymap_add_keyframe(rolo_keymap* km, const float* corner, int n_corner,
 int rolo_keymap_set_pose(rolo_keymap* km, int index, const float* pose6) {
   if (!km || !pose6 || index < 0 || index >= (int)km->frames.size()) return ROLO_EINVAL;
   std::memcpy(km->frames[index].pose, pose6, sizeof(float) * 6);
+  km->pose_epoch++;
   return ROLO_OK;
 }
 
 int rolo_keymap_set_poses(rolo_keymap* km, const float* pose6, int n) {
   if (!km || n < 0 || (n && !pose6) || n > (int)km->frames.size()) return ROLO_EINVAL;
   for (int k = 0; k < n; k++) std::memcpy(km->frames[k].pose, pose6 + 6 * (size_t)k, sizeof(float) * 6);
+  km->pose_epoch++;
   return ROLO_OK;
 }
 
