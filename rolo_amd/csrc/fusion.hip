@@ -13,6 +13,7 @@
 
 #include "../../include/rolo_fusion.h"
 #include "polar_f32.hpp"
+#include "pcl_affine.hpp"
 #include "../../include/rolo_hip.h"
 
 namespace {
@@ -283,37 +284,10 @@ struct rolo_eskf {
   }
 };
 
+using namespace rolo;   // Aff and the pcl / Eigen rules: pcl_affine.hpp; the products here are its aff_mul_padded, as odometry.hip's
+
 namespace {
 
-struct Aff { float m[16]; };
-Aff aff_identity() { Aff a; for (int i = 0; i < 16; i++) a.m[i] = (i % 5 == 0) ? 1.f : 0.f; return a; }
-Aff get_transformation(float x, float y, float z, float roll, float pitch, float yaw) {   // pcl::getTransformation
-  const float A = std::cos(yaw), B = std::sin(yaw), C = std::cos(pitch), D = std::sin(pitch), E = std::cos(roll), F = std::sin(roll);
-  const float DE = D * E, DF = D * F;
-  Aff t;
-  t.m[0] = A * C; t.m[1] = A * DF - B * E; t.m[2] = B * F + A * DE; t.m[3] = x;
-  t.m[4] = B * C; t.m[5] = A * E + B * DF; t.m[6] = B * DE - A * F; t.m[7] = y;
-  t.m[8] = -D; t.m[9] = C * F; t.m[10] = C * E; t.m[11] = z;
-  t.m[12] = 0; t.m[13] = 0; t.m[14] = 0; t.m[15] = 1;
-  return t;
-}
-Aff aff_mul(const Aff& a, const Aff& b) {
-  Aff c;
-  for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) { float s = 0; for (int k = 0; k < 4; k++) s += a.m[i * 4 + k] * b.m[k * 4 + j]; c.m[i * 4 + j] = s; }
-  return c;
-}
-Aff aff_inverse(const Aff& T) {   // Eigen::Transform<float,3,Affine>::inverse()
-  const float* a = T.m; float c[9];
-  c[0] = a[5] * a[10] - a[6] * a[9]; c[1] = a[2] * a[9] - a[1] * a[10]; c[2] = a[1] * a[6] - a[2] * a[5];
-  c[3] = a[6] * a[8] - a[4] * a[10]; c[4] = a[0] * a[10] - a[2] * a[8]; c[5] = a[2] * a[4] - a[0] * a[6];
-  c[6] = a[4] * a[9] - a[5] * a[8]; c[7] = a[1] * a[8] - a[0] * a[9]; c[8] = a[0] * a[5] - a[1] * a[4];
-  const float det = a[0] * c[0] + a[1] * c[3] + a[2] * c[6], inv = 1.0f / det;
-  Aff o;
-  for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) o.m[i * 4 + j] = c[i * 3 + j] * inv;
-  for (int i = 0; i < 3; i++) o.m[i * 4 + 3] = -(o.m[i * 4] * a[3] + o.m[i * 4 + 1] * a[7] + o.m[i * 4 + 2] * a[11]);
-  o.m[12] = o.m[13] = o.m[14] = 0; o.m[15] = 1;
-  return o;
-}
 // tf::Matrix3x3(q).getRPY (setRotation + getEulerYPR, solution 1)
 void get_rpy(const double q[4], double& roll, double& pitch, double& yaw) {
   const double d = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3], s = 2.0 / d;
@@ -329,7 +303,7 @@ void get_rpy(const double q[4], double& roll, double& pitch, double& yaw) {
 // odom2affine (lidarOdometry.cpp:34-45): doubles narrowed to the float arguments of pcl::getTransformation
 Aff odom2affine(const double* p, const double* q) {
   double r, pi, y; get_rpy(q, r, pi, y);
-  return get_transformation((float)p[0], (float)p[1], (float)p[2], (float)r, (float)pi, (float)y);
+  return aff_of_xyzrpy((float)p[0], (float)p[1], (float)p[2], (float)r, (float)pi, (float)y);
 }
 // affineToPose :127-136. affine.rotation() of an Affine3f is Eigen's float polar factor of the linear part (polar_f32.hpp), cast to double,
 // then Quaterniond(rotation).normalize()
@@ -452,8 +426,8 @@ int rolo_fusion_timer(rolo_fusion* f, double now, rolo_fusion_odometry* out) {  
   Aff back = aff_identity();
   double R[9]; q_to_R(pq, R);
   for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) back.m[i * 4 + j] = (float)R[i * 3 + j]; back.m[i * 4 + 3] = (float)preview.x.pos[i]; }
-  const Aff incre = aff_mul(aff_inverse(f->lidarOdomAffineFront), back);
-  const Aff last = aff_mul(f->mappingOdomAffine, incre);
+  const Aff incre = aff_mul_padded(aff_inverse(f->lidarOdomAffineFront), back);
+  const Aff last = aff_mul_padded(f->mappingOdomAffine, incre);
   Quat oq; affine_to_pose(last, out->position, oq);
   out->orientation[0] = oq.x; out->orientation[1] = oq.y; out->orientation[2] = oq.z; out->orientation[3] = oq.w;
   for (int i = 0; i < 3; i++) out->velocity[i] = preview.x.vel[i];

@@ -8,9 +8,10 @@
 // residence: the scan's filtered clouds stay in the key map's scan_ds slots from the filter to the key-frame store; streams are ordered by events (scan_ready for the
 // registration's pack, the key map's own stream for the append); no host wait beyond those of the composed calls.
 //
-// The float pose algebra restates pcl::getTransformation, pcl::getTranslationAndEulerAngles and Eigen::Affine3f products / inverse (PCL, Eigen: not in the reference
-// tree) as odometry.hip does; tests/mapper_twin.py holds it to a float64 statement within a derived bound.
+// The float pose algebra (pcl::getTransformation, pcl::getTranslationAndEulerAngles, Eigen::Affine3f inverse and products) is pcl_affine.hpp's; the products here are
+// its aff_mul, the affine form; tests/mapper_twin.py holds the node's bookkeeping to a float64 statement within a derived bound.
 #include "keymap.hpp"
+#include "pcl_affine.hpp"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -21,49 +22,6 @@ using namespace rolo;
 
 namespace {
 
-struct Aff { float m[12]; };   // rows 0..2 of an Affine3f, row-major 3 x 4
-
-// pcl::getTransformation(x, y, z, roll, pitch, yaw) = trans2Affine3f :339-342 of a transformTobeMapped-order pose
-Aff aff_of_pose(const float* p /* roll pitch yaw x y z */) {
-  const float A = std::cos(p[2]), B = std::sin(p[2]), C = std::cos(p[1]), D = std::sin(p[1]), E = std::cos(p[0]), F = std::sin(p[0]);
-  const float DE = D * E, DF = D * F;
-  Aff t;
-  t.m[0] = A * C; t.m[1] = A * DF - B * E; t.m[2] = B * F + A * DE; t.m[3] = p[3];
-  t.m[4] = B * C; t.m[5] = A * E + B * DF; t.m[6] = B * DE - A * F; t.m[7] = p[4];
-  t.m[8] = -D;    t.m[9] = C * F;          t.m[10] = C * E;         t.m[11] = p[5];
-  return t;
-}
-// pcl::getTranslationAndEulerAngles: x y z roll pitch yaw
-void xyzrpy_of(const Aff& t, float* o) {
-  o[0] = t.m[3]; o[1] = t.m[7]; o[2] = t.m[11];
-  o[3] = std::atan2(t.m[9], t.m[10]);
-  o[4] = std::asin(-t.m[8]);
-  o[5] = std::atan2(t.m[4], t.m[0]);
-}
-// a b with the implicit last row (0 0 0 1): every entry summed over k left to right
-Aff aff_mul(const Aff& a, const Aff& b) {
-  Aff c;
-  for (int i = 0; i < 3; i++) {
-    for (int j = 0; j < 3; j++) c.m[i * 4 + j] = a.m[i * 4] * b.m[j] + a.m[i * 4 + 1] * b.m[4 + j] + a.m[i * 4 + 2] * b.m[8 + j];
-    c.m[i * 4 + 3] = a.m[i * 4] * b.m[3] + a.m[i * 4 + 1] * b.m[7] + a.m[i * 4 + 2] * b.m[11] + a.m[i * 4 + 3];
-  }
-  return c;
-}
-// Eigen::Transform<float, 3, Affine>::inverse(): the cofactor inverse of the linear part, translation -L^-1 t
-Aff aff_inverse(const Aff& T) {
-  const float* a = T.m;
-  float c[9];
-  c[0] = a[5] * a[10] - a[6] * a[9]; c[1] = a[2] * a[9] - a[1] * a[10]; c[2] = a[1] * a[6] - a[2] * a[5];
-  c[3] = a[6] * a[8] - a[4] * a[10]; c[4] = a[0] * a[10] - a[2] * a[8]; c[5] = a[2] * a[4] - a[0] * a[6];
-  c[6] = a[4] * a[9] - a[5] * a[8];  c[7] = a[1] * a[8] - a[0] * a[9];  c[8] = a[0] * a[5] - a[1] * a[4];
-  const float det = a[0] * c[0] + a[1] * c[3] + a[2] * c[6];
-  const float inv = 1.0f / det;
-  Aff o;
-  for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) o.m[i * 4 + j] = c[i * 3 + j] * inv;
-  for (int i = 0; i < 3; i++) o.m[i * 4 + 3] = -(o.m[i * 4] * a[3] + o.m[i * 4 + 1] * a[7] + o.m[i * 4 + 2] * a[11]);
-  return o;
-}
-
 // constraintTransformation :282-290
 float clamp_sym(float value, float limit) {
   if (value < -limit) value = -limit;
@@ -73,13 +31,8 @@ float clamp_sym(float value, float limit) {
 
 // gtsam::Pose3(Rot3::RzRyRx(double(roll), double(pitch), double(yaw)), Point3(double(x), ...)) :322-332 as a row-major 4 x 4: pcl::getTransformation's
 // formula in double on the widened floats
-void T16_of_pose(const float* p, double* T) {
-  const double r = (double)p[0], q = (double)p[1], y = (double)p[2];
-  const double A = std::cos(y), B = std::sin(y), C = std::cos(q), D = std::sin(q), E = std::cos(r), F = std::sin(r);
-  const double DE = D * E, DF = D * F;
-  T[0] = A * C; T[1] = A * DF - B * E; T[2] = B * F + A * DE; T[3] = (double)p[3];
-  T[4] = B * C; T[5] = A * E + B * DF; T[6] = B * DE - A * F; T[7] = (double)p[4];
-  T[8] = -D;    T[9] = C * F;          T[10] = C * E;         T[11] = (double)p[5];
+void T16_of_rpyxyz(const float* p, double* T) {
+  pcl_rows_of_xyzrpy<double>(p[3], p[4], p[5], p[0], p[1], p[2], T);
   T[12] = 0.0; T[13] = 0.0; T[14] = 0.0; T[15] = 1.0;
 }
 // poseFrom.between(poseTo) = poseFrom^-1 poseTo for rigid poses: R = Rf^T Rt, t = Rf^T (tt - tf), every sum over k left to right
@@ -198,7 +151,7 @@ int mapper_save_keyframe(rolo_mapper* m, double stamp, NodeState* S, rolo_mapper
   }
   // addOdomFactor :1224-1243
   double To[16], Z[16];
-  T16_of_pose(S->tf, To);
+  T16_of_rpyxyz(S->tf, To);
   if ((rc = rolo_pgo_add_pose(m->pgo, To)) < 0) return rc;
   if (K == 0) {
     const double v[6] = {1e-2, 1e-2, M_PI * M_PI, 1e8, 1e8, 1e8};
@@ -206,7 +159,7 @@ int mapper_save_keyframe(rolo_mapper* m, double stamp, NodeState* S, rolo_mapper
   } else {
     const double v[6] = {1e-6, 1e-6, 1e-6, 1e-4, 1e-4, 1e-4};
     double From[16];
-    T16_of_pose(km->frames[K - 1].pose, From);   // pclPointTogtsamPose3(cloudKeyPoses6D->points.back())
+    T16_of_rpyxyz(km->frames[K - 1].pose, From);   // pclPointTogtsamPose3(cloudKeyPoses6D->points.back())
     T16_between(From, To, Z);
     if ((rc = rolo_pgo_add_between(m->pgo, K - 1, K, Z, v))) return rc;
   }
@@ -453,19 +406,19 @@ int rolo_mapper_initial_guess(const float* tf6_in, int have_keyposes, const floa
   if (!have_keyposes) {   // :524-531
     tf[0] = 0.f; tf[1] = 0.f; tf[2] = 0.f;
   } else if (odomAvailable) {
-    const Aff transBack = aff_of_pose(guess6);   // :538-539
+    const Aff transBack = aff_of_rpyxyz(guess6);   // :538-539
     if (!*lastOdomAvailable) {                   // :540-543
-      std::memcpy(lastOdom12, transBack.m, sizeof(transBack.m));
+      std::memcpy(lastOdom12, transBack.m, 12 * sizeof(float));
       *lastOdomAvailable = 1;
     } else {                                     // :545-551
-      Aff last;
-      std::memcpy(last.m, lastOdom12, sizeof(last.m));
+      Aff last = aff_identity();
+      std::memcpy(last.m, lastOdom12, 12 * sizeof(float));
       const Aff transIncre = aff_mul(aff_inverse(last), transBack);
-      const Aff transFinal = aff_mul(aff_of_pose(tf), transIncre);
+      const Aff transFinal = aff_mul(aff_of_rpyxyz(tf), transIncre);
       float o[6];
       xyzrpy_of(transFinal, o);
       tf[0] = o[3]; tf[1] = o[4]; tf[2] = o[5]; tf[3] = o[0]; tf[4] = o[1]; tf[5] = o[2];
-      std::memcpy(lastOdom12, transBack.m, sizeof(transBack.m));
+      std::memcpy(lastOdom12, transBack.m, 12 * sizeof(float));
     }
   }
   std::memcpy(tf6_out, tf, sizeof(tf));
@@ -475,7 +428,7 @@ int rolo_mapper_initial_guess(const float* tf6_in, int have_keyposes, const floa
 int rolo_mapper_save_frame(const float* last_keypose6, const float* tf6, float dist_thr, float angle_thr) {
   if (!tf6) return ROLO_EINVAL;
   if (!last_keypose6) return 1;   // :1073-1074
-  const Aff transBetween = aff_mul(aff_inverse(aff_of_pose(last_keypose6)), aff_of_pose(tf6));   // :1076-1080
+  const Aff transBetween = aff_mul(aff_inverse(aff_of_rpyxyz(last_keypose6)), aff_of_rpyxyz(tf6));   // :1076-1080
   float o[6];
   xyzrpy_of(transBetween, o);
   if (std::fabs(o[3]) < angle_thr && std::fabs(o[4]) < angle_thr && std::fabs(o[5]) < angle_thr && std::sqrt(o[0] * o[0] + o[1] * o[1] + o[2] * o[2]) < dist_thr) return 0;
@@ -486,13 +439,13 @@ int rolo_mapper_incremental(const float* front6, const float* back6, const float
   if (!incre12 || !pose6_out || (!started && !tf6) || (started && (!front6 || !back6))) return ROLO_EINVAL;
   Aff inc;
   if (!started) {   // :1365-1369
-    inc = aff_of_pose(tf6);
+    inc = aff_of_rpyxyz(tf6);
   } else {          // :1372-1373
-    Aff cur;
-    std::memcpy(cur.m, incre12, sizeof(cur.m));
-    inc = aff_mul(cur, aff_mul(aff_inverse(aff_of_pose(front6)), aff_of_pose(back6)));
+    Aff cur = aff_identity();
+    std::memcpy(cur.m, incre12, 12 * sizeof(float));
+    inc = aff_mul(cur, aff_mul(aff_inverse(aff_of_rpyxyz(front6)), aff_of_rpyxyz(back6)));
   }
-  std::memcpy(incre12, inc.m, sizeof(inc.m));
+  std::memcpy(incre12, inc.m, 12 * sizeof(float));
   xyzrpy_of(inc, pose6_out);
   return ROLO_OK;
 }

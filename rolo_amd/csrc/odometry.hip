@@ -3,62 +3,18 @@
 // (reference src/lidarOdometry.cpp:503-570, 700-712, 448-501, 572-626) on feature clouds, i.e. everything of the
 // rolo_lidarOdometry node between "fromROSMsg" and "publish". The registration itself is the HIP path
 // (rolo_register_async / rolo_register_wait: both LM stages enqueued back to back, one host wait per frame).
-// The fp32 pose algebra restates pcl::getTransformation / getTranslationAndEulerAngles / Eigen::Affine3f products
-// (PCL, Eigen: not vendored by the reference).
+// The fp32 pose algebra (pcl::getTransformation / getTranslationAndEulerAngles / Eigen::Affine3f inverse and products) is pcl_affine.hpp's; the products
+// here are its aff_mul_padded, the oracle's mat4f_mul.
 #include "ctx_access.hpp"
 #include "switches.hpp"
 #include "polar_f32.hpp"
+#include "pcl_affine.hpp"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
-namespace {
-
-struct Aff { float m[16]; };  // row-major 4x4
-
-Aff aff_identity() { Aff a; for (int i = 0; i < 16; i++) a.m[i] = (i % 5 == 0) ? 1.f : 0.f; return a; }
-
-// pcl::getTransformation(x, y, z, roll, pitch, yaw)
-Aff get_transformation(float x, float y, float z, float roll, float pitch, float yaw) {
-  const float A = std::cos(yaw), B = std::sin(yaw), C = std::cos(pitch), D = std::sin(pitch), E = std::cos(roll), F = std::sin(roll);
-  const float DE = D * E, DF = D * F;
-  Aff t;
-  t.m[0] = A * C; t.m[1] = A * DF - B * E; t.m[2] = B * F + A * DE; t.m[3] = x;
-  t.m[4] = B * C; t.m[5] = A * E + B * DF; t.m[6] = B * DE - A * F; t.m[7] = y;
-  t.m[8] = -D;    t.m[9] = C * F;          t.m[10] = C * E;         t.m[11] = z;
-  t.m[12] = 0; t.m[13] = 0; t.m[14] = 0; t.m[15] = 1;
-  return t;
-}
-// pcl::getTranslationAndEulerAngles
-void get_translation_and_euler(const Aff& t, float* o) {
-  o[0] = t.m[3]; o[1] = t.m[7]; o[2] = t.m[11];
-  o[3] = std::atan2(t.m[9], t.m[10]);
-  o[4] = std::asin(-t.m[8]);
-  o[5] = std::atan2(t.m[4], t.m[0]);
-}
-Aff aff_mul(const Aff& a, const Aff& b) {
-  Aff c;
-  for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) { float s = 0; for (int k = 0; k < 4; k++) s += a.m[i * 4 + k] * b.m[k * 4 + j]; c.m[i * 4 + j] = s; }
-  return c;
-}
-// Eigen::Transform<float,3,Affine>::inverse(): cofactor inverse of the linear part, translation -inv * t
-Aff aff_inverse(const Aff& T) {
-  const float* a = T.m;
-  float c[9];
-  c[0] = a[5] * a[10] - a[6] * a[9]; c[1] = a[2] * a[9] - a[1] * a[10]; c[2] = a[1] * a[6] - a[2] * a[5];
-  c[3] = a[6] * a[8] - a[4] * a[10]; c[4] = a[0] * a[10] - a[2] * a[8]; c[5] = a[2] * a[4] - a[0] * a[6];
-  c[6] = a[4] * a[9] - a[5] * a[8];  c[7] = a[1] * a[8] - a[0] * a[9];  c[8] = a[0] * a[5] - a[1] * a[4];
-  const float det = a[0] * c[0] + a[1] * c[3] + a[2] * c[6];
-  const float inv = 1.0f / det;
-  Aff o;
-  for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) o.m[i * 4 + j] = c[i * 3 + j] * inv;
-  for (int i = 0; i < 3; i++) o.m[i * 4 + 3] = -(o.m[i * 4] * a[3] + o.m[i * 4 + 1] * a[7] + o.m[i * 4 + 2] * a[11]);
-  o.m[12] = o.m[13] = o.m[14] = 0; o.m[15] = 1;
-  return o;
-}
-
-}  // namespace
+using namespace rolo;
 
 struct rolo_odom {
   rolo_ctx* ctx;
@@ -106,10 +62,10 @@ void update_transform(rolo_odom* o) {  // lidarOdometry.cpp:572-626, pose part
   Aff step;
   for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) step.m[i * 4 + j] = (float)o->Rotation[i * 3 + j]; step.m[i * 4 + 3] = (float)o->Translation[i]; }
   step.m[12] = step.m[13] = step.m[14] = 0; step.m[15] = 1;
-  const Aff pose = get_transformation(o->LaserOdomPose[0], o->LaserOdomPose[1], o->LaserOdomPose[2], o->LaserOdomPose[3], o->LaserOdomPose[4], o->LaserOdomPose[5]);
-  const Aff moved = aff_mul(pose, aff_inverse(step));
+  const Aff pose = aff_of_xyzrpy(o->LaserOdomPose[0], o->LaserOdomPose[1], o->LaserOdomPose[2], o->LaserOdomPose[3], o->LaserOdomPose[4], o->LaserOdomPose[5]);
+  const Aff moved = aff_mul_padded(pose, aff_inverse(step));
   o->lidarMappingAffine = step;
-  get_translation_and_euler(moved, o->LaserOdomPose);
+  xyzrpy_of(moved, o->LaserOdomPose);
   for (int i = 0; i < 3; i++) o->TranslationOld[i] = o->Translation[i];
 }
 }  // namespace
@@ -143,9 +99,9 @@ void rolo_affine3f_rotation(const float* T16, float* R9) {   // lidarOdometry.cp
   rolo::polar::rotation_f32(L, R9);
 }
 void rolo_odom_increment(const float* front6, const float* back6, float* incre6) {  // imageProjection.cpp:345-351
-  const Aff F = get_transformation(front6[0], front6[1], front6[2], front6[3], front6[4], front6[5]);
-  const Aff B = get_transformation(back6[0], back6[1], back6[2], back6[3], back6[4], back6[5]);
-  get_translation_and_euler(aff_mul(aff_inverse(F), B), incre6);
+  const Aff F = aff_of_xyzrpy(front6[0], front6[1], front6[2], front6[3], front6[4], front6[5]);
+  const Aff B = aff_of_xyzrpy(back6[0], back6[1], back6[2], back6[3], back6[4], back6[5]);
+  xyzrpy_of(aff_mul_padded(aff_inverse(F), B), incre6);
 }
 
 static int ensure_front_ctx(rolo_odom* o) {
@@ -203,10 +159,10 @@ int rolo_odom_cloud(rolo_odom* o, double stamp, const float* corner, int n_corne
     // stateLinearPropagation :700-712
     const double ratio = latestInterval / o->lastMappingInterval;
     float v[6];
-    get_translation_and_euler(o->lidarMappingAffine, v);
+    xyzrpy_of(o->lidarMappingAffine, v);
     v[3] = v[4] = v[5] = 0;
     for (int i = 0; i < 6; i++) v[i] *= (float)ratio;
-    o->transformation_interpolated = get_transformation(v[0], v[1], v[2], v[3], v[4], v[5]);
+    o->transformation_interpolated = aff_of_xyzrpy(v[0], v[1], v[2], v[3], v[4], v[5]);
     o->cloudTimeLast = o->cloudTimeCur;
     o->lastMappingInterval = latestInterval;
     // scanRegeistration :448-501
@@ -224,7 +180,7 @@ int rolo_odom_cloud(rolo_odom* o, double stamp, const float* corner, int n_corne
     float Tf[16]; double reg_t[3];
     if ((rc = rolo_register_wait(o->ctx, Tf, nullptr, reg_t, &o->last_rot, &o->last_trans))) return rc;
     Aff step; memcpy(step.m, Tf, sizeof(Tf));
-    o->transformation_interpolated = aff_mul(o->transformation_interpolated, step);  // :472
+    o->transformation_interpolated = aff_mul_padded(o->transformation_interpolated, step);  // :472
     set_rotation_translation(o);   // :474-475
     for (int i = 0; i < 3; i++) o->Translation[i] += reg_t[i];  // :500
     update_transform(o);
@@ -242,10 +198,10 @@ static Aff predicted_transform(const rolo_odom* o, double stamp) {
   const double latestInterval = stamp - o->cloudTimeLast;
   const double ratio = latestInterval / o->lastMappingInterval;
   float v[6];
-  get_translation_and_euler(o->lidarMappingAffine, v);
+  xyzrpy_of(o->lidarMappingAffine, v);
   v[3] = v[4] = v[5] = 0;
   for (int i = 0; i < 6; i++) v[i] *= (float)ratio;
-  return get_transformation(v[0], v[1], v[2], v[3], v[4], v[5]);
+  return aff_of_xyzrpy(v[0], v[1], v[2], v[3], v[4], v[5]);
 }
 
 static int submit_common(rolo_odom* o, const rolo_front_params* P, double stamp, const void* pts, int stride, const uint16_t* ring,
@@ -348,7 +304,7 @@ int rolo_odom_collect(rolo_odom* o, float* pose6, double* rot9, double* trans3, 
     if ((rc = rolo_register_wait(o->ctx, Tf, nullptr, reg_t, &o->last_rot, &o->last_trans))) return rc;
     o->cov_chain = true;  // the context now holds the covariances of d_featNew as its target's
     Aff step; memcpy(step.m, Tf, sizeof(Tf));
-    o->transformation_interpolated = aff_mul(o->transformation_interpolated, step);  // :472
+    o->transformation_interpolated = aff_mul_padded(o->transformation_interpolated, step);  // :472
     set_rotation_translation(o);   // :474-475
     for (int i = 0; i < 3; i++) o->Translation[i] += reg_t[i];  // :500
     update_transform(o);

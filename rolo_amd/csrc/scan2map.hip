@@ -18,6 +18,7 @@
 #include "switches.hpp"
 #include "dev_rows.hpp"
 #include "knn_packet.hpp"
+#include "pcl_affine.hpp"
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -739,14 +740,7 @@ int s2m_optimize_core(rolo_ctx* c, const float* corner, int n_corner, const floa
   if (!W->h_sum && (rg = W->store.alloc_pinned(W->h_sum, S2M_NV))) return rg;
   double* h_sum = W->h_sum;
   for (int iterCount = 0; iterCount < 30; iterCount++) {
-    // trans2Affine3f :339-342 = pcl::getTransformation(x, y, z, roll, pitch, yaw), float
-    {
-      const float Ax = std::cos(tf[2]), Bx = std::sin(tf[2]), Cx = std::cos(tf[1]), Dx = std::sin(tf[1]), Ex = std::cos(tf[0]), Fx = std::sin(tf[0]);
-      const float DE = Dx * Ex, DF = Dx * Fx;
-      A.T[0] = Ax * Cx; A.T[1] = Ax * DF - Bx * Ex; A.T[2] = Bx * Fx + Ax * DE; A.T[3] = tf[3];
-      A.T[4] = Bx * Cx; A.T[5] = Ax * Ex + Bx * DF; A.T[6] = Bx * DE - Ax * Fx; A.T[7] = tf[4];
-      A.T[8] = -Dx; A.T[9] = Cx * Fx; A.T[10] = Cx * Ex; A.T[11] = tf[5];
-    }
+    pcl_rows_of_rpyxyz(tf, A.T);   // trans2Affine3f :339-342
     A.srx = std::sin(tf[1]); A.crx = std::cos(tf[1]); A.sry = std::sin(tf[2]); A.cry = std::cos(tf[2]); A.srz = std::sin(tf[0]); A.crz = std::cos(tf[0]);
     if (use_packets) s2m_assoc_kernel<<<grid, 256, 0, s>>>(A, split);
     else s2m_kernel<<<grid, S2M_THREADS, 0, s>>>(A);

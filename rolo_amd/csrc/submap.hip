@@ -20,6 +20,7 @@
 #include "keymap.hpp"
 #include "dev_rows.hpp"
 #include "sort_dev.hpp"
+#include "pcl_affine.hpp"
 #include <algorithm>
 #include <array>
 #include <cfloat>
@@ -211,15 +212,6 @@ int host_voxelgrid(const std::vector<std::array<float, 4>>& in, float leaf, std:
   return (int)out.size();
 }
 
-// pcl::getTransformation(x, y, z, roll, pitch, yaw) in float (pcl/common/impl/eigen.hpp), rows 0..2
-void pose_to_T(const float* pose6 /* roll pitch yaw x y z */, float* T) {
-  const float A = std::cos(pose6[2]), B = std::sin(pose6[2]), C = std::cos(pose6[1]), D = std::sin(pose6[1]), E = std::cos(pose6[0]), F = std::sin(pose6[0]);
-  const float DE = D * E, DF = D * F;
-  T[0] = A * C; T[1] = A * DF - B * E; T[2] = B * F + A * DE; T[3] = pose6[3];
-  T[4] = B * C; T[5] = A * E + B * DF; T[6] = B * DE - A * F; T[7] = pose6[4];
-  T[8] = -D; T[9] = C * F; T[10] = C * E; T[11] = pose6[5];
-}
-
 }  // namespace
 }  // namespace rolo
 
@@ -373,7 +365,7 @@ int gm_enqueue_batch(rolo_keymap* km, const std::vector<GmPiece>& pieces, size_t
     const long long lo = std::max(pc.off, b0), hi = std::min(pc.off + pc.n, b0 + nb);
     Seg& g = km->h_segs[nsegs++];
     g.src = pc.src + (lo - pc.off); g.n = (int)(hi - lo); g.dst = (int)(lo - b0);
-    pose_to_T(km->frames[pc.frame].pose, g.T);
+    pcl_rows_of_rpyxyz(km->frames[pc.frame].pose, g.T);
     max_n = std::max(max_n, g.n);
   }
   hipStream_t s = km->stream;
@@ -602,7 +594,7 @@ int keymap_registered(rolo_keymap* km, const float4* const* pieces, const int* n
     if (!n[k]) continue;
     Seg& g = km->h_segs[nsegs++];
     g.src = pieces[k]; g.n = n[k]; g.dst = dst;
-    pose_to_T(pose6, g.T);
+    pcl_rows_of_rpyxyz(pose6, g.T);
     dst += n[k];
   }
   HIPCHK(hipMemcpyAsync(km->segs, km->h_segs, nsegs * sizeof(Seg), hipMemcpyHostToDevice, s));
@@ -729,7 +721,7 @@ int rolo_keymap_extract(rolo_keymap* km, const int32_t* indices, int n, float co
       if (!f.n[t]) continue;
       Seg& g = km->h_segs[k++];
       g.src = f.pts[t]; g.n = f.n[t]; g.dst = dst;
-      pose_to_T(f.pose, g.T);
+      pcl_rows_of_rpyxyz(f.pose, g.T);
       dst += f.n[t];
     }
   }
@@ -855,7 +847,7 @@ int rolo_keymap_loop_cloud(rolo_keymap* km, int slot, int key, int search_num, i
       if (!f.n[t]) continue;
       Seg& g = km->h_segs[q++];
       g.src = f.pts[t]; g.n = f.n[t]; g.dst = dst;
-      pose_to_T(wrt_key >= 0 ? km->frames[wrt_key].pose : f.pose, g.T);
+      pcl_rows_of_rpyxyz(wrt_key >= 0 ? km->frames[wrt_key].pose : f.pose, g.T);
       dst += f.n[t];
     }
   }

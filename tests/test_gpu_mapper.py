@@ -46,7 +46,7 @@ def params(**kw):
     return mapper_params(mappingSurfLeafSize=SURF_LEAF, surroundingKeyframeDensity=DENSITY, **kw)
 
 
-# ---- the graph's measurements in double, in the library's operation order (mapper.hip: T16_of_pose, T16_between), with libm's cos / sin ----
+# ---- the graph's measurements in double, in the library's operation order (mapper.hip: T16_of_rpyxyz, T16_between), with libm's cos / sin ----
 def T16_of_pose(p):
     r, q, y = float(p[0]), float(p[1]), float(p[2])
     A, B, C, D, E, F = math.cos(y), math.sin(y), math.cos(q), math.sin(q), math.cos(r), math.sin(r)
