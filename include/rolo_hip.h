@@ -65,7 +65,7 @@ typedef struct rolo_params {
                                     1 = ONE launch per LM trial (the controller runs in the prologue of the next pass, in every workgroup): the shortest chain of rounds 1-5 for
                                         one frame at a time (the odometry driver turns it on), slower with several contexts in flight (-22 % with four);
                                     2 = ONE launch per FRAME (round 6, the default): 64 (other contexts' frames in flight) ... 256 (idle device) workgroups stay resident for the
-                                        whole chain of both stages and exchange their rows through self-validating words between the trials (passes.hip lm_persist_kernel) — no
+                                        whole chain of both stages and exchange their rows through self-validating words between the trials (lm_persist.hip lm_persist_kernel) — no
                                         kernel boundary inside the chain, no schedule that can fall short. Spin-waits are bounded: a launch that cannot get all its workgroups
                                         onto the chip within ROLO_LM_PERSIST_ADMIT_US (1000) leaves the stage untouched and the frame is finished as with 0
                                         (rolo_ctx_counters[12]); a later poll longer than ROLO_LM_PERSIST_TIMEOUT_MS (200) ends the frame with ROLO_ECOMM.

@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librolo_hip.so")
-SOURCES = ["api.hip", "schedule.hip", "debug.hip", "knn_cov.hip", "voxelmap.hip", "passes.hip", "misc.hip", "front.hip", "odometry.hip", "fusion.hip", "scan2map.hip", "submap.hip", "scancontext.hip", "loopicp.hip", "posegraph.hip", "peer.hip", "groundprior.hip", "mapper.hip"]
+SOURCES = ["api.hip", "schedule.hip", "debug.hip", "knn_cov.hip", "voxelmap.hip", "passes.hip", "lm_persist.hip", "misc.hip", "front.hip", "odometry.hip", "fusion.hip", "scan2map.hip", "submap.hip", "scancontext.hip", "loopicp.hip", "posegraph.hip", "peer.hip", "groundprior.hip", "mapper.hip"]
 # every unit is rebuilt when any header changes: the private ones are whatever *.hpp csrc/ holds (a hand-kept list that misses one leaves stale objects linked in silently)
 HEADERS = sorted(h for h in os.listdir(CSRC) if h.endswith(".hpp")) + [os.path.join("..", "..", "include", "rolo_hip.h"), os.path.join("..", "..", "include", "rolo_fusion.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -155,7 +155,7 @@ int build_clouds(rolo_ctx* c, bool do_src, bool do_tgt, hipStream_t stream, bool
     // without a communicator / peers (rolo_set_shard test hook) only the own slice is valid afterwards
     HIPCHK(launch_knn_unstage(A, c->comm == nullptr && !peers(c), vf, stream));
   }
-  // (the tail leaves the PLANE covariances as I - m m^T too — CloudDev::nrm — unless the slices went through an exchange buffer: passes.hip load_pt)
+  // (the tail leaves the PLANE covariances as I - m m^T too — CloudDev::nrm — unless the slices went through an exchange buffer: lm_point.hpp load_pt)
   const bool nrm_written = !sharded && c->P.regularization == ROLO_REG_PLANE;
   if (do_src) { c->src.have_cov = true; c->src.have_sorted = true; c->src.cov_user = false; c->src.have_nrm = nrm_written; c->src.bbox6 = S.bbox; }
   if (do_tgt) { c->tgt.have_cov = true; c->tgt.have_sorted = true; c->tgt.cov_user = false; c->tgt.have_nrm = nrm_written; c->tgt.bbox6 = S.bbox + (do_src ? 6 : 0); }

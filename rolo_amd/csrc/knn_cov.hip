@@ -552,7 +552,7 @@ ROLO_DEV void knn_covariance_finish(double cxx, double cxy, double cxz, double c
     const double mx = al * V[0 * 3 + 2], my = al * V[1 * 3 + 2], mz = al * V[2 * 3 + 2];
     // The identity needs u0 = v0 and u1 = v1. A neighbourhood of rank <= 1 (collinear or coincident neighbours: TWO singular values ~ 0) can leave the sweep with the
     // sign fix on the second column as well (or, for coincident points, on all three): the six entries above are then NOT I - m m^T, and they are what the voxel map
-    // and every getter see. Such a point is poisoned — NaN in m.x — and the passes take its six entries instead (passes.hip load_pt / rotated_cov): advisor, round 5.
+    // and every getter see. Such a point is poisoned — NaN in m.x — and the passes take its six entries instead (lm_point.hpp load_pt / rotated_cov): advisor, round 5.
     const double s1 = U[0 * 3 + 0] * V[0 * 3 + 0] + U[1 * 3 + 0] * V[1 * 3 + 0] + U[2 * 3 + 0] * V[2 * 3 + 0];
     const double s2 = U[0 * 3 + 1] * V[0 * 3 + 1] + U[1 * 3 + 1] * V[1 * 3 + 1] + U[2 * 3 + 1] * V[2 * 3 + 1];
     const bool plane_form = s1 > 0 && s2 > 0;

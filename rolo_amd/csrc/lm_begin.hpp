@@ -1,4 +1,4 @@
-// The LM state at the start of a stage / frame: shared by passes.hip (rot_begin / frame_begin kernels, batches) and voxelmap.hip, whose
+// The LM state at the start of a stage / frame: shared by passes.hip (rot_begin / frame_begin / evaluation kernels, batches), lm_step.hpp (lm_set_rrt) and voxelmap.hip, whose
 // finalize kernel — the last launch before a frame's LM chain — writes it on the way (one launch less per frame).
 #pragma once
 #include "rolo_internal.hpp"
@@ -31,14 +31,19 @@ __device__ inline void rot_begin_dev(LmState* st, const RotBegin& a) {
   st->inv_rot_eps = 1.0 / a.rot_eps; st->inv_trans_eps = 1.0 / a.trans_eps;
 }
 
+// a translation stage's inputs: the start value, the guess, the last translation, the two intervals and the constant-velocity weight
+// (twin: trans_begin_kernel, which writes them itself)
+__device__ inline void trans_inputs_dev(LmState* st, const TransBegin& t) {
+  for (int i = 0; i < 3; i++) { st->t0[i] = t.t0[i]; st->g[i] = t.g[i]; st->l[i] = t.l[i]; }
+  st->dtn = t.dtn; st->dtn1 = t.dtn1; st->ct_lambda = t.ct_lambda;
+}
 
 // rolo_register_async: both stages' inputs from the frame's argument block (pinned host memory or device)
 __device__ inline void frame_begin_dev(LmState* st, const FrameArgs* a) {
   const RotBegin r = a->rot;
   const TransBegin t = a->trans;
   rot_begin_dev(st, r);
-  for (int i = 0; i < 3; i++) { st->t0[i] = t.t0[i]; st->g[i] = t.g[i]; st->l[i] = t.l[i]; }
-  st->dtn = t.dtn; st->dtn1 = t.dtn1; st->ct_lambda = t.ct_lambda;
+  trans_inputs_dev(st, t);
 }
 
 }  // namespace rolo

@@ -123,18 +123,18 @@ struct LmState {
   // linearises at the accepted pose: the state after it is the one the full pass would have left, one launch later. spec_lin = 0 (ROLO_LM_SPEC_LIN=0) never skips.
   int lin_skip, spec_lin;
   // keep_cost (ROLO_LM_KEEP_COST, default 1): with forced iterations a converged-but-rejected trial is followed by the SAME trial until the iterations are used up; the step
-  // answers those repeats from the cost it holds instead of asking for another pass (passes.hip rot_step_t). rot_kept counts the trials of rot_passes answered that way.
+  // answers those repeats from the cost it holds instead of asking for another pass (lm_step.hpp rot_step_t). rot_kept counts the trials of rot_passes answered that way.
   int keep_cost, rot_kept;
   // trans_model (ROLO_LM_TRANS_MODEL, default 1): within the translation stage a trial's cost is a quadratic in the translation whose coefficients are in the sums of the
   // stage's linearisation (trans_model.hpp); the step answers the trials that follow a linearisation itself — trace record, counts and damping of each as if its pass had
-  // run — and asks for a pass only to linearise again after an accepted trial (passes.hip trans_step). trans_modelled counts the trials of trans_passes answered
+  // run — and asks for a pass only to linearise again after an accepted trial (lm_step.hpp trans_step). trans_modelled counts the trials of trans_passes answered
   // that way. tm_free_lin: the linearise-only pass now pending stands in for the (B) half of an accepted trial's full pass, which the solve's count already holds — the
   // step that consumes it counts it in trans_lin_extra instead of trans_passes. Launches of the stage that ran = trans_passes - trans_modelled + trans_lin_extra.
   int trans_model, trans_modelled, trans_lin_extra, tm_free_lin;
   TransModel tm;   // the model of the stage's last linearisation: written and read within one call of the step (it never crosses a launch), kept here because the state is in LDS
   int rot_cost_only, trans_cost_only;   // passes of rot_passes / trans_passes that ran with lin_skip set (counted by the step that consumes them): rolo_stats::n_cost_only
   int lmp_bailed;   // the resident LM kernel (fused_lm = 2) did not get all its workgroups resident within the admission time and left WITHOUT touching the stage: the host
-                    // finishes the frame with pass + controller launches (passes.hip lm_persist_kernel, schedule.hip run_stage)
+                    // finishes the frame with pass + controller launches (lm_persist.hip lm_persist_kernel, schedule.hip run_stage)
   // parameters
   int optimizer, max_iterations, fixed_iterations, lm_max, q2_intended;
   double rot_eps, trans_eps, lm_init;
@@ -150,7 +150,7 @@ struct PassArgs {
   int n_off;          // 1, 7 or 27 neighbour offsets
   int* corr[2];       // n_total * n_off voxel ids (-1 = none)
   double* partials;   // gridDim.x x NV_MAX
-  int xcd_map;        // 1: XCD x evaluates the x-th eighth of the point blocks (passes.hip pass_xcd_block); 0: blocks dealt round-robin (ROLO_PASS_XCD=0, the A/B)
+  int xcd_map;        // 1: XCD x evaluates the x-th eighth of the point blocks (lm_point.hpp pass_xcd_block); 0: blocks dealt round-robin (ROLO_PASS_XCD=0, the A/B)
   VoxelTable tab;
 };
 
@@ -238,12 +238,12 @@ hipError_t launch_trans_pass(const PassArgs& a, const LmState* st, int grid, hip
 // evaluate the next pass into rows_out; threads in {256, 512, 1024}; nrows = workgroups of a pass; do_body = 0: closing launch
 hipError_t launch_lm(int dof, int threads, int ppt /* slabs of `threads` points per workgroup */, const PassArgs& a, const LmState* st_in, LmState* st_out, const double* rows_in, double* rows_out, int nrows,
                      rolo_trace_rec* trace, int do_body, hipStream_t s, LmState* pub = nullptr /* pinned host copy of the state written by workgroup 0 */);
-// one launch per frame (passes.hip lm_persist_kernel): nrows resident workgroups of 512 threads x ppt points, rows exchanged through xbuf (lm_persist_words(nrows) 64-bit words,
+// one launch per frame (lm_persist.hip lm_persist_kernel): nrows resident workgroups of 512 threads x ppt points, rows exchanged through xbuf (lm_persist_words(nrows) 64-bit words,
 // zeroed once); the state starts and ends in st; admit_ticks: wall-clock ticks (100 MHz) the workgroups wait for each other to become resident before they leave the stage to the
 // host (LmState::lmp_bailed); timeout_ticks: what a poll may last after that (a bug guard: ROLO_ECOMM); max_trials: hard cap on the trials of one launch
 hipError_t launch_lm_persist(int dof, int threads, int ppt, const PassArgs& a, LmState* st, unsigned long long* xbuf, int nrows, rolo_trace_rec* trace, LmState* pub, unsigned long long timeout_ticks,
                              unsigned long long admit_ticks, int max_trials, hipStream_t s);
-// the instantiation one resident launch takes (passes.hip lm_persist_form): launch_lm_persist launches exactly this and rolo_ctx_lm_form reports it
+// the instantiation one resident launch takes (lm_persist.hip lm_persist_form): launch_lm_persist launches exactly this and rolo_ctx_lm_form reports it
 struct LmpForm {
   int rows = 0, threads = 0, ppt = 0;
   int sp = 0;       // points per thread of the interleaved body (1, 2, 4); 0: the generic body, one point after the other

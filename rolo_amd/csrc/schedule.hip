@@ -106,7 +106,7 @@ static int enqueue_lm_chunk(rolo_ctx* c, const PassArgs& a, int k, bool publish 
   return ROLO_OK;
 }
 
-// both stages (or the one the state is in) to completion in ONE launch (passes.hip lm_persist_kernel); the state starts and ends in c->state[0]
+// both stages (or the one the state is in) to completion in ONE launch (lm_persist.hip lm_persist_kernel); the state starts and ends in c->state[0]
 static int enqueue_lm_persist(rolo_ctx* c, const PassArgs& a, bool publish = false) {
   ProfScope ps(c, ROLO_PROF_LM_PASS);
   const int cap = (std::max(c->P.max_iterations, c->P.fixed_iterations) + 2) * (std::max(c->P.lm_max_iterations, 0) + 2) * 2 + 16;

@@ -46,7 +46,7 @@ struct Switches {
   bool pass_nrm = env::unless_zero("ROLO_PASS_NRM");                 // =0: the passes read the six-entry covariances always, never the PLANE form I - m m^T
   bool pass_xcd = env::unless_zero("ROLO_PASS_XCD");                  // =0: point blocks dealt to the XCDs round-robin, not an eighth of the cloud per XCD
   bool stamp = env::if_nonzero("ROLO_STAMP");                         // =1: a device timestamp at five points of every frame (rolo_debug_stamps)
-  // ---- the resident LM kernel (schedule.hip, passes.hip) ----
+  // ---- the resident LM kernel (schedule.hip, lm_persist.hip) ----
   int lm_persist_wgs = (int)env::in_range((int)env::num("ROLO_LM_PERSIST_WGS", 0), 8, 256, 0);           // 8..256 pins its workgroup count; unset or outside 0: 256 on an idle device, 64 on a busy one
   int lm_persist_busy_threads = env::one_of("ROLO_LM_PERSIST_BUSY_THREADS", {256}, 512);    // =256: on a busy device twice the workgroups of half the size
   long lm_persist_admit_us = env::in_range(env::num("ROLO_LM_PERSIST_ADMIT_US", 1000), 0, LONG_MAX, 1000);     // microseconds its workgroups wait for each other to become resident (negative: 1000; 0: every frame bails out — a test switch)

@@ -1,4 +1,4 @@
-// The translation stage's trial cost as a quadratic in the translation, from the 30 sums of the stage's own linearisation (passes.hip trans_step).
+// The translation stage's trial cost as a quadratic in the translation, from the 30 sums of the stage's own linearisation (lm_step.hpp trans_step).
 //
 // Within the stage the correspondences, the Mahalanobis matrices M and the weights w are constant (those of the last rotation linearisation), the residual
 // e = mean - (q + t) is linear in t, and the continuous-time term's vector dv - last / dt_{n-1} = -(g + t) / dt_n - last / dt_{n-1} is the same for every point (up to the
@@ -10,7 +10,7 @@
 //   cost(t0 + d)        = c - 2 d^T v + d^T A d + lam_over_n ctA(t0 + d)^T A ctA(t0 + d)
 // ctA / ctB are the vector above with the `last` term of compute_t_error / of t3_linearize (they differ as written, LmState::lastA_q / lastB_q).
 //
-// Pure C++: device code (passes.hip) and a host test program (tests/cpp/trans_model_test.cpp) compile the same two functions, each one fixed order of operations
+// Pure C++: device code (lm_step.hpp) and a host test program (tests/cpp/trans_model_test.cpp) compile the same two functions, each one fixed order of operations
 // (no contraction into fused multiply-adds: the host compiler has none to offer by default, the device compiler is told so below).
 #pragma once
 #include <cmath>
@@ -25,7 +25,7 @@
 
 namespace rolo {
 
-struct TransModelConsts {   // the stage's constants (passes.hip trans_start / trans_consts)
+struct TransModelConsts {   // the stage's constants (lm_step.hpp trans_start / trans_consts)
   double lam_over_n, inv_dtn;
   double g[3], lastA_q[3], lastB_q[3];
 };

@@ -403,7 +403,7 @@ print(json.dumps(out))
 @pytest.mark.parametrize("sensor,leaf,hint,wgs", [("os1-128", 0.5, 1, None), ("os1-64", 1.0, 1, None), ("os1-128", 0.5, 0, None), ("os1-128", 0.5, 1, "128")])
 def test_resident_kernel_forms_and_cache_follow_the_pass_launches(sensor, leaf, hint, wgs):
     """The resident LM kernel in the forms the load picks — 64 workgroups x 4 points per thread (the headline's), x 2 (65 536-point clouds; 128 workgroups forced), 256 x 1 on an
-    idle device — with its Mahalanobis cache (passes.hip lmp_rot_body: written by the (B) halves, read by the (A) halves and the translation passes, refilled after a rejected
+    idle device — with its Mahalanobis cache (lm_persist.hip lmp_rot_body: written by the (B) halves, read by the (A) halves and the translation passes, refilled after a rejected
     speculation) against pass + controller launches, which invert per trial: forced iterations (the cost-only run after convergence), the reference's own loop, a small initial
     damping (rejections early in the stage) and a large one with four trials per iteration (LM failure). Same exits, counts, cost-only passes and decisions; costs to 1e-9,
     poses to 1e-10 (the rows are sums over other groups of points)."""
@@ -459,7 +459,7 @@ print(json.dumps(out))
 
 def test_resident_kernel_on_a_cloud_beyond_the_cache_capacity():
     """524 288 points per cloud on an idle device: 256 workgroups x 4 points per thread — 60 KB of exchange rows + 96 KB of Mahalanobis cache would not fit a CU's 160 KB of LDS
-    beside the state, so the launch takes the form without the cache (passes.hip launch_lm_persist: `fits`). Same exits and counts as pass + controller launches, poses to 1e-10,
+    beside the state, so the launch takes the form without the cache (lm_persist.hip launch_lm_persist: `fits`). Same exits and counts as pass + controller launches, poses to 1e-10,
     no bail-out."""
     import json
     r = subprocess.run([sys.executable, "-c", _BIG, ROOT], capture_output=True, text=True, cwd=ROOT, timeout=900)

@@ -1,4 +1,4 @@
-"""GPU: forced LM iterations answered from the kept cost (passes.hip rot_step_t, ROLO_LM_KEEP_COST) change no observable bit.
+"""GPU: forced LM iterations answered from the kept cost (lm_step.hpp rot_step_t, ROLO_LM_KEEP_COST) change no observable bit.
 
 With fixed_iterations > 0 the rotation stage, once a trial is rejected although the step has converged, repeats that very trial until the iterations are used up. The step
 takes those repeats itself instead of asking for one pass each. Every case below runs the library in two child processes, ROLO_LM_KEEP_COST=1 and =0 (the parent form:

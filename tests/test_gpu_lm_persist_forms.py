@@ -1,7 +1,7 @@
-"""GPU: the resident LM kernel (fused_lm = 2, passes.hip lm_persist_kernel) in every launch form it has, against the CPU oracle AND against pass + controller launches.
+"""GPU: the resident LM kernel (fused_lm = 2, lm_persist.hip lm_persist_kernel) in every launch form it has, against the CPU oracle AND against pass + controller launches.
 
 Which instantiation runs, on how many workgroups, with how many points per thread and whether the Mahalanobis cache sits in LDS follows from the cloud size, the load
-(schedule.hip prepare_pass), the optimiser and the neighbour search (passes.hip lm_persist_form) and five environment switches. Each case registers a source cloud of exactly n
+(schedule.hip prepare_pass), the optimiser and the neighbour search (lm_persist.hip lm_persist_form) and five environment switches. Each case registers a source cloud of exactly n
 points through register_async / register_wait with a pinned load hint and checks:
 * lm_form() reports the form the case is there for (a case that silently takes another form fails) — the expected rows below are worked out by hand from
   schedule.hip prepare_pass: threads T = 512, workgroups at most 256 (idle) / 64 (busy), points per thread = ceil(n / (T * max workgroups)) with 3 rounded up to 4,

@@ -1,4 +1,4 @@
-"""GPU: the translation stage's trials answered from the sums of its own linearisation (passes.hip trans_step, trans_model.hpp, ROLO_LM_TRANS_MODEL).
+"""GPU: the translation stage's trials answered from the sums of its own linearisation (lm_step.hpp trans_step, trans_model.hpp, ROLO_LM_TRANS_MODEL).
 
 Within the stage a trial's cost is a quadratic in the translation; the step that has just unpacked a linearisation takes the trials that follow itself and asks for a pass
 only to linearise again after an accepted trial. Every case below runs the library in two child processes, ROLO_LM_TRANS_MODEL=1 and =0 (the parent form: every trial is

@@ -235,7 +235,7 @@ def test_three_lm_forms_look_up_through_the_chain(fixed):
 @pytest.mark.parametrize("fixed", [0, 4])
 def test_three_lm_forms_end_at_the_same_bytes(fixed):
     """final_transformation_d the same bytes under fused_lm = 0, 1 and 2. The 510 points are two workgroups of 256 under pass + controller launches and one of 512 in the
-    other two forms; a fat workgroup adds its wavefronts' sums in the groups of four that the pass kernel's rows are (passes.hip block_reduce_store), so the one row is the
+    other two forms; a fat workgroup adds its wavefronts' sums in the groups of four that the pass kernel's rows are (lm_point.hpp block_reduce_store), so the one row is the
     sum of the two. (Added in one run of eight, as they were, the forms ended one ulp apart in one entry of the pose: 8.67e-19 on 0.0033, lookups and decisions equal.)"""
     out, _ = lm_forms_through_the_chain(fixed)
     assert out[0][1] == out[1][1] == out[2][1]

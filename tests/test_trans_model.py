@@ -66,7 +66,7 @@ def model(tmp_path_factory):
 
 
 def stage_consts(n_corr, g, l, q2, dtn=DTN, dtn1=DTN1, lam=LAM):
-    """what trans_start / trans_consts leave in the LM state (passes.hip), as the oracle's t3_eval forms them"""
+    """what trans_start / trans_consts leave in the LM state (lm_step.hpp), as the oracle's t3_eval forms them"""
     lastA = np.asarray(l, float) if q2 else np.array([1.0, 0.0, 0.0])
     lastB = np.asarray(l, float) if q2 else np.zeros(3)
     return dict(lam_over_n=float(np.float32(lam) / np.float32(n_corr)), inv_dtn=1.0 / dtn, g=np.asarray(g, float), lastA_q=lastA / dtn1, lastB_q=lastB / dtn1)
