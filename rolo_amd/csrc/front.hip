@@ -12,7 +12,7 @@
 //       pass adds the ring offsets and scatters (x,y,z,intensity), column and range — coalesced on both sides;
 //   K3  a stencil kernel (11-tap float sum in the reference's written order) plus a mark kernel — the marks only
 //       ever store 1 and depend only on ranges / columns, so the serial loop is order-free;
-//   K4  one workgroup of 1024 threads per ring, everything for the ring staged in LDS: all six sectors in one segmented bitonic sort of
+//   K4  (front_extract.hpp, with K3 inside) one workgroup of 1024 threads per ring, everything for the ring staged in LDS: all six sectors in one segmented bitonic sort of
 //       packed (curvature bits << 32 | index) keys; the greedy corner / surface picks — a serial walk in the reference — as the equivalent
 //       fixed point "picked iff no better-ranked candidate that reaches it is picked", every lane owning a position, a few rounds per
 //       sector (only the two sectors touching the cloud ends keep the serial walk); the label<=0 collection is a ballot
@@ -21,6 +21,7 @@
 #include "ctx_access.hpp"
 #include <atomic>
 #include "dev_math.hpp"
+#include "front_extract.hpp"   // K3 + K4: extract_kernel in phases, FeatArgs, XT, the ring's working set (front_ring_bytes, FRONT_GUARD)
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -31,14 +32,9 @@
 
 namespace rolo {
 
-constexpr int FRONT_GUARD = 8;       // guard cells in front of / behind the per-point arrays (reference reads index -1.. )
 constexpr int FRONT_MAX_H = 2048;      // Horizon_SCAN up to here: one ring's working set lives in LDS (shipped configs: 1024, 1800, 2048)
 constexpr int FRONT_MAX_H_BIG = 4096;  // ... and up to here in a per-ring scratch area in HBM (the same kernel through global pointers: correct, several times slower;
                                        // no sensor the reference accepts has that many columns — its params.yaml mentions a Livox Horizon at 4000)
-// bitonic capacity (elements) for a Horizon_SCAN limit of maxh: 6 sector segments of <= maxh / 4, which also holds one ring's surface scan (<= maxh)
-constexpr int front_sort_cap(int maxh) { return 6 * (maxh / 4); }
-constexpr size_t front_ring_bytes(int maxh) { return sizeof(unsigned long long) * (size_t)front_sort_cap(maxh) + sizeof(int) * (size_t)(maxh + 32) * 8 + sizeof(int) * (size_t)(maxh + 16); }
-constexpr int ST_OUT = 0, ST_UNDECIDED = 1, ST_PICKED = 2;
 
 namespace {
 
@@ -233,681 +229,7 @@ __global__ __launch_bounds__(256) void ring_scatter_kernel(const float* __restri
   }
 }
 
-// ---- K3 (calculateSmoothness, markOccludedPoints) lives in the window load of extract_kernel below ----
-
-// ---- K4 ----
-// Ascending bitonic sort of every aligned `seg`-element segment of key[0, total) in LDS (seg a power of two, total a
-// multiple of seg; NT threads). Exchange distances >= 64 are block-wide steps with a barrier each; the distances
-// 32..1 that close every merge stage stay inside an aligned 64-element chunk, so one wavefront takes the chunk into
-// registers and finishes the stage with cross-lane exchanges (DPP / permlane swaps) — one barrier per stage instead of
-// one per step.
-template <int J2>
-ROLO_DEV void bitonic_lane_step(unsigned long long& v, int lane, bool up) {
-  const unsigned long long o = lane_xor_u64<J2>(v);   // DPP / v_permlane*_swap: no LDS crossbar (dev_math.hpp)
-  const bool take_min = ((lane & J2) == 0) == up;     // the lane with the smaller index of the pair keeps the minimum when ascending
-  v = take_min ? (o < v ? o : v) : (o > v ? o : v);
-}
-template <int NT>
-ROLO_DEV void bitonic_sort_lds_seg(unsigned long long* key, int total, int seg) {
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int n_chunks = (total + 63) >> 6;
-  for (int k = 2; k <= seg; k <<= 1) {
-    int jj = k >> 1;
-    for (; jj >= 64; jj >>= 1) {
-      for (int i = t; i < total; i += NT) {
-        const int ixj = i ^ jj;
-        if (ixj > i) {
-          const unsigned long long a = key[i], b = key[ixj];
-          const bool up = ((i & (seg - 1)) & k) == 0;
-          if ((a > b) == up) { key[i] = b; key[ixj] = a; }
-        }
-      }
-      __syncthreads();
-    }
-    for (int c = wv; c < n_chunks; c += NT / 64) {
-      const int i = (c << 6) + lane;
-      unsigned long long v = i < total ? key[i] : ~0ull;
-      const bool up = ((i & (seg - 1)) & k) == 0;
-      if (jj >= 32) bitonic_lane_step<32>(v, lane, up);
-      if (jj >= 16) bitonic_lane_step<16>(v, lane, up);
-      if (jj >= 8) bitonic_lane_step<8>(v, lane, up);
-      if (jj >= 4) bitonic_lane_step<4>(v, lane, up);
-      if (jj >= 2) bitonic_lane_step<2>(v, lane, up);
-      bitonic_lane_step<1>(v, lane, up);
-      if (i < total) key[i] = v;
-    }
-    __syncthreads();
-  }
-}
-template <int NT>
-ROLO_DEV void bitonic_sort_lds(unsigned long long* key, int n_pow2) { bitonic_sort_lds_seg<NT>(key, n_pow2, n_pow2); }
-
-struct FeatArgs {
-  const float4* extracted; const int* col; const float* range; float* curv; int* picked; int* label;  // global, guard-offset pointers
-  const int* start_ring; const int* end_ring;
-  const int* n_ptr; int n_scan; float edge_threshold, surf_threshold, leaf;
-  float4* corner_stage; int* corner_cnt;  // [n_scan][6][20], [n_scan][6]
-  float4* surf_stage; int* surf_cnt;      // [n_scan][MAXH], [n_scan]
-  unsigned char* big;                     // Horizon_SCAN > 2048: front_ring_bytes(MAXH) of scratch per ring
-  int* paths;                             // [n_scan]: which way the ring's picks were made (ROLO_XPATH_*, rolo_hip.h) — one lane's store per ring
-};
-
-// One workgroup of XT = 1024 threads per ring: 128 rings are only 128 workgroups, so the parallelism has to come from inside —
-// 16 wavefronts (4 per SIMD) hide the LDS / cross-lane latency of the sorts that 4 wavefronts (1 per SIMD) exposed.
-#ifndef ROLO_XT
-#define ROLO_XT 1024
-#endif
-constexpr int XT = ROLO_XT, XW = XT / 64;   // threads, wavefronts
-#ifdef ROLO_XT_STATS
-__device__ unsigned long long g_xt[128][8];   // per ring: phase time stamps of extract_kernel (shader clock)
-#define XT_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 128) g_xt[blockIdx.x][k] = clock64(); } while (0)
-extern "C" int rolo_debug_extract_times(unsigned long long* out /* 128 x 8 */) {
-  (void)hipDeviceSynchronize();
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_xt), sizeof(unsigned long long) * 128 * 8) == hipSuccess ? 0 : -1;
-}
-#else
-#define XT_STAMP(k)
-#endif
-template <int MAXH, bool GLOBAL>
-__global__ __launch_bounds__(XT) void extract_kernel(FeatArgs A) {
-  extern __shared__ unsigned char smem_lds[];
-  constexpr int SORT_CAP = front_sort_cap(MAXH), SEGMAX = MAXH / 4, UP = (SEGMAX + XT - 1) / XT;   // UP: sector positions per thread
-  unsigned char* smem_raw = GLOBAL ? A.big + (size_t)blockIdx.x * front_ring_bytes(MAXH) : smem_lds;
-  // layout: keys[SORT_CAP] u64 | l_picked | l_col | l_label | l_curv (ring window) | list[MAXH+16] | l_brk | l_rank | l_stat | l_reach (window)
-  unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem_raw);
-  const int WIN = MAXH + 2 * 16;
-  int* l_picked = reinterpret_cast<int*>(keys + SORT_CAP);
-  int* l_col = l_picked + WIN;
-  int* l_label = l_col + WIN;
-  float* l_curv = reinterpret_cast<float*>(l_label + WIN);
-  int* list = reinterpret_cast<int*>(l_curv + WIN);
-  int* l_brk = list + (MAXH + 16);
-  int* l_rank = l_brk + WIN;
-  int* l_stat = l_rank + WIN;
-  int* l_reach = l_stat + WIN;   // how far a pick's suppression marks go from this cell: forward | backward << 4 (0..5 each)
-  __shared__ int s_heads, s_ep;
-  __shared__ int s_pk[UP][XW], s_cw[2][XW];
-  __shared__ float s_red[2][3][XW];
-  __shared__ int s_wsum[XW];
-
-  const int ring = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  XT_STAMP(0);
-  const int s = A.start_ring[ring], e = A.end_ring[ring];
-  const int n = *A.n_ptr;
-  // ring window in LDS: global indices [w0, w0 + wlen)
-  const int w0 = s - 16;
-  int wlen = (e - s) + 32 + 1;
-  if (wlen < 0) wlen = 0;
-  if (wlen > WIN) wlen = WIN;  // guarded by the host (ring population <= MAXH)
-  // K3 inside this kernel (was: smoothness_kernel + occlusion_kernel, two launches on the frame's critical path): curvature
-  // (calculateSmoothness, featureExtraction.cpp:87-110) and the occlusion / parallel-beam marks (markOccludedPoints, :112-149) of the window's
-  // cells straight from range / col. The reference SCATTERS the marks (point j marks j-5..j or j+1..j+6); here every cell GATHERS the three
-  // conditions of the points that could mark it — the same set, no write shared between workgroups.
-  {
-    int* l_flag = reinterpret_cast<int*>(keys);   // scratch (the sector sort fills keys later): conditions of the points [w0 - 6, w0 + wlen + 6)
-    for (int i = t; i < wlen + 12; i += XT) {
-      const int j = w0 - 6 + i;
-      int fl = 0;
-      if (j >= 5 && j < n - 6) {   // :116
-        const float depth1 = A.range[j], depth2 = A.range[j + 1];
-        const int columnDiff = abs(A.col[j + 1] - A.col[j]);
-        if (columnDiff < 10) {
-          if (depth1 - depth2 > 0.3) fl |= 1;        // marks j-5 .. j
-          else if (depth2 - depth1 > 0.3) fl |= 2;   // marks j+1 .. j+6
-        }
-        const float diff1 = fabsf(float(A.range[j - 1] - A.range[j]));
-        const float diff2 = fabsf(float(A.range[j + 1] - A.range[j]));
-        if (diff1 > 0.02 * A.range[j] && diff2 > 0.02 * A.range[j]) fl |= 4;   // marks j
-      }
-      l_flag[i] = fl;
-    }
-    __syncthreads();
-    for (int i = t; i < wlen; i += XT) {
-      const int gi = w0 + i;
-      const bool in = gi >= -FRONT_GUARD && gi < n + FRONT_GUARD;
-      float c = 0.f;
-      if (gi >= 5 && gi < n - 5) {  // :91-99, float sum in the written order
-        const float* range = A.range;
-        const float diffRange = range[gi - 5] + range[gi - 4] + range[gi - 3] + range[gi - 2] + range[gi - 1] - range[gi] * 10
-                              + range[gi + 1] + range[gi + 2] + range[gi + 3] + range[gi + 4] + range[gi + 5];
-        c = diffRange * diffRange;
-      }
-      int pk = (l_flag[i + 6] >> 2) & 1;
-#pragma unroll
-      for (int k = 0; k <= 5; k++) pk |= l_flag[i + 6 + k] & 1;
-#pragma unroll
-      for (int k = 1; k <= 6; k++) pk |= (l_flag[i + 6 - k] >> 1) & 1;
-      l_picked[i] = pk;
-      l_col[i] = in ? A.col[gi] : 0;
-      l_label[i] = 0;
-      l_curv[i] = c;
-      if (gi >= s - 4 && gi <= e + 5 && gi >= 0 && gi < n) A.curv[gi] = c;   // the ring's own cells (rings tile [0, n)): cloudCurvature as the reference leaves it
-    }
-    __syncthreads();   // keys is scratch no longer
-  }
-  int scan_cnt = 0, par = 0;  // surface-scan length so far (every thread keeps the same count)
-  // brk[i]: the suppression marks of a pick stop between window cells i and i + 1 (|columnDiff| > 10, :199-210)
-  for (int i = t; i < wlen; i += XT) { l_rank[i] = INT_MAX; l_stat[i] = ST_OUT; }
-  __syncthreads();
-  for (int i = t; i + 1 < wlen; i += XT) l_brk[i] = abs(l_col[i + 1] - l_col[i]) > 10 ? 1 : 0;
-  __syncthreads();
-  for (int i = t; i < wlen; i += XT) {   // once per ring: the rounds below then read their neighbours without a dependent chain of break tests
-    int fr = 0, br = 0;
-    if (i >= 5 && i + 5 < wlen) {
-      for (int d = 1; d <= 5; d++) { if (l_brk[i + d - 1]) break; fr = d; }
-      for (int d = 1; d <= 5; d++) { if (l_brk[i - d]) break; br = d; }
-    }
-    l_reach[i] = fr | (br << 4);
-  }
-
-  // ---- all six sector sorts at once (they depend on the curvatures only): a segmented bitonic sort, 6 x seg keys ----
-  int seg = 2;
-  {
-    int maxlen = 0;
-    for (int j = 0; j < 6; j++) {
-      const int sp = (s * (6 - j) + e * j) / 6, ep = (s * (5 - j) + e * (j + 1)) / 6 - 1;
-      maxlen = max(maxlen, ep - sp);
-    }
-    while (seg < maxlen) seg <<= 1;  // <= SEGMAX: a sector holds at most Horizon_SCAN / 6 + 1 points
-  }
-  for (int i = t; i < 6 * seg; i += XT) {
-    const int j = i / seg, li = i - j * seg;
-    const int sp = (s * (6 - j) + e * j) / 6, ep = (s * (5 - j) + e * (j + 1)) / 6 - 1;
-    unsigned long long kv = ~0ull;
-    if (li < ep - sp) {
-      const int k = sp + li;
-      // cloudSmoothness[k] = {curvature, k} for k in [5, n-5), else the zero-initialised {0, 0}
-      const bool live = k >= 5 && k < n - 5;
-      const float cv = live ? l_curv[k - w0] : 0.f;
-      const int ind = live ? k : 0;
-      kv = ((unsigned long long)__float_as_uint(cv) << 32) | (unsigned)ind;
-    }
-    keys[i] = kv;
-  }
-  __syncthreads();
-  XT_STAMP(1);
-  bitonic_sort_lds_seg<XT>(keys, 6 * seg, seg);   // std::sort(begin+sp, begin+ep) with the (value, ind) tie order
-  XT_STAMP(2);
-
-  // ---- all twelve pick stages of the ring as ONE fixed point (rings away from the cloud's two ends, at most 20 corners per sector) ----
-  // The reference walks sector 0 corners, sector 0 surfaces, sector 1 corners, ... (featureExtraction.cpp:168-252); a pick marks its +-5
-  // neighbours (up to a column break) and later candidates that are marked are skipped. Order every candidate of the ring by (sector, pass,
-  // rank in its walk): a candidate is picked iff no candidate EARLIER in that order that reaches it is picked — the stage-by-stage rule
-  // below with the order extended across stages, so the chains of twelve stages resolve together (a stage costs ~4 us of barriers with
-  // a third of the threads busy). Not covered here and left to the staged code: sectors at the cloud's ends (stale smoothness entries),
-  // thresholds that let a cell be corner AND surface candidate, and the cap — the corner walk stops after its 20th pick
-  // (largestPickedNum, :186-193), so a sector with more corner picks than that is redone stage by stage (checked before anything is applied).
-  bool global_done = false;
-  int path = ROLO_XPATH_RING_NONE;   // uniform: every branch below that sets it is taken by the whole workgroup
-#ifndef ROLO_XT_STAGED
-  {
-    constexpr int UPG = (6 * SEGMAX + XT - 1) / XT;   // entries (sector, position) per thread
-    __shared__ int s_gpk[UPG][XW], s_gep[6], s_gbad;
-    bool eligible = A.surf_threshold > 0.f && A.edge_threshold >= A.surf_threshold && seg >= 64 && e - s >= 12;
-    int sps[6], eps[6];
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-      sps[j] = (s * (6 - j) + e * j) / 6; eps[j] = (s * (5 - j) + e * (j + 1)) / 6 - 1;
-      eligible = eligible && eps[j] > sps[j] && eps[j] - sps[j] < SEGMAX;
-    }
-    // the cloud's ends (as in the staged code below): the head ring's stale {0, 0} entries name point 0 — inside this ring's window,
-    // an ordinary surface candidate of curvature 0; a tail ring's name point 0 too, which the first ring marked long ago: out of the window, skipped
-    const bool head = s < 5, tail = eps[5] >= n - 5;
-    if (head) eligible = eligible && !tail && eps[0] >= 5 && w0 <= 0 && -w0 < wlen;
-    if (tail) eligible = eligible && !head && n >= 64 && A.start_ring[0] == 4 && A.end_ring[0] >= 30;
-    if (eligible) {   // uniform
-      if (t < 6) s_gep[t] = 0;
-      if (t == 0) s_gbad = 0;
-      int my_li[UPG], my_rank[UPG];
-#pragma unroll
-      for (int u = 0; u < UPG; u++) {
-        const int i = t + XT * u, j = i / SEGMAX, p = i - j * SEGMAX;
-        my_li[u] = -1; my_rank[u] = INT_MAX;
-        if (j < 6) {
-          int sp = sps[0], ep = eps[0];
-#pragma unroll
-          for (int jj = 1; jj < 6; jj++) if (j == jj) { sp = sps[jj]; ep = eps[jj]; }
-          const int len = ep - sp;
-          if (p <= len) {
-            const int k = sp + p;
-            const int ind = (k == ep) ? ((ep >= 5 && ep < n - 5) ? ep : 0) : (int)(unsigned)(keys[j * seg + p] & 0xffffffffull);   // smooth[ep] is outside the sorted range
-            const int li = ind - w0;
-            const bool in_win = li >= 0 && li < wlen;   // a stale entry of a tail ring names point 0, far outside this ring's window: a no-op
-            const float cv = (ind == 0 || !in_win) ? 0.f : l_curv[li];   // stale entry: curvature 0 whatever the window holds
-            const bool corner = cv > A.edge_threshold, surf = cv < A.surf_threshold;   // never both: edge_threshold >= surf_threshold
-            if (in_win && (corner || surf)) {
-              const int rank = corner ? ((k == ep) ? 0 : ep - k) : p;   // corners walk k = ep .. sp, surfaces k = sp .. ep
-              my_li[u] = li; my_rank[u] = ((2 * j + (corner ? 0 : 1)) << 12) | rank;
-              l_rank[li] = my_rank[u];
-              l_stat[li] = l_picked[li] == 0 ? ST_UNDECIDED : ST_OUT;
-            }
-          }
-        }
-      }
-      __syncthreads();
-      unsigned my_nb[UPG];
-#pragma unroll
-      for (int u = 0; u < UPG; u++) {
-        my_nb[u] = 0u;
-        const int li = my_li[u];
-        if (li < 0) continue;
-        const int rc = l_reach[li], fr = rc & 15, br = rc >> 4;
-#pragma unroll
-        for (int d = 1; d <= 5; d++) {
-          const int rf = l_rank[li + d], rb = l_rank[li - d];
-          if (d <= fr && rf < my_rank[u]) my_nb[u] |= 1u << (d - 1);
-          if (d <= br && rb < my_rank[u]) my_nb[u] |= 1u << (4 + d);
-        }
-      }
-      while (true) {
-        int undecided = 0;
-#pragma unroll
-        for (int u = 0; u < UPG; u++) {
-          const int li = my_li[u];
-          if (li < 0 || l_stat[li] != ST_UNDECIDED) continue;
-          bool any_sel = false, any_und = false;
-#pragma unroll
-          for (int d = 1; d <= 5; d++) {
-            const int sf = l_stat[li + d], sb = l_stat[li - d];
-            if (my_nb[u] & (1u << (d - 1))) { any_sel |= sf == ST_PICKED; any_und |= sf == ST_UNDECIDED; }
-            if (my_nb[u] & (1u << (4 + d))) { any_sel |= sb == ST_PICKED; any_und |= sb == ST_UNDECIDED; }
-          }
-          if (any_sel) l_stat[li] = ST_OUT;
-          else if (!any_und) l_stat[li] = ST_PICKED;
-          else undecided = 1;
-        }
-        if (!__syncthreads_or(undecided)) break;
-      }
-      // corner picks per (entry slot, wavefront); the k == ep entry of a sector leads its walk
-      bool pk[UPG];
-#pragma unroll
-      for (int u = 0; u < UPG; u++) {
-        const int i = t + XT * u, j = i / SEGMAX, p = i - j * SEGMAX;
-        const bool is_corner = my_li[u] >= 0 && ((my_rank[u] >> 12) & 1) == 0;
-        pk[u] = is_corner && l_stat[my_li[u]] == ST_PICKED;
-        bool is_ep = false;
-        if (j < 6 && is_corner) { int len = eps[0] - sps[0];
-#pragma unroll
-          for (int jj = 1; jj < 6; jj++) if (j == jj) len = eps[jj] - sps[jj];
-          is_ep = p == len; }
-        if (is_ep && pk[u]) s_gep[j] = 1;
-        const unsigned long long bal = __ballot(pk[u] && !is_ep);
-        if (lane == 0) s_gpk[u][wv] = __popcll(bal);
-        // ordinal inside the slot: picks at higher positions of this wavefront's 64
-        my_rank[u] = (my_rank[u] & ~0xfff) | (is_ep ? 0xfff : __popcll(bal & ~((2ull << lane) - 1ull)));   // rank no longer needed: low 12 bits = picks above in the wave (0xfff: the ep entry)
-      }
-      __syncthreads();
-      // a sector's total and, per entry, the picks at higher positions in other wavefront slots of the same sector
-      int higher[UPG];
-#pragma unroll
-      for (int u = 0; u < UPG; u++) {
-        higher[u] = 0;
-        const int i0 = wv * 64 + XT * u, j = i0 / SEGMAX;
-        int total = j < 6 ? s_gep[min(j, 5)] : 0;
-#pragma unroll
-        for (int u2 = 0; u2 < UPG; u2++)
-#pragma unroll
-          for (int w2 = 0; w2 < XW; w2++) {
-            const int i2 = w2 * 64 + XT * u2;
-            if (i2 / SEGMAX == j) { const int c = s_gpk[u2][w2]; total += c; if (i2 > i0) higher[u] += c; }
-          }
-        if (j < 6 && total > 20) s_gbad = 1;
-        if (j < 6 && lane == 0 && (i0 - j * SEGMAX) == 0) A.corner_cnt[ring * 6 + j] = total;   // (rewritten by the staged code if the cap strikes)
-      }
-      __syncthreads();
-      path = s_gbad == 0 ? ROLO_XPATH_RING_APPLIED : ROLO_XPATH_RING_CAPPED;
-      if (s_gbad == 0) {
-#pragma unroll
-        for (int u = 0; u < UPG; u++) {
-          const int li = my_li[u];
-          if (li < 0 || l_stat[li] != ST_PICKED) continue;
-          const int j = (t + XT * u) / SEGMAX;
-          if (((my_rank[u] >> 12) & 1) == 0) {
-            const int within = my_rank[u] & 0xfff;
-            const int ordinal = within == 0xfff ? 0 : s_gep[j] + higher[u] + within;
-            l_label[li] = 1;
-            A.corner_stage[(ring * 6 + j) * 20 + ordinal] = A.extracted[li + w0];
-          } else {
-            l_label[li] = -1;
-          }
-          l_picked[li] = 1;
-          const int rc = l_reach[li], fr = rc & 15, br = rc >> 4;
-#pragma unroll
-          for (int d = 1; d <= 5; d++) { if (d <= fr) l_picked[li + d] = 1; if (d <= br) l_picked[li - d] = 1; }
-        }
-        __syncthreads();
-        // every k of a sector with label <= 0 joins the ring's surface scan, in k order (:240-252); the sectors tile [s, e - 1]
-        const int e_last = eps[5];
-        for (int base = s; base <= e_last; base += XT) {
-          const int k = base + t;
-          const bool v = k <= e_last && l_label[k - w0] <= 0;
-          const unsigned long long bal = __ballot(v);
-          if (lane == 0) s_cw[par][wv] = __popcll(bal);
-          __syncthreads();
-          int woff = 0, tot = 0;
-#pragma unroll
-          for (int w = 0; w < XW; w++) { const int c = s_cw[par][w]; tot += c; if (w < wv) woff += c; }
-          if (v) list[scan_cnt + woff + __popcll(bal & ((1ull << lane) - 1ull))] = k;
-          scan_cnt += tot;
-          par ^= 1;
-        }
-        global_done = true;
-      } else {
-        // the cap strikes somewhere on this ring: nothing has been applied; neutral rank / state cells for the staged code
-#pragma unroll
-        for (int u = 0; u < UPG; u++) if (my_li[u] >= 0) { l_rank[my_li[u]] = INT_MAX; l_stat[my_li[u]] = ST_OUT; }
-        __syncthreads();
-      }
-    }
-  }
-#endif
-
-  if (!global_done)
-  for (int j = 0; j < 6; j++) {
-    const int sp = (s * (6 - j) + e * j) / 6;
-    const int ep = (s * (5 - j) + e * (j + 1)) / 6 - 1;
-    if (sp >= ep) { if (t == 0) A.corner_cnt[ring * 6 + j] = 0; path |= ROLO_XPATH_SECTOR_EMPTY << (2 + 2 * j); continue; }  // uniform
-    const unsigned long long* skeys = keys + j * seg;
-    const int len = ep - sp;  // sorted range [sp, ep); positions sp..ep take part in the picks
-    // Sectors at the two ends of the cloud hold the reference's stale {0, 0} smoothness entries: entries that all name POINT 0,
-    // with curvature 0. With sane thresholds (0 is a surface candidate, not a corner) they amount to "point 0 is the best-ranked surface
-    // candidate": in the sector that holds point 0 the parallel picks below handle that as it stands (the duplicates fold onto one window
-    // cell); in the last sector of the cloud point 0 was picked long ago — the ring that holds it ran first in the reference — so the
-    // entries do nothing and are skipped. Anything odder (tiny clouds, both ends in one sector, thresholds that flip the argument) takes the
-    // serial walk as written. (Both end sectors on the serial walk: 155 us of this kernel's 170 on the OS1-128 frame.)
-    const bool head_sp = sp < 5, tail_sp = ep >= n - 5;
-    const bool thr_ok = A.surf_threshold > 0.f && A.edge_threshold >= 0.f;
-    const bool head_ok = !head_sp || (thr_ok && !tail_sp && ep >= 5 && w0 <= 0 && -w0 < wlen);
-    const bool tail_ok = !tail_sp || (thr_ok && !head_sp && n >= 64 && A.start_ring[0] == 4 && A.end_ring[0] >= 30);   // ring 0 starts at 0 - 1 + 5 and its stale entry marked point 0
-    const bool parallel = head_ok && tail_ok && len < SEGMAX;
-    path |= (parallel ? ROLO_XPATH_SECTOR_PARALLEL : ROLO_XPATH_SECTOR_SERIAL) << (2 + 2 * j);
-    if (parallel) {
-      // ---- parallel greedy picks ----
-      // The reference walks the sector in curvature order and a pick marks its +-5 neighbours (up to a column break) as
-      // taken. Equivalent fixed point: a candidate is picked iff no better-ranked candidate that reaches it is picked.
-      // Every round decides the candidates whose better-ranked reaching candidates are all decided; the chains are a
-      // handful of links long, so a sector takes a few rounds of ~20 LDS reads instead of ~10^3 dependent LDS steps
-      // on one lane.
-      int my_li[UP], my_rank[UP];
-      for (int pass = 0; pass < 2; pass++) {   // 0: corners (:181-211), 1: surfaces (:213-238)
-        const float thr = pass == 0 ? A.edge_threshold : A.surf_threshold;
-#pragma unroll
-        for (int u = 0; u < UP; u++) {
-          const int p = t + XT * u;
-          my_li[u] = -1; my_rank[u] = INT_MAX;
-          if (p <= len) {
-            const int k = sp + p;
-            const int ind = (k == ep) ? ((ep >= 5 && ep < n - 5) ? ep : 0) : (int)(unsigned)(skeys[p] & 0xffffffffull);   // smooth[ep] is outside the sorted range
-            const int li = ind - w0;
-            if (li >= 0 && li < wlen) {   // a stale entry of the cloud's last sector names point 0, far outside this ring's window: a no-op (above)
-              const bool stale = ind == 0;   // (head sector) curvature 0 whatever l_curv holds
-              const int rank = pass == 0 ? ((k == ep) ? 0 : ep - k) : p;   // corners walk k = ep .. sp, surfaces k = sp .. ep
-              const float cv = stale ? 0.f : l_curv[li];
-              const bool cand = l_picked[li] == 0 && (pass == 0 ? cv > thr : cv < thr);
-              my_li[u] = li; my_rank[u] = rank;
-              l_rank[li] = rank;
-              l_stat[li] = cand ? ST_UNDECIDED : ST_OUT;
-            }
-          }
-        }
-        __syncthreads();
-        // which of the ten neighbours can suppress this candidate: within reach and better ranked — fixed for the stage
-        unsigned my_nb[UP];
-#pragma unroll
-        for (int u = 0; u < UP; u++) {
-          my_nb[u] = 0u;
-          const int li = my_li[u];
-          if (li < 0) continue;
-          const int rc = l_reach[li], fr = rc & 15, br = rc >> 4;
-#pragma unroll
-          for (int d = 1; d <= 5; d++) {
-            const int rf = l_rank[li + d], rb = l_rank[li - d];
-            if (d <= fr && rf < my_rank[u]) my_nb[u] |= 1u << (d - 1);
-            if (d <= br && rb < my_rank[u]) my_nb[u] |= 1u << (4 + d);
-          }
-        }
-        while (true) {   // states only ever move UNDECIDED -> final, so a neighbour's state read mid-update is either still valid
-          int undecided = 0;
-#pragma unroll
-          for (int u = 0; u < UP; u++) {
-            const int li = my_li[u];
-            if (li < 0 || l_stat[li] != ST_UNDECIDED) continue;
-            bool any_sel = false, any_und = false;
-#pragma unroll
-            for (int d = 1; d <= 5; d++) {   // ten independent LDS reads
-              const int sf = l_stat[li + d], sb = l_stat[li - d];
-              if (my_nb[u] & (1u << (d - 1))) { any_sel |= sf == ST_PICKED; any_und |= sf == ST_UNDECIDED; }
-              if (my_nb[u] & (1u << (4 + d))) { any_sel |= sb == ST_PICKED; any_und |= sb == ST_UNDECIDED; }
-            }
-            if (any_sel) l_stat[li] = ST_OUT;
-            else if (!any_und) l_stat[li] = ST_PICKED;
-            else undecided = 1;
-          }
-          if (!__syncthreads_or(undecided)) break;
-        }
-        // apply the picks; corners: only the first 20 in walk order exist (largestPickedNum, :186-193)
-        int ordinal[UP] = {};
-        if (pass == 0) {
-          // walk order = position len first, then len - 1 .. 0: a pick's ordinal is the number of picks at higher positions
-          int higher[UP];
-#pragma unroll
-          for (int u = 0; u < UP; u++) {
-            const int p = t + XT * u;
-            const bool pk = my_li[u] >= 0 && l_stat[my_li[u]] == ST_PICKED;
-            if (p == len) s_ep = pk ? 1 : 0;
-            const unsigned long long bal = __ballot(pk && p != len);
-            higher[u] = __popcll(bal & ~((2ull << lane) - 1ull));
-            if (lane == 0) s_pk[u][wv] = __popcll(bal);
-          }
-          __syncthreads();
-          int total = s_ep;
-#pragma unroll
-          for (int u = 0; u < UP; u++) {
-#pragma unroll
-            for (int w = 0; w < XW; w++) {
-              total += s_pk[u][w];
-#pragma unroll
-              for (int u2 = 0; u2 < UP; u2++) if (u > u2 || (u == u2 && w > wv)) higher[u2] += s_pk[u][w];
-            }
-          }
-#pragma unroll
-          for (int u = 0; u < UP; u++) ordinal[u] = (t + XT * u == len) ? 0 : s_ep + higher[u];
-          if (t == 0) A.corner_cnt[ring * 6 + j] = min(total, 20);
-        }
-#pragma unroll
-        for (int u = 0; u < UP; u++) {
-          const int li = my_li[u];
-          if (li < 0 || l_stat[li] != ST_PICKED) continue;
-          if (pass == 0) {
-            if (ordinal[u] >= 20) continue;
-            l_label[li] = 1;
-            A.corner_stage[(ring * 6 + j) * 20 + ordinal[u]] = A.extracted[li + w0];
-          } else {
-            l_label[li] = -1;
-          }
-          l_picked[li] = 1;
-          const int rc = l_reach[li], fr = rc & 15, br = rc >> 4;
-#pragma unroll
-          for (int d = 1; d <= 5; d++) { if (d <= fr) l_picked[li + d] = 1; if (d <= br) l_picked[li - d] = 1; }
-        }
-        __syncthreads();
-      }
-      // leave the rank / state cells of this sector neutral for the next one
-#pragma unroll
-      for (int u = 0; u < UP; u++) if (my_li[u] >= 0) { l_rank[my_li[u]] = INT_MAX; l_stat[my_li[u]] = ST_OUT; }
-    } else if (t == 0) {
-      // sector at a cloud end (stale {0, 0} smoothness entries): the reference's serial walk as written
-      // smooth[ep] is outside the sorted range but inside both loops
-      const bool live_ep = ep >= 5 && ep < n - 5;
-      const int ind_ep = live_ep ? ep : 0;
-      // corners: featureExtraction.cpp:181-211
-      int largestPickedNum = 0, ncorner = 0;
-      for (int k = ep; k >= sp; k--) {
-        const int ind = (k == ep) ? ind_ep : (int)(unsigned)(skeys[k - sp] & 0xffffffffull);
-        const int li = ind - w0;
-        const bool in_win = li >= 0 && li < wlen;
-        const int pk = in_win ? l_picked[li] : A.picked[ind];
-        const float cv = in_win ? l_curv[li] : A.curv[ind];
-        if (pk == 0 && cv > A.edge_threshold) {
-          largestPickedNum++;
-          if (largestPickedNum <= 20) {
-            if (in_win) l_label[li] = 1; else A.label[ind] = 1;
-            A.corner_stage[(ring * 6 + j) * 20 + ncorner] = A.extracted[ind];
-            ncorner++;
-          } else break;
-          if (in_win) l_picked[li] = 1; else A.picked[ind] = 1;
-          for (int l = 1; l <= 5; l++) {
-            const int a = ind + l, b = ind + l - 1;
-            const int ca = (a - w0 >= 0 && a - w0 < wlen) ? l_col[a - w0] : A.col[a];
-            const int cb = (b - w0 >= 0 && b - w0 < wlen) ? l_col[b - w0] : A.col[b];
-            if (abs(ca - cb) > 10) break;
-            if (a - w0 >= 0 && a - w0 < wlen) l_picked[a - w0] = 1; else A.picked[a] = 1;
-          }
-          for (int l = -1; l >= -5; l--) {
-            const int a = ind + l, b = ind + l + 1;
-            const int ca = (a - w0 >= 0 && a - w0 < wlen) ? l_col[a - w0] : A.col[a];
-            const int cb = (b - w0 >= 0 && b - w0 < wlen) ? l_col[b - w0] : A.col[b];
-            if (abs(ca - cb) > 10) break;
-            if (a - w0 >= 0 && a - w0 < wlen) l_picked[a - w0] = 1; else A.picked[a] = 1;
-          }
-        }
-      }
-      A.corner_cnt[ring * 6 + j] = ncorner;
-      // surfaces: :213-238
-      for (int k = sp; k <= ep; k++) {
-        const int ind = (k == ep) ? ind_ep : (int)(unsigned)(skeys[k - sp] & 0xffffffffull);
-        const int li = ind - w0;
-        const bool in_win = li >= 0 && li < wlen;
-        const int pk = in_win ? l_picked[li] : A.picked[ind];
-        const float cv = in_win ? l_curv[li] : A.curv[ind];
-        if (pk == 0 && cv < A.surf_threshold) {
-          if (in_win) { l_label[li] = -1; l_picked[li] = 1; } else { A.label[ind] = -1; A.picked[ind] = 1; }
-          for (int l = 1; l <= 5; l++) {
-            const int a = ind + l, b = ind + l - 1;
-            const int ca = (a - w0 >= 0 && a - w0 < wlen) ? l_col[a - w0] : A.col[a];
-            const int cb = (b - w0 >= 0 && b - w0 < wlen) ? l_col[b - w0] : A.col[b];
-            if (abs(ca - cb) > 10) break;
-            if (a - w0 >= 0 && a - w0 < wlen) l_picked[a - w0] = 1; else A.picked[a] = 1;
-          }
-          for (int l = -1; l >= -5; l--) {
-            const int a = ind + l, b = ind + l + 1;
-            const int ca = (a - w0 >= 0 && a - w0 < wlen) ? l_col[a - w0] : A.col[a];
-            const int cb = (b - w0 >= 0 && b - w0 < wlen) ? l_col[b - w0] : A.col[b];
-            if (abs(ca - cb) > 10) break;
-            if (a - w0 >= 0 && a - w0 < wlen) l_picked[a - w0] = 1; else A.picked[a] = 1;
-          }
-        }
-      }
-    }
-    __syncthreads();
-    // every k in [sp, ep] with label <= 0 joins the ring's surface scan, in k order (:240-252): ballot compaction
-    for (int base = sp; base <= ep; base += XT) {
-      const int k = base + t;
-      const bool v = k <= ep && l_label[k - w0] <= 0;
-      const unsigned long long bal = __ballot(v);
-      if (lane == 0) s_cw[par][wv] = __popcll(bal);
-      __syncthreads();
-      int woff = 0, tot = 0;
-#pragma unroll
-      for (int w = 0; w < XW; w++) { const int c = s_cw[par][w]; tot += c; if (w < wv) woff += c; }
-      if (v) list[scan_cnt + woff + __popcll(bal & ((1ull << lane) - 1ull))] = k;
-      scan_cnt += tot;
-      par ^= 1;
-    }
-  }
-  XT_STAMP(3);
-  if (t == 0) A.paths[ring] = path;
-  // write the ring's picked / label window back (the oracle's arrays after extraction)
-  for (int i = t; i < wlen; i += XT) {
-    const int gi = w0 + i;
-    if (gi >= s - 10 && gi <= e + 10 && gi >= -FRONT_GUARD && gi < n + FRONT_GUARD) {
-      if (l_picked[i]) A.picked[gi] = 1;
-      if (gi >= s && gi <= e) A.label[gi] = l_label[i];
-      else if (l_label[i] != 0) A.label[gi] = l_label[i];
-    }
-  }
-  __syncthreads();
-
-  // ---- pcl::VoxelGrid on the ring's surface scan (featureExtraction.cpp:254-258) ----
-  const int m = scan_cnt;
-  if (m == 0) { if (t == 0) A.surf_cnt[ring] = 0; return; }
-  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  for (int i = t; i < m; i += XT) {
-    const float4 p = A.extracted[list[i]];
-    mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
-    mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
-  }
-#pragma unroll
-  for (int d = 0; d < 3; d++) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { mn[d] = fminf(mn[d], __shfl_xor(mn[d], off, 64)); mx[d] = fmaxf(mx[d], __shfl_xor(mx[d], off, 64)); }
-    if (lane == 0) { s_red[0][d][wv] = mn[d]; s_red[1][d][wv] = mx[d]; }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int d = 0; d < 3; d++) {
-    float lo = s_red[0][d][0], hi = s_red[1][d][0];
-#pragma unroll
-    for (int w = 1; w < XW; w++) { lo = fminf(lo, s_red[0][d][w]); hi = fmaxf(hi, s_red[1][d][w]); }
-    mn[d] = lo; mx[d] = hi;
-  }
-  const float inv = 1.0f / A.leaf;
-  const long long dx = (long long)((mx[0] - mn[0]) * inv) + 1, dy = (long long)((mx[1] - mn[1]) * inv) + 1, dz = (long long)((mx[2] - mn[2]) * inv) + 1;
-  float4* out = A.surf_stage + (size_t)ring * MAXH;
-  if (dx * dy * dz > (long long)INT_MAX) {  // PCL: warn and copy the input through
-    for (int i = t; i < m; i += XT) out[i] = A.extracted[list[i]];
-    if (t == 0) A.surf_cnt[ring] = m;
-    return;
-  }
-  const int min_b0 = (int)floorf(mn[0] * inv), min_b1 = (int)floorf(mn[1] * inv), min_b2 = (int)floorf(mn[2] * inv);
-  const int div_b0 = (int)floorf(mx[0] * inv) - min_b0 + 1, div_b1 = (int)floorf(mx[1] * inv) - min_b1 + 1;
-  int np2 = 2; while (np2 < m) np2 <<= 1;
-  for (int i = t; i < np2; i += XT) {
-    unsigned long long kv = ~0ull;
-    if (i < m) {
-      const float4 p = A.extracted[list[i]];
-      const int ijk0 = (int)floorf(p.x * inv) - min_b0, ijk1 = (int)floorf(p.y * inv) - min_b1, ijk2 = (int)floorf(p.z * inv) - min_b2;
-      const int cell = ijk0 + ijk1 * div_b0 + ijk2 * div_b0 * div_b1;
-      kv = ((unsigned long long)(unsigned)cell << 32) | (unsigned)i;
-    }
-    keys[i] = kv;
-  }
-  __syncthreads();
-  XT_STAMP(4);
-  bitonic_sort_lds<XT>(keys, np2);  // std::sort by cell index, ties by point order
-  XT_STAMP(5);
-  // run heads -> output slot; each head accumulates its run in order with float accumulators (pcl::CentroidPoint)
-  if (t == 0) s_heads = 0;
-  __syncthreads();
-  for (int base = 0; base < m; base += XT) {
-    const int i = base + t;
-    const bool head = i < m && (i == 0 || (keys[i] >> 32) != (keys[i - 1] >> 32));
-    int inc = head ? 1 : 0;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { int o = __shfl_up(inc, off, 64); if (lane >= off) inc += o; }
-    if (lane == 63) s_wsum[wv] = inc;
-    __syncthreads();
-    int woff = 0;
-    for (int w = 0; w < wv; w++) woff += s_wsum[w];
-    const int c = s_heads;
-    if (head) {
-      const unsigned cell = (unsigned)(keys[i] >> 32);
-      float sx = 0, sy = 0, sz = 0, si = 0;
-      int cnt = 0;
-      for (int r = i; r < m && (unsigned)(keys[r] >> 32) == cell; r++) {
-        const float4 p = A.extracted[list[(int)(unsigned)(keys[r] & 0xffffffffull)]];
-        sx += p.x; sy += p.y; sz += p.z; si += p.w; cnt++;
-      }
-      const float fc = (float)cnt;
-      out[c + woff + inc - 1] = make_float4(sx / fc, sy / fc, sz / fc, si / fc);
-    }
-    __syncthreads();
-    if (t == XT - 1) s_heads = c + woff + inc;
-    __syncthreads();
-  }
-  XT_STAMP(6);
-  if (t == 0) A.surf_cnt[ring] = s_heads;
-}
+// ---- K3 (calculateSmoothness, markOccludedPoints) and K4: extract_kernel, front_extract.hpp (K3 is its window load) ----
 
 // concatenate per-ring / per-sector staging areas in order
 __global__ __launch_bounds__(256) void concat_kernel(const float4* __restrict__ stage, const int* __restrict__ cnt, int n_groups, int group_cap,

@@ -1,4 +1,4 @@
-"""Constructed rings for extract_kernel (rolo_amd/csrc/front.hip): projections made as arrays, one case per path and edge of the kernel.
+"""Constructed rings for extract_kernel (rolo_amd/csrc/front_extract.hpp): projections made as arrays, one case per path and edge of the kernel.
 
 A case is a projection dict — what FrontEnd.project() / pyorc.project return, and what FrontEnd.loadProjection / pyorc.extract_features /
 twin_front.extract_features take — plus the feature parameters, a one-line purpose and `expect_paths`: the path word (ROLO_XPATH_*,
